@@ -12,8 +12,20 @@ to one preallocated history, each followed by the Gelman check (device reduction
 all-reduce over RCCL when N > 1); the threshold is set so that no check stops the run and every step does the same work.
 Inputs (X, y, initial states) are resident in HBM before the timed region.
 
-  python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c4|c5] [--scaling weak|strong]
+  python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c4|c5] [--scaling weak|strong] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what its headline figure needs: set-up, W warm-up steps, exactly K timed steps, the outputs of the
+last timed step if --dump-outputs DIR is given, and the JSON line.  Everything else the benchmark measures takes runs of
+its own and is reported only under --full: the library's default path beside the fed one (C2 / C3), the other scaling of
+an N > 1 call, the strong-scaling projection and the short sweeps of C3 / C4 / C5 (one GPU), and the CPU baseline.
+
+--dump-outputs DIR writes what the last timed step computed, the arrays a caller of the timed path receives, as
+DIR/<name>.npy in float64 (rank r > 0: DIR/<name>_rank<r>.npy): kept rows (samples, logpost, draws where recorded),
+accept_count, the last kept row of every sampled chain (final_state) and, for C4, the Gelman checks of the step.  Where the
+whole output exceeds the size limit (DUMP_LIMIT_BYTES over all ranks), a fixed, seeded sample of chains (chain_index) and,
+if needed, of kept rows (row_index) is written.  Inputs are seeded, so two runs with the same arguments compute on the same
+data and can be compared output for output.
 
 N > 1: one process per GPU.  Under a launcher (WORLD_SIZE set) the rank count must equal --gpus; WITHOUT one,
 `python bench.py --gpus N` starts its N rank processes itself (launch_ranks: fresh children with RANK / LOCAL_RANK /
@@ -27,8 +39,9 @@ did not pick the kernel the config is tuned for), roofline.kernel_ms comes from 
 (PMC counters): it is the figure of the newest COMMITTED PMC pass of this same command, labelled as such in
 roofline.traffic_source (file, the commit that pass measured, its kernel and duration) and shown only while the dispatcher
 still picks the kernel that pass measured; null otherwise (profiles/README.md says how those passes are taken).
-The default (headline) invocation on one GPU additionally runs a short full-size sweep of C3, C4 and C5 and reports them
-under `configs` (value, kernel, kernel_ms, bound, frac each), so that one driver-timed run covers all four GPU configs.
+With --full, the default (headline) invocation on one GPU additionally runs a short full-size sweep of C3, C4 and C5 and
+reports them under `configs` (value, kernel, kernel_ms, bound, frac each), so that one driver-timed run covers all four GPU
+configs.
 """
 import argparse
 import json
@@ -224,10 +237,53 @@ KERNEL_FN = {"mfma": "mh_sweep_mfma", "wide-dataflow": "mh_sweep_wide2", "spec":
 BOUND = {"c2": "mfma", "c3": "valu", "c4": "mfma", "c5": "valu"}
 DEFAULT_STEPS = {"c2": 240, "c3": 140, "c4": 20, "c5": 6}
 EXTRA_STEPS = {"c3": 20, "c4": 3, "c5": 2}     # the short sweeps of the other configs inside the default (headline) invocation
+DUMP_LIMIT_BYTES = 60 * 10 ** 6                # --dump-outputs: all files of all ranks together
+DUMP_SEED = 20260317                           # the seeded sample of chains / kept rows when the outputs exceed the limit
+ROW_OUTPUTS = ("samples", "logpost", "draws")   # the outputs with a kept-row axis (last)
 
 
-def run_config(cfg, chains, iters, steps, warmup, world, rank, dev, dist, torch, E, abi):
-    """W warm-up steps, then exactly K timed steps of one config between barriers; returns what was measured."""
+def dump_outputs(dirpath, outputs, rank, world, torch):
+    """Writes the outputs of a step as float64 .npy files; per-chain arrays (chain axis first, kept rows last where they
+    have rows) are restricted to a fixed, seeded sample of chains and rows when the whole would exceed this rank's share
+    of DUMP_LIMIT_BYTES.  Returns a description for the JSON line."""
+    os.makedirs(dirpath, exist_ok=True)
+    per_chain = {n: a for n, a in outputs.items() if isinstance(a, torch.Tensor)}
+    whole = {n: np.asarray(a, dtype=np.float64) for n, a in outputs.items() if not isinstance(a, torch.Tensor)}
+    budget = DUMP_LIMIT_BYTES // world - sum(a.nbytes for a in whole.values())
+    C = int(next(iter(per_chain.values())).shape[0])
+    S = max([int(a.shape[-1]) for n, a in per_chain.items() if n in ROW_OUTPUTS] + [0])
+    chain_bytes = sum(8 * a.numel() // max(C, 1) for a in per_chain.values())
+    rng = np.random.default_rng(DUMP_SEED)
+    nc = C if C * chain_bytes <= budget else int(min(C, max(16, budget // max(chain_bytes, 1))))
+    ci = np.arange(C) if nc == C else np.sort(rng.choice(C, nc, replace=False))
+    ri = None
+    if nc * chain_bytes > budget and S > 0:          # even the fewest chains are too long: a sample of their kept rows too
+        row_bytes = sum(8 * a.numel() // max(C, 1) // S for n, a in per_chain.items() if n in ROW_OUTPUTS)
+        fixed = chain_bytes - row_bytes * S
+        nr = int(max(1, min(S, (budget // nc - fixed) // max(row_bytes, 1))))
+        ri = np.sort(rng.choice(S, nr, replace=False))
+    sfx = "" if rank == 0 else "_rank%d" % rank
+    written = {}
+    cit = torch.as_tensor(ci, device=next(iter(per_chain.values())).device)
+    for n, a in per_chain.items():
+        a = a.index_select(0, cit)
+        if ri is not None and n in ROW_OUTPUTS:
+            a = a.index_select(a.dim() - 1, torch.as_tensor(ri, device=a.device))
+        whole[n] = a.double().cpu().numpy()
+    if nc < C:
+        whole["chain_index"] = ci.astype(np.float64)
+    if ri is not None:
+        whole["row_index"] = ri.astype(np.float64)
+    for n, a in whole.items():
+        np.save(os.path.join(dirpath, n + sfx + ".npy"), np.ascontiguousarray(a))
+        written[n + sfx] = list(a.shape)
+    return {"dir": dirpath, "arrays": written, "chains": "%d of %d" % (nc, C),
+            "rows": "all" if ri is None else "%d of %d" % (len(ri), S)}
+
+
+def run_config(cfg, chains, iters, steps, warmup, world, rank, dev, dist, torch, E, abi, full=False, dump_dir=None):
+    """W warm-up steps, then exactly K timed steps of one config between barriers; returns what was measured.  full: also
+    time the library's default path (C2 / C3); dump_dir: write the outputs of the last timed step there."""
     thin, k = cfg.thin, cfg.k
     chain_base = rank * chains
     X, y, init = cfg.workload(chains, chain_base)
@@ -330,10 +386,22 @@ def run_config(cfg, chains, iters, steps, warmup, world, rank, dev, dist, torch,
         dist.all_reduce(b, op=dist.ReduceOp.SUM)
         bases = [int(v) for v in b.tolist()]
     assert int(out.status.abs().sum().item()) == 0, "a chain reported an error"
+    dumped = None
+    if dump_dir:
+        if cfg.name == "c4":        # the step's whole history (all bulks) and its Gelman checks
+            outs = {"samples": hist.samples, "logpost": hist.logpost, "accept_count": out.accept_count,
+                    "gelman_value": np.array([h[1] for h in chk.history], dtype=np.float64),
+                    "gelman_psrf": np.array([h[2] for h in chk.history], dtype=np.float64)}
+        else:
+            outs = {"samples": out.samples, "logpost": out.logpost, "draws": out.draws, "accept_count": out.accept_count}
+        outs = {n: a for n, a in outs.items() if a is not None}
+        if outs["samples"].shape[-1] > 0:
+            outs["final_state"] = outs["samples"][:, :, -1]
+        dumped = dump_outputs(dump_dir, outs, rank, world, torch)
     # the library's DEFAULT path of the same sweep (no materialised stream handed in: the library fills its own per step
     # window, mh_engine.hip launch_sweep), timed beside the fed form the steps above used: what a plain MCMC() call gets
     default_ms = None
-    if cfg.name in ("c2", "c3") and not getattr(cfg, "no_default_path", False):
+    if full and cfg.name in ("c2", "c3") and not getattr(cfg, "no_default_path", False):
         nd = max(2, min(steps, 12))
         d0, d1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         outs_d = None
@@ -359,8 +427,10 @@ def run_config(cfg, chains, iters, steps, warmup, world, rank, dev, dist, torch,
                                             "launches_per_step": len(bulks), "rhat_last": chk.last}
     elif cfg.name in ("c2", "c3"):
         kern_ms = float(np.mean([ev_mid[s].elapsed_time(ev[s][1]) for s in range(steps)]))   # sweep kernel (+ output memsets)
-        extra = {"rng_fill_kernel_ms": step_ms - kern_ms, "default_path_ms_per_step": default_ms,
-                 "default_path_note": "the same sweep through the library's own step windows (stream filled per window), bit-equal outputs"}
+        extra = {"rng_fill_kernel_ms": step_ms - kern_ms}
+        if default_ms is not None:
+            extra.update(default_path_ms_per_step=default_ms,
+                         default_path_note="the same sweep through the library's own step windows (stream filled per window), bit-equal outputs")
     else:
         kern_ms, extra = step_ms, {}
     samples_per_step = chains * (iters - 1)
@@ -369,7 +439,7 @@ def run_config(cfg, chains, iters, steps, warmup, world, rank, dev, dist, torch,
             "elapsed": elapsed, "value": world * samples_per_step * steps / elapsed, "ms_per_step": 1e3 * elapsed / steps,
             "kern_ms": kern_ms, "extra": extra, "picked": sorted(set(picked)), "accept_rate": acc,
             "samples_per_step": samples_per_step, "chain_base": chain_base, "chain_bases": bases,
-            "all_reduce_calls_in_timed_steps": ncoll["all_reduce"]}
+            "all_reduce_calls_in_timed_steps": ncoll["all_reduce"], "dumped": dumped}
 
 
 def roofline_block(res, traffic_from=None):
@@ -506,6 +576,11 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: every rank runs the config's per-GPU share (C2/C3 1024 chains per rank); strong: C2/C3's 1024 chains "
                          "are divided over the ranks (north_star: '1024 chains ... at 1/2/4/8 MI355X'); C4/C5 keep their per-GPU share")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the library's default path (C2 / C3), the other scaling "
+                         "(N > 1), the strong-scaling projection and the short C3 / C4 / C5 sweeps (one GPU), the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float64; a seeded sample where large)")
     args = ap.parse_args()
     cfg = Config(args.config)
     cfg.any_kernel = args.any_kernel
@@ -558,39 +633,40 @@ def main():
     if world > 1:
         ranks_seen = [None] * world
         dist.all_gather_object(ranks_seen, me)
-    res = run_config(cfg, chains, iters, args.steps, args.warmup, world, rank, dev, dist, torch, E, abi)
-    # N > 1 GPUs: BOTH scalings in one invocation (every config since round 5).  The reference scales a FIXED number of chains over its workers
+    res = run_config(cfg, chains, iters, args.steps, args.warmup, world, rank, dev, dist, torch, E, abi, full=args.full,
+                     dump_dir=args.dump_outputs)
+    # N > 1 GPUs with --full: BOTH scalings in one invocation.  The reference scales a FIXED number of chains over its workers
     # (R/mcmc.R:536-641), i.e. strong scaling -- 1024 / N chains per GPU, the latency form of the kernels below 1024 --, the
     # contract's line is per-GPU work fixed (weak).  `value` / `scaling` are the leg --scaling names; `scalings` holds both.
     scalings = {scaling: {"value": res["value"], "chains_per_gpu": chains, "total_chains": chains * world, "ms_per_step": res["ms_per_step"],
                           "kernel": res["picked"]}}
-    if strong_ok:
+    if strong_ok and args.full:
         other = "strong" if scaling == "weak" else "weak"
         oc = cfg.chains // world if other == "strong" else cfg.chains
-        ores = run_config(cfg, oc, iters, max(3, args.steps // 4), 1, world, rank, dev, dist, torch, E, abi)
+        ores = run_config(cfg, oc, iters, max(3, args.steps // 4), 1, world, rank, dev, dist, torch, E, abi, full=True)
         scalings[other] = {"value": ores["value"], "chains_per_gpu": oc, "total_chains": oc * world, "ms_per_step": ores["ms_per_step"],
                            "kernel": ores["picked"], "steps": ores["steps"]}
-    # one GPU: what a GPU of a strong-scaled call of this config would see -- 1024 / G chains, measured HERE -- and the curve
+    # one GPU, --full: what a GPU of a strong-scaled call of this config would see -- 1024 / G chains, measured HERE -- and the curve
     # that follows from it (G x the samples/s of 1024 / G chains on one GPU: chains never interact, R/mcmc.R:590-673)
     projection = None
-    if world == 1 and not args.chains and not args.iters and not args.no_extra_configs:
+    if args.full and world == 1 and not args.chains and not args.iters and not args.no_extra_configs:
         projection = {"note": "measured on this one GPU with %d / G chains; value_G = G x samples/s of that run (%s)" %
                               (cfg.chains, "the all-reduce of a Gelman check, 1 + 5p + 2p^2 doubles per 1000 iterations, not included" if cfg.name == "c4"
                                else "no data-path collective exists"),
                       "1": {"chains_per_gpu": cfg.chains, "ms_per_step": res["ms_per_step"], "value": res["value"], "kernel": res["picked"]}}
         for G in (2, 4, 8):
-            pr = run_config(cfg, cfg.chains // G, iters, max(3, args.steps // 8), 1, 1, 0, dev, dist, torch, E, abi)
+            pr = run_config(cfg, cfg.chains // G, iters, max(3, args.steps // 8), 1, 1, 0, dev, dist, torch, E, abi, full=True)
             projection[str(G)] = {"chains_per_gpu": cfg.chains // G, "ms_per_step": pr["ms_per_step"], "value": G * pr["value"],
                                   "kernel": pr["picked"], "speedup_vs_1": G * pr["value"] / res["value"]}
 
     # the other GPU configs of BASELINE.md section 4 as short full-size sweeps, so that the driver's clock covers them too
-    # (headline invocation on one GPU only; `--config cX` gives each its own full line, `--gpus N` its scaling)
+    # (headline invocation on one GPU with --full only; `--config cX` gives each its own line, `--gpus N` its scaling)
     extras = {}
-    if cfg.name == "c2" and world == 1 and not args.no_extra_configs and not args.chains and not args.iters:
+    if args.full and cfg.name == "c2" and world == 1 and not args.no_extra_configs and not args.chains and not args.iters:
         for name in ("c3", "c4", "c5"):
             xc = Config(name)
             t_x = time.perf_counter()
-            xr = run_config(xc, xc.chains, xc.iters, EXTRA_STEPS[name], 1, 1, 0, dev, dist, torch, E, abi)
+            xr = run_config(xc, xc.chains, xc.iters, EXTRA_STEPS[name], 1, 1, 0, dev, dist, torch, E, abi, full=True)
             rl = roofline_block(xr)
             extras[name] = {"workload": workload_text(xr), "value": xr["value"], "unit": "MH samples/s", "steps": xr["steps"], "warmup": 1,
                             "ms_per_step": xr["ms_per_step"], "accept_rate": xr["accept_rate"], "kernel": rl["kernel"],
@@ -630,7 +706,9 @@ def main():
             line["strong_scaling_projection"] = projection
         if extras:
             line["configs"] = extras
-        if world == 1 and not args.no_cpu_baseline:
+        if res["dumped"]:
+            line["dump_outputs"] = res["dumped"]
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg)
         print(json.dumps(line))
     if world > 1:

@@ -187,7 +187,7 @@ def test_bench_gpus_2_with_no_rank_variables_launches_two_ranks_itself():
 
 def test_bench_strong_scaling_divides_the_headline_chains():
     """--scaling strong: C2's 1024 chains divided over the ranks (512 each), chain ids continuing; the line says which
-    scaling ran.  A launcher world that differs from --gpus is refused."""
+    scaling ran; under --full it holds the other scaling too.  A launcher world that differs from --gpus is refused."""
     import json
     import torch
     if not torch.cuda.is_available():
@@ -195,7 +195,8 @@ def test_bench_strong_scaling_divides_the_headline_chains():
     drop = ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "LOCAL_WORLD_SIZE")
     env = {k: v for k, v in os.environ.items() if k not in drop}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--scaling", "strong",
-                        "--iters", "2000", "--steps", "2", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--iters", "2000", "--steps", "2", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True,
+                       timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
     assert line["scaling"] == "strong" and line["n_gpus"] == 2
