@@ -5,7 +5,7 @@
 namespace fmh {
 FMH_HIDDEN const void* k_lat_kv2b(int p) {
   switch (p) {
-    case 3: return (const void*)mh_sweep_lat<2, 3, 20>;
+    case 3: return (const void*)mh_sweep_lat<2, 3, reg_slots(3)>;
     default: return nullptr;
   }
 }

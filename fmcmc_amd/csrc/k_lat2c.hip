@@ -5,10 +5,10 @@
 namespace fmh {
 FMH_HIDDEN const void* k_lat_kv2c(int p) {
   switch (p) {
-    case 4: return (const void*)mh_sweep_lat<2, 4, 10>;
-    case 5: return (const void*)mh_sweep_lat<2, 5, 10>;
-    case 6: return (const void*)mh_sweep_lat<2, 6, 8>;
-    case 7: return (const void*)mh_sweep_lat<2, 7, 8>;
+    case 4: return (const void*)mh_sweep_lat<2, 4, reg_slots(4)>;
+    case 5: return (const void*)mh_sweep_lat<2, 5, reg_slots(5)>;
+    case 6: return (const void*)mh_sweep_lat<2, 6, reg_slots(6)>;
+    case 7: return (const void*)mh_sweep_lat<2, 7, reg_slots(7)>;
     default: return nullptr;
   }
 }

@@ -5,10 +5,10 @@
 namespace fmh {
 FMH_HIDDEN const void* k_lat_lg1b(int p) {
   switch (p) {
-    case 4: return (const void*)mh_sweep_lat<1, 4, 10, FMCMC_FAM_LOGISTIC>;
-    case 5: return (const void*)mh_sweep_lat<1, 5, 10, FMCMC_FAM_LOGISTIC>;
-    case 6: return (const void*)mh_sweep_lat<1, 6, 8, FMCMC_FAM_LOGISTIC>;
-    case 7: return (const void*)mh_sweep_lat<1, 7, 8, FMCMC_FAM_LOGISTIC>;
+    case 4: return (const void*)mh_sweep_lat<1, 4, reg_slots(4), FMCMC_FAM_LOGISTIC>;
+    case 5: return (const void*)mh_sweep_lat<1, 5, reg_slots(5), FMCMC_FAM_LOGISTIC>;
+    case 6: return (const void*)mh_sweep_lat<1, 6, reg_slots(6), FMCMC_FAM_LOGISTIC>;
+    case 7: return (const void*)mh_sweep_lat<1, 7, reg_slots(7), FMCMC_FAM_LOGISTIC>;
     default: return nullptr;
   }
 }

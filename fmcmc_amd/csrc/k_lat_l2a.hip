@@ -6,8 +6,8 @@ namespace fmh {
 FMH_HIDDEN const void* k_lat_lg2c();   // k_lat_l2c.hip: p = 3
 FMH_HIDDEN const void* k_lat_lg2a(int p) {
   switch (p) {
-    case 1: return (const void*)mh_sweep_lat<2, 1, 20, FMCMC_FAM_LOGISTIC>;
-    case 2: return (const void*)mh_sweep_lat<2, 2, 20, FMCMC_FAM_LOGISTIC>;
+    case 1: return (const void*)mh_sweep_lat<2, 1, reg_slots(1), FMCMC_FAM_LOGISTIC>;
+    case 2: return (const void*)mh_sweep_lat<2, 2, reg_slots(2), FMCMC_FAM_LOGISTIC>;
     case 3: return k_lat_lg2c();
     default: return nullptr;
   }

@@ -5,10 +5,10 @@
 namespace fmh {
 FMH_HIDDEN const void* k_lat_lg2b(int p) {
   switch (p) {
-    case 4: return (const void*)mh_sweep_lat<2, 4, 10, FMCMC_FAM_LOGISTIC>;
-    case 5: return (const void*)mh_sweep_lat<2, 5, 10, FMCMC_FAM_LOGISTIC>;
-    case 6: return (const void*)mh_sweep_lat<2, 6, 8, FMCMC_FAM_LOGISTIC>;
-    case 7: return (const void*)mh_sweep_lat<2, 7, 8, FMCMC_FAM_LOGISTIC>;
+    case 4: return (const void*)mh_sweep_lat<2, 4, reg_slots(4), FMCMC_FAM_LOGISTIC>;
+    case 5: return (const void*)mh_sweep_lat<2, 5, reg_slots(5), FMCMC_FAM_LOGISTIC>;
+    case 6: return (const void*)mh_sweep_lat<2, 6, reg_slots(6), FMCMC_FAM_LOGISTIC>;
+    case 7: return (const void*)mh_sweep_lat<2, 7, reg_slots(7), FMCMC_FAM_LOGISTIC>;
     default: return nullptr;
   }
 }

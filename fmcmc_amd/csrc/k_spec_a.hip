@@ -16,16 +16,16 @@ const void* k_spec(int p, int kind) {
   if (kind == FMCMC_KERNEL_NORMAL || kind == FMCMC_KERNEL_NORMAL_REFLECTIVE) return k_spec_normal(p, kind);
   if (kind == FMCMC_KERNEL_NMIRROR || kind == FMCMC_KERNEL_UMIRROR) return k_spec_mirror(p, kind);
   if (kind != FMCMC_KERNEL_ADAPT && kind != FMCMC_KERNEL_RAM) return nullptr;
-#define SPEC_AD(PV, OV) ((kind == 3) ? (const void*)mh_sweep_spec<PV, OV, 3> : (const void*)mh_sweep_spec<PV, OV, 4>)
+#define SPEC_AD(PV) ((kind == 3) ? (const void*)mh_sweep_spec<PV, reg_slots(PV), 3> : (const void*)mh_sweep_spec<PV, reg_slots(PV), 4>)
   switch (p) {
-    case 0: return SPEC_AD(0, 20);   // (no covariate: the iid Normal family)
-    case 1: return SPEC_AD(1, 20);
-    case 2: return SPEC_AD(2, 20);
-    case 3: return SPEC_AD(3, 20);
-    case 4: return SPEC_AD(4, 10);
-    case 5: return SPEC_AD(5, 10);
-    case 6: return SPEC_AD(6, 8);
-    case 7: return SPEC_AD(7, 8);
+    case 0: return SPEC_AD(0);   // (no covariate: the iid Normal family)
+    case 1: return SPEC_AD(1);
+    case 2: return SPEC_AD(2);
+    case 3: return SPEC_AD(3);
+    case 4: return SPEC_AD(4);
+    case 5: return SPEC_AD(5);
+    case 6: return SPEC_AD(6);
+    case 7: return SPEC_AD(7);
     default: return nullptr;
   }
 #undef SPEC_AD

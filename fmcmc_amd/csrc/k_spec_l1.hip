@@ -4,15 +4,15 @@
 
 namespace fmh {
 FMH_HIDDEN const void* k_spec_logit_n(int p, int kind) {
-#define SPEC_L(PV, OV) ((kind == 1) ? (const void*)mh_sweep_spec<PV, OV, 1, FMCMC_FAM_LOGISTIC> : (const void*)mh_sweep_spec<PV, OV, 2, FMCMC_FAM_LOGISTIC>)
+#define SPEC_L(PV) ((kind == 1) ? (const void*)mh_sweep_spec<PV, reg_slots(PV), 1, FMCMC_FAM_LOGISTIC> : (const void*)mh_sweep_spec<PV, reg_slots(PV), 2, FMCMC_FAM_LOGISTIC>)
   switch (p) {
-    case 1: return SPEC_L(1, 20);
-    case 2: return SPEC_L(2, 20);
-    case 3: return SPEC_L(3, 20);
-    case 4: return SPEC_L(4, 10);
-    case 5: return SPEC_L(5, 10);
-    case 6: return SPEC_L(6, 8);
-    case 7: return SPEC_L(7, 8);
+    case 1: return SPEC_L(1);
+    case 2: return SPEC_L(2);
+    case 3: return SPEC_L(3);
+    case 4: return SPEC_L(4);
+    case 5: return SPEC_L(5);
+    case 6: return SPEC_L(6);
+    case 7: return SPEC_L(7);
     default: return nullptr;
   }
 #undef SPEC_L

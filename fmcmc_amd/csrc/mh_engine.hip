@@ -1,5 +1,5 @@
-// mh_engine.hip — gfx950 (MI355X) many-chain Metropolis-Hastings engine: the C-ABI (include/fmcmc_amd.h), validation,
-// kernel selection and launches.  The sweep kernels are instantiated in the k_*.hip translation units (compiled in parallel,
+// mh_engine.hip — gfx950 (MI355X) many-chain Metropolis-Hastings engine: the C-ABI (include/fmcmc_amd.h), validation
+// and launches (the kernel selection, plan_route, is in mh_route.hpp).  The sweep kernels are instantiated in the k_*.hip translation units (compiled in parallel,
 // fmcmc_amd/build.py) and reached through the look-ups of mh_kernels.hpp; their source is in the headers:
 //   mh_common.hpp  shared device helpers      mh_streamed.hpp  general kernel (all families / kernels / schemes)
 //   mh_rng.hpp     RNG stream kernel          mh_mfma.hpp      fp64-MFMA kernel, owner waves (headline)
@@ -35,6 +35,7 @@
 #include "mh_wide2.hpp"
 #include "mh_mfma_ad.hpp"
 #include "mh_bigk.hpp"
+#include "mh_route.hpp"   // (kernel selection: plan_route)
 
 namespace {
 
@@ -200,16 +201,17 @@ __global__ void shard_build_mfma(const double* X, const double* y, long long n, 
   }
 }
 
+// the canonical stream of chains [chain_base, + nchains) x steps [step_base, + nsteps) into logu [C][rows], z [C][rows][kz]
+static void fill_rng(const fmcmc_run* run, long long step_base, long long nchains, long long nsteps, int kz, double df, double* ws, hipStream_t s) {
+  const size_t items = (size_t)nchains * (size_t)nsteps;
+  hipLaunchKernelGGL(rng_fill_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, (unsigned long long)run->seed, step_base,
+                     (long long)run->chain_base, nchains, nsteps, kz, df, ws, ws + items);
+}
+
 // accept counts of a continuation window (step windows, launch_sweep) added to the call's
 __global__ void add_counts_kernel(long long* total, const long long* part, long long n) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) total[i] += part[i];
-}
-
-size_t sweep_lds_bytes(int k, int kf, int kind, int CW, int tb, int kz, bool resident) {
-  size_t d = 5 * (size_t)k + (k / 2 + 1) + (size_t)NW * CW + 1 + (size_t)CW * tb * (kz + 1) + (size_t)CW * k +
-             (resident ? (size_t)CW * NT : 0) + (size_t)CW * chain_lds_doubles(k, kf, kind);
-  return d * sizeof(double);
 }
 
 }  // namespace
@@ -376,119 +378,6 @@ static SweepArgs chain_window(const SweepArgs& A, long long off, long long cnt, 
   return W;
 }
 
-// Observation-sharded evaluation (mh_common.hpp, eval_sharded): `nb` workgroups per launch must split the 512 canonical
-// lanes evenly (128 or 256 of them), be co-resident (cooperative launch) and hold their slice in SH_MAXO registers.
-// Returns the canonical lanes per workgroup (2 or 4), or 0 when the shape is not eligible or the cost model prefers the
-// chain-sharded kernel.  Cost model (us per step, fitted at k = 50): chain-sharded ~4 + X bytes / 65 GB/s (the per-CU L2
-// rate); sharded ~14 of hand-overs and fixed work + 0.0085 per column and walked observation slot (+ ~6 of barrier
-// imbalance under kernel_ram): n = 2500 loses (23.9 vs 19.1), n = 5000 wins (24.3 vs 30.1), C4 wins 2x.
-// Knob shard=1 (FMCMC_AMD_DEBUG) forces the sharded kernel for every eligible shape (tests), shard=0 disables it.
-// ---- diagnosis knobs: ONE environment variable, read once per call --------------------------------------------------------
-//   FMCMC_AMD_DEBUG="key=value,key=value"   (unset = product behaviour; nothing else in the environment is looked at)
-//   streamed=1   general streamed kernel for everything          cw=1|2|4|8  chains per workgroup of the streamed kernels
-//   pipe=0       no materialised-stream kernels (mfma / spec)      lat=0|1|2|3 latency form of mh_sweep_spec: off / chains per workgroup
-//   mfma=0       VALU evaluation instead of the fp64-MFMA kernels
-//   shard=0|1    wide models: never / always (when eligible) observation-sharded; unset: cost model
-//   shard_mfma=0 VALU form of the sharded slice product           wide2=0|1   never / always (when eligible) the dataflow form
-//   groups=4     four chain groups in the dataflow form (default two)       tiles=0     even N-tile shares of its evaluator waves
-//   window=N     step-window length of the stream-fed kernels (multiple of 32; default: ~256 MiB of stream per window)
-//   t10=0        the sharded slice product's third M-tile as a 16x16x4 tile even where 8 of its rows are padding
-//   shadow=0     logistic, observation-sharded: the normal / uniform kernels on the general kernel's form, not on mh_sweep_logit2
-//   speclogit=0  logistic family: not on the wave-specialised kernel (mh_sweep_spec<.., LOGISTIC>)
-//   specbnd=0    the bounded kernel_ram: not on the wave-specialised kernel (SpecSyncB)
-//   specmirror=0 the mirror kernels: not on the wave-specialised kernel
-//   tinymfma=0   the streamed MFMA forms (8 .. 15 covariates, mirror / adaptive kernels) only from 513 observations on
-//   specwide=0   kernel_adapt / kernel_ram with 8 .. 14 covariates on small data: not on the wave-specialised kernel
-//   specp0=0     models without a covariate (iid Normal): adaptive / mirror kernels not on the wave-specialised kernel
-//   turn=<t>     logit_shard's issue-priority turn (timing only): thousandths of the younger wave's passes it starts from, + 10000: and
-//                stays at, + 100000 x (lead in units of 256 cycles it is regulated towards); turn=0: no turn
-//   mode=<bits>  timing ablations and stamps (SweepArgs.debug)
-// The kernel a call ended up on is reported by fmcmc_last_kernel(); DESIGN.md section 5 has the shape -> kernel table.
-struct Knobs {
-  int streamed = -1, cw = -1, pipe = -1, lat = -1, mfma = -1, shard = -1, shard_mfma = -1, wide2 = -1, groups = -1, tiles = -1, t10 = -1, window = -1, mode = 0;
-  int shadow = -1, turn = -1, speclogit = -1, specbnd = -1, specmirror = -1, specp0 = -1, tinymfma = -1, specwide = -1;
-};
-static Knobs read_knobs() {
-  Knobs K;
-  const char* e = getenv("FMCMC_AMD_DEBUG");
-  if (!e) return K;
-  struct { const char* name; int* dst; } tab[] = {{"streamed", &K.streamed}, {"cw", &K.cw}, {"pipe", &K.pipe}, {"lat", &K.lat},
-      {"mfma", &K.mfma}, {"shard_mfma", &K.shard_mfma}, {"shard", &K.shard}, {"wide2", &K.wide2}, {"groups", &K.groups}, {"tiles", &K.tiles}, {"t10", &K.t10}, {"window", &K.window}, {"mode", &K.mode}, {"shadow", &K.shadow}, {"turn", &K.turn}, {"speclogit", &K.speclogit}, {"specbnd", &K.specbnd}, {"specmirror", &K.specmirror}, {"specp0", &K.specp0}, {"tinymfma", &K.tinymfma}, {"specwide", &K.specwide}};
-  while (*e) {
-    const char* eq = strchr(e, '=');
-    const char* end = strchr(e, ',');
-    if (!end) end = e + strlen(e);
-    if (eq && eq < end)
-      for (auto& t : tab)
-        if ((size_t)(eq - e) == strlen(t.name) && !strncmp(e, t.name, (size_t)(eq - e))) *t.dst = atoi(eq + 1);
-    e = (*end == ',') ? end + 1 : end;
-  }
-  return K;
-}
-static bool shard_mfma_enabled(const Knobs& K) { return K.shard_mfma != 0; }
-static int wide_sharded_lanes(const Knobs& K, const fmcmc_model* m, const fmcmc_kernel* kn, const fmcmc_run* run, int ram_bounded, int ncu, long long nb,
-                              int cw_now = 2 /* chains per workgroup the call would run with on the chain-sharded / general kernel */) {
-  if (K.shard == 0) return 0;
-  if (m->family != FMCMC_FAM_GAUSSIAN_LINREG || m->p < 16) return 0;
-  if (kn->kind != FMCMC_KERNEL_RAM && kn->kind != FMCMC_KERNEL_NORMAL && kn->kind != FMCMC_KERNEL_NORMAL_REFLECTIVE) return 0;
-  const int nslots = (int)((m->n + NT - 1) / NT);
-  const int lpw = (nb == 128 || nb == 256) ? (int)(NT / nb) : 0;
-  const long long per_launch = nb * 2;   // (upper bound of the chains of one launch: at most two per workgroup)
-  // A slice of more than 49 columns (15.5 KB) no longer stays in the scalar cache: 2.1x per walked slot, still ahead for the
-  // normal kernels (k = 64, n = 10k: 57 us per step against 78); kernel_ram stays chain-sharded there, its owner phase
-  // dominates at that width and runs slower in the sharded instantiation (121 against 108).
-  const bool cached = shard_mfma_enabled(K) || (size_t)m->p * SH_MAXO * sizeof(double) <= 15872;   // (the MFMA form keeps the slice in LDS)
-  // (a slice holds up to SH_MAXO = 40 observations in the scalar / register form, up to 4 SHM_T = 96 -- six M-tiles -- in LDS for the
-  //  matrix-core form: n <= 24,576 at 256 workgroups)
-  const bool mf_ok = shard_mfma_enabled(K) && m->p <= 4 * SHM_KBMAX;
-  const bool ok = lpw > 0 && !(kn->kind == FMCMC_KERNEL_RAM && (ram_bounded || !cached)) && lpw * nslots <= (mf_ok ? 4 * SHM_T : SH_MAXO) && nb <= ncu &&
-                  (long long)m->p * SH_MAXO * nb < (1ll << 28) && (long long)(m->p + 1) * (per_launch + SH_PAD) < (1ll << 31) &&
-                  run->nsteps < 30000000;   /* barrier epochs (2 per step) x workgroups per group stay below 2^32 */
-  if (!ok) return 0;
-  if (K.shard != 1) {
-    // us per step, refitted to tools/dispatch_audit.py (profiles/r04_dispatch_audit.md: p = 16 .. 60, n = 1e3 .. 1e4, 64 .. 2048
-    // chains): the chain-sharded kernel streams the data set per workgroup and pays kernel_ram's owner phase (~0.15 us per
-    // parameter) in the open; the sharded forms cost ~9 us of hand-overs plus a slice product that grows with the chains of a
-    // launch -- on the matrix cores p (0.08 + 0.00475 slice observations) per 512 chains -- and hide the RAM owners in the
-    // dataflow form (more than 256 chains), pay ~0.17 us per parameter in the sequential one
-    const bool ram = kn->kind == FMCMC_KERNEL_RAM;
-    // (with four / eight chains per workgroup -- more than 512 / 1024 chains -- the data stream is shared by more chains but a
-    //  step takes 1.3x / 2.4x as long (and the owners of a workgroup queue), and the workgroups run in rounds; the sharded sweep runs as consecutive launches)
-    const double rounds = (double)((run->nchains + (long long)cw_now * ncu - 1) / ((long long)cw_now * ncu));
-    const double launches = (double)((run->nchains + per_launch - 1) / per_launch);
-    const double est_chain = (4.0 + (double)m->n * (double)m->p * 8.0 / 65000.0 * (cw_now >= 8 ? 2.4 : (cw_now == 4 ? 1.3 : 1.0)) +
-                              (ram ? (cw_now <= 2 ? 0.12 : 0.075 * (double)cw_now) * (double)kn->k : 0.0)) * rounds;
-    const double frac = (double)(run->nchains < per_launch ? run->nchains : per_launch) / 512.0;
-    double est_shard;
-    if (shard_mfma_enabled(K) && m->p <= 4 * SHM_KBMAX) {
-      // (more than three M-tiles: the run-time K-block loop, +5 us; kernel_ram's owners are hidden by the dataflow form only -- more
-      //  than 256 chains, at most three M-tiles --, else ~0.17 us per parameter for few chains, ~0.3 in full launches)
-      const bool tall = lpw * nslots > SH_MAXO;
-      // (round 5: the dataflow form for 256 chains and fewer too -- two chains per workgroup, half of the workgroups without chains:
-      //  C4's shape at 256 / 128 / 64 chains 15.0 / 14.7 / 12.7 us per step against 20.6 / 18.0 / 17.1 on the sequential form)
-      const bool hidden = ram && !tall && !kn->constr && K.wide2 != 0 && (run->nchains > 256 || cw_now == 2);
-      // (refitted once more after the compile-time K-block counts of every width: ~10 of hand-overs, 0.4 + p (0.083 + 0.004 slice observations) per 512
-      //  chains at up to three M-tiles; the dataflow form's kernel_ram runs ~2 us UNDER the normal kernels' sequential form)
-      const bool tall_rt = tall && (m->p + 3) / 4 > 12;     // (tall slices beyond 12 K-blocks keep the run-time loop: ~5 us more)
-      est_shard = 10.2 + (tall_rt ? 5.0 : 0.0) + frac * ((tall ? 0.6 : 0.4) + (double)m->p * ((tall ? 0.08 : 0.083) + (tall ? 0.00475 : 0.004) * (double)(lpw * nslots))) +
-                  ((ram && !hidden) ? (run->nchains <= 256 ? 0.17 : 0.3) * (double)kn->k : 0.0);
-      if (hidden) {   // (what the dataflow form hides is at most a quarter of its slice product)
-        const double prod = frac * (0.4 + (double)m->p * (0.083 + 0.004 * (double)(lpw * nslots)));
-        est_shard -= (prod * 0.25 < 2.0 * frac) ? prod * 0.25 : 2.0 * frac;
-      }
-    }
-    else {
-      const double walked = (cached ? 1.0 : 2.1) * ((lpw * nslots <= SH_MAXO / 2) ? SH_MAXO / 2 : SH_MAXO);
-      est_shard = 14.0 + 0.0085 * (double)m->p * walked + (ram ? 6.0 : 0.0);
-    }
-    if (!(est_shard * launches < 0.95 * est_chain)) return 0;
-  }
-  return lpw;
-}
-static bool wide_sharded_pays(const Knobs& K, const fmcmc_model* m, const fmcmc_kernel* kn, const fmcmc_run* run, int ram_bounded, int ncu, long long nb, int cw_now) {
-  return wide_sharded_lanes(K, m, kn, run, ram_bounded, ncu, nb, cw_now) > 0;
-}
-
 // stream-ordered scratch that is released on EVERY way out of launch_sweep
 struct AsyncScratch {
   void* p = nullptr;
@@ -505,6 +394,42 @@ static hipError_t launch_k(const void* kfn, long long grid, int block, size_t ld
   }
   void* kargs[] = {(void*)&A};
   return hipLaunchKernel(kfn, dim3((unsigned)grid), dim3((unsigned)block), kargs, lds, stream);
+}
+
+// Can `nb` workgroups of kernel `kfn` with `lds` bytes of LDS be co-resident, i.e. may it run as ONE cooperative launch?
+// `what`: the A.debug & 256 diagnostic of a refusal (nullptr: none).  A refusal leaves no error behind.
+static bool coop_fits(const void* kfn, size_t lds, long long nb, int ncu, int dev, int debug, const char* what) {
+  int coop = 0, perCU = 0;
+  (void)hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev);
+  const hipError_t e = kfn ? hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipErrorInvalidDeviceFunction;
+  if (e != hipSuccess || !coop || hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kfn, NT, lds) != hipSuccess || (long long)perCU * ncu < nb) {
+    if (what && (debug & 256)) fprintf(stderr, "fmcmc_amd: %s not launched: err=%d coop=%d perCU=%d lds=%zu\n", what, (int)e, coop, perCU, lds);
+    (void)hipGetLastError();
+    return false;
+  }
+  return true;
+}
+
+// The chains of a call as consecutive cooperative launches of `nb` workgroups, `per` chains each (the observation-sharded forms:
+// the slices and tables serve every launch; the grid barrier words `bar` are cleared in front of each).
+enum CoopRun { COOP_OK, COOP_NOTHING_RAN, COOP_LATER_FAILED };
+static CoopRun coop_chain_windows(const void* kfn, long long nb, size_t lds, const SweepArgs& A, long long nchains, long long per, int kf,
+                                  unsigned* bar, size_t nbar, hipStream_t stream) {
+  hipError_t e = hipSuccess;
+  long long done = 0;
+  for (; done < nchains && e == hipSuccess; done += per) {
+    SweepArgs W = chain_window(A, done, (nchains - done < per) ? nchains - done : per, kf);
+    (void)hipMemsetAsync(bar, 0, sizeof(double) * nbar, stream);
+    void* kargs[] = {(void*)&W};
+    e = hipLaunchCooperativeKernel(kfn, dim3((unsigned)nb), dim3(NT), kargs, (unsigned int)lds, stream);
+  }
+  if (e == hipSuccess) return COOP_OK;
+  (void)hipGetLastError();
+  if (done <= per) return COOP_NOTHING_RAN;     // the runtime refused the first cooperative launch
+  // a LATER window failed: the chains of the earlier windows have run
+  set_err("HIP launch of chain window %lld failed (%s): the state of the first %lld chains is already advanced, the results of this call are invalid",
+          (long long)(done / per), hipGetErrorString(e), (long long)(done - per));
+  return COOP_LATER_FAILED;
 }
 
 // kernel->fixed etc. are DEVICE pointers here; kf and bounds info come via `kf`/`ram_bounded`.
@@ -593,367 +518,68 @@ static int launch_sweep(const fmcmc_model* m_in, const fmcmc_kernel* kn_in, cons
     }
     if (!arch_ok) { set_err("this library is built for gfx950 (MI355X); the current device is another architecture"); return FMCMC_ERR_DEVICE; }
   }
-  // more parameters than a wavefront has lanes: one workgroup per chain (mh_bigk.hpp); fmcmc_validate has refused what it lacks
-  if (kn->k > FMCMC_MAX_K_WAVE) {
-    const size_t blds = sizeof(double) * bigk_lds_doubles(kn->k, kf, kn->kind);
-    if (blds > 160 * 1024) { set_err("LDS budget exceeded (k=%d)", kn->k); return FMCMC_ERR_UNSUPPORTED; }
-    g_kernel = "big-k";
-    hipError_t eb = launch_k(fmh::k_bigk(), run->nchains, NT, blds, stream, A);
-    if (eb == hipSuccess) eb = hipGetLastError();
-    if (eb != hipSuccess) { set_err("HIP launch failed: %s", hipGetErrorString(eb)); return FMCMC_ERR_DEVICE; }
+  Route R = plan_route(m, kn, run, kf, ram_bounded, A.kz, A.ldS, ncu, K);
+  if (R.lds_exceeded) { set_err("LDS budget exceeded (k=%d)", kn->k); return FMCMC_ERR_UNSUPPORTED; }
+  hipError_t e = hipSuccess;
+  if (R.form == Form::BIGK) {
+    g_kernel = kernel_name(R);
+    e = launch_k(R.kfn, run->nchains, NT, R.lds, stream, A);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) { set_err("HIP launch failed: %s", hipGetErrorString(e)); return FMCMC_ERR_DEVICE; }
     return FMCMC_OK;
   }
-  // register-resident variant: Gaussian linreg whose data fits the VGPR budget of 512 threads
-  int res_p = -1, res_opt = 0;
-  const bool force = K.streamed == 1;
-  if (!force && m->family == FMCMC_FAM_GAUSSIAN_LINREG && !mirror) {
-    static const int variants[][2] = {{1, 4}, {3, 20}};
-    for (auto& v : variants)
-      if (m->p == v[0] && m->n > (long long)NT * (v[1] - RES_MASKED) && m->n <= (long long)NT * v[1]) {
-        res_p = v[0];
-        res_opt = v[1];
-      }
-  }
-  const bool resident = res_p >= 0;
-  // chains per workgroup: fill the CUs first, then stack chains on a workgroup
-  int cw = 1;
-  bool wide_switched = false;   // two chains per workgroup BECAUSE the observation-sharded sweep pays: the decision stands below
-  if (resident) {
-    cw = 4;
-  } else {
-    while (cw < NW && (long long)cw * ncu < run->nchains) cw <<= 1;
-    if (K.cw == 1 || K.cw == 2 || K.cw == 4 || K.cw == 8) cw = K.cw;   // diagnosis: chains per workgroup of the streamed kernel
-    // wide linear models with more than two chains per CU: two chains per workgroup, so that the sweep can run as
-    // consecutive observation-sharded launches of 2 x CUs chains each (below) when that pays off
-    // (measured at k = 50, n = 10k: 1024 chains 63.8 us per step instead of 71.6 with four chains per workgroup; at 2048
-    //  chains the general kernel with eight chains per workgroup is level, 123 vs 128, and keeps the sweep)
-    else if (cw >= 4 && wide_sharded_pays(K, m, kn, run, ram_bounded, ncu, (long long)ncu, cw)) { cw = 2; wide_switched = true; }
-    // kernel_ram on a wide model with ONE chain per CU or fewer: two per workgroup all the same, so that the sweep is eligible for the
-    // dataflow form (mh_wide2.hpp: two chain groups half a step out of phase; workgroups without chains evaluate like the others)
-    else if (cw == 1 && ncu == 256 && K.wide2 != 0 && m->family == FMCMC_FAM_GAUSSIAN_LINREG && m->p >= 16 && m->p <= 4 * SHM_KBMAX &&
-             kn->kind == FMCMC_KERNEL_RAM && !ram_bounded && !kn->constr && shard_mfma_enabled(K) &&
-             2 * ((m->n + NT - 1) / NT) <= SH_MAXO && run->nchains >= 2 &&
-             !((run->nchains + 1) / 2 == 128 && 4 * ((m->n + NT - 1) / NT) <= SH_MAXO) &&      /* (exactly 128 workgroups of four lanes: the sequential form's own shape) */
-             (m->n + NT - 1) / NT >= 6 &&      /* (short data: the chain-sharded sweep is ahead -- p = 30, n = 1000, 64 chains: 9.7 against 11.6 us) */
-             [&]() {                           /* (the dataflow form's LDS: two owners' factor and partial sums + the slice block -- k = 62 does not fit) */
-               const int nsl = (int)((m->n + NT - 1) / NT), spg = (nsl + 1) / 2, nmt_ = (spg + 3) / 4;
-               const int mblk_ = shm_hdr(nmt_) + nmt_ * ((m->p + 3) / 4) * 64;
-               return nmt_ >= 1 && nmt_ <= 3 && sizeof(double) * wide2_lds_doubles(kn->k, kf, kn->kind, A.kz, mblk_) <= 160 * 1024;
-             }() &&
-             wide_sharded_pays(K, m, kn, run, ram_bounded, ncu, (long long)ncu, 2)) { cw = 2; wide_switched = true; }
-    // the logistic-only instantiations (table in LDS; observation-sharded form) exist for up to four chains per workgroup: more
-    // than 1024 chains run as more workgroups / consecutive sharded launches there, not on the all-family kernel with eight
-    // chains per workgroup (tools/dispatch_audit.py: 4096 chains, n = 1e5, p = 5 took 1244 us per step, 4.7x four launches)
-    else if (cw > 4 && m->family == FMCMC_FAM_LOGISTIC && kn->kind >= FMCMC_KERNEL_NORMAL && kn->kind <= FMCMC_KERNEL_RAM) cw = 4;
-  }
-  int tb = 32;
-  while (tb > 1 && sweep_lds_bytes(kn->k, kf, kn->kind, cw, tb, A.kz, resident) > 60 * 1024) tb >>= 1;
-  while (cw > 1 && !resident && sweep_lds_bytes(kn->k, kf, kn->kind, cw, tb, A.kz, resident) > 150 * 1024) cw >>= 1;
-  A.tb = tb;
-  size_t lds = sweep_lds_bytes(kn->k, kf, kn->kind, cw, tb, A.kz, resident);
-  if (lds > 160 * 1024) { set_err("LDS budget exceeded (k=%d)", kn->k); return FMCMC_ERR_UNSUPPORTED; }
-  const long long nblk = (run->nchains + cw - 1) / cw;
-  hipError_t e = hipSuccess;
-  // software-pipelined fast path: normal kernels, joint scheme, k <= 16, linreg data in registers
-  const bool nopipe = K.pipe == 0;
-  int pipe_opt = 0, mfma_ng = 0, mfma_ad = 0, mfma_ext = 0, spec_cw = 4;
-  // kernel_adapt(freq = 2 .. 8, bw = 0) on the register owner of mh_sweep_spec (round 5: the last `freq` rows of a chain in an LDS ring;
-  // tools/option_audit.py had it on the general kernel at 14.7 us per step where freq = 1 takes 3.3): no fixed parameter, k <= 8, and a
-  // call that is ONE step window (the ring does not travel between windows)
-  bool adapt_ring = false;
-  if (kn->kind == FMCMC_KERNEL_ADAPT && kn->bw == 0 && kn->freq >= 2 && kn->freq <= SPEC_FREQMAX && kf == kn->k && A.kz == kn->k && kn->k <= SPEC_KA) {
-    const long long per_step = (long long)run->nchains * (A.kz + 1) * 8;
-    long long win = ((256ll << 20) / (per_step > 0 ? per_step : 1)) & ~31ll;
-    if (win < 32) win = 32;
-    if (K.window >= 32) win = (long long)K.window & ~31ll;
-    adapt_ring = run->nsteps <= win + 1 || run->rng_mode != FMCMC_RNG_PHILOX;
-  }
-  bool lat_normal = false;   // the normal / uniform kernels in the latency form (mh_sweep_lat)   // mfma_ext: resident slots of the EXT form (0: everything resident)
-  // single-parameter schemes of the normal / uniform kernels ("ordered", an explicit sequence, "random"): on mh_sweep_lat's candidate
-  // wave (round 5: they ran on the general kernel, 2.9 us per step at the README's size where the joint scheme takes 0.63), one to FOUR
-  // chains per workgroup; "random" draws its plan in the kernel and hands it back (a caller-fed plan stays general)
-  const bool single_lat = (kn->kind == FMCMC_KERNEL_NORMAL || kn->kind == FMCMC_KERNEL_NORMAL_REFLECTIVE) && kn->scheme != FMCMC_SCHEME_JOINT &&
-                          K.lat != 0 && (kn->scheme != FMCMC_SCHEME_RANDOM || run->rng_mode == FMCMC_RNG_PHILOX);
-  AsyncScratch mfs_guard;
-  if (!force && !nopipe && m->family == FMCMC_FAM_GAUSSIAN_LINREG &&
-      (kn->kind == FMCMC_KERNEL_NORMAL || kn->kind == FMCMC_KERNEL_NORMAL_REFLECTIVE ||
-       ((kn->kind == FMCMC_KERNEL_ADAPT && (!adapt_hist || adapt_ring)) || (kn->kind == FMCMC_KERNEL_RAM && !kn->constr)) ||
-       (mirror && kn->scheme == FMCMC_SCHEME_JOINT && kf == kn->k && K.mfma != 0)) &&
-      (kn->scheme == FMCMC_SCHEME_JOINT || kn->kind == FMCMC_KERNEL_ADAPT || kn->kind == FMCMC_KERNEL_RAM || single_lat) && kn->k <= PIPE_KMAX &&
-      // Sizes (round 3: rows and variates are addressed as 64-bit chain base + 32-bit offset, and a long call runs as step
-      // windows with a bounded stream, so a call no longer leaves these kernels at 4 GiB of samples or stream).  What is
-      // left: offsets inside one chain's blocks are 32 bits.
-      (unsigned long long)run->nsteps * (unsigned long long)A.kz * 8ull < (1ull << 32) && run->nsteps < (1ll << 30) &&
-      (unsigned long long)kn->k * (unsigned long long)A.ldS * 8ull < (1ull << 32) &&      /* 32-bit offsets inside ONE chain's block */
-      /* (round 5: kernel_adapt / kernel_ram run in step windows too -- their step-dependent rules read the CALL's step, see below;
-          what still materialises its whole stream, kept below 8 GiB: host-fed variates are the caller's, and the mirror kernels) */
-      (!mirror || (unsigned long long)run->nchains * (unsigned long long)run->nsteps * (unsigned long long)(A.kz + 1) * 8ull < (8ull << 30))) {
-    // the wave-specialised kernel (mh_sweep_spec): x of a compute lane in VGPRs, the slot count an (even) run-time choice among
-    // its compute loops: any n <= 10240 at p <= 3, n <= 5120 at p = 4, 5, n <= 4096 at p = 6, 7 (OPTMAX P doubles per lane)
-    {
-      const long long nsl = (m->n + NT - 1) / NT, nsl2 = (nsl + 1) & ~1ll;
-      // (round 5: 8 .. 14 covariates on up to 2048 observations -- four slots of P doubles per compute lane, the register owner at the
-      //  compile-time width k <= 16; knob specwide=0: the streamed MFMA evaluation with the owners in LDS, as before)
-      const int optmax = (m->p >= 0 && m->p <= 3) ? 20 : (m->p <= 5 ? 10 : (m->p <= 7 ? 8 : ((m->p <= 14 && K.specwide != 0) ? 4 : 0)));
-      // (the bounded kernel_ram decides on f of the REFLECTED proposal: a second evaluation in the steps in which the reflection
-      //  moved something -- the barrier-synchronised owners of mh_sweep_mfma_ad ask for it between barriers, this kernel's register
-      //  owners through a second evaluation slot per step (round 5, SpecSyncB: k <= 8, no fixed parameter; knob specbnd=0: off))
-      const bool bnd_ok = K.specbnd != 0 && kf == kn->k && (kn->k <= SPEC_KA || (kn->k == 9 && m->p == 7)) && A.kz == kn->k && !kn->constr;   // (k = 9: the compile-time owner of p = 7)
-      // (round 5: no covariate at all -- the iid Normal family, intercept + sigma -- too: the compute lanes then hold no x)
-      if ((m->p >= 1 || (m->p == 0 && m->intercept && K.specp0 != 0)) && nsl2 <= optmax && (kn->kind == FMCMC_KERNEL_ADAPT || kn->kind == FMCMC_KERNEL_RAM) && (!(kn->kind == FMCMC_KERNEL_RAM && ram_bounded) || bnd_ok)) pipe_opt = (int)nsl2;
-      // (normal / uniform kernels run on the MFMA kernel; knob mfma=0 keeps them here for the two shapes they were tuned at)
-      if (m->p == 3 && nsl == 20 && kn->kind < FMCMC_KERNEL_ADAPT && kn->scheme == FMCMC_SCHEME_JOINT) pipe_opt = 20;
-      if (m->p == 1 && nsl == 2 && kn->kind < FMCMC_KERNEL_ADAPT && kn->scheme == FMCMC_SCHEME_JOINT) pipe_opt = 2;
-    }
-    // (round 5: the streamed forms from ONE observation on -- up to 512 the one resident slot is the last, nothing is streamed; models with
-    //  8 .. 15 covariates on small data ran on the general kernel, 2.4 - 5 / 9 - 26 us per step.  Knob tinymfma=0: from 513 on, as before)
-    const long long nt_min = (K.tinymfma != 0) ? 0 : (long long)NT;
-    // fp64-MFMA evaluation: general in n and p up to what 80 operand registers per lane hold (normal / uniform kernels)
-    if (K.mfma != 0 && kn->kind <= FMCMC_KERNEL_NORMAL_REFLECTIVE && kn->scheme == FMCMC_SCHEME_JOINT) {
-      if (m->p <= 3 && m->n <= (long long)NT * 20) mfma_ng = 1;
-      else if (m->p <= 7 && m->n <= (long long)NT * 10) mfma_ng = 2;
-      // beyond the operand registers: 16 (8) slots resident, the rest streamed from an operand-order copy every step (EXT)
-      else if (m->p <= 3 && m->n < (1ll << 29)) { mfma_ng = 1; mfma_ext = 16; }
-      else if (m->p <= 7 && m->n < (1ll << 29)) { mfma_ng = 2; mfma_ext = 8; }
-      // 8 .. 15 covariates (k <= 16): three / four operand groups per observation slot, four / two slots resident (one for short
-      // data), the rest streamed -- tools/dispatch_audit.py found these models on the general kernel at 0.10 of the fp64 peak where
-      // p = 7 runs at 0.44
-      else if (m->p <= 11 && m->n > nt_min && m->n < (1ll << 29)) { mfma_ng = 3; mfma_ext = (m->n > (long long)NT * 4) ? 4 : 1; }
-      else if (m->p <= 15 && m->n > nt_min && m->n < (1ll << 29)) { mfma_ng = 4; mfma_ext = (m->n > (long long)NT * 2) ? 2 : 1; }
-      // (the wave-specialised VALU kernel, which overlaps owners and evaluation, used to win at its small shape
-      //  (p = 1, n ~ 1000); since the instruction diet of the owner phase the MFMA kernel is 1.2-1.35x ahead there too:
-      //  tools/bench_small.py.  Knob mfma=0 still selects it.)
-    }
-    // kernel_adapt / kernel_ram beyond mh_sweep_spec's registers: the same streamed MFMA evaluation with the register-row
-    // adaptive owners between barriers (mh_mfma_ad.hpp); no fixed parameter, k <= 8
-    // (k = 9 -- seven covariates, intercept and sigma -- as a compile-time row count: tools/dispatch_audit.py found these calls on
-    //  the general kernel, 7x the time of the normal kernels at the same shape)
-    // (mfma_ad == 2: the owners with their matrices in LDS -- 8 .. 15 covariates, or a fixed parameter; not the bounded kernel_ram)
-    if (K.mfma != 0 && !pipe_opt && !adapt_hist && (kn->kind == FMCMC_KERNEL_ADAPT || kn->kind == FMCMC_KERNEL_RAM) && m->p >= 0 && m->p <= 15 && m->n < (1ll << 29)) {   // (p = 0: iid Normal)
-      // (round 5: the run-time-width register owner takes fixed parameters -- free ones first, the fixed ones as passengers)
-      const bool reg_owner = m->p <= 7 && A.kz == kf && kf >= 1 && ((kf == kn->k && (kn->k <= SPEC_KA || kn->k == 9)) || (kf < kn->k && kn->k <= SPEC_KA));
-      const int ng = (m->p <= 3) ? 1 : (m->p <= 7 ? 2 : (m->p <= 11 ? 3 : 4));
-      const int nsr = (ng == 1) ? MfmaAdShape<1>::NSR : (ng == 2 ? MfmaAdShape<2>::NSR : MfmaAdShape<3>::NSR);
-      if (m->n > (long long)NT * nsr && (reg_owner || !(kn->kind == FMCMC_KERNEL_RAM && ram_bounded))) {   // (its resident slots are all full)
-        mfma_ad = reg_owner ? 1 : 2;
-        mfma_ng = ng;
-        mfma_ext = nsr;
-      } else if (m->n > nt_min && ((reg_owner && ((kn->kind == FMCMC_KERNEL_RAM && ram_bounded) || m->p == 0)) || (!reg_owner && !(kn->kind == FMCMC_KERNEL_RAM && ram_bounded) && run->nchains <= 2048 /* (beyond: level with the general kernel at eight chains per workgroup) */))) {
-        // short data (one slot resident, the rest streamed) for what the wave-specialised kernel does not take: the bounded
-        // kernel_ram, 8 .. 15 covariates, no covariate at all (iid Normal)
-        mfma_ad = reg_owner ? 1 : 2;
-        mfma_ng = ng;
-        mfma_ext = 1;
-      }
-    }
-    if (kn->kind == FMCMC_KERNEL_RAM && ram_bounded && !mfma_ad && !pipe_opt) mfma_ng = 0;   // (general kernel)
-    // the mirror kernels (joint scheme, no fixed parameter): their owner between the barriers of the same streamed MFMA evaluation
-    if (mirror) {
-      const int ng = (m->p <= 3) ? 1 : (m->p <= 7 ? 2 : (m->p <= 11 ? 3 : 4));
-      const int nsr = (ng == 1) ? MfmaAdShape<1>::NSR : (ng == 2 ? MfmaAdShape<2>::NSR : MfmaAdShape<3>::NSR);
-      pipe_opt = 0; mfma_ng = 0;
-      // (round 5: within mh_sweep_spec's registers their owner runs there -- beside the evaluation instead of between barriers, and in
-      //  the latency forms; up to 512 observations they ran on the general kernel.  Knob specmirror=0: off)
-      const long long nsl2 = (((m->n + NT - 1) / NT) + 1) & ~1ll;
-      if (K.specmirror != 0 && (m->p >= 1 || (m->p == 0 && m->intercept && K.specp0 != 0)) && (m->p <= 7 || (m->p <= 14 && K.specwide != 0)) && nsl2 <= fmh::k_spec_optmax(m->p, kn->kind) && fmh::k_spec(m->p, kn->kind)) pipe_opt = (int)nsl2;
-      else
-      if (m->p <= 15 && m->n > nt_min && m->n < (1ll << 29)) { mfma_ad = 3; mfma_ng = ng; mfma_ext = (m->n > (long long)NT * nsr) ? nsr : 1; }
-    }
-    // ---- the LATENCY form (round 5): fewer than four chains per compute unit.  The reference scales a FIXED number of chains
-    // over its workers (R/mcmc.R:536-641), and a sharded call leaves every GPU nchains / G of them: with four chains per
-    // workgroup a step of C2's shape costs the same 2 us at 64 chains and at 1024.  Here the wave-specialised kernel runs one,
-    // two or three chains per workgroup -- all eight compute waves on the chain(s) there are (an evaluation of n = 10,000 is
-    // 0.33 us of one CU's fp64 issue), no owner queued behind the evaluation of other chains -- for every shape its compute
-    // lanes hold in registers: kernel_adapt / kernel_ram on mh_sweep_spec (its owners no longer queue behind the evaluation of
-    // other chains), the normal / uniform kernels on mh_sweep_lat (mh_lat.hpp: chain state replicated in every wave, ONE barrier
-    // per step).  Same canonical lanes and tree: the bits do not depend on the form.  Knob lat=0: off; lat=1|2|3: forced.
-    // (8 .. 15 covariates on up to 2048 observations, round 5: mh_sweep_lat<KIND, P, 4> -- the joint scheme with ONE chain per compute unit
-    //  (1.2 us per step on the streamed MFMA form at any chain count), the single-parameter schemes up to four (general kernel before))
-    const long long nsl2w = (((m->n + NT - 1) / NT) + 1) & ~1ll, per_cuw = (run->nchains + ncu - 1) / ncu;
-    const bool wide_lat = K.lat != 0 && K.specwide != 0 && !mirror && m->p >= 8 && m->p <= 15 && kn->k <= PIPE_KMAX && nsl2w <= 4 &&
-                          kn->kind <= FMCMC_KERNEL_NORMAL_REFLECTIVE && kn->kind >= FMCMC_KERNEL_NORMAL && kf >= 1 && fmh::k_lat(m->p, kn->kind) != nullptr;
-    if (wide_lat && kn->scheme == FMCMC_SCHEME_JOINT && (per_cuw <= 1 || (K.lat >= 1 && K.lat <= 3))) {
-      pipe_opt = (int)nsl2w; mfma_ng = 0; mfma_ext = 0; lat_normal = true;
-      spec_cw = (K.lat >= 1 && K.lat <= 3) ? K.lat : 1;
-    } else
-    if (single_lat && !mirror) {
-      const long long per_cu = (run->nchains + ncu - 1) / ncu, nsl2 = (((m->n + NT - 1) / NT) + 1) & ~1ll;
-      if (per_cu <= 4 && m->p >= 0 && (m->p <= 7 ? nsl2 <= fmh::k_spec_optmax(m->p, kn->kind) : wide_lat) && fmh::k_lat(m->p, kn->kind)) {
-        pipe_opt = (int)nsl2; mfma_ng = 0; lat_normal = true;
-        spec_cw = (K.lat >= 1 && K.lat <= 3) ? K.lat : (int)per_cu;
-      }
-    } else
-    if (K.lat != 0 && (!mirror || pipe_opt) && (pipe_opt || (mfma_ng && !mfma_ext && !mfma_ad))) {
-      const long long per_cu = (run->nchains + ncu - 1) / ncu;
-      // kernel_adapt / kernel_ram (mh_sweep_spec) gain up to 25 % with one chain per workgroup, 18 % with two, 6 % with three at
-      // n = 10,000 and are level at small n -- their step is the owner's dependent chain --: one to three, always.  The normal
-      // kernels by a cost model (us per step, fitted to tools/bench_lat_grid.sh and `tools/dispatch_audit.py --only=few`,
-      // profiles/r05_dispatch_audit_few.md): mh_sweep_lat costs ~0.45 us of fold, barrier and decision plus, per chain of the
-      // workgroup, its evaluation (n (p + 2) fp64 instructions at ~4.7 cycles over four SIMDs; shorter lanes of p >= 4 run
-      // at a lower rate) or -- short data -- its coefficient broadcast and tree; the MFMA kernel's four chains cost ~0.8 us
-      // + 0.06 us per operand group and observation slot.  n = 10,000, p = 3: 1.03 | 1.62 | 2.15 us with 1 | 2 | 3 chains
-      // against 2.0; p = 1: three chains still win (1.54 against 2.07); p = 7, n = 1000: two lose (1.22 against 1.13).
-      int lcw_auto = 4;
-      if (per_cu <= 3) {
-        if (kn->kind <= FMCMC_KERNEL_NORMAL_REFLECTIVE) {
-          const double w = (double)m->n * (double)(m->p + 2), rate = (m->p <= 3) ? 9.2e-6 : 1.25e-5;
-          const double per_chain = (0.10 + rate * w > 0.18 + 0.025 * (double)m->p) ? 0.10 + rate * w : 0.18 + 0.025 * (double)m->p;
-          const double t_lat = 0.45 + (double)per_cu * per_chain;
-          const double ns = (double)((m->n + NT - 1) / NT), ng = (m->p <= 3) ? 1.0 : 2.0;
-          const double t_floor = 0.98 + 0.10 * (ng - 1.0);
-          const double t_mfma = (0.80 + 0.06 * ng * ns > t_floor) ? 0.80 + 0.06 * ng * ns : t_floor;
-          if (t_lat < t_mfma) lcw_auto = (int)per_cu;
-        } else {
-          lcw_auto = (int)per_cu;
-        }
-      }
-      const int lcw = (K.lat >= 1 && K.lat <= 3) ? K.lat : lcw_auto;
-      const long long nsl2 = (((m->n + NT - 1) / NT) + 1) & ~1ll;
-      // (p = 0 -- the iid Normal family -- included: the compute lanes then hold no x)
-      if (lcw < 4 && nsl2 <= fmh::k_spec_optmax(m->p, kn->kind)) {
-        if (kn->kind <= FMCMC_KERNEL_NORMAL_REFLECTIVE) { pipe_opt = (int)nsl2; mfma_ng = 0; lat_normal = true; }
-        if (pipe_opt && !mfma_ng) spec_cw = lcw;
-      }
-    }
-  }
-  // ---- the logistic family on the wave-specialised kernel (round 5; mh_spec.hpp, FAM = LOGISTIC): data in the compute lanes'
-  // registers, g table in LDS, the register owners.  The workflow vignette's own model (mcmc::logit: 100 observations, k = 5) ran
-  // on the general kernel at 2.6 / 5.9 us per step (kernel_normal / kernel_adapt).  Knob speclogit=0: off.
-  bool spec_logit = false;
-  // (a fixed parameter under the normal / uniform kernels: the latency form's candidate wave handles it, the owners of mh_sweep_spec do not)
-  const bool lg_lat_fixed = kn->kind <= FMCMC_KERNEL_NORMAL_REFLECTIVE && kn->kind >= FMCMC_KERNEL_NORMAL && kn->scheme == FMCMC_SCHEME_JOINT &&
-                            kf != kn->k && K.lat != 0 && K.speclogit != 2;
-  // (8 .. 15 covariates, k <= 16, up to 2048 observations, the normal / uniform kernels: the latency form only -- four slots of P doubles
-  //  per lane; they ran on the general kernel, 3 - 4.5 us per step at n = 200)
-  const bool lg_lat_wide = m->p >= 8 && m->p <= 15 && kn->k <= PIPE_KMAX && kn->kind <= FMCMC_KERNEL_NORMAL_REFLECTIVE && kn->kind >= FMCMC_KERNEL_NORMAL &&
-                           K.lat != 0 && K.speclogit != 2 && kf >= 1 && (kn->scheme == FMCMC_SCHEME_JOINT || single_lat);
-  // (and under kernel_adapt / kernel_ram -- unbounded, stride 1, no fixed parameter --: mh_sweep_spec<P, 4, KIND, LOGISTIC> with the register
-  //  owner at the compile-time width k <= 16; general kernel: 6 - 14 us per step at n = 200.  Knob specwide=0: off)
-  const bool lg_spec_wide = m->p >= 8 && m->p <= 15 && kn->k <= PIPE_KMAX && K.specwide != 0 &&
-                            ((kn->kind == FMCMC_KERNEL_ADAPT && !adapt_hist) || (kn->kind == FMCMC_KERNEL_RAM && !ram_bounded && !kn->constr));
-  if (!force && !nopipe && K.speclogit != 0 && K.shard < 0 && m->family == FMCMC_FAM_LOGISTIC && !mirror && m->p >= 1 && (m->p <= 7 || lg_lat_wide || lg_spec_wide) &&
-      kn->k == m->p + (m->intercept ? 1 : 0) && ((kf == kn->k && A.kz == kn->k) || single_lat || (lg_lat_fixed && kf >= 1)) &&
-      (((kn->kind == FMCMC_KERNEL_NORMAL || kn->kind == FMCMC_KERNEL_NORMAL_REFLECTIVE) && (kn->scheme == FMCMC_SCHEME_JOINT || single_lat)) ||
-       (kn->kind == FMCMC_KERNEL_ADAPT && (!adapt_hist || adapt_ring)) || (kn->kind == FMCMC_KERNEL_RAM && !kn->constr && (!ram_bounded || K.specbnd != 0))) &&
-      (unsigned long long)run->nsteps * (unsigned long long)A.kz * 8ull < (1ull << 32) && run->nsteps < (1ll << 28) &&
-      (unsigned long long)kn->k * (unsigned long long)A.ldS * 8ull < (1ull << 32)) {
-    const long long nsl2 = (((m->n + NT - 1) / NT) + 1) & ~1ll;
-    const long long per_cu = (run->nchains + ncu - 1) / ncu;
-    if ((kn->scheme != FMCMC_SCHEME_JOINT || lg_lat_fixed || lg_lat_wide) && kn->kind <= FMCMC_KERNEL_NORMAL_REFLECTIVE) {
-      // single-parameter schemes: the latency form's candidate wave, one to four chains per workgroup (as for the linear model above)
-      if (per_cu <= 4 && nsl2 <= (lg_lat_wide ? 4 : (lg_lat_fixed && fmh::k_spec_optmax(m->p, kn->kind) > 12 ? 12 : fmh::k_spec_optmax(m->p, kn->kind))) && fmh::k_lat_logit(m->p, kn->kind)) {   // (never beyond the kernel's own slot count: the randomised soak's case 1566)
-        pipe_opt = (int)nsl2; spec_logit = true; lat_normal = true;
-        spec_cw = (K.lat >= 1 && K.lat <= 3) ? K.lat : (int)per_cu;
-      }
-    } else
-    if (nsl2 <= fmh::k_spec_optmax(m->p, kn->kind) && fmh::k_spec_logit(m->p, kn->kind)) {
-      pipe_opt = (int)nsl2;
-      spec_logit = true;
-      spec_cw = (K.lat >= 1 && K.lat <= 3) ? K.lat : ((K.lat != 0 && per_cu <= 3) ? (int)per_cu : 4);
-      // the normal / uniform kernels with fewer than four chains per CU: the latency form (mh_sweep_lat<.., LOGISTIC>: replicated decision)
-      // (measured, tools/bench_small_logit.py and the pair of forms at 256 / 512 / 768 chains: the replicated decision wins up to ~3,000
-      //  observations at any count -- 0.85 / 1.18 / 1.59 us against 1.25 / 1.34 / 1.78 at n = 1000 -- and up to ~6,000 with one chain
-      //  per workgroup, 1.66 against 2.15 at n = 5000; beyond, the lookups' LDS time is the step and the owners' overlap pays:
-      //  n = 10,000: 6.4 against 4.8 at 512 chains.  Knob speclogit=2: never.)
-      if (spec_cw < 4 && K.speclogit != 2 && kn->kind <= FMCMC_KERNEL_NORMAL_REFLECTIVE && fmh::k_lat_logit(m->p, kn->kind) &&
-          nsl2 <= (spec_cw == 1 ? 12 : 6)) lat_normal = true;
-    }
-  }
-  // (a launch with a slot count its instantiation does not hold would run no loop and hand back zeros -- round 5's soak found one such
-  //  route --: whatever the rules above decided, a count beyond the kernel's own goes to the general kernels)
-  if (pipe_opt && !mfma_ng) {
-    const int own = (m->p <= 3) ? 20 : (m->p <= 5 ? 10 : (m->p <= 7 ? 8 : 4));
-    if (pipe_opt > own || (pipe_opt & 1)) {
-      if (A.debug) fprintf(stderr, "fmcmc_amd: slot count %d beyond the register kernels' %d at p = %d: general kernel\n", pipe_opt, own, m->p);
-      pipe_opt = 0; lat_normal = false; spec_logit = false; spec_cw = 4;
-    }
-  }
-  A.spec_opt = pipe_opt;
-  A.spec_cw = spec_cw;
+  A.tb = R.tb;
+  const double fill_df = (kn->kind == FMCMC_KERNEL_RAM) ? A.ram_df : (A.variate == 1 ? -1.0 : 0.0);   // (rng_fill_kernel: t / U(0,1) / normal)
+  A.spec_opt = R.pipe_opt;
+  A.spec_cw = R.spec_cw;
   A.nsteps_call = run->nsteps;
-  // ---- the LONG-DATA form (mh_common.hpp, shard_long): few chains on long data.  Up to four chains are one workgroup of the
-  // chain-sharded kernels, i.e. ONE compute unit walks the whole data set per step (n = 1e5, p = 3: 34 us per step, 255 CUs idle);
-  // here all 256 workgroups evaluate their 1/256 of the observations for every chain and the canonical lane sums cross the chip as
-  // in the other observation-sharded forms.  try_long(kernel, its LDS bytes without the term block, what the call costs otherwise)
-  // launches it when the cost model -- or knob shard=1 -- says so; us per step, fitted on `tools/dispatch_audit.py --only=long`
-  // (profiles/r04_dispatch_audit.md): ~8 us of hand-overs, the walk of a lane's slots (1.6e-5 us per observation; sums of the
-  // logistic terms 1.0e-5) once per group of chains whose terms fit the LDS, and per chain its terms and its share of the exchange.
+  // the long-data form first, where the plan has it: a refused cooperative launch leaves the planned form
   bool launched_long = false;
-  auto try_long = [&](const void* kfn, size_t lds_base, double est_now, bool logistic) -> int {
-    if (force || K.shard == 0 || cw != 1 || ncu != 256 || run->nchains > 64 || m->n < 8 * NT || m->n >= (1ll << 31) || run->nsteps >= 30000000 ||
-        (kn->kind == FMCMC_KERNEL_RAM && ram_bounded) || kn->kind < FMCMC_KERNEL_NORMAL || kn->kind > FMCMC_KERNEL_RAM) return FMCMC_OK;
-    const int nslots = (int)((m->n + NT - 1) / NT), nobs = 2 * nslots;
-    const long long room = ((long long)150 * 1024 - (long long)lds_base) / 8 - 2;
-    const long long lrow = 2ll * shard_long_row(nslots) + SHL_BS;     // LDS doubles per chain of a group
-    long long lcg = room / lrow;
-    if (lcg > run->nchains) lcg = run->nchains;
-    if (lcg < 1) return FMCMC_OK;
-    const double pn = (double)m->n;
-    const double groups = (double)((run->nchains + lcg - 1) / lcg);
-    const double est_long = 8.3 + groups * (logistic ? 1.0e-5 : 1.6e-5) * pn + (logistic ? 2.0e-6 : 0.5e-6) * pn * (double)(m->p + 1) +
-                            (double)run->nchains * (0.17 + 0.028 * (double)m->p + (logistic ? 3.0e-6 : 1.2e-6) * pn) +
-                            (kn->kind >= FMCMC_KERNEL_ADAPT ? 3.5 : 0.0);
-    if (!(K.shard == 1 || est_long < 0.9 * est_now)) return FMCMC_OK;
-    const size_t llds = lds_base + sizeof(double) * (size_t)(lcg * lrow + 2);
-    int coop = 0, perCU = 0;
-    (void)hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev);
-    hipError_t el = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)llds);
-    if (el != hipSuccess || !coop || hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kfn, NT, llds) != hipSuccess || perCU < 1) return FMCMC_OK;
+  if (R.kfn_long && coop_fits(R.kfn_long, R.lds_long, 256, ncu, dev, K.mode, nullptr)) {
     double* shw = nullptr;
+    const int nobs = 2 * R.nslots;
     const size_t nxs = (size_t)256 * (m->p + 1) * nobs, nth = ((size_t)kn->k * (run->nchains + SH_PAD) + 7) & ~(size_t)7,
                  npt = (size_t)(NT + SH_PAD) * run->nchains, nbar = 32 * 20 / 2;
     hipError_t ea = hipMallocAsync((void**)&shw, sizeof(double) * (nxs + nth + npt + nbar), stream);
     if (ea != hipSuccess) { set_err("hipMallocAsync(sharded evaluation) failed: %s", hipGetErrorString(ea)); return FMCMC_ERR_DEVICE; }
     shw_guard.p = shw; shw_guard.s = stream;
     double* thw = shw; double* ptw = thw + nth; unsigned* bar = (unsigned*)(ptw + npt); double* xs = ptw + npt + nbar;
-    hipLaunchKernelGGL(long_build_slices, dim3(256), dim3(256), 0, stream, m->X, m->y, (long long)m->n, m->p, nslots, xs);
-    (void)hipMemsetAsync(bar, 0, sizeof(double) * nbar, stream);
+    hipLaunchKernelGGL(long_build_slices, dim3(256), dim3(256), 0, stream, m->X, m->y, (long long)m->n, m->p, R.nslots, xs);
     SweepArgs W = A;
-    W.shard = 2; W.sh_nslots = nslots; W.sh_xs = xs; W.sh_ys = nullptr; W.sh_th = thw; W.sh_part = ptw; W.sh_bar = bar;
-    W.sh_long = 1; W.sh_lcg = (int)lcg; W.sh_mblk = (int)(lcg * lrow);
-    void* kargs[] = {(void*)&W};
-    hipError_t ec = hipLaunchCooperativeKernel(kfn, dim3(256), dim3(NT), kargs, (unsigned int)llds, stream);
-    if (ec == hipSuccess) { launched_long = true; g_kernel = "long-sharded"; }
-    else {                            // the runtime refused the cooperative launch: nothing ran, take the usual kernels
-      (void)hipGetLastError();
-      (void)hipFreeAsync(shw, stream);   // (the paths below put their own block into shw_guard)
+    W.shard = 2; W.sh_nslots = R.nslots; W.sh_xs = xs; W.sh_ys = nullptr; W.sh_th = thw; W.sh_part = ptw; W.sh_bar = bar;
+    W.sh_long = 1; W.sh_lcg = (int)R.lcg; W.sh_mblk = (int)(R.lcg * R.lrow);
+    // (all chains in one launch: at most 64)
+    if (coop_chain_windows(R.kfn_long, 256, R.lds_long, W, run->nchains, run->nchains, kf, bar, nbar, stream) == COOP_OK) {
+      launched_long = true;
+      R.form = Form::LONG;
+    } else {                            // the runtime refused the cooperative launch: nothing ran, take the planned form
+      (void)hipFreeAsync(shw, stream);   // (the forms below put their own block into shw_guard)
       shw_guard.p = nullptr;
     }
-    return FMCMC_OK;
-  };
-  // (wide linear models, p >= 16: where the matrix-core slices end -- 96 observations per workgroup, n = 24,576 -- the chain-sharded
-  //  kernel is what is left: 4 + n p 8 / 65000 us per step)
-  if (m->family == FMCMC_FAM_GAUSSIAN_LINREG && (m->p <= 15 || (m->p <= 62 && m->n > (long long)NT * 2 * SHM_T))) {
-    const double pn = (double)m->n;
-    const double now_rate = (m->p <= 3) ? (pn <= 2e5 ? 3.3e-4 : 5.1e-4) : (m->p <= 7 ? 4.9e-4 /* (round 5 audit: n = 2e4, p = 7, one chain: 9.75 us on the streamed MFMA kernel, the long-data form 10.6) */ : (m->p <= 11 ? 8.5e-4 : 1.17e-3));
-    const double est_now = (m->p >= 16) ? 4.0 + pn * (double)m->p * 8.0 / 65000.0
-                         : (m->n <= (long long)NT * (m->p <= 3 ? 20 : (m->p <= 7 ? 10 : 0)) ? 2.2 : now_rate * pn) + (kn->kind >= FMCMC_KERNEL_ADAPT ? 2.0 : 0.0);
-    const void* kfn = fmh::k_wide(1, 2, kn->kind);       // (the long-data form: one chain per workgroup, every proposal kernel)
-    const int rcl = try_long(kfn, lds, est_now, false);
-    if (rcl != FMCMC_OK) return rcl;
   }
   // the operand-order copy of the observation slots beyond the registers (EXT / adaptive MFMA forms): 4 ng doubles per streamed
   // observation -- for p = 1 several times the size of X.  When the device cannot give that memory the call still runs: on
-  // the general streamed kernel, which needs none
-  if (!launched_long && mfma_ng && mfma_ext) {
-    const int ns_all = (int)((m->n + NT - 1) / NT), next = ns_all - mfma_ext;
+  // the chain-sharded form beneath (for these shapes the resident or the general kernel), which needs none
+  AsyncScratch mfs_guard;
+  if (!launched_long && R.mfma_ng && R.mfma_ext) {
+    const int next = R.nslots - R.mfma_ext;
     double* mfs = nullptr;
-    const size_t nd = (size_t)NW * (next > 0 ? next : 1) * mfma_ng * 64 * 4;   // (everything resident: one slot of stand-in, read and never used)
+    const size_t nd = (size_t)NW * (next > 0 ? next : 1) * R.mfma_ng * 64 * 4;   // (everything resident: one slot of stand-in, read and never used)
     if (hipMallocAsync((void**)&mfs, sizeof(double) * nd, stream) != hipSuccess) {
       (void)hipGetLastError();
-      mfma_ng = 0; mfma_ext = 0; mfma_ad = 0; pipe_opt = 0; lat_normal = false;
+      R.form = R.base; R.kfn = R.kfn_base;
+      R.mfma_ng = 0; R.mfma_ext = 0; R.mfma_ad = 0; R.pipe_opt = 0;
     } else {
       mfs_guard.p = mfs; mfs_guard.s = stream;
-      if (next > 0) hipLaunchKernelGGL(mfma_build_stream, dim3(512), dim3(256), 0, stream, m->X, m->y, (long long)m->n, m->p, mfma_ng, mfma_ext, next, mfs);
+      if (next > 0) hipLaunchKernelGGL(mfma_build_stream, dim3(512), dim3(256), 0, stream, m->X, m->y, (long long)m->n, m->p, R.mfma_ng, R.mfma_ext, next, mfs);
       else (void)hipMemsetAsync(mfs, 0, sizeof(double) * nd, stream);
       A.mf_stream = mfs; A.mf_next = next > 0 ? next : 0;
     }
   }
   if (launched_long) {
   } else
-  if (pipe_opt || mfma_ng) {
+  if (stream_fed(R.form)) {
     double* ws = nullptr;
-    const double fill_df = (kn->kind == FMCMC_KERNEL_RAM) ? A.ram_df : (A.variate == 1 ? -1.0 : 0.0);
     // Step windows: the normal / uniform kernels with the library's own stream.  Window 0 is an ordinary launch of the call's
     // first n0 steps; every later window is a launch of w + 1 steps whose step 1 re-evaluates the state the window starts
     // from (bit for bit the f0 it replaces) and whose steps 2 .. w + 1 are the call's next w steps (SweepArgs.win_cont).
@@ -967,16 +593,8 @@ static int launch_sweep(const fmcmc_model* m_in, const fmcmc_kernel* kn_in, cons
     // depends on the step -- `i > 2`, the mean of this call's rows before the first adaptation, eta(i, k), `i %% freq` -- reads
     // the call's step (SweepArgs.step_off + the window's), the running sum of the rows travels from window to window
     // (SweepArgs.win_sum), everything else (Sigma / S, the running mean, abs_iter) is the state the windows hand on anyway.
-    const bool windowed = A.rng_mode == FMCMC_RNG_PHILOX && !mirror &&
-                          (kn->kind <= FMCMC_KERNEL_NORMAL_REFLECTIVE || kn->kind == FMCMC_KERNEL_ADAPT || kn->kind == FMCMC_KERNEL_RAM);
-    long long win = run->nsteps;
-    if (windowed) {
-      const long long per_step = (long long)run->nchains * (A.kz + 1) * 8;
-      win = ((256ll << 20) / (per_step > 0 ? per_step : 1)) & ~31ll;
-      if (win < 32) win = 32;     // (the kernels take windows from 32 steps; a 512-step floor let the buffer grow with nchains without bound)
-      if (K.window >= 32) win = (long long)K.window & ~31ll;      // (diagnosis / tests: a window length)
-    }
-    const long long n0 = (windowed && run->nsteps > win + 1) ? win + 1 : run->nsteps;   // steps of window 0
+    const long long win = R.win ? R.win : run->nsteps;
+    const long long n0 = (R.win && run->nsteps > win + 1) ? win + 1 : run->nsteps;   // steps of window 0
     if (A.rng_mode == FMCMC_RNG_PHILOX) {
       // materialise the canonical stream: [C][rows] log u, then [C][rows][kz] z; rows = a window's steps (or the whole call)
       const long long rows = (n0 < run->nsteps) ? win + 1 : run->nsteps;
@@ -986,176 +604,80 @@ static int launch_sweep(const fmcmc_model* m_in, const fmcmc_kernel* kn_in, cons
       ws_guard.p = ws; ws_guard.s = stream;
     }
     auto fill_stream = [&](SweepArgs& W, long long step_base_eff) {   // the stream of launch W, rows = W.nsteps
-      const size_t items = (size_t)W.nchains * (size_t)W.nsteps;
-      hipLaunchKernelGGL(rng_fill_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream,
-                         (unsigned long long)run->seed, step_base_eff, (long long)run->chain_base,
-                         (long long)W.nchains, (long long)W.nsteps, A.kz, fill_df, ws, ws + items);
-      W.fed_logu = ws;
-      W.fed_z = ws + items;
-      W.rng_mode = FMCMC_RNG_FED;
+      fill_rng(run, step_base_eff, W.nchains, W.nsteps, A.kz, fill_df, ws, stream);
+      W.fed_logu = ws; W.fed_z = ws + (size_t)W.nchains * (size_t)W.nsteps; W.rng_mode = FMCMC_RNG_FED;
     };
-    auto launch_fast = [&](const SweepArgs& A) {   // (shadows the call's arguments: one launch of the call, or one step window of it)
-      const long long pblk = (A.nchains + 3) / 4;
-      if (mfma_ng) {
-        // fp64-MFMA evaluation (mh_mfma.hpp), four chains per workgroup
-        const int ns = (int)((m->n + NT - 1) / NT);   // observation slots of 512
-        const int kv = (kn->kind == FMCMC_KERNEL_NORMAL) ? 1 : 2;
-        // (offsets from the buffer bases stay 32 bits -- the cheaper form, see mh_sweep_mfma's BIG -- while the samples of all chains
-        //  and the stream of this launch stay below 4 GiB)
-        const bool big = (unsigned long long)A.nchains * kn->k * (unsigned long long)A.ldS * 8ull >= (1ull << 32) ||
-                         (unsigned long long)A.nchains * (unsigned long long)A.nsteps * (unsigned long long)A.kz * 8ull >= (1ull << 32);
-        if (mfma_ad) {
-          // kernel_adapt / kernel_ram / mirror kernels: the adaptive owners between the barriers of the streamed evaluation (mh_mfma_ad.hpp)
-          g_kernel = "mfma-adaptive";
-          const bool ad_short = mfma_ext == 1;    // (short data: one resident slot)
-          const int kx = (mfma_ad == 3) ? -2 : (mfma_ad == 2) ? -1 : ((kf != kn->k) ? 0 : (mfma_ng == 1 ? (kn->k == 5 ? 5 : 0) : (kn->k == 9 ? 9 : 0)));
-          const bool bnd = mfma_ad == 1 && kn->kind == FMCMC_KERNEL_RAM && ram_bounded;
-          e = launch_k(fmh::k_mfma_ad(kn->kind, mfma_ng, kx, bnd ? 1 : 0, ad_short ? 1 : 0), pblk, NT, mfma_ad_lds_bytes(mfma_ad == 2), stream, A);
-        } else if (mfma_ext) {
-          g_kernel = "mfma-streamed";
-          e = launch_k(fmh::k_mfma_ext(kv, mfma_ng, mfma_ext, big ? 1 : 0), pblk, NT, mfma_lds_bytes(), stream, A);
-        } else {
-          g_kernel = "mfma";
-          e = launch_k(fmh::k_mfma(kv, mfma_ng, ns, big ? 1 : 0), pblk, NT, mfma_lds_bytes(), stream, A);
-        }
-      } else if (lat_normal) {
-        // the latency form of the normal / uniform kernels (mh_lat.hpp): A.spec_cw = 1 .. 3 chains per workgroup
-        if (spec_logit) {
-          g_kernel = A.spec_cw == 1 ? "lat-logit1" : A.spec_cw == 2 ? "lat-logit2" : A.spec_cw == 3 ? "lat-logit3" : "lat-logit4";
-          e = launch_k(fmh::k_lat_logit(m->p, kn->kind), (A.nchains + A.spec_cw - 1) / A.spec_cw, NT, fmh::k_lat_logit_lds(), stream, A);
-        } else {
-        g_kernel = A.spec_cw == 1 ? "lat1" : A.spec_cw == 2 ? "lat2" : A.spec_cw == 3 ? "lat3" : "lat4";
-        e = launch_k(fmh::k_lat(m->p, kn->kind), (A.nchains + A.spec_cw - 1) / A.spec_cw, NT, lat_lds_bytes(), stream, A);
-        }
-      } else {
-        // the wave-specialised kernel (mh_spec.hpp): A.spec_cw chains per workgroup
-        const long long sblk = (A.nchains + A.spec_cw - 1) / A.spec_cw;
-        if (spec_logit) {
-          g_kernel = A.spec_cw == 1 ? "spec-logit-lat1" : A.spec_cw == 2 ? "spec-logit-lat2" : A.spec_cw == 3 ? "spec-logit-lat3" : "spec-logit";
-          e = launch_k((kn->kind == FMCMC_KERNEL_ADAPT && kn->freq > 1) ? fmh::k_spec_ring(m->p, 1) : fmh::k_spec_logit(m->p, kn->kind), sblk, SPEC_NT, fmh::k_spec_logit_lds(kn->kind >= FMCMC_KERNEL_ADAPT ? 1 : 0), stream, A);
-        } else {
-        g_kernel = A.spec_cw == 1 ? "spec-lat1" : A.spec_cw == 2 ? "spec-lat2" : A.spec_cw == 3 ? "spec-lat3" : "spec";
-        e = launch_k((kn->kind == FMCMC_KERNEL_ADAPT && kn->freq > 1 && adapt_ring) ? fmh::k_spec_ring(m->p, 0) : fmh::k_spec(m->p, kn->kind), sblk, SPEC_NT, spec_lds_bytes(pipe_opt, kn->kind == FMCMC_KERNEL_ADAPT || kn->kind == FMCMC_KERNEL_RAM), stream, A);
-        }
+    auto launch_fast = [&](const SweepArgs& W) {   // one launch of the call, or one step window of it
+      const long long pblk = (W.nchains + 3) / 4, sblk = (W.nchains + R.spec_cw - 1) / R.spec_cw;
+      // (MFMA forms: offsets from the buffer bases stay 32 bits -- the cheaper form, see mh_sweep_mfma's BIG -- while the samples of
+      //  all chains and the stream of this launch stay below 4 GiB)
+      const bool big = (unsigned long long)W.nchains * kn->k * (unsigned long long)W.ldS * 8ull >= (1ull << 32) ||
+                       (unsigned long long)W.nchains * (unsigned long long)W.nsteps * (unsigned long long)W.kz * 8ull >= (1ull << 32);
+      const int kv = (kn->kind == FMCMC_KERNEL_NORMAL) ? 1 : 2;
+      switch (R.form) {
+        case Form::MFMA_ADAPTIVE: e = launch_k(R.kfn, pblk, NT, mfma_ad_lds_bytes(R.mfma_ad == 2), stream, W); break;
+        case Form::MFMA_STREAMED: e = launch_k(fmh::k_mfma_ext(kv, R.mfma_ng, R.mfma_ext, big ? 1 : 0), pblk, NT, mfma_lds_bytes(), stream, W); break;
+        case Form::MFMA: e = launch_k(fmh::k_mfma(kv, R.mfma_ng, R.nslots, big ? 1 : 0), pblk, NT, mfma_lds_bytes(), stream, W); break;
+        // the latency form (mh_lat.hpp): 1 .. 3 chains per workgroup
+        case Form::LAT_LOGIT: e = launch_k(R.kfn, sblk, NT, fmh::k_lat_logit_lds(), stream, W); break;
+        case Form::LAT: e = launch_k(R.kfn, sblk, NT, lat_lds_bytes(), stream, W); break;
+        // the wave-specialised kernel (mh_spec.hpp): spec_cw chains per workgroup
+        case Form::SPEC_LOGIT: e = launch_k(R.kfn, sblk, SPEC_NT, fmh::k_spec_logit_lds(kn->kind >= FMCMC_KERNEL_ADAPT ? 1 : 0), stream, W); break;
+        default: e = launch_k(R.kfn, sblk, SPEC_NT, spec_lds_bytes(R.pipe_opt, kn->kind == FMCMC_KERNEL_ADAPT || kn->kind == FMCMC_KERNEL_RAM), stream, W); break;
       }
-    };   // launch_fast
-    {
-      SweepArgs W = A;
-      W.nsteps = n0;
-      W.bits_stride = (run->nsteps + 31) >> 5;
-      const long long kept_all = A.S;
-      long long* wcount = nullptr;                                          // accept counts of one continuation window
-      double* wsum = nullptr;
-      if (n0 < run->nsteps) {   // (window counts, and behind them kernel_adapt's running sums of the call's rows)
-        const size_t nsum = (kn->kind == FMCMC_KERNEL_ADAPT) ? (size_t)run->nchains * (size_t)kf : 0;
-        e = hipMallocAsync((void**)&wcount, sizeof(long long) * (size_t)run->nchains + sizeof(double) * nsum, stream);
-        if (e != hipSuccess) { set_err("hipMallocAsync(window counts) failed: %s", hipGetErrorString(e)); return FMCMC_ERR_DEVICE; }
-        wc_guard.p = wcount; wc_guard.s = stream;
-        if (nsum) wsum = reinterpret_cast<double*>(wcount + run->nchains);
-      }
+    };
+    SweepArgs W = A;
+    W.nsteps = n0;
+    W.bits_stride = (run->nsteps + 31) >> 5;
+    const long long kept_all = A.S;
+    long long* wcount = nullptr;                                          // accept counts of one continuation window
+    double* wsum = nullptr;
+    if (n0 < run->nsteps) {   // (window counts, and behind them kernel_adapt's running sums of the call's rows)
+      const size_t nsum = (kn->kind == FMCMC_KERNEL_ADAPT) ? (size_t)run->nchains * (size_t)kf : 0;
+      e = hipMallocAsync((void**)&wcount, sizeof(long long) * (size_t)run->nchains + sizeof(double) * nsum, stream);
+      if (e != hipSuccess) { set_err("hipMallocAsync(window counts) failed: %s", hipGetErrorString(e)); return FMCMC_ERR_DEVICE; }
+      wc_guard.p = wcount; wc_guard.s = stream;
+      if (nsum) wsum = reinterpret_cast<double*>(wcount + run->nchains);
+    }
+    W.win_sum = wsum;
+    if (A.rng_mode == FMCMC_RNG_PHILOX) fill_stream(W, (long long)run->step_base);
+    launch_fast(W);
+    for (long long s0 = n0; s0 < run->nsteps && e == hipSuccess; ) {     // continuation windows
+      const long long w = (run->nsteps - s0 < win) ? run->nsteps - s0 : win;
+      const long long rows_done = fmcmc_kept_rows(s0, run->burnin, run->thin);
+      W = A;
+      W.nsteps = w + 1;
+      W.win_cont = 1;
+      W.fresh = 0;                 // (kernel state: what the window before wrote back)
       W.win_sum = wsum;
-      if (A.rng_mode == FMCMC_RNG_PHILOX) fill_stream(W, (long long)run->step_base);
+      W.step_off = s0 - 1;
+      W.burnin = (run->burnin - s0 + 1 > 1) ? run->burnin - s0 + 1 : 1;
+      W.thin_ctr0 = (s0 > run->burnin) ? (int)((s0 - run->burnin) % run->thin) : 0;
+      W.bits_stride = (run->nsteps + 31) >> 5;
+      W.samples = A.samples + rows_done;
+      if (A.logpost) W.logpost = A.logpost + rows_done;
+      if (A.draws) W.draws = A.draws + rows_done;
+      if (A.accept_bits) W.accept_bits = A.accept_bits + ((s0 - 1) >> 5);
+      W.S = kept_all - rows_done;
+      W.accept_count = wcount;
+      fill_stream(W, (long long)run->step_base + s0 - 1);
       launch_fast(W);
-      for (long long s0 = n0; s0 < run->nsteps && e == hipSuccess; ) {     // continuation windows
-        const long long w = (run->nsteps - s0 < win) ? run->nsteps - s0 : win;
-        const long long rows_done = fmcmc_kept_rows(s0, run->burnin, run->thin);
-        W = A;
-        W.nsteps = w + 1;
-        W.win_cont = 1;
-        W.fresh = 0;                 // (kernel state: what the window before wrote back)
-        W.win_sum = wsum;
-        W.step_off = s0 - 1;
-        W.burnin = (run->burnin - s0 + 1 > 1) ? run->burnin - s0 + 1 : 1;
-        W.thin_ctr0 = (s0 > run->burnin) ? (int)((s0 - run->burnin) % run->thin) : 0;
-        W.bits_stride = (run->nsteps + 31) >> 5;
-        W.samples = A.samples + rows_done;
-        if (A.logpost) W.logpost = A.logpost + rows_done;
-        if (A.draws) W.draws = A.draws + rows_done;
-        if (A.accept_bits) W.accept_bits = A.accept_bits + ((s0 - 1) >> 5);
-        W.S = kept_all - rows_done;
-        W.accept_count = wcount;
-        fill_stream(W, (long long)run->step_base + s0 - 1);
-        launch_fast(W);
-        hipLaunchKernelGGL(add_counts_kernel, dim3((unsigned)((run->nchains + 255) / 256)), dim3(256), 0, stream, A.accept_count, wcount,
-                           (long long)run->nchains);
-        s0 += w;
-      }
+      hipLaunchKernelGGL(add_counts_kernel, dim3((unsigned)((run->nchains + 255) / 256)), dim3(256), 0, stream, A.accept_count, wcount,
+                         (long long)run->nchains);
+      s0 += w;
     }
   } else
-  if (resident) { g_kernel = "resident"; e = launch_k(fmh::k_resident(res_p, kn->kind), nblk, NT, lds, stream, A); }
-  else if (!force && m->family == FMCMC_FAM_LOGISTIC && cw <= 4 && lds + sizeof(double) * (LG_LDS_DOUBLES + LG_LDS_TAIL) <= 160 * 1024 &&
-           (kn->kind == FMCMC_KERNEL_NORMAL || kn->kind == FMCMC_KERNEL_NORMAL_REFLECTIVE || kn->kind == FMCMC_KERNEL_ADAPT ||
-            kn->kind == FMCMC_KERNEL_RAM)) {
-    // (round 4: kernel_adapt / kernel_ram too -- the workflow vignette's own model is a logistic regression under kernel_adapt;
-    //  tools/option_audit.py found them on the all-family kernel at 3.9x the time per step of the normal kernels)
-    // logistic-only instantiations: the g table in LDS; up to 28 / cw - 1 covariates their number is a compile-time constant
-    // of the evaluation loop and the coefficients of the CW chains live in SGPRs (mh_common.hpp, logit_partials), beyond that
-    // the run-time loop (logit_partials_any) -- still with the table in LDS, which is what the all-family kernel lacks
-    g_kernel = "streamed-logistic";
-    const int lkv = kn->kind;   // 1 .. 4
-    lds += sizeof(double) * (LG_LDS_DOUBLES + LG_LDS_TAIL);   // the table staged behind the chain blocks (16-byte aligned), logit_shard's control words
-    // Observation-sharded form (mh_common.hpp, logit_shard): 256 workgroups of two canonical lanes each evaluate ALL chains
-    // of the launch, up to 256 x cw of them; more chains run as consecutive launches.  Cost model (us per step): the
-    // chain-sharded loop costs ~(p + 12) instructions per observation and chain, 4.5 + n cw (p + 12) 1.35e-5 with the
-    // coefficients in SGPRs (p <= 28 / cw - 1; 2.8e-5 on the run-time loop beyond that) -- its lookups scatter over the table:
-    // LDS-bound -- but never less than one pass of the workgroup over the data set at ~90 GB/s; the sharded form ~10 us of
-    // hand-overs + n (p + 10.3) 1.78e-5 per 512 chains of a launch.  Knob shard=1 forces it for every eligible shape (tests),
-    // shard=0 disables it.
-    bool lshard = false;
-    // few chains: the long-data form (shard_long<LOGISTIC>) -- the sharded loop below keeps ONE thread per chain busy with its whole
-    // slice (n = 1e5, 1 .. 64 chains: 31 .. 36 us per step), the chain-sharded one walks the data set in one workgroup
-    if (m->p >= 1 && m->p <= 16) {
-      const double w1 = (double)m->n * (double)(m->p + 12), stream1 = (double)m->n * (double)(m->p + 1) * 8.0 / 9.0e4;
-      const double chain1 = 4.5 + ((w1 * 1.35e-5 > stream1) ? w1 * 1.35e-5 : stream1);
-      const double shard1 = 10.3 + 1.78e-5 * (double)m->n * ((double)m->p + 10.3);
-      const void* kfl = fmh::k_logit(1, 1, lkv);
-      const int rcl = try_long(kfl, lds, (chain1 < shard1 || m->p > 16) ? chain1 : shard1, true);
-      if (rcl != FMCMC_OK) return rcl;
-    }
-    if (launched_long) {
-    } else {
-    const long long nb_launch = 256;
-    const long long ch_launch = (nblk > nb_launch) ? nb_launch * cw : (long long)run->nchains;
-    const int nslots = (int)((m->n + NT - 1) / NT);
-    // (not the bounded kernel_ram: its second evaluation of a step runs only in the workgroups where a proposal was reflected
-    //  -- the grid-wide evaluation needs every workgroup in every hand-over)
-    if (K.shard != 0 && m->p >= 1 && m->p <= 16 && ncu == 256 && m->n >= 2 * NT && m->n < (1ll << 28) &&
-        !(kn->kind == FMCMC_KERNEL_RAM && ram_bounded)) {
-      // (refitted to tools/dispatch_audit.py, profiles/r04_dispatch_audit.md: n = 2e3 .. 1e5, p = 2, 5, 8, 64 .. 4096 chains)
-      const double w = (double)m->n * (double)(m->p + 12);
-      const double stream_us = (double)m->n * ((double)m->p + 0.5) * 8.0 / 9.0e4;      // a workgroup's pass over the data set (X only: the term does not read y) at ~90 GB/s
-      const double loop_us = w * cw * ((m->p <= 28 / cw - 1) ? 1.35e-5 : 2.8e-5);
-      const double rounds = (double)((nblk + ncu - 1) / ncu), launches = (double)((run->nchains + ch_launch - 1) / ch_launch);
-      const double est_chain = (4.5 + (loop_us > stream_us ? loop_us : stream_us)) * rounds;
-      const double passes = (double)((ch_launch + NT - 1) / NT);                       // chains per thread of the sharded loop
-      // (round 5: the issue-priority turns of logit_shard, and for the normal / uniform kernels mh_sweep_logit2 -- four chains per
-      //  workgroup whatever cw says --: 5 .. 15 % off every row of profiles/r05_dispatch_audit_logistic.md)
-      const bool shadow_ok = K.shadow != 0 && kn->kind <= FMCMC_KERNEL_NORMAL_REFLECTIVE && kn->scheme == FMCMC_SCHEME_JOINT && kf == kn->k;
-      const double launches_s = shadow_ok ? (double)((run->nchains + 4 * nb_launch - 1) / (4 * nb_launch)) : launches;
-      const double passes_s = shadow_ok ? (double)(((run->nchains < 4 * nb_launch ? run->nchains : 4 * nb_launch) + NT - 1) / NT) : passes;
-      const double est_shard = ((shadow_ok ? 8.5 : 10.0) + 2.2 * (passes_s - 1.0) +
-                                (shadow_ok ? 1.62e-5 : 1.72e-5) * (double)m->n * ((double)m->p + 10.3) * passes_s) * launches_s;
-      lshard = K.shard == 1 || est_shard < 0.95 * est_chain;
-    }
-    const void* kfn = nullptr;
-    if (lshard) kfn = fmh::k_logit(cw <= 2 ? cw : 4, 1, lkv);
-    if (lshard) {
-      int coop = 0, perCU = 0;
-      (void)hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev);
-      e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess || !coop ||
-          hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kfn, NT, lds) != hipSuccess || (long long)perCU * ncu < nb_launch) {
-        if (A.debug & 256) fprintf(stderr, "fmcmc_amd: sharded logistic evaluation not launched: err=%d coop=%d perCU=%d lds=%zu\n", (int)e, coop, perCU, lds);
-        lshard = false;
-      }
-      e = hipSuccess;
-    }
-    if (lshard) {
+  if (R.base == Form::LOGISTIC) {
+    // the logistic-only instantiations: observation-sharded (logistic-sharded / -shadow) where the plan has it and the launch is
+    // resident, else chain-sharded
+    if (R.form == Form::LOGISTIC_SHARDED && !coop_fits(R.kfn, R.lds_run, R.nb_launch, ncu, dev, K.mode, "sharded logistic evaluation")) R.form = Form::LOGISTIC;
+    if (R.form == Form::LOGISTIC_SHARDED) {
       double* shw = nullptr;
+      const long long nb_launch = R.nb_launch;
+      const int nslots = R.nslots;
       // (+ 8 observations behind the last slice: the pipelined loop's scalar loads run up to three passes ahead without a clamp)
       // (mh_sweep_logit2 holds four chains per workgroup whatever cw says: tables for the larger of the two launch widths)
-      const long long ch_shadow = (run->nchains < 4 * nb_launch) ? (long long)run->nchains : 4 * nb_launch;
-      const long long ch_tab = (ch_shadow > ch_launch) ? ch_shadow : ch_launch;
+      const long long ch_tab = (R.ch_shadow > R.ch_launch) ? R.ch_shadow : R.ch_launch;
       const size_t nxs = (size_t)nb_launch * nslots * 2 * m->p + 8 * (size_t)m->p, nth = ((size_t)kn->k * (ch_tab + SH_PAD) + 7) & ~(size_t)7,
                    npt = (size_t)(NT + SH_PAD) * ch_tab, nbar = 32 * 20 / 2;
       e = hipMallocAsync((void**)&shw, sizeof(double) * (nxs + nth + npt + nbar), stream);
@@ -1166,7 +688,6 @@ static int launch_sweep(const fmcmc_model* m_in, const fmcmc_kernel* kn_in, cons
       hipLaunchKernelGGL(logit_build_slices, dim3((unsigned)nb_launch), dim3(256), 0, stream, m->X, (long long)m->n, m->p, nslots, xs);
       A.shard = 2; A.sh_nslots = nslots; A.sh_xs = xs; A.sh_ys = nullptr; A.sh_th = thw; A.sh_part = ptw; A.sh_bar = bar;
       A.sh_t10 = (K.turn >= 0) ? K.turn : 1600700;   // (logit_shard's issue-priority turn: starts at 0.700 of the younger wave's passes, regulated towards a lead of 16 x 256 cycles; knob turn)
-      g_kernel = "logistic-sharded";
       // Round 5: the canonical stream of the call materialised in front of the sweep (rng_fill_kernel), where it fits 1 GiB, instead
       // of being drawn inside the cooperative kernel: there the draws of a tile of steps -- Philox, AS241 with its ~50 constants
       // reloaded from scratch -- sit between two grid-wide hand-overs with 255 workgroups waiting (C5: 1.4 us of a 66 us step,
@@ -1178,187 +699,75 @@ static int launch_sweep(const fmcmc_model* m_in, const fmcmc_kernel* kn_in, cons
         double* wsl = nullptr;
         if (hipMallocAsync((void**)&wsl, (size_t)stream_bytes, stream) == hipSuccess) {
           ws_guard.p = wsl; ws_guard.s = stream;
-          const size_t items = (size_t)run->nchains * (size_t)run->nsteps;
-          const double fill_df = (kn->kind == FMCMC_KERNEL_RAM) ? A.ram_df : (A.variate == 1 ? -1.0 : 0.0);
-          hipLaunchKernelGGL(rng_fill_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream,
-                             (unsigned long long)run->seed, (long long)run->step_base, (long long)run->chain_base,
-                             (long long)run->nchains, (long long)run->nsteps, A.kz, fill_df, wsl, wsl + items);
-          A.fed_logu = wsl; A.fed_z = wsl + items; A.rng_mode = FMCMC_RNG_FED;
+          fill_rng(run, run->step_base, run->nchains, run->nsteps, A.kz, fill_df, wsl, stream);
+          A.fed_logu = wsl; A.fed_z = wsl + (size_t)run->nchains * (size_t)run->nsteps; A.rng_mode = FMCMC_RNG_FED;
         } else {
           (void)hipGetLastError();
         }
       }
-      // (variates from a stream, the library's or the caller's: the instantiation without the generators in its body)
-      const void* kfr = kfn;
-      size_t lds_run = lds;
-      long long ch_run = ch_launch;
+      // (variates from a stream, the library's or the caller's: the instantiation without the generators in its body, and where the
+      //  plan has one the shadow form)
+      const void* kfr = R.kfn;
+      size_t lds_run = R.lds_run;
+      long long ch_run = R.ch_launch;
       if (A.rng_mode == FMCMC_RNG_FED) {
-        const void* kf2 = fmh::k_logit(cw <= 2 ? cw : 4, 2, lkv);
-        if (kf2 && hipFuncSetAttribute(kf2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) kfr = kf2;
+        if (R.kfn_fed && hipFuncSetAttribute(R.kfn_fed, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R.lds_run) == hipSuccess) kfr = R.kfn_fed;
         else (void)hipGetLastError();
-        // the normal / uniform proposal kernels, joint scheme, no fixed parameter: mh_sweep_logit2 (mh_logit2.hpp) -- four chains per
-        // workgroup whatever cw says, the owners' work in the shadow of the hand-overs (knob shadow=0: off)
-        // (kernel_adapt / kernel_ram with up to eight parameters, none fixed, no window / constraint / bound: the same sweep with the
-        //  register owner of mh_spec.hpp, mh_sweep_logit2a)
-        const bool adaptive3 = (kn->kind == FMCMC_KERNEL_ADAPT && !adapt_hist) || (kn->kind == FMCMC_KERNEL_RAM && !kn->constr && !ram_bounded);
-        const void* kf3 = (K.shadow == 0 || kf != kn->k || A.kz != kn->k) ? nullptr
-                        : (kn->kind <= FMCMC_KERNEL_NORMAL_REFLECTIVE ? (kn->scheme == FMCMC_SCHEME_JOINT ? fmh::k_logit2(lkv) : nullptr)
-                           : ((adaptive3 && kn->k <= SPEC_KA && kn->k <= PIPE_KMAX) ? fmh::k_logit2a(lkv) : nullptr));
-        if (kf3) {
-          const size_t lds3 = (kn->kind <= FMCMC_KERNEL_NORMAL_REFLECTIVE) ? fmh::k_logit2_lds(kn->k) : fmh::k_logit2a_lds();
-          int per3 = 0;
-          if (hipFuncSetAttribute(kf3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3) == hipSuccess &&
-              hipOccupancyMaxActiveBlocksPerMultiprocessor(&per3, kf3, NT, lds3) == hipSuccess && (long long)per3 * ncu >= nb_launch) {
-            kfr = kf3; lds_run = lds3; ch_run = ch_shadow;
-            g_kernel = "logistic-shadow";
-          } else {
-            (void)hipGetLastError();
-          }
+        if (R.kfn_shadow && coop_fits(R.kfn_shadow, R.lds_shadow, nb_launch, ncu, dev, K.mode, nullptr)) {
+          kfr = R.kfn_shadow; lds_run = R.lds_shadow; ch_run = R.ch_shadow;
+          R.form = Form::LOGISTIC_SHADOW;
         }
       }
-      long long done = 0;
-      for (; done < run->nchains && e == hipSuccess; done += ch_run) {   // (the slices and tables serve every launch)
-        SweepArgs W = chain_window(A, done, (run->nchains - done < ch_run) ? run->nchains - done : ch_run, kf);
-        W.bits_stride = (run->nsteps + 31) >> 5;       // (the owners of mh_spec.hpp address the accept bitmap through it)
-        (void)hipMemsetAsync(bar, 0, sizeof(double) * nbar, stream);
-        void* kargs[] = {(void*)&W};
-        e = hipLaunchCooperativeKernel(kfr, dim3((unsigned)nb_launch), dim3(NT), kargs, (unsigned int)lds_run, stream);
-      }
-      if (e != hipSuccess && done > ch_run) {    // a LATER window failed: the chains of the earlier windows have run
-        set_err("HIP launch of chain window %lld failed (%s): the state of the first %lld chains is already advanced, the results of this call are invalid",
-                (long long)(done / ch_run), hipGetErrorString(e), (long long)(done - ch_run));
-        (void)hipGetLastError();
-        return FMCMC_ERR_DEVICE;
-      }
-      if (e != hipSuccess) {                         // the runtime refused the first cooperative launch: nothing ran
-        (void)hipGetLastError();
-        e = hipSuccess;
-        lshard = false;
-        g_kernel = "streamed-logistic";
+      SweepArgs Ab = A;
+      Ab.bits_stride = (run->nsteps + 31) >> 5;       // (the owners of mh_spec.hpp address the accept bitmap through it)
+      const CoopRun cr = coop_chain_windows(kfr, nb_launch, lds_run, Ab, run->nchains, ch_run, kf, bar, nbar, stream);
+      if (cr == COOP_LATER_FAILED) return FMCMC_ERR_DEVICE;
+      if (cr == COOP_NOTHING_RAN) {                  // the runtime refused the first cooperative launch: the chain-sharded kernel
+        R.form = Form::LOGISTIC;
         A = A_own;
         A.shard = 0; A.sh_xs = nullptr; A.sh_th = nullptr; A.sh_part = nullptr; A.sh_bar = nullptr;
       }
     }
-    if (!lshard) {
-      e = launch_k(fmh::k_logit(cw <= 2 ? cw : 4, 0, lkv), nblk, NT, lds, stream, A);
-    }
-    }   // (not the long-data form)
-  }
-  else if (m->family == FMCMC_FAM_GAUSSIAN_LINREG && m->p >= 16 && cw <= 2 &&
-           (kn->kind == FMCMC_KERNEL_RAM || kn->kind == FMCMC_KERNEL_NORMAL || kn->kind == FMCMC_KERNEL_NORMAL_REFLECTIVE)) {
-    // wide linear models (config C4: k = 50): one family and one proposal kernel compiled in, which leaves the streamed
-    // evaluation the registers for 4 observations x 8 columns in flight per thread (mh_common.hpp)
-    const int kv = kn->kind;   // 1, 2 or 4
-    // Observation-sharded evaluation: one cooperative launch when the call has 128 or 256 workgroups, consecutive launches
-    // of 256 workgroups when it has a multiple of that (more than 512 chains per GPU at two chains per workgroup)
-    const int nslots = (int)((m->n + NT - 1) / NT);
-    // (a launch may hold workgroups WITHOUT chains -- they own canonical lanes like the others -- so any chain count works:
-    //  up to 512 chains run as one launch of 256 workgroups, exactly 128 workgroups keep 4 lanes each when n allows)
-    const long long nb_launch = (nblk == 128 && 4 * nslots <= SH_MAXO) ? 128 : 256;
-    const long long ch_launch = (nblk > nb_launch) ? nb_launch * cw : (long long)run->nchains;
-    Knobs Kw = K;
-    if (wide_switched && K.shard != 0) Kw.shard = 1;
-    const int lpw = wide_sharded_lanes(Kw, m, kn, run, ram_bounded, ncu, nb_launch, cw);
-    bool shard = lpw > 0;
-    // the sharded evaluation is its own instantiation (OPT = lanes per workgroup): sharing one with the streamed loop
-    // cost 200-300 spilled registers in BOTH paths
-    const void* kfn = nullptr;
-    if (shard) kfn = fmh::k_wide(cw, lpw, kv);
-    if (A.debug & 256) fprintf(stderr, "fmcmc_amd: wide path nblk=%lld lpw=%d nslots=%d p=%d bounded=%d shard=%d\n", nblk, lpw, nslots, m->p, (int)ram_bounded, (int)shard);
-    double* shw = nullptr;
-    g_kernel = shard ? "streamed-wide-sharded" : "streamed-wide";
-    const size_t lds_plain = lds;   // what the chain-sharded kernel needs, should the sharded forms below not launch
-    // the slice product on the matrix cores (shard_columns_mfma): the slice lives in LDS behind the chain blocks
-    const int mf_spg = shard ? (nslots + 4 / lpw - 1) / (4 / lpw) : 0, nmt = (mf_spg + 3) / 4;
-    const int mblk = shm_hdr(nmt) + nmt * ((m->p + 3) / 4) * 64;
-    // (three M-tiles of which the third holds values 8, 9 only, at the width with a compile-time K-block count -- config C4:
-    //  its 8 rows go through two 4x4x4 MFMAs per K-block instead of a 16x16x4 that is half padding; knob t10=0: off)
-    //  (the form reads values 0 .. SHM_T10_FULL - 1 of every lane group without a mask: slots spg h + t <= nslots - 2 are full)
-    const bool t10_full = shard && mf_spg * (4 / lpw - 1) + (SHM_T10_FULL - 1) <= nslots - 2;
-    const int t10 = (nmt == 3 && mf_spg <= 10 && (m->p + 3) / 4 == 12 && t10_full && K.t10 != 0) ? 1 : 0;
-    bool mfma_form = shard && shard_mfma_enabled(K) && m->p <= 4 * SHM_KBMAX && mf_spg <= SHM_T &&
-                     lds + sizeof(double) * (size_t)(mblk + 1) <= 160 * 1024;
-    if (mfma_form) lds += sizeof(double) * (size_t)(mblk + 1);
-    if (shard && !mfma_form && lpw * nslots > SH_MAXO) shard = false;      // (more than 40 observations per slice: the matrix-core form or none)
-    if (shard) g_kernel = mfma_form ? "streamed-wide-sharded-mfma" : "streamed-wide-sharded";
-    // the dataflow form (mh_wide2.hpp): owner and evaluator waves decoupled, two chain groups half a step out of phase.
-    // It pays where the owners have real work to hide -- kernel_ram: 35.8 -> 27.9 us per step at C4 -- and costs the normal
-    // kernels 6 % (26.2 against 24.6: their owner phase is short and two of eight waves no longer evaluate).
-    // Knob wide2=0 keeps the sequential form everywhere, wide2=1 takes the dataflow form for every eligible call (tests).
-    bool wide2 = false;
-    {
-      const bool w2on = K.wide2 == 1 || (K.wide2 != 0 && kn->kind == FMCMC_KERNEL_RAM);
-      wide2 = shard && mfma_form && w2on && lpw == 2 && cw == 2 && nb_launch == 256 && ncu == 256 &&
-              !(kn->kind == FMCMC_KERNEL_RAM && kn->constr) && (kn->kind == FMCMC_KERNEL_RAM || kn->scheme == FMCMC_SCHEME_JOINT) &&
-              nmt >= 1 && nmt <= 3 && run->nsteps < 100000000 &&
-              sizeof(double) * wide2_lds_doubles(kn->k, kf, kn->kind, A.kz, mblk) <= 160 * 1024;
-    }
-    if (wide2) {
-      kfn = fmh::k_wide2(kv, nmt);
-      lds = sizeof(double) * wide2_lds_doubles(kn->k, kf, kn->kind, A.kz, mblk);
-      g_kernel = "wide-dataflow";
-      A.sh_ngrp = (K.groups == 4) ? 4 : 2;
-      A.sh_tiles = (K.tiles == 0 || A.sh_ngrp == 4) ? 0 : 1;
-    }
-    if (shard) {
-      int coop = 0, perCU = 0;
-      (void)hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev);
-      if (lds > 48 * 1024) e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess || !coop ||
-          hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kfn, NT, lds) != hipSuccess || (long long)perCU * ncu < nb_launch) {
-        if (A.debug & 256) fprintf(stderr, "fmcmc_amd: sharded evaluation not launched: err=%d coop=%d perCU=%d lds=%zu\n", (int)e, coop, perCU, lds);
-        shard = false;
-        g_kernel = "streamed-wide";
-        lds = lds_plain;
-      }
-      e = hipSuccess;
-    }
-    if (shard) {
+    if (R.form == Form::LOGISTIC) e = launch_k(R.kfn_base, R.nblk, NT, R.lds, stream, A);
+  } else
+  if (R.base == Form::WIDE) {
+    // wide linear models: observation-sharded (sequential, matrix-core or dataflow form) where the plan has it and the launch is
+    // resident, else chain-sharded
+    if (R.wide2) { A.sh_ngrp = R.ngrp; A.sh_tiles = R.tiles; }
+    if (R.form != Form::WIDE && !coop_fits(R.kfn, R.lds_run, R.nb_launch, ncu, dev, K.mode, "sharded evaluation")) R.form = Form::WIDE;
+    if (R.form != Form::WIDE) {
+      double* shw = nullptr;
+      const long long nb_launch = R.nb_launch, ch_launch = R.ch_launch;
+      const bool mfma_form = R.mfma_form;
       const size_t nxs = mfma_form ? 0 : (size_t)nb_launch * m->p * SH_MAXO, nys = mfma_form ? 0 : (size_t)nb_launch * SH_MAXO, nth = ((size_t)kn->k * (ch_launch + SH_PAD) + 7) & ~(size_t)7,   // (the partials behind it stay 64-byte aligned)
-                   npt = (size_t)(NT + SH_PAD) * ch_launch, nbar = wide2 ? 8 * W2_BARW / 2 : 32 * 20 / 2;   // (barrier words counted in doubles)
-      const size_t nmf = mfma_form ? (size_t)nb_launch * mblk : 0;
+                   npt = (size_t)(NT + SH_PAD) * ch_launch, nbar = R.wide2 ? 8 * W2_BARW / 2 : 32 * 20 / 2;   // (barrier words counted in doubles)
+      const size_t nmf = mfma_form ? (size_t)nb_launch * R.mblk : 0;
       e = hipMallocAsync((void**)&shw, sizeof(double) * (nxs + nys + nth + npt + nbar + nmf), stream);
       if (e != hipSuccess) { set_err("hipMallocAsync(sharded evaluation) failed: %s", hipGetErrorString(e)); return FMCMC_ERR_DEVICE; }
       shw_guard.p = shw; shw_guard.s = stream;
       double* xs = shw; double* ys = xs + nxs; double* thw = ys + nys; double* ptw = thw + nth;
       unsigned* bar = (unsigned*)(ptw + npt);
       if (!mfma_form)
-        hipLaunchKernelGGL(shard_build_slices, dim3((unsigned)nb_launch), dim3(256), 0, stream, m->X, m->y, (long long)m->n, m->p, lpw, nslots, xs, ys);
-      A.shard = lpw; A.sh_nslots = nslots; A.sh_xs = xs; A.sh_ys = ys; A.sh_th = thw; A.sh_part = ptw; A.sh_bar = bar;
+        hipLaunchKernelGGL(shard_build_slices, dim3((unsigned)nb_launch), dim3(256), 0, stream, m->X, m->y, (long long)m->n, m->p, R.lpw, R.nslots, xs, ys);
+      A.shard = R.lpw; A.sh_nslots = R.nslots; A.sh_xs = xs; A.sh_ys = ys; A.sh_th = thw; A.sh_part = ptw; A.sh_bar = bar;
       if (mfma_form) {
         double* mf = ptw + npt + nbar;
-        hipLaunchKernelGGL(shard_build_mfma, dim3((unsigned)nb_launch), dim3(256), 0, stream, m->X, m->y, (long long)m->n, m->p, lpw, nslots,
-                           nmt, t10, mf, mblk);
-        A.sh_mfma = mf; A.sh_mblk = mblk; A.sh_nmt = nmt; A.sh_t10 = t10;
+        hipLaunchKernelGGL(shard_build_mfma, dim3((unsigned)nb_launch), dim3(256), 0, stream, m->X, m->y, (long long)m->n, m->p, R.lpw, R.nslots,
+                           R.nmt, R.t10, mf, R.mblk);
+        A.sh_mfma = mf; A.sh_mblk = R.mblk; A.sh_nmt = R.nmt; A.sh_t10 = R.t10;
       }
-      long long done = 0;
-      for (; done < run->nchains && e == hipSuccess; done += ch_launch) {   // (the slices and tables serve every launch)
-        SweepArgs W = chain_window(A, done, (run->nchains - done < ch_launch) ? run->nchains - done : ch_launch, kf);
-        (void)hipMemsetAsync(bar, 0, sizeof(double) * nbar, stream);
-        void* kargs[] = {(void*)&W};
-        e = hipLaunchCooperativeKernel(kfn, dim3((unsigned)nb_launch), dim3(NT), kargs, (unsigned int)lds, stream);
-      }
-      if (e != hipSuccess && done > ch_launch) {    // a LATER window failed: the chains of the earlier windows have run
-        set_err("HIP launch of chain window %lld failed (%s): the state of the first %lld chains is already advanced, the results of this call are invalid",
-                (long long)(done / ch_launch), hipGetErrorString(e), (long long)(done - ch_launch));
-        (void)hipGetLastError();
-        return FMCMC_ERR_DEVICE;
-      }
-      if (e != hipSuccess && done <= ch_launch) {   // the runtime refused the first cooperative launch after all: nothing ran,
-        (void)hipGetLastError();                    // take the chain-sharded kernel
-        e = hipSuccess;
-        shard = false;
-        g_kernel = "streamed-wide";
+      const CoopRun cr = coop_chain_windows(R.kfn, nb_launch, R.lds_run, A, run->nchains, ch_launch, kf, bar, nbar, stream);
+      if (cr == COOP_LATER_FAILED) return FMCMC_ERR_DEVICE;
+      if (cr == COOP_NOTHING_RAN) {                  // the runtime refused the first cooperative launch: the chain-sharded kernel
+        R.form = Form::WIDE;
         A.shard = 0; A.sh_xs = nullptr; A.sh_ys = nullptr; A.sh_th = nullptr; A.sh_part = nullptr; A.sh_bar = nullptr;
         A.sh_mfma = nullptr; A.sh_mblk = 0; A.sh_nmt = 0; A.sh_t10 = 0;
-        lds = lds_plain;
       }
     }
-    if (shard) {
-    } else
-    e = launch_k(fmh::k_wide(cw, 0, kv), nblk, NT, lds, stream, A);
+    if (R.form == Form::WIDE) e = launch_k(R.kfn_base, R.nblk, NT, R.lds, stream, A);
   }
-  else { g_kernel = "streamed"; e = launch_k(fmh::k_general(cw), nblk, NT, lds, stream, A); }
+  else e = launch_k(R.kfn, R.nblk, NT, R.lds, stream, A);   // resident / general kernel
+  g_kernel = kernel_name(R);
   if (e == hipSuccess) e = hipGetLastError();
   if (e != hipSuccess) { set_err("HIP launch failed: %s", hipGetErrorString(e)); return FMCMC_ERR_DEVICE; }
   // timing ablations and stamps (knob mode=<bits>: 8 stamps in the draws buffer, 32 / 64 / 128 / 1024 parts of a step left out)

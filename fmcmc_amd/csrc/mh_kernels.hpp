@@ -1,11 +1,16 @@
 // mh_kernels.hpp -- kernel look-ups: shape -> the host handle of the instantiation that runs it (nullptr: none compiled).
-// launch_sweep (mh_engine.hip) launches the handle with hipLaunchKernel / hipLaunchCooperativeKernel; every kernel takes ONE
-// argument, the SweepArgs of the launch, by value.
+// plan_route (mh_route.hpp) picks the handle, launch_sweep (mh_engine.hip) launches it with hipLaunchKernel /
+// hipLaunchCooperativeKernel; every kernel takes ONE argument, the SweepArgs of the launch, by value.
 #pragma once
 
 #define FMH_HIDDEN __attribute__((visibility("hidden")))
 
 namespace fmh {
+// Observation slots (of 512) the register kernels hold per compute lane at p covariates: the OPTMAX of every mh_sweep_lat /
+// mh_sweep_spec instantiation (k_lat*.hip, k_lat_l*.hip, k_spec*.hip) -- P doubles per slot; 0: no instantiation
+constexpr int reg_slots(int p) { return p < 0 ? 0 : p <= 3 ? 20 : p <= 5 ? 10 : p <= 7 ? 8 : p <= 15 ? 4 : 0; }
+// Observation slots mh_sweep_mfma holds in its 80 operand registers per lane (one / two operand groups); 0: none, streamed forms only
+constexpr int mfma_reg_slots(int p) { return p < 0 ? 0 : p <= 3 ? 20 : p <= 7 ? 10 : 0; }
 // k_general.hip: mh_sweep_kernel<CW, -1, 0, 0> (every family / proposal kernel / scheme), cw = 1, 2, 4, 8;
 //                the register-resident shapes mh_sweep_kernel<4, P, OPT, KIND>: (p, opt) = (1, 4), (3, 20), kind 1..4
 FMH_HIDDEN const void* k_general(int cw);
@@ -29,11 +34,14 @@ FMH_HIDDEN const void* k_mfma_ad(int kind, int ng, int kx, int bnd, int shrt);
 // k_spec.hip: mh_sweep_spec<P, OPTMAX, KIND>
 FMH_HIDDEN const void* k_spec(int p, int kind);
 FMH_HIDDEN const void* k_spec_ring(int p, int logistic);   // k_spec_r.hip: kernel_adapt(freq = 2 .. 8)
-FMH_HIDDEN int k_spec_optmax(int p, int kind);
-// k_spec_l*.hip: mh_sweep_spec<P, OPTMAX, KIND, LOGISTIC>: p = 1 .. 7, kind 1 .. 4
+// (the slot count of mh_sweep_spec at p covariates under a proposal kernel: 8 .. 15 covariates, the adaptive and mirror kernels only)
+inline int k_spec_optmax(int p, int kind) {
+  return (p <= 7 || kind == FMCMC_KERNEL_ADAPT || kind == FMCMC_KERNEL_RAM || kind == FMCMC_KERNEL_NMIRROR || kind == FMCMC_KERNEL_UMIRROR) ? reg_slots(p) : 0;
+}
+// k_spec_l*.hip: mh_sweep_spec<P, OPTMAX, KIND, LOGISTIC>: p = 1 .. 15, kind 1 .. 4 (8 .. 15: kind 3, 4)
 FMH_HIDDEN const void* k_spec_logit(int p, int kind);
 FMH_HIDDEN size_t k_spec_logit_lds(int adaptive);
-// k_lat*.hip: mh_sweep_lat<KIND, P, OPTMAX> (kind 1, 2; p = 1 .. 7; the slot counts of k_spec_optmax)
+// k_lat*.hip: mh_sweep_lat<KIND, P, OPTMAX> (kind 1, 2; p = 0 .. 15; OPTMAX = reg_slots(P))
 FMH_HIDDEN const void* k_lat(int p, int kind);
 // k_lat_l*.hip: mh_sweep_lat<KIND, P, OPTMAX, LOGISTIC> (kind 1, 2; p = 1 .. 7)
 FMH_HIDDEN const void* k_lat_logit(int p, int kind);

@@ -1,5 +1,5 @@
 // mh_tu.hpp -- what every translation unit of libfmcmc_amd.so starts with.  The device code is split over several .hip files so
-// that they compile in parallel (fmcmc_amd/build.py): mh_engine.hip holds the C-ABI, validation and kernel selection, every
+// that they compile in parallel (fmcmc_amd/build.py): mh_engine.hip holds the C-ABI, validation and launches (selection: mh_route.hpp), every
 // k_*.hip instantiates one kernel family and hands its kernels out by (run-time) shape through the look-ups of mh_kernels.hpp.
 // All device helpers live in anonymous namespaces: each translation unit has its own copy, nothing device-side is linked.
 #pragma once
