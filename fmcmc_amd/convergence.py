@@ -67,7 +67,7 @@ class convergence_gelman:
             dist.all_reduce(center, op=dist.ReduceOp.SUM, group=group)
         if Cn > 0 and p > abi.MAX_K_WAVE:
             # more free parameters than the MFMA window reduction tiles (64): the same per-chain statistics -- window mean relative
-            # to the centre, window covariance -- and their sums over the chains with torch on the device (64 < k <= 128 is the
+            # to the centre, window covariance -- and their sums over the chains with torch on the device (64 < k <= 256 is the
             # big-k kernel's territory: one chain per workgroup, speed is not the point there)
             # in blocks of chains, so that the gathered window, its centred copy and the products stay bounded (1024 chains x k = 100 x
             # N = 5000 rows were three 4 GB tensors at once): per-chain statistics are independent, the sums over the chains add up

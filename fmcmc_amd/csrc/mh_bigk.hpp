@@ -1,6 +1,6 @@
-// mh_bigk.hpp -- mh_sweep_bigk: 64 < k <= 128 parameters (round 4; R/kernel_ram.R:93-121 and R/kernel_adapt.R:87-115 take any k,
-// the authors' own benchmark is k = 100, playground/benchmarks.Rmd; until round 4 FMCMC_MAX_K was 64: the lane = row mapping
-// of the owner wavefronts).
+// mh_bigk.hpp -- mh_sweep_bigk: 64 < k <= 256 parameters (R/kernel_ram.R:93-121 and R/kernel_adapt.R:87-115 take any k, the
+// authors' own benchmark is k = 100, playground/benchmarks.Rmd; until round 4 FMCMC_MAX_K was 64: the lane = row mapping of the
+// owner wavefronts; 128 until the HBM form below).
 #pragma once
 
 namespace {
@@ -15,16 +15,32 @@ namespace {
 // Cholesky column costs two barriers (~0.3 us), a kernel_adapt step at k = 128 ~40 us on top of its evaluation.
 // Takes: every family; kernel_normal(_reflective) / kernel_unif(_reflective) with the joint scheme, kernel_adapt (bw = 0,
 // freq = 1), kernel_ram (any freq, bounds, constr).  The host refuses the rest for k > 64 with a message.
-__host__ __device__ inline size_t bigk_lds_doubles(int k, int kf, int kind) {
+//
+// Two forms of the one kernel body (template argument HBM), with the same arithmetic in the same order:
+//  * LDS (HBM = false, "big-k"): the packed triangles above.  They fit the 160 KiB of a CU up to k = 133 (kernel_adapt) and
+//    183 (kernel_ram); the joint simple kernels keep only O(k) vectors (40 KB at k = 256).
+//  * HBM (HBM = true, "big-k-hbm"): the matrices stay in the chain's own A.Sigma square [kf][kf] (a device buffer), worked in
+//    place: Sigma (adapt) / S (ram) in its lower triangle, and the strictly lower part of the kernel_adapt factor, rebuilt
+//    every step and never carried, TRANSPOSED into the upper half (L[r][b] at [b][r]: the loads of L[r][b] across rows are
+//    coalesced, L[j][b] is a broadcast), its diagonal in an LDS vector.  The end of the launch hands on what the LDS form
+//    writes (the symmetric Sigma / the lower factor with +0 above).  LDS keeps the O(k) vectors only.  Hand-offs through
+//    global memory inside the workgroup are ordered by __syncthreads() (s_waitcnt vmcnt(0) lgkmcnt(0); all waves of the
+//    chain share one CU's L1), never by lds_barrier(), which waits on lgkmcnt only; nothing crosses workgroups.
+// The host takes the LDS form wherever it fits (every k <= 128), the HBM form beyond (knob bigkhbm=1: always, k > 64).
+__host__ __device__ inline size_t bigk_lds_doubles(int k, int kf, int kind, bool hbm = false) {
   const size_t tri = (size_t)kf * (kf + 1) / 2;
-  const size_t mats = (kind == FMCMC_KERNEL_ADAPT) ? 2 * tri : (kind == FMCMC_KERNEL_RAM ? tri : 0);
+  const size_t mats = hbm ? ((kind == FMCMC_KERNEL_ADAPT) ? (size_t)kf /* the factor's diagonal */ : 0)
+                          : ((kind == FMCMC_KERNEL_ADAPT) ? 2 * tri : (kind == FMCMC_KERNEL_RAM ? tri : 0));
   return 5 * (size_t)k + (k / 2 + 1) + NW + 2 /* flags */ + (size_t)(k + 1) /* variates */ + (size_t)k /* scaled copy */ +
          2 * (size_t)k /* th0, th1 */ + 8 * (size_t)kf /* vectors */ + 2 * (size_t)kf /* scan buffers */ + mats + 4;
 }
 
 #ifdef FMH_WITH_BIGK_KERNEL   /* compiled into k_wide2.hip only; the engine takes bigk_lds_doubles above */
+template <bool HBM>
 __global__ __launch_bounds__(NT) void mh_sweep_bigk(const SweepArgs A0) {
   SweepArgs A = A0;
+  // workgroup barrier: LDS ordering only in the LDS form, global memory too in the HBM form
+  auto bar = []() { if constexpr (HBM) __syncthreads(); else lds_barrier(); };
   extern __shared__ double smem[];
   const int tid = threadIdx.x, r = tid;
   const int k = A.k, kz = A.kz;
@@ -63,12 +79,17 @@ __global__ __launch_bounds__(NT) void mh_sweep_bigk(const SweepArgs A0) {
   double* vq = vP + kf;        // [kf] scan buffer A
   double* vt = vq + kf;        // [kf] scan buffer B
   double* vx = vt + kf;        // [kf] spare
-  double* MA = vx + kf;        // packed lower: Sigma (adapt) / S (ram)
+  double* MA = vx + kf;        // LDS form: packed lower: Sigma (adapt) / S (ram) | HBM form: [kf] the factor's diagonal (adapt)
   const int tri = kf * (kf + 1) / 2;
-  double* MB = MA + tri;       // packed lower: Cholesky factor (adapt)
+  double* MB = MA + tri;       // LDS form: packed lower: Cholesky factor (adapt)
   auto at = [](int i, int j) -> int { return i * (i + 1) / 2 + j; };   // j <= i
 
   const long long cl = blockIdx.x;            // one chain per workgroup
+  double* const Mg = A.Sigma + cl * kf * kf;  // HBM form: the chain's Sigma square
+  // the matrices' elements: Sigma / S (i >= j), the factor's strictly lower part (i > j) and its diagonal
+  auto ma = [&](int i, int j) -> double& { if constexpr (HBM) return Mg[i * kf + j]; else return MA[at(i, j)]; };
+  auto mbl = [&](int i, int j) -> double& { if constexpr (HBM) return Mg[j * kf + i]; else return MB[at(i, j)]; };
+  auto mbd = [&](int j) -> double& { if constexpr (HBM) return MA[j]; else return MB[at(j, j)]; };
   const unsigned int cgid = (unsigned int)(A.chain_base + cl);
   const bool row = r < kf;                    // this thread owns matrix row r
   const bool par = r < k;                     // this thread owns parameter r
@@ -82,12 +103,20 @@ __global__ __launch_bounds__(NT) void mh_sweep_bigk(const SweepArgs A0) {
   unsigned int bitword = 0;
   if (par) { const double t = A.theta0[cl * k + r]; th0[r] = t; th1[r] = t; }
   if (adapt || ram) {
-    for (int e = tid; e < tri; e += NT) {
-      int i = 0;
-      while ((i + 1) * (i + 2) / 2 <= e) i++;
-      const int j = e - i * (i + 1) / 2;
-      MA[e] = A.fresh ? ((i == j) ? 1.0 * A.eps : 0.0) : A.Sigma[(cl * kf + i) * kf + j];
-      if (adapt) MB[e] = 0.0;
+    if constexpr (HBM) {     // (in place: a carried Sigma / S is already there)
+      if (A.fresh)
+        for (int e = tid; e < kf * kf; e += NT) {
+          const int i = e / kf, j = e - i * kf;
+          if (j <= i) Mg[e] = (i == j) ? 1.0 * A.eps : 0.0;
+        }
+    } else {
+      for (int e = tid; e < tri; e += NT) {
+        int i = 0;
+        while ((i + 1) * (i + 2) / 2 <= e) i++;
+        const int j = e - i * (i + 1) / 2;
+        MA[e] = A.fresh ? ((i == j) ? 1.0 * A.eps : 0.0) : A.Sigma[(cl * kf + i) * kf + j];
+        if (adapt) MB[e] = 0.0;
+      }
     }
     if (!A.fresh) {
       abs_iter = A.abs_iter[cl];
@@ -95,7 +124,7 @@ __global__ __launch_bounds__(NT) void mh_sweep_bigk(const SweepArgs A0) {
       if (adapt) { have_mean = A.have_mean[cl]; if (row) vmp[r] = A.mean_prev[cl * kf + r]; }
     }
   }
-  lds_barrier();
+  bar();
 
   double* thp[1] = {th1};
   unsigned sh_epoch = 0;
@@ -126,12 +155,12 @@ __global__ __launch_bounds__(NT) void mh_sweep_bigk(const SweepArgs A0) {
 
   // ---- row 1
   evaluate();
-  lds_barrier();
+  bar();
   f0 = finish_logpost<0>(A, th1, total(), s_hs);
   f1 = f0;
   if (row) vrs[r] = th0[s_which[r]];
   store_row(1, f0);
-  lds_barrier();
+  bar();
 
   for (int i = 2; i <= nsteps; i++) {
     // ================= variates of this step (canonical Philox stream, or the fed one) =================
@@ -145,13 +174,13 @@ __global__ __launch_bounds__(NT) void mh_sweep_bigk(const SweepArgs A0) {
       else v = fmh_normal(A.seed, st, cgid, (unsigned int)tid);
       s_z[tid] = v;
     }
-    lds_barrier();
+    bar();
     bool ram_gate = false;
     // ================= proposal =================
     if (status == FMCMC_CHAIN_OK) {
       if (!adapt && !ram) {   // kernel_normal(_reflective), joint scheme (R/kernel_normal.R:67-72, :159-164)
         if (par) th1[r] = th0[r];
-        lds_barrier();
+        bar();
         if (row) {
           const int j = s_which[r];
           double t = th0[j] + (s_mu[j] + s_scale[j] * s_z[r]);
@@ -168,16 +197,16 @@ __global__ __launch_bounds__(NT) void mh_sweep_bigk(const SweepArgs A0) {
             mt = (mp * t + x) / (t + 1);
             vv[r] = x; vmp[r] = mp; vmt[r] = mt;
           }
-          lds_barrier();
+          bar();
           if (row) {
             const double c1 = (t - 1) / t, c2 = 1.0 / t;
             for (int b = 0; b <= r; b++) {      // (the element (r, b) of the symmetric update: the same bits as (b, r))
               const double ik = (b == r) ? 1.0 * A.eps : 0.0;
               const double inner = t * (mp * vmp[b]) - (t + 1) * (mt * vmt[b]) + x * vv[b] + 1e-5 * ik;
-              MA[at(r, b)] = c1 * MA[at(r, b)] + c2 * inner;
+              ma(r, b) = c1 * ma(r, b) + c2 * inner;
             }
           }
-          lds_barrier();
+          bar();
           if (row) vmp[r] = mt;
           have_mean = 1;
         }
@@ -187,26 +216,31 @@ __global__ __launch_bounds__(NT) void mh_sweep_bigk(const SweepArgs A0) {
         for (int j = 0; j < kf; j++) {
           double s = 0.0;
           if (row && r >= j) {
-            s = MA[at(r, j)];
-            for (int b = 0; b < j; b++) s = fmh_fma(-MB[at(r, b)], MB[at(j, b)], s);
+            s = ma(r, j);
+            for (int b = 0; b < j; b++) s = fmh_fma(-mbl(r, b), mbl(j, b), s);
             if (r == j) vd[0] = s;
           }
-          lds_barrier();
+          bar();
           const double d = vd[0];
           if (!(d > 0.0) || !fmh_isfinite(d)) { notpd = true; break; }   // (uniform)
           const double ljj = fmh_sqrt(d);
-          if (row && r == j) MB[at(j, j)] = ljj;
-          else if (row && r > j) MB[at(r, j)] = s / ljj;
-          lds_barrier();
+          if (row && r == j) mbd(j) = ljj;
+          else if (row && r > j) mbl(r, j) = s / ljj;
+          bar();
         }
         if (notpd) {
           status = FMCMC_CHAIN_NOT_PD;
         } else {
           if (par) th1[r] = th0[r];
-          lds_barrier();
+          bar();
           if (row) {
             double s = 0.0;
-            for (int b = 0; b <= r; b++) s = fmh_fma(MB[at(r, b)], s_z[b], s);
+            if constexpr (HBM) {
+              for (int b = 0; b < r; b++) s = fmh_fma(mbl(r, b), s_z[b], s);
+              s = fmh_fma(mbd(r), s_z[r], s);
+            } else {
+              for (int b = 0; b <= r; b++) s = fmh_fma(MB[at(r, b)], s_z[b], s);
+            }
             const int j = s_which[r];
             th1[j] = reflect1(th0[j] + (s_mu[j] + s), s_lb[j], s_ub[j]);
           }
@@ -214,7 +248,7 @@ __global__ __launch_bounds__(NT) void mh_sweep_bigk(const SweepArgs A0) {
       } else {                // kernel_ram, R/kernel_ram.R:123-126 (theta1 keeps its previous values in fixed coordinates)
         if (row) {
           double s = 0.0;
-          for (int b = r; b >= 0; b--) s = fmh_fma(MA[at(r, b)], s_z[b], s);
+          for (int b = r; b >= 0; b--) s = fmh_fma(ma(r, b), s_z[b], s);
           const int j = s_which[r];
           th1[j] = th0[j] + s;
         }
@@ -222,10 +256,10 @@ __global__ __launch_bounds__(NT) void mh_sweep_bigk(const SweepArgs A0) {
       }
       if (status != FMCMC_CHAIN_OK) fail(i);
     }
-    lds_barrier();
+    bar();
     // ================= evaluation of f(theta1) =================
     evaluate();
-    lds_barrier();
+    bar();
     // ================= kernel_ram: adaptation with f(theta1) of the un-reflected proposal (R/kernel_ram.R:129-152) =================
     double f1_pre = 0.0;
     bool have_f1 = false;
@@ -245,16 +279,16 @@ __global__ __launch_bounds__(NT) void mh_sweep_bigk(const SweepArgs A0) {
           double* qa = vq;
           double* qb = vt;
           if (row) qa[r] = s_z[r] * s_z[r];
-          lds_barrier();
+          bar();
           for (int s = 1; s < kf; s <<= 1) {
             if (row) qb[r] = (r >= s) ? qa[r] + qa[r - s] : qa[r];
-            lds_barrier();
+            bar();
             double* tmp = qa; qa = qb; qb = tmp;
           }
           const double nrm2 = qa[kf - 1];
           const double cp = (eta * (a_n - A.arate)) / nrm2;
           if (tid == 0) s_flag[1] = 0;
-          lds_barrier();
+          bar();
           if (cp != 0.0 && fmh_isfinite(cp)) {
             double dl = 0.0, kl = 0.0;
             if (row) {
@@ -263,38 +297,38 @@ __global__ __launch_bounds__(NT) void mh_sweep_bigk(const SweepArgs A0) {
               if (!okl) s_flag[1] = 1;
               vd[r] = dl; vk[r] = kl;
             }
-            lds_barrier();
+            bar();
             if (s_flag[1] != 0) {
               nerr += 1;
             } else if (row) {   // S'_rj = S_rj d_j + G_rj kappa_j, G re-formed from the diagonal down (ram_factor_update_canon)
               double G = 0.0;
               for (int j = r; j >= 0; j--) {
-                const double sij = MA[at(r, j)];
-                MA[at(r, j)] = fmh_fma(G, vk[j], sij * vd[j]);
+                const double sij = ma(r, j);
+                ma(r, j) = fmh_fma(G, vk[j], sij * vd[j]);
                 G = fmh_fma(sij, s_z[j], G);
               }
             }
           }
           if (A.constr) {  // Sigma <<- constr[which., which.] * Sigma (R/kernel_ram.R:149-150)
             if (row)
-              for (int b = 0; b <= r; b++) MA[at(r, b)] = A.constr[r * kf + b] * MA[at(r, b)];
+              for (int b = 0; b <= r; b++) ma(r, b) = A.constr[r * kf + b] * ma(r, b);
           }
-          lds_barrier();
+          bar();
         }
         abs_iter += 1;
       }
       if (A.ram_bounded) {
         if (tid == 0) s_flag[2] = 0;
-        lds_barrier();
+        bar();
         if (status == FMCMC_CHAIN_OK && row) {
           const int j = s_which[r];
           const double t0 = th1[j], t1 = reflect1(t0, s_lb[j], s_ub[j]);
           if (!(t1 == t0)) { th1[j] = t1; s_flag[2] = 1; }
         }
-        lds_barrier();
+        bar();
         if (s_flag[2] != 0) {     // (uniform)
           evaluate();
-          lds_barrier();
+          bar();
         }
       }
     }
@@ -314,7 +348,7 @@ __global__ __launch_bounds__(NT) void mh_sweep_bigk(const SweepArgs A0) {
           nacc += 1;
           bitword |= (1u << ((i - 1) & 31));
         }
-        lds_barrier();
+        bar();
         store_row(i, f1);
         if (adapt && row) vrs[r] = vrs[r] + th0[s_which[r]];
       }
@@ -323,7 +357,7 @@ __global__ __launch_bounds__(NT) void mh_sweep_bigk(const SweepArgs A0) {
       A.accept_bits[cl * (long long)((nsteps + 31) >> 5) + ((i - 1) >> 5)] = bitword;
       bitword = 0;
     }
-    lds_barrier();
+    bar();
   }
 
   // ---- write state back
@@ -339,10 +373,17 @@ __global__ __launch_bounds__(NT) void mh_sweep_bigk(const SweepArgs A0) {
     }
   }
   if (adapt || ram) {
-    for (int e = tid; e < kf * kf; e += NT) {
-      const int a = e / kf, b = e % kf;
-      // kernel_adapt hands on the full symmetric Sigma, kernel_ram its lower factor (+0 above the diagonal)
-      A.Sigma[(cl * kf + a) * kf + b] = (b <= a) ? MA[at(a, b)] : (adapt ? MA[at(b, a)] : 0.0);
+    if constexpr (HBM) {     // (the lower triangle is in place; the last barrier of the sweep ordered its stores)
+      for (int e = tid; e < kf * kf; e += NT) {
+        const int a = e / kf, b = e - a * kf;
+        if (b > a) Mg[e] = adapt ? Mg[b * kf + a] : 0.0;
+      }
+    } else {
+      for (int e = tid; e < kf * kf; e += NT) {
+        const int a = e / kf, b = e % kf;
+        // kernel_adapt hands on the full symmetric Sigma, kernel_ram its lower factor (+0 above the diagonal)
+        A.Sigma[(cl * kf + a) * kf + b] = (b <= a) ? MA[at(a, b)] : (adapt ? MA[at(b, a)] : 0.0);
+      }
     }
     if (adapt && row) A.mean_prev[cl * kf + r] = vmp[r];
   }

@@ -520,8 +520,9 @@ static int launch_sweep(const fmcmc_model* m_in, const fmcmc_kernel* kn_in, cons
   }
   Route R = plan_route(m, kn, run, kf, ram_bounded, A.kz, A.ldS, ncu, K);
   if (R.lds_exceeded) { set_err("LDS budget exceeded (k=%d)", kn->k); return FMCMC_ERR_UNSUPPORTED; }
+  if (R.no_kernel) { set_err("no device kernel for the %s form (k=%d)", kernel_name(R), kn->k); return FMCMC_ERR_DEVICE; }
   hipError_t e = hipSuccess;
-  if (R.form == Form::BIGK) {
+  if (R.form == Form::BIGK || R.form == Form::BIGK_HBM) {
     g_kernel = kernel_name(R);
     e = launch_k(R.kfn, run->nchains, NT, R.lds, stream, A);
     if (e == hipSuccess) e = hipGetLastError();

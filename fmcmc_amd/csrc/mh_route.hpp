@@ -37,18 +37,20 @@ static size_t sweep_lds_bytes(int k, int kf, int kind, int CW, int tb, int kz, b
 //   specp0=0     models without a covariate (iid Normal): adaptive / mirror kernels not on the wave-specialised kernel
 //   turn=<t>     logit_shard's issue-priority turn (timing only): thousandths of the younger wave's passes it starts from, + 10000: and
 //                stays at, + 100000 x (lead in units of 256 cycles it is regulated towards); turn=0: no turn
+//   bigkhbm=1    more parameters than a wavefront has lanes: the HBM form of mh_sweep_bigk even where the LDS form fits
 //   mode=<bits>  timing ablations and stamps (SweepArgs.debug)
 // The kernel a call ended up on is reported by fmcmc_last_kernel(); DESIGN.md section 5 has the shape -> kernel table.
 struct Knobs {
   int streamed = -1, cw = -1, pipe = -1, lat = -1, mfma = -1, shard = -1, shard_mfma = -1, wide2 = -1, groups = -1, tiles = -1, t10 = -1, window = -1, mode = 0;
   int shadow = -1, turn = -1, speclogit = -1, specbnd = -1, specmirror = -1, specp0 = -1, tinymfma = -1, specwide = -1;
+  int bigkhbm = -1;
 };
 static Knobs read_knobs() {
   Knobs K;
   const char* e = getenv("FMCMC_AMD_DEBUG");
   if (!e) return K;
   struct { const char* name; int* dst; } tab[] = {{"streamed", &K.streamed}, {"cw", &K.cw}, {"pipe", &K.pipe}, {"lat", &K.lat},
-      {"mfma", &K.mfma}, {"shard_mfma", &K.shard_mfma}, {"shard", &K.shard}, {"wide2", &K.wide2}, {"groups", &K.groups}, {"tiles", &K.tiles}, {"t10", &K.t10}, {"window", &K.window}, {"mode", &K.mode}, {"shadow", &K.shadow}, {"turn", &K.turn}, {"speclogit", &K.speclogit}, {"specbnd", &K.specbnd}, {"specmirror", &K.specmirror}, {"specp0", &K.specp0}, {"tinymfma", &K.tinymfma}, {"specwide", &K.specwide}};
+      {"mfma", &K.mfma}, {"shard_mfma", &K.shard_mfma}, {"shard", &K.shard}, {"wide2", &K.wide2}, {"groups", &K.groups}, {"tiles", &K.tiles}, {"t10", &K.t10}, {"window", &K.window}, {"mode", &K.mode}, {"shadow", &K.shadow}, {"turn", &K.turn}, {"speclogit", &K.speclogit}, {"specbnd", &K.specbnd}, {"specmirror", &K.specmirror}, {"specp0", &K.specp0}, {"tinymfma", &K.tinymfma}, {"specwide", &K.specwide}, {"bigkhbm", &K.bigkhbm}};
   while (*e) {
     const char* eq = strchr(e, '=');
     const char* end = strchr(e, ',');
@@ -134,13 +136,14 @@ static long long step_window(const fmcmc_run* run, int kz, const Knobs& K) {
 // ---- the route of a call: which kernel runs it, and in which shape (DESIGN.md section 5 has the table) ------------------------
 // (one per kernel family and form; kernel_name: what fmcmc_last_kernel() reports for it)
 enum class Form { BIGK, RESIDENT, GENERAL, LONG, MFMA, MFMA_STREAMED, MFMA_ADAPTIVE, LAT, LAT_LOGIT, SPEC, SPEC_LOGIT,
-                  LOGISTIC, LOGISTIC_SHARDED, LOGISTIC_SHADOW, WIDE, WIDE_SHARDED, WIDE_SHARDED_MFMA, WIDE_DATAFLOW };
+                  LOGISTIC, LOGISTIC_SHARDED, LOGISTIC_SHADOW, WIDE, WIDE_SHARDED, WIDE_SHARDED_MFMA, WIDE_DATAFLOW, BIGK_HBM };
 struct Route {
   Form form = Form::GENERAL;   // what runs the call
   Form base = Form::GENERAL;   // the chain-sharded form beneath a fast or sharded one: what a run-time step down takes
   const void* kfn = nullptr, *kfn_base = nullptr;   // their handles (MFMA forms: chosen per launch, BIG depends on its size)
   size_t lds = 0, lds_run = 0;  // LDS bytes of `base`, of a sharded `form`
   bool lds_exceeded = false;   // the call's chain blocks do not fit the LDS: unsupported
+  bool no_kernel = false;      // the planned form has no kernel handle and nothing beneath it: refused with a message
   int cw = 1, tb = 32, res_p = -1;
   long long nblk = 0;
   bool wide_switched = false;  // two chains per workgroup BECAUSE the observation-sharded sweep pays
@@ -171,7 +174,7 @@ static bool stream_fed(Form f) {
 static const char* kernel_name(const Route& R) {
   static const char* const name[] = {"big-k", "resident", "streamed", "long-sharded", "mfma", "mfma-streamed", "mfma-adaptive", "lat",
       "lat-logit", "spec", "spec-logit", "streamed-logistic", "logistic-sharded", "logistic-shadow", "streamed-wide",
-      "streamed-wide-sharded", "streamed-wide-sharded-mfma", "wide-dataflow"};
+      "streamed-wide-sharded", "streamed-wide-sharded-mfma", "wide-dataflow", "big-k-hbm"};
   // (the register forms by their chains per workgroup: lat1 .. lat4, lat-logit1 .. 4; spec-lat1 .. 3 | spec, spec-logit-lat1 .. 3 | spec-logit)
   static const char* const by_cw[4][4] = {{"lat1", "lat2", "lat3", "lat4"}, {"lat-logit1", "lat-logit2", "lat-logit3", "lat-logit4"},
       {"spec-lat1", "spec-lat2", "spec-lat3", "spec"}, {"spec-logit-lat1", "spec-logit-lat2", "spec-logit-lat3", "spec-logit"}};
@@ -186,12 +189,17 @@ static const char* kernel_name(const Route& R) {
 static Route plan_route(const fmcmc_model* m, const fmcmc_kernel* kn, const fmcmc_run* run, int kf, int ram_bounded, int kz, long long ldS,
                         int ncu, const Knobs& K) {
   Route R;
-  // more parameters than a wavefront has lanes: one workgroup per chain (mh_bigk.hpp); fmcmc_validate has refused what it lacks
+  // more parameters than a wavefront has lanes: one workgroup per chain (mh_bigk.hpp); fmcmc_validate has refused what it lacks.
+  // Its matrices in LDS wherever they fit (every k <= 128; kernel_adapt up to 133, kernel_ram up to 183 free parameters),
+  // in the chain's own Sigma square in HBM beyond (knob bigkhbm=1: always)
   if (kn->k > FMCMC_MAX_K_WAVE) {
-    R.form = R.base = Form::BIGK;
-    R.kfn = R.kfn_base = fmh::k_bigk();
-    R.lds = sizeof(double) * bigk_lds_doubles(kn->k, kf, kn->kind);
+    const size_t lds = sizeof(double) * bigk_lds_doubles(kn->k, kf, kn->kind);
+    const bool hbm = K.bigkhbm == 1 || lds > 160 * 1024;
+    R.form = R.base = hbm ? Form::BIGK_HBM : Form::BIGK;
+    R.kfn = R.kfn_base = fmh::k_bigk(hbm ? 1 : 0);
+    R.lds = hbm ? sizeof(double) * bigk_lds_doubles(kn->k, kf, kn->kind, true) : lds;
     R.lds_exceeded = R.lds > 160 * 1024;
+    R.no_kernel = R.kfn == nullptr;
     return R;
   }
   const bool mirror = (kn->kind == FMCMC_KERNEL_NMIRROR || kn->kind == FMCMC_KERNEL_UMIRROR);

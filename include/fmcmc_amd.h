@@ -37,10 +37,13 @@ extern "C" {
 #endif
 
 #define FMCMC_ABI_VERSION 6
-#define FMCMC_MAX_K 128 /* parameters per chain supported by the device kernels (R/kernel_ram.R:93-121, R/kernel_adapt.R:87-115: any k) */
+#define FMCMC_MAX_K 256 /* parameters per chain supported by the device kernels (R/kernel_ram.R:93-121, R/kernel_adapt.R:87-115: any k) */
 /* Up to FMCMC_MAX_K_WAVE parameters a chain's rows live in the lanes of one wavefront and every kernel, scheme and option is
  * available; from there to FMCMC_MAX_K one workgroup serves a chain (mh_sweep_bigk): kernel_normal(_reflective) /
  * kernel_unif(_reflective) with scheme = "joint", kernel_adapt(bw = 0, freq = 1), kernel_ram -- anything else is refused above FMCMC_MAX_K_WAVE with FMCMC_ERR_UNSUPPORTED;
+ * its matrices live in LDS while they fit and in the chain's own Sigma buffer beyond (kernel_adapt from 134, kernel_ram from 184
+ * free parameters).  Raised from 128 to 256 under the same FMCMC_ABI_VERSION: no struct, signature or buffer layout changed
+ * (INTEGRATION.md); 256 and not more because the host oracle's stack frame grows as k^2;
  * fmcmc_gelman_partial_dev (MFMA window tiles) takes p <= FMCMC_MAX_K_WAVE columns (above it the host side forms the same partial
  * sums itself, fmcmc_amd/convergence.py), fmcmc_gelman_finish any p <= FMCMC_MAX_K. */
 #define FMCMC_MAX_K_WAVE 64
