@@ -17,7 +17,7 @@ SIMPLE_KERNELS = (KERNEL_NORMAL, KERNEL_NORMAL_REFLECTIVE, KERNEL_UNIF, KERNEL_U
 SCHEME_JOINT, SCHEME_ORDERED, SCHEME_RANDOM, SCHEME_EXPLICIT = 0, 1, 2, 3
 ABI_VERSION = 6
 RNG_PHILOX, RNG_FED = 0, 1
-OK, ERR_ARG, ERR_DEVICE, ERR_CHAIN, ERR_UNSUPPORTED = 0, 1, 2, 3, 4
+OK, ERR_ARG, ERR_DEVICE, ERR_CHAIN, ERR_UNSUPPORTED, ERR_FUN = 0, 1, 2, 3, 4, 5
 CHAIN_OK, CHAIN_NAN_LOGPOST, CHAIN_NAN_RATIO, CHAIN_NOT_PD, CHAIN_BAD_WINDOW, CHAIN_SYNC_TIMEOUT = 0, 1, 2, 3, 4, 5
 MAX_K = 256        # (FMCMC_MAX_K; every kernel / option up to MAX_K_WAVE, the joint simple kernels, kernel_adapt and kernel_ram beyond)
 MAX_K_WAVE = 64
@@ -25,7 +25,11 @@ MAX_K_WAVE = 64
 EXPORTS = ["fmcmc_abi_version", "fmcmc_last_error", "fmcmc_last_kernel", "fmcmc_device_count", "fmcmc_kept_rows",
            "fmcmc_validate", "fmcmc_mcmc_run_dev", "fmcmc_mcmc_run_host", "fmcmc_gelman_partial_len",
            "fmcmc_gelman_work_len",
-           "fmcmc_gelman_partial_dev", "fmcmc_gelman_finish", "fmcmc_detmath_dev", "fmcmc_rng_stream_dev"]
+           "fmcmc_gelman_partial_dev", "fmcmc_gelman_finish", "fmcmc_detmath_dev", "fmcmc_rng_stream_dev",
+           "fmcmc_validate_fun", "fmcmc_mcmc_run_fun_dev", "fmcmc_mcmc_run_fun_host"]
+
+# fmcmc_logpost_fn: out[c] = log f(theta[c][0..k-1]) for c < nchains; 0 = ok (theta, out, hip_stream, user: addresses)
+LOGPOST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p)
 
 
 class Model(C.Structure):
@@ -96,6 +100,14 @@ def lib():
                                          C.POINTER(State), C.POINTER(Out), C.c_void_p]
         L.fmcmc_mcmc_run_host.argtypes = [C.POINTER(Model), C.POINTER(Kernel), C.POINTER(Run),
                                           C.POINTER(State), C.POINTER(Out), C.c_int]
+        L.fmcmc_validate_fun.restype = C.c_int
+        L.fmcmc_validate_fun.argtypes = [C.POINTER(Kernel), C.POINTER(Run)]
+        L.fmcmc_mcmc_run_fun_dev.restype = C.c_int
+        L.fmcmc_mcmc_run_fun_dev.argtypes = [C.POINTER(Kernel), C.POINTER(Run), C.POINTER(State), C.POINTER(Out),
+                                             LOGPOST_FN, C.c_void_p, C.c_void_p]
+        L.fmcmc_mcmc_run_fun_host.restype = C.c_int
+        L.fmcmc_mcmc_run_fun_host.argtypes = [C.POINTER(Kernel), C.POINTER(Run), C.POINTER(State), C.POINTER(Out),
+                                              LOGPOST_FN, C.c_void_p, C.c_int]
         L.fmcmc_gelman_partial_len.restype = C.c_int64
         L.fmcmc_gelman_partial_len.argtypes = [C.c_int32]
         L.fmcmc_gelman_partial_dev.restype = C.c_int

@@ -1,0 +1,9 @@
+// k_fun.hip -- mh_fun_step<NTH> (mh_fun.hpp: the sweep around a caller-evaluated log-posterior, fmcmc_mcmc_run_fun_*):
+// NTH = 64 (k <= 64, one wavefront per chain) and 256 (k > 64, one workgroup per chain)
+#define FMH_WITH_FUN_KERNEL
+#include "mh_tu.hpp"
+#include "mh_fun.hpp"
+
+namespace fmh {
+const void* k_fun(int nth) { return nth == 64 ? (const void*)mh_fun_step<64> : nth == 256 ? (const void*)mh_fun_step<256> : nullptr; }
+}  // namespace fmh

@@ -36,6 +36,7 @@
 #include "mh_mfma_ad.hpp"
 #include "mh_bigk.hpp"
 #include "mh_route.hpp"   // (kernel selection: plan_route)
+#include "mh_fun.hpp"     // (the callback path: FunArgs, its LDS size; mh_fun_step is instantiated in k_fun.hip)
 
 namespace {
 
@@ -208,6 +209,14 @@ static void fill_rng(const fmcmc_run* run, long long step_base, long long nchain
                      (long long)run->chain_base, nchains, nsteps, kz, df, ws, ws + items);
 }
 
+// the free parameters which(!fixed) of a kernel, 0-based, into which[0 .. kf) (the callback path, once per call)
+__global__ void fun_which_kernel(const uint8_t* fixed, int k, int* which) {
+  if (threadIdx.x != 0) return;
+  int kf = 0;
+  for (int j = 0; j < k; j++)
+    if (!fixed[j]) which[kf++] = j;
+}
+
 // accept counts of a continuation window (step windows, launch_sweep) added to the call's
 __global__ void add_counts_kernel(long long* total, const long long* part, long long n) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -254,8 +263,8 @@ static int variates_per_step(const fmcmc_kernel* kn, int kf) {  // single-parame
   return (is_simple_kind(kn->kind) && kn->scheme != FMCMC_SCHEME_JOINT) ? 1 : kf;
 }
 
-int fmcmc_validate(const fmcmc_model* m, const fmcmc_kernel* kn, const fmcmc_run* run) {
-  if (!m || !kn || !run) { set_err("null argument"); return FMCMC_ERR_ARG; }
+// the run arguments and the parameter count (R/mcmc.R:501-520), the checks fmcmc_validate and fmcmc_validate_fun share first
+static int validate_run(const fmcmc_kernel* kn, const fmcmc_run* run) {
   if (run->nchains < 1) { set_err("`nchains` must be an integer greater than 1."); return FMCMC_ERR_ARG; }
   if (run->burnin >= run->nsteps) {
     set_err("-burnin- (%lld) cannot be >= than -nsteps- (%lld).", (long long)run->burnin, (long long)run->nsteps);
@@ -270,6 +279,16 @@ int fmcmc_validate(const fmcmc_model* m, const fmcmc_kernel* kn, const fmcmc_run
     set_err("number of parameters k=%d outside [1, %d]", kn->k, FMCMC_MAX_K);
     return FMCMC_ERR_UNSUPPORTED;
   }
+  return FMCMC_OK;
+}
+
+// the kernel's own arguments (R/kernel.R:9,129-132, R/kernel_normal.R:134-135, ...) and the fed stream, shared as well
+static int validate_kernel(const fmcmc_kernel* kn, const fmcmc_run* run);
+
+int fmcmc_validate(const fmcmc_model* m, const fmcmc_kernel* kn, const fmcmc_run* run) {
+  if (!m || !kn || !run) { set_err("null argument"); return FMCMC_ERR_ARG; }
+  const int rr = validate_run(kn, run);
+  if (rr != FMCMC_OK) return rr;
   if (kn->k > FMCMC_MAX_K_WAVE) {   // one workgroup per chain (mh_sweep_bigk): what it implements
     const bool simple_joint = (kn->kind <= FMCMC_KERNEL_NORMAL_REFLECTIVE || kn->kind == FMCMC_KERNEL_UNIF || kn->kind == FMCMC_KERNEL_UNIF_REFLECTIVE) &&
                               kn->scheme == FMCMC_SCHEME_JOINT;
@@ -292,6 +311,10 @@ int fmcmc_validate(const fmcmc_model* m, const fmcmc_kernel* kn, const fmcmc_run
     return FMCMC_ERR_ARG;
   }
   if (m->n < 1) { set_err("the model needs at least one observation"); return FMCMC_ERR_ARG; }
+  return validate_kernel(kn, run);
+}
+
+static int validate_kernel(const fmcmc_kernel* kn, const fmcmc_run* run) {
   if (kn->kind < FMCMC_KERNEL_NORMAL || kn->kind > FMCMC_KERNEL_UMIRROR) {
     set_err("unknown kernel kind %d", kn->kind);
     return FMCMC_ERR_ARG;
@@ -799,17 +822,11 @@ int fmcmc_detmath_dev(int which, const double* x, double* out, int64_t n, uint64
   return hipGetLastError() == hipSuccess ? FMCMC_OK : FMCMC_ERR_DEVICE;
 }
 
-int fmcmc_mcmc_run_dev(const fmcmc_model* m, const fmcmc_kernel* kn, const fmcmc_run* run,
-                       fmcmc_state* st, fmcmc_out* out, void* hip_stream) {
-  if (!m || !kn || !run || !st || !out) { set_err("null argument"); return FMCMC_ERR_ARG; }
-  // `fixed`, `lb`, `ub` (and scale / scheme_seq where they are checked) live on the device.  A caller that passes their
-  // host copies (fmcmc_kernel.h_*) gets a call that only enqueues work; otherwise the few bytes are read back here, which
-  // synchronises the stream.
-  uint8_t fx[MAXK];
-  double lb[MAXK], ub[MAXK], sc[MAXK];
-  int32_t seq[MAXK];
+// Reads the kernel arrays the host side needs (fixed, lb, ub; scale of the uniform kernels; scheme_seq) from their host mirrors,
+// or from the device, which synchronises `stream` (fmcmc_mcmc_run_dev's rule), and returns a copy of *kn pointing at them.
+static int kernel_host_view(const fmcmc_kernel* kn, hipStream_t stream, uint8_t* fx, double* lb, double* ub, double* sc, int32_t* seq,
+                            fmcmc_kernel* kh) {
   if (kn->k < 1 || kn->k > MAXK) { set_err("k=%d outside [1,%d]", kn->k, MAXK); return FMCMC_ERR_UNSUPPORTED; }
-  hipStream_t stream = (hipStream_t)hip_stream;
   const bool unif = (kn->kind == FMCMC_KERNEL_UNIF || kn->kind == FMCMC_KERNEL_UNIF_REFLECTIVE);
   const bool expl = (is_simple_kind(kn->kind) && kn->scheme == FMCMC_SCHEME_EXPLICIT && kn->scheme_seq &&
                      kn->scheme_len >= 1 && kn->scheme_len <= MAXK);
@@ -829,10 +846,26 @@ int fmcmc_mcmc_run_dev(const fmcmc_model* m, const fmcmc_kernel* kn, const fmcmc
     set_err("cannot read kernel parameters from device memory");
     return FMCMC_ERR_DEVICE;
   }
-  fmcmc_kernel kh = *kn;
-  kh.fixed = fx; kh.lb = lb; kh.ub = ub;
-  kh.scale = unif ? sc : nullptr;
-  kh.scheme_seq = expl ? seq : nullptr;
+  *kh = *kn;
+  kh->fixed = fx; kh->lb = lb; kh->ub = ub;
+  kh->scale = unif ? sc : nullptr;
+  kh->scheme_seq = expl ? seq : nullptr;
+  return FMCMC_OK;
+}
+
+int fmcmc_mcmc_run_dev(const fmcmc_model* m, const fmcmc_kernel* kn, const fmcmc_run* run,
+                       fmcmc_state* st, fmcmc_out* out, void* hip_stream) {
+  if (!m || !kn || !run || !st || !out) { set_err("null argument"); return FMCMC_ERR_ARG; }
+  // `fixed`, `lb`, `ub` (and scale / scheme_seq where they are checked) live on the device.  A caller that passes their
+  // host copies (fmcmc_kernel.h_*) gets a call that only enqueues work; otherwise the few bytes are read back here, which
+  // synchronises the stream.
+  uint8_t fx[MAXK];
+  double lb[MAXK], ub[MAXK], sc[MAXK];
+  int32_t seq[MAXK];
+  hipStream_t stream = (hipStream_t)hip_stream;
+  fmcmc_kernel kh;
+  const int rv = kernel_host_view(kn, stream, fx, lb, ub, sc, seq, &kh);
+  if (rv != FMCMC_OK) return rv;
   int rc = fmcmc_validate(m, &kh, run);
   if (rc != FMCMC_OK) return rc;
   int kf = count_free(kn, fx);
@@ -992,6 +1025,288 @@ int fmcmc_mcmc_run_host(const fmcmc_model* m, const fmcmc_kernel* kn, const fmcm
       break;
     }
 done:
+  for (void* p : allocs) hipFree(p);
+  if (stream) hipStreamDestroy(stream);
+  return rc;
+}
+
+// ==============================================================================================
+// user-defined log-posteriors: the sweep around a batched callback (fmcmc_logpost_fn; mh_fun.hpp)
+// ==============================================================================================
+int fmcmc_validate_fun(const fmcmc_kernel* kn, const fmcmc_run* run) {
+  if (!kn || !run) { set_err("null argument"); return FMCMC_ERR_ARG; }
+  const int rr = validate_run(kn, run);
+  if (rr != FMCMC_OK) return rr;
+  if (kn->kind == FMCMC_KERNEL_NMIRROR || kn->kind == FMCMC_KERNEL_UMIRROR) {
+    set_err("a user-defined -fun- runs with kernel_normal(_reflective), kernel_unif(_reflective), kernel_adapt(bw = 0, freq = 1) "
+            "and kernel_ram; the mirror kernels are not supported on this path");
+    return FMCMC_ERR_UNSUPPORTED;
+  }
+  if (kn->kind == FMCMC_KERNEL_ADAPT && (kn->bw > 0 || kn->freq > 1)) {
+    set_err("a user-defined -fun- runs kernel_adapt with bw = 0 and freq = 1 only (got bw=%d, freq=%d): the windowed and the "
+            "strided adaptation are not supported on this path", kn->bw, kn->freq);
+    return FMCMC_ERR_UNSUPPORTED;
+  }
+  return validate_kernel(kn, run);
+}
+
+// The call: every pointer of kn / run / st / out is a DEVICE pointer (fx, lb, ub: host copies of the kernel's).  host_fun: `fun`
+// takes host buffers (the theta1 of every chain is copied out and f(theta1) back in around each evaluation).
+static int run_fun(const fmcmc_kernel* kn, const uint8_t* fx, const double* lb, const double* ub, const fmcmc_run* run,
+                   fmcmc_state* st, fmcmc_out* out, fmcmc_logpost_fn fun, void* user, hipStream_t stream, bool host_fun) {
+  if (!fun) { set_err("null log-posterior callback"); return FMCMC_ERR_ARG; }
+  const int k = kn->k, kf = count_free(kn, fx);
+  const long long C = run->nchains;
+  const bool adapt = kn->kind == FMCMC_KERNEL_ADAPT, ram = kn->kind == FMCMC_KERNEL_RAM;
+  if ((adapt || ram) && (!st->Sigma || !st->abs_iter || (adapt && (!st->mean_prev || !st->have_mean)))) {
+    set_err("kernel_adapt / kernel_ram need state->Sigma and abs_iter (kernel_adapt: mean_prev and have_mean as well)");
+    return FMCMC_ERR_ARG;
+  }
+  if (is_simple_kind(kn->kind) && kn->scheme == FMCMC_SCHEME_RANDOM && run->rng_mode == FMCMC_RNG_FED && !st->scheme_cols) {
+    set_err("rng_mode = FED with scheme = 'random' needs state->scheme_cols");
+    return FMCMC_ERR_ARG;
+  }
+  int bounded = 0;
+  for (int j = 0; j < k; j++)
+    if (!fx[j] && (lb[j] > -DBL_MAX || ub[j] < DBL_MAX)) bounded = 1;
+  FunArgs A;
+  memset(&A, 0, sizeof(A));
+  A.kind = kn->kind; A.k = k; A.kf = kf; A.scheme = kn->scheme; A.warmup = kn->warmup; A.freq = kn->freq < 1 ? 1 : kn->freq;
+  A.scheme_len = kn->scheme_len; A.ram_bounded = ram ? bounded : 0;
+  A.until = kn->until; A.eps = kn->eps; A.arate = kn->arate;
+  A.ram_df = (kn->ram_qfun == FMCMC_RAM_QFUN_NORMAL) ? 0.0 : (kn->ram_qfun == FMCMC_RAM_QFUN_T_DF ? kn->ram_df : (double)kf);
+  A.ram_neg_exp = (kn->ram_eta_exp != 0.0) ? -kn->ram_eta_exp : (-2.0 / 3.0);
+  A.mu = kn->mu; A.scale = kn->scale; A.lb = kn->lb; A.ub = kn->ub; A.scheme_seq = kn->scheme_seq;
+  A.constr = ram ? kn->constr : nullptr;
+  A.nchains = C; A.nsteps = run->nsteps; A.burnin = run->burnin; A.thin = run->thin;
+  const long long S = fmcmc_kept_rows(run->nsteps, run->burnin, run->thin);
+  A.ldS = out->ld_rows > 0 ? out->ld_rows : S;
+  if (A.ldS < S) { set_err("fmcmc_out.ld_rows (%lld) is smaller than the %lld kept rows of this call", (long long)out->ld_rows, S); return FMCMC_ERR_ARG; }
+  A.chain_base = run->chain_base; A.step_base = run->step_base; A.seed = run->seed;
+  A.rng_mode = run->rng_mode; A.kz = variates_per_step(kn, kf); A.fresh = st->fresh;
+  A.fed_logu = run->fed_logu; A.fed_z = run->fed_z;
+  A.theta0 = st->theta0; A.f0 = st->f0; A.abs_iter = (long long*)st->abs_iter; A.Sigma = st->Sigma; A.mean_prev = st->mean_prev;
+  A.have_mean = st->have_mean; A.nerrors = st->nerrors; A.scheme_cols = st->scheme_cols;
+  A.samples = out->samples; A.logpost = out->logpost; A.draws = out->draws; A.accept_count = (long long*)out->accept_count;
+  A.accept_bits = out->accept_bits; A.status = out->status; A.status_step = (long long*)out->status_step; A.status_theta = out->status_theta;
+  {   // the code object is gfx950 only
+    int dev = 0;
+    hipDeviceProp_t prop;
+    (void)hipGetDevice(&dev);
+    if (hipGetDeviceProperties(&prop, dev) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+      set_err("this library is built for gfx950 (MI355X); the current device is another architecture");
+      return FMCMC_ERR_DEVICE;
+    }
+  }
+  // scratch of the call: theta1 [C][k] and f(theta1) [C] (what `fun` reads and writes), kernel_adapt's running row sum [C][kf],
+  // nerrors [C] when the caller keeps none, the free-parameter list [kf]
+  const size_t n_th = (size_t)C * k, n_rs = adapt ? (size_t)C * kf : 0, n_ne = ((adapt || ram) && !st->nerrors) ? (size_t)C : 0;
+  const size_t bytes = sizeof(double) * (n_th + (size_t)C + n_rs) + sizeof(int) * (n_ne + (size_t)kf);
+  AsyncScratch scr;
+  if (hipMallocAsync(&scr.p, bytes, stream) != hipSuccess) {
+    (void)hipGetLastError();
+    set_err("hipMallocAsync(%zu) for the callback sweep failed", bytes);
+    return FMCMC_ERR_DEVICE;
+  }
+  scr.s = stream;
+  double* th1 = (double*)scr.p;
+  double* f1 = th1 + n_th;
+  A.rsum = adapt ? f1 + C : nullptr;
+  int* ne = (int*)(f1 + C + n_rs);
+  int* which = ne + n_ne;
+  if (n_ne) { A.nerrors = ne; (void)hipMemsetAsync(ne, 0, sizeof(int) * n_ne, stream); }
+  A.which = which; A.th1 = th1; A.f1 = f1;
+  hipLaunchKernelGGL(fun_which_kernel, dim3(1), dim3(64), 0, stream, kn->fixed, k, which);
+  (void)hipMemcpyAsync(th1, st->theta0, sizeof(double) * n_th, hipMemcpyDeviceToDevice, stream);   // row 1: f(initial)
+
+  const int nth = (k <= FMCMC_MAX_K_WAVE) ? 64 : 256;
+  const void* kfn = fmh::k_fun(nth);
+  const size_t lds = sizeof(double) * fun_lds_doubles(k, kf, kn->kind, nth);
+  if (!kfn) { set_err("no device kernel for the callback sweep (k=%d)", k); return FMCMC_ERR_DEVICE; }
+  if (lds > 48 * 1024 && hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    (void)hipGetLastError();
+    set_err("LDS budget exceeded (k=%d)", k);
+    return FMCMC_ERR_UNSUPPORTED;
+  }
+  g_kernel = (nth == 64) ? "fun" : "fun-wg";
+  std::vector<double> h_th, h_f;
+  if (host_fun) { h_th.resize(n_th); h_f.resize((size_t)C); }
+  auto evaluate = [&](long long step) -> int {
+    int rc;
+    if (host_fun) {
+      if (hipMemcpyAsync(h_th.data(), th1, sizeof(double) * n_th, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+          hipStreamSynchronize(stream) != hipSuccess) {
+        set_err("cannot read the proposals of loop step i = %lld back from the device", step);
+        return FMCMC_ERR_DEVICE;
+      }
+      rc = fun(h_th.data(), (int64_t)C, (int32_t)k, h_f.data(), (void*)stream, user);
+      if (rc == 0 && hipMemcpyAsync(f1, h_f.data(), sizeof(double) * (size_t)C, hipMemcpyHostToDevice, stream) != hipSuccess) {
+        set_err("cannot copy the log-posterior of loop step i = %lld to the device", step);
+        return FMCMC_ERR_DEVICE;
+      }
+    } else {
+      rc = fun(th1, (int64_t)C, (int32_t)k, f1, (void*)stream, user);
+    }
+    if (rc != 0) {
+      set_err("the log-posterior callback returned %d at loop step i = %lld%s", rc, step, step == 1 ? " (row 1: the initial values)" : "");
+      return FMCMC_ERR_FUN;
+    }
+    return FMCMC_OK;
+  };
+  auto launch = [&](long long step, int phase) -> int {
+    A.step = step; A.phase = phase;
+    void* kargs[] = {(void*)&A};
+    hipError_t e = hipLaunchKernel(kfn, dim3((unsigned)C), dim3((unsigned)nth), kargs, lds, stream);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) { set_err("HIP launch failed at loop step i = %lld: %s", step, hipGetErrorString(e)); return FMCMC_ERR_DEVICE; }
+    return FMCMC_OK;
+  };
+  const long long nsteps = run->nsteps;
+  int rc = evaluate(1);
+  if (rc == FMCMC_OK) rc = launch(1, FPH_START | (nsteps >= 2 ? FPH_PROPOSE : FPH_FINISH));
+  for (long long i = 2; i <= nsteps && rc == FMCMC_OK; i++) {
+    const int tail = (i < nsteps ? FPH_PROPOSE : FPH_FINISH);
+    rc = evaluate(i);
+    if (rc != FMCMC_OK) break;
+    if (ram && bounded) {   // f(un-reflected theta1) for the adaptation, then f(theta1) (R/kernel_ram.R:129-152)
+      rc = launch(i, FPH_RAM);
+      if (rc == FMCMC_OK) rc = evaluate(i);
+      if (rc == FMCMC_OK) rc = launch(i, FPH_ACCEPT | tail);
+    } else {
+      rc = launch(i, (ram ? FPH_RAM : 0) | FPH_ACCEPT | tail);
+    }
+  }
+  return rc;
+}
+
+int fmcmc_mcmc_run_fun_dev(const fmcmc_kernel* kn, const fmcmc_run* run, fmcmc_state* st, fmcmc_out* out,
+                           fmcmc_logpost_fn fun, void* user, void* hip_stream) {
+  if (!kn || !run || !st || !out) { set_err("null argument"); return FMCMC_ERR_ARG; }
+  hipStream_t stream = (hipStream_t)hip_stream;
+  uint8_t fx[MAXK];
+  double lb[MAXK], ub[MAXK], sc[MAXK];
+  int32_t seq[MAXK];
+  fmcmc_kernel kh;
+  int rc = kernel_host_view(kn, stream, fx, lb, ub, sc, seq, &kh);
+  if (rc != FMCMC_OK) return rc;
+  rc = fmcmc_validate_fun(&kh, run);
+  if (rc != FMCMC_OK) return rc;
+  return run_fun(kn, fx, lb, ub, run, st, out, fun, user, stream, false);
+}
+
+int fmcmc_mcmc_run_fun_host(const fmcmc_kernel* kn, const fmcmc_run* run, fmcmc_state* st, fmcmc_out* out,
+                            fmcmc_logpost_fn fun, void* user, int device) {
+  if (!kn || !run || !st || !out) { set_err("null argument"); return FMCMC_ERR_ARG; }
+  int rc = fmcmc_validate_fun(kn, run);
+  if (rc != FMCMC_OK) return rc;
+  if (!kn->fixed || !kn->lb || !kn->ub || !kn->mu || !kn->scale) { set_err("kernel arrays mu, scale, lb, ub and fixed are required"); return FMCMC_ERR_ARG; }
+  if (fmcmc_device_count() < 1) { set_err("no HIP device: the engine has no CPU fallback"); return FMCMC_ERR_DEVICE; }
+  const int k = kn->k;
+  const int kf = count_free(kn, kn->fixed);
+  const int64_t C = run->nchains, S = fmcmc_kept_rows(run->nsteps, run->burnin, run->thin);
+  const int64_t nwords = (run->nsteps + 31) / 32;
+  const bool adaptive = (kn->kind == FMCMC_KERNEL_ADAPT || kn->kind == FMCMC_KERNEL_RAM);
+  if (adaptive && (!st->Sigma || !st->abs_iter || !st->mean_prev || !st->have_mean)) {
+    set_err("kernel_adapt / kernel_ram need state->Sigma, abs_iter, mean_prev and have_mean");
+    return FMCMC_ERR_ARG;
+  }
+  if (out->ld_rows != 0 && out->ld_rows != S) { set_err("fmcmc_out.ld_rows is honoured by fmcmc_mcmc_run_fun_dev only (host buffers are dense)"); return FMCMC_ERR_ARG; }
+  std::vector<void*> allocs;
+  auto dalloc = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    if (bytes == 0) bytes = 8;
+    if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
+    allocs.push_back(p);
+    return p;
+  };
+  fmcmc_kernel dk = *kn;
+  fmcmc_run dr = *run;
+  fmcmc_state ds = *st;
+  fmcmc_out dout = *out;
+  dout.ld_rows = 0;
+  hipStream_t stream = nullptr;
+  HCHK(hipSetDevice(device));
+  HCHK(hipStreamCreate(&stream));
+#define UP(dst, src, bytes)                                                                  \
+  do {                                                                                       \
+    void* p_ = dalloc(bytes);                                                                \
+    if (!p_) { set_err("hipMalloc(%zu) failed", (size_t)(bytes)); rc = FMCMC_ERR_DEVICE; goto done; } \
+    if ((src) != nullptr) HCHK(hipMemcpyAsync(p_, (src), (bytes), hipMemcpyHostToDevice, stream)); \
+    dst = (decltype(dst))p_;                                                                 \
+  } while (0)
+  UP(dk.mu, kn->mu, sizeof(double) * k);
+  UP(dk.scale, kn->scale, sizeof(double) * k);
+  UP(dk.lb, kn->lb, sizeof(double) * k);
+  UP(dk.ub, kn->ub, sizeof(double) * k);
+  UP(dk.fixed, kn->fixed, (size_t)k);
+  if (kn->scheme_seq && kn->scheme_len > 0) UP(dk.scheme_seq, kn->scheme_seq, sizeof(int32_t) * (size_t)kn->scheme_len);
+  if (kn->constr && kn->kind == FMCMC_KERNEL_RAM) UP(dk.constr, kn->constr, sizeof(double) * (size_t)kf * kf);
+  if (st->scheme_cols) UP(ds.scheme_cols, st->scheme_cols, sizeof(int32_t) * (size_t)C * run->nsteps);
+  if (run->rng_mode == FMCMC_RNG_FED) {
+    const int kz = variates_per_step(kn, kf);
+    UP(dr.fed_logu, run->fed_logu, sizeof(double) * (size_t)C * run->nsteps);
+    UP(dr.fed_z, run->fed_z, sizeof(double) * (size_t)C * run->nsteps * kz);
+  }
+  UP(ds.theta0, st->theta0, sizeof(double) * (size_t)C * k);
+  UP(ds.f0, (double*)nullptr, sizeof(double) * (size_t)C);
+  if (adaptive) {
+    UP(ds.abs_iter, st->fresh ? nullptr : st->abs_iter, sizeof(int64_t) * (size_t)C);
+    UP(ds.Sigma, st->fresh ? nullptr : st->Sigma, sizeof(double) * (size_t)C * kf * kf);
+    UP(ds.mean_prev, st->fresh ? nullptr : st->mean_prev, sizeof(double) * (size_t)C * kf);
+    UP(ds.have_mean, st->fresh ? nullptr : st->have_mean, sizeof(int32_t) * (size_t)C);
+    UP(ds.nerrors, (st->fresh || !st->nerrors) ? nullptr : st->nerrors, sizeof(int32_t) * (size_t)C);
+    if (st->fresh || !st->nerrors) HCHK(hipMemsetAsync(ds.nerrors, 0, sizeof(int32_t) * (size_t)C, stream));
+  }
+  UP(dout.samples, (double*)nullptr, sizeof(double) * (size_t)C * k * S);
+  HCHK(hipMemsetAsync(dout.samples, 0xff, sizeof(double) * (size_t)C * k * S, stream));  // NaN fill
+  if (out->logpost) UP(dout.logpost, (double*)nullptr, sizeof(double) * (size_t)C * S);
+  if (out->draws) UP(dout.draws, (double*)nullptr, sizeof(double) * (size_t)C * k * S);
+  UP(dout.accept_count, (int64_t*)nullptr, sizeof(int64_t) * (size_t)C);
+  if (out->accept_bits) UP(dout.accept_bits, (uint32_t*)nullptr, sizeof(uint32_t) * (size_t)C * nwords);
+  UP(dout.status, (int32_t*)nullptr, sizeof(int32_t) * (size_t)C);
+  UP(dout.status_step, (int64_t*)nullptr, sizeof(int64_t) * (size_t)C);
+  UP(dout.status_theta, (double*)nullptr, sizeof(double) * (size_t)C * k);
+  HCHK(hipMemsetAsync(dout.status_theta, 0, sizeof(double) * (size_t)C * k, stream));
+#undef UP
+  rc = run_fun(&dk, kn->fixed, kn->lb, kn->ub, &dr, &ds, &dout, fun, user, stream, true);
+  if (rc != FMCMC_OK) goto done;
+#define DOWN(dst, src, bytes) HCHK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, stream))
+  DOWN(st->theta0, ds.theta0, sizeof(double) * (size_t)C * k);
+  DOWN(st->f0, ds.f0, sizeof(double) * (size_t)C);
+  if (adaptive) {
+    DOWN(st->abs_iter, ds.abs_iter, sizeof(int64_t) * (size_t)C);
+    DOWN(st->Sigma, ds.Sigma, sizeof(double) * (size_t)C * kf * kf);
+    DOWN(st->mean_prev, ds.mean_prev, sizeof(double) * (size_t)C * kf);
+    DOWN(st->have_mean, ds.have_mean, sizeof(int32_t) * (size_t)C);
+    if (st->nerrors) DOWN(st->nerrors, ds.nerrors, sizeof(int32_t) * (size_t)C);
+  }
+  if (st->scheme_cols && run->rng_mode != FMCMC_RNG_FED && is_simple_kind(kn->kind) && kn->scheme == FMCMC_SCHEME_RANDOM)
+    DOWN(st->scheme_cols, ds.scheme_cols, sizeof(int32_t) * (size_t)C * run->nsteps);
+  DOWN(out->samples, dout.samples, sizeof(double) * (size_t)C * k * S);
+  if (out->logpost) DOWN(out->logpost, dout.logpost, sizeof(double) * (size_t)C * S);
+  if (out->draws) DOWN(out->draws, dout.draws, sizeof(double) * (size_t)C * k * S);
+  DOWN(out->accept_count, dout.accept_count, sizeof(int64_t) * (size_t)C);
+  if (out->accept_bits) DOWN(out->accept_bits, dout.accept_bits, sizeof(uint32_t) * (size_t)C * nwords);
+  DOWN(out->status, dout.status, sizeof(int32_t) * (size_t)C);
+  DOWN(out->status_step, dout.status_step, sizeof(int64_t) * (size_t)C);
+  DOWN(out->status_theta, dout.status_theta, sizeof(double) * (size_t)C * k);
+#undef DOWN
+  HCHK(hipStreamSynchronize(stream));
+  st->fresh = 0;
+  for (int64_t c = 0; c < C; c++)
+    if (out->status[c] != FMCMC_CHAIN_OK) {
+      const char* what = out->status[c] == FMCMC_CHAIN_NAN_LOGPOST ? "fun(par) is undefined (NaN)."
+                       : out->status[c] == FMCMC_CHAIN_NAN_RATIO ? "fun(par) is undefined (f1 - f0 is NaN)."
+                       : out->status[c] == FMCMC_CHAIN_NOT_PD ? "'Sigma' is not positive definite." : "fun(par) is undefined.";
+      const bool nan_status = out->status[c] == FMCMC_CHAIN_NAN_LOGPOST || out->status[c] == FMCMC_CHAIN_NAN_RATIO;
+      set_err("%s (chain %lld, status %d).%s This error ocurred during step i = %lld",
+              what, (long long)(run->chain_base + c), out->status[c],
+              nan_status ? " Check either -fun- or the -lb- and -ub- parameters." : "", (long long)out->status_step[c]);
+      rc = FMCMC_ERR_CHAIN;
+      break;
+    }
+done:
+  if (stream) (void)hipStreamSynchronize(stream);   // (the call's stream-ordered scratch is released before its buffers)
   for (void* p : allocs) hipFree(p);
   if (stream) hipStreamDestroy(stream);
   return rc;

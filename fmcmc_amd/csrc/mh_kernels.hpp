@@ -49,4 +49,6 @@ FMH_HIDDEN size_t k_lat_logit_lds();
 // k_wide2.hip: mh_sweep_wide2<KIND, NMT> (kind 1, 2, 4; nmt 1..3) and mh_sweep_bigk<HBM> (hbm 0: matrices in LDS, 1: in HBM)
 FMH_HIDDEN const void* k_wide2(int kind, int nmt);
 FMH_HIDDEN const void* k_bigk(int hbm);
+// k_fun.hip: mh_fun_step<NTH> (mh_fun.hpp), the steps around a caller-evaluated log-posterior: nth = 64 (k <= 64), 256 (k > 64)
+FMH_HIDDEN const void* k_fun(int nth);
 }  // namespace fmh

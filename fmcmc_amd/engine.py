@@ -67,6 +67,63 @@ class DeviceModel:
                          self.y.data_ptr(), self.intercept, self.guard, self.prior_div)
 
 
+class DeviceFun:
+    """A batched user-defined log-posterior (models.BatchedFun) bound to a device: what sweep() hands to
+    fmcmc_mcmc_run_fun_dev instead of a family's fmcmc_model."""
+
+    def __init__(self, fun, device=None):
+        dev = _dev(device)
+        # (an indexed device: what the tensors fn returns report as theirs, device="cuda" included)
+        self.device = dev if dev.index is not None else torch.device(dev.type, torch.cuda.current_device())
+        self.fun, self.k = fun, fun.k
+
+
+class _DevArray:
+    """A device buffer of the engine as a torch tensor, without a copy (__cuda_array_interface__, no stream: no sync)."""
+
+    def __init__(self, ptr, shape):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f8", "data": (int(ptr), False), "version": 2,
+                                         "strides": None}
+
+
+def _run_fun_dev(model, ck, crun, cs, cout, stream):
+    """fmcmc_mcmc_run_fun_dev with model.fun.fn behind a ctypes trampoline: an exception raised in fn is kept, the trampoline
+    returns non-zero (the engine abandons the call, FMCMC_ERR_FUN) and the exception is raised again here.  fn runs with the
+    engine's stream as torch's current stream, so its work is ordered with the engine's launches whatever stream sweep() got."""
+    L = abi.lib()
+    dev, fn = model.device, model.fun.fn
+    caught, views = [], {}
+
+    def view(ptr, shape):
+        key = (ptr, shape)
+        if key not in views:
+            views[key] = torch.as_tensor(_DevArray(ptr, shape), device=dev)
+        return views[key]
+
+    def trampoline(theta_p, nchains, k, out_p, stream_p, user):
+        try:
+            with torch.cuda.stream(stream):
+                th = view(theta_p, (nchains, k))
+                f = fn(th)
+                if not torch.is_tensor(f) or f.dtype != torch.float64 or f.device != dev or tuple(f.shape) != (nchains,):
+                    raise ValueError("batched_fun: fn(theta) must return a float64 tensor of shape [%d] on %s; got %s" % (
+                        nchains, dev, ("%s %s on %s" % (f.dtype, tuple(f.shape), f.device)) if torch.is_tensor(f)
+                        else type(f).__name__))
+                view(out_p, (nchains,)).copy_(f)
+            return 0
+        except BaseException as e:   # (nothing may unwind through the C frames)
+            caught.append(e)
+            return 1
+
+    cb = abi.LOGPOST_FN(trampoline)
+    with torch.cuda.device(dev):
+        rc = L.fmcmc_mcmc_run_fun_dev(C.byref(ck), C.byref(crun), C.byref(cs), C.byref(cout), cb, None,
+                                      C.c_void_p(stream.cuda_stream))
+    if caught:
+        raise caught[0]
+    return rc
+
+
 class KernelSpec:
     """Expanded (recycled) kernel parameters on the device (fmcmc_kernel)."""
 
@@ -168,6 +225,9 @@ def sweep(model, kernel, state, nsteps, burnin=0, thin=1, seed=0, chain_base=0,
     call at rows row0.. of a preallocated history (fmcmc_out.ld_rows = cap) instead of allocating; the result then holds
     views of those rows.
 
+    model: a DeviceModel (a closed-form family) or a DeviceFun (a batched user-defined log-posterior, called between the
+    engine's launches with `stream` as torch's current stream).
+
     Raises ValueError for argument errors (messages mirror the reference's stop() texts) and
     RuntimeError for chain errors ("fun(par) is undefined", R/mcmc.R:758-765)."""
     L = abi.lib()
@@ -211,16 +271,24 @@ def sweep(model, kernel, state, nsteps, burnin=0, thin=1, seed=0, chain_base=0,
         if rng_mode == abi.RNG_FED:
             raise ValueError("rng_mode = FED with scheme = 'random' needs state.scheme_cols (the plan R drew)")
         state.scheme_cols = torch.zeros((Cn, nsteps), dtype=torch.int32, device=dev)
-    cm, ck, cs = model.c(), kernel.c(), state.c(nsteps)
     if stream is None:
         stream = torch.cuda.current_stream(dev)
-    with torch.cuda.device(dev):
-        rc = L.fmcmc_mcmc_run_dev(C.byref(cm), C.byref(ck), C.byref(crun), C.byref(cs), C.byref(cout),
-                                  C.c_void_p(stream.cuda_stream))
+    if isinstance(model, DeviceFun):
+        if k != model.k:
+            raise ValueError("Incorrect length of -initial-: the model has %d parameters, got %d." % (model.k, k))
+        # (the output buffers above were made on the current stream: the engine's stream starts behind them)
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        rc = _run_fun_dev(model, kernel.c(), crun, state.c(nsteps), cout, stream)
+    else:
+        cm, ck, cs = model.c(), kernel.c(), state.c(nsteps)
+        with torch.cuda.device(dev):
+            rc = L.fmcmc_mcmc_run_dev(C.byref(cm), C.byref(ck), C.byref(crun), C.byref(cs), C.byref(cout),
+                                      C.c_void_p(stream.cuda_stream))
     if rc in (abi.ERR_ARG, abi.ERR_UNSUPPORTED):
         raise ValueError(abi.last_error())
     if rc != abi.OK:
-        raise RuntimeError("fmcmc_mcmc_run_dev failed (%d): %s" % (rc, abi.last_error()))
+        entry = "fmcmc_mcmc_run_fun_dev" if isinstance(model, DeviceFun) else "fmcmc_mcmc_run_dev"
+        raise RuntimeError("%s failed (%d): %s" % (entry, rc, abi.last_error()))
     state.fresh = 0
     state.step_base += nsteps
     out.iters = burnin + thin * np.arange(1, S + 1)

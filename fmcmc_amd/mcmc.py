@@ -9,7 +9,8 @@
 
 The per-chain loop itself (R/mcmc.R:720-838) is NOT here: it is the HIP sweep kernel reached through
 engine.sweep() -> C-ABI fmcmc_mcmc_run_dev.  `multicore`/`cl` select nothing on a GPU (all chains of
-the call already run concurrently); with torch.distributed initialised the chains are sharded over
+the call already run concurrently); `fun` is a closed-form family or a batched_fun (a vectorised torch log-posterior the
+engine calls between its kernels' steps); with torch.distributed initialised the chains are sharded over
 the ranks in contiguous blocks (one process per GPU) and RCCL is used only by the Gelman check.
 """
 import time
@@ -20,7 +21,7 @@ import numpy as np
 from . import _abi as abi
 from . import engine
 from .kernels import fmcmc_kernel, kernel_normal
-from .models import LogPosterior
+from .models import BatchedFun, LogPosterior
 
 
 # ------------------------------------------------------------------------------ coda-like containers
@@ -308,18 +309,26 @@ def _run_call(initial_local, fun, nsteps, burnin, thin, kernel, seed, chain_base
     return dc
 
 
+def _fun_names(fun, initial, names):
+    """batched_fun(names=...) names the parameters unless `initial` does (a named vector or a previous result)."""
+    if isinstance(fun, BatchedFun) and fun.names and not isinstance(initial, (dict, McmcList)) and len(fun.names) == len(names):
+        return list(fun.names)
+    return names
+
+
 def MCMC_without_conv_checker(initial, fun, nsteps, nchains=1, burnin=0, thin=1, kernel=None, multicore=False,
                               conv_checker=None, cl=None, progress=False, chain_id=1, seed=0, device=None,
                               _return_device=False, keep_logpost=True, keep_draws=True, fed=None):
     """R/mcmc.R:485-838 for all chains at once."""
     if kernel is None:
         kernel = kernel_normal()
-    if not isinstance(fun, LogPosterior):
+    if not isinstance(fun, (LogPosterior, BatchedFun)):
         raise TypeError("-fun- must be one of the engine's closed-form families (gaussian_linreg, logistic, "
                         "iid_normal): an arbitrary closure cannot run inside the fused GPU kernel.")
     if not isinstance(kernel, fmcmc_kernel):
         raise TypeError("-kernel- must be an fmcmc_kernel (kernel_normal, kernel_normal_reflective, kernel_adapt, kernel_ram).")
     init, names = check_initial(initial, nchains)
+    names = _fun_names(fun, initial, names)
     _validate_common(nsteps, nchains, burnin, thin, multicore)
     if init.shape[1] != fun.k:
         raise ValueError("Incorrect length of -initial-: the model has %d parameters, got %d." % (fun.k, init.shape[1]))
@@ -362,12 +371,15 @@ def MCMC_with_conv_checker(initial, fun, nsteps, nchains, burnin, thin, kernel, 
     bulks[0] += burnin
     if kernel is None:
         kernel = kernel_normal()
-    if not isinstance(fun, LogPosterior):
+    if not isinstance(fun, (LogPosterior, BatchedFun)):
         raise TypeError("-fun- must be one of the engine's closed-form families (gaussian_linreg, logistic, "
                         "iid_normal): an arbitrary closure cannot run inside the fused GPU kernel.")
     if not isinstance(kernel, fmcmc_kernel):
         raise TypeError("-kernel- must be an fmcmc_kernel (kernel_normal, kernel_normal_reflective, kernel_adapt, kernel_ram).")
     init, names = check_initial(initial, nchains)
+    if isinstance(fun, BatchedFun) and init.shape[1] != fun.k:
+        raise ValueError("Incorrect length of -initial-: the model has %d parameters, got %d." % (fun.k, init.shape[1]))
+    names = _fun_names(fun, initial, names)
     dist, rank, world = _dist()
     lo, hi = shard_bounds(nchains, world, rank)
     init_local = init[lo:hi]
@@ -420,7 +432,7 @@ def MCMC(initial, fun, nsteps, *, seed=None, nchains=1, burnin=0, thin=1, kernel
 
     initial: vector, [nchains x k] matrix, or a previous result (Mcmc: its last `nchains` rows,
     R/mcmc.R:344-378; McmcList: each chain's last row, :382-422).  fun: gaussian_linreg / logistic /
-    iid_normal object.  seed: Philox key (None: a fresh one per call; with torch.distributed every rank uses rank 0's).
+    iid_normal object, or batched_fun(fn, k) for any other model.  seed: Philox key (None: a fresh one per call; with torch.distributed every rank uses rank 0's).
     keep_logpost / keep_draws = False: do not record MCMC_OUTPUT's logpost / draws (R always does, R/mcmc.R:822-823; at
     config C4 the draws alone are 2 GB per GPU).  fed: callable (nchains, nsteps, kz, kernel) -> (logu [C][nsteps],
     z [C][nsteps][kz]) supplying the variates of every call instead of the Philox stream (fmcmc_run.rng_mode = FED; one
@@ -441,7 +453,7 @@ def MCMC(initial, fun, nsteps, *, seed=None, nchains=1, burnin=0, thin=1, kernel
         if dist is not None:
             # the RNG is keyed by (seed, GLOBAL chain id): every rank must use the same key or sharding would change the chains
             import torch
-            dev = fun.device_model(device).device if isinstance(fun, LogPosterior) else "cpu"
+            dev = fun.device_model(device).device if isinstance(fun, (LogPosterior, BatchedFun)) else "cpu"
             t = torch.tensor([seed], dtype=torch.int64, device=dev)
             dist.broadcast(t, src=0)
             seed = int(t.item())

@@ -10,6 +10,10 @@ fused GPU kernel cannot, so the engine ships the families the reference's own do
 Each constructor returns a LogPosterior: a tagged object carrying the data (moved to HBM once per
 device) that MCMC() recognises.  Calling it, fun(theta), evaluates the same closed form in numpy for
 inspection only -- MCMC() never calls it.
+
+Any other model goes through batched_fun(fn, k): fn evaluates the log-posterior of ALL local chains at
+once as a vectorised torch function on the device, called by the engine between the steps of its
+kernels (include/fmcmc_amd.h, fmcmc_logpost_fn).
 """
 import numpy as np
 
@@ -90,3 +94,42 @@ def logistic(X, y, intercept=False, prior_div=8.0, guard=False):
 def iid_normal(D, guard=False):
     """sum(log(dnorm(D, mu, sigma))); theta = (mu, sigma)."""
     return LogPosterior(abi.FAM_IID_NORMAL, None, D, True, guard, 0.0)
+
+
+class BatchedFun:
+    """A user-defined log-posterior evaluated for all local chains at once: fn(theta) takes a float64 tensor [C_local, k] on
+    the device (read-only: it is the engine's proposal buffer) and returns the float64 tensor [C_local] of log f(theta[c, ]),
+    enqueued on the current torch stream.  MCMC() runs it with kernel_normal(_reflective), kernel_unif(_reflective) (every
+    scheme), kernel_adapt(bw = 0, freq = 1) and kernel_ram; fn is called once for row 1, then once per loop step (bounded
+    kernel_ram: twice, on the un-reflected and on the reflected proposal, R/kernel_ram.R:129-152)."""
+
+    def __init__(self, fn, k, names=None):
+        if not callable(fn):
+            raise TypeError("batched_fun: -fn- must be callable.")
+        k = int(k)
+        if not 1 <= k <= abi.MAX_K:
+            raise ValueError("batched_fun: k = %d outside [1, %d]." % (k, abi.MAX_K))
+        if names is not None and len(names) != k:
+            raise ValueError("batched_fun: %d names for k = %d parameters." % (len(names), k))
+        self.fn, self.names = fn, (list(names) if names is not None else None)
+        self._k = k
+
+    @property
+    def k(self):
+        return self._k
+
+    def device_model(self, device):
+        from .engine import DeviceFun
+        return DeviceFun(self, device)
+
+    def __call__(self, theta):
+        """fn on one parameter vector (inspection only), on the current device."""
+        import torch
+        th = torch.as_tensor(np.asarray(theta, dtype=np.float64)).reshape(1, self.k).to("cuda")
+        return float(self.fn(th)[0].item())
+
+
+def batched_fun(fn, k, names=None):
+    """A user-defined log-posterior for MCMC(): fn(theta [C_local, k] float64 tensor on the device) -> [C_local] float64
+    tensor on the same device.  names: optional parameter names (as the names of a named `initial`)."""
+    return BatchedFun(fn, k, names)

@@ -220,7 +220,8 @@ enum {
   FMCMC_ERR_ARG = 1,     /* invalid argument; message mirrors the reference's stop() text */
   FMCMC_ERR_DEVICE = 2,  /* HIP runtime failure / no device */
   FMCMC_ERR_CHAIN = 3,   /* at least one chain raised a FMCMC_CHAIN_* status */
-  FMCMC_ERR_UNSUPPORTED = 4
+  FMCMC_ERR_UNSUPPORTED = 4,
+  FMCMC_ERR_FUN = 5      /* the caller's log-posterior callback (fmcmc_logpost_fn) returned non-zero; the call was abandoned */
 };
 
 int fmcmc_abi_version(void);
@@ -242,6 +243,26 @@ int fmcmc_mcmc_run_dev(const fmcmc_model* model, const fmcmc_kernel* kernel,
 int fmcmc_mcmc_run_host(const fmcmc_model* model, const fmcmc_kernel* kernel,
                         const fmcmc_run* run, fmcmc_state* state, fmcmc_out* out,
                         int device);
+
+/* ---- user-defined log-posteriors: the `fun` of MCMC() as a batched callback (R/mcmc.R:754) ---------------------------------
+ * Batched log-posterior: out[c] = log f(theta[c][0..k-1]) for c < nchains.  Called on the calling host thread.  Work is
+ * enqueued on hip_stream, or the function synchronises before returning.  0 = ok; anything else aborts the call. */
+typedef int (*fmcmc_logpost_fn)(const double* theta, int64_t nchains, int32_t k, double* out, void* hip_stream, void* user);
+
+/* The semantics of fmcmc_mcmc_run_* with the family replaced by `fun`: the same run / state / out layouts (ld_rows, FED mode,
+ * chain_base, step_base, carried kernel state), chain statuses and outputs.  `fun` is called once for row 1 (f0), then once per
+ * loop step; bounded kernel_ram calls it twice per step, on the un-reflected proposal and on the reflected one
+ * (R/kernel_ram.R:129-152).  A non-zero return of `fun` ends the call with FMCMC_ERR_FUN (fmcmc_last_error() names the step and
+ * the code); the chain state of such a call is undefined.  Kernels: kernel_normal(_reflective) / kernel_unif(_reflective) with
+ * every scheme, kernel_adapt(bw = 0, freq = 1), kernel_ram with every option, 1 <= k <= FMCMC_MAX_K; the mirror kernels and the
+ * windowed / strided kernel_adapt are refused with FMCMC_ERR_UNSUPPORTED.  fmcmc_last_kernel(): "fun" (k <= FMCMC_MAX_K_WAVE,
+ * one wavefront per chain) or "fun-wg" (one workgroup per chain).  Pointers inside `kernel` follow the domain of the entry
+ * point, as for fmcmc_mcmc_run_dev / _host. */
+int fmcmc_validate_fun(const fmcmc_kernel* kernel, const fmcmc_run* run);
+int fmcmc_mcmc_run_fun_dev(const fmcmc_kernel* kernel, const fmcmc_run* run, fmcmc_state* state, fmcmc_out* out,
+                           fmcmc_logpost_fn fun, void* user, void* hip_stream);   /* theta/out of `fun`: device pointers */
+int fmcmc_mcmc_run_fun_host(const fmcmc_kernel* kernel, const fmcmc_run* run, fmcmc_state* state, fmcmc_out* out,
+                            fmcmc_logpost_fn fun, void* user, int device);      /* theta/out of `fun`: host pointers */
 
 /* Gelman-Rubin partial sums over local chains (R/convergence.R:191-246 -> coda::gelman.diag).
  * Window = kept rows [row0, row0+N) of each chain. partial has fmcmc_gelman_partial_len(p)
