@@ -26,7 +26,9 @@ EXPORTS = ["fmcmc_abi_version", "fmcmc_last_error", "fmcmc_last_kernel", "fmcmc_
            "fmcmc_validate", "fmcmc_mcmc_run_dev", "fmcmc_mcmc_run_host", "fmcmc_gelman_partial_len",
            "fmcmc_gelman_work_len",
            "fmcmc_gelman_partial_dev", "fmcmc_gelman_finish", "fmcmc_detmath_dev", "fmcmc_rng_stream_dev",
-           "fmcmc_validate_fun", "fmcmc_mcmc_run_fun_dev", "fmcmc_mcmc_run_fun_host"]
+           "fmcmc_validate_fun", "fmcmc_mcmc_run_fun_dev", "fmcmc_mcmc_run_fun_host",
+           "fmcmc_summary_work_len", "fmcmc_summary_pooled_len", "fmcmc_summary_dev"]
+SUMMARY_MAX_PROBS = 16
 
 # fmcmc_logpost_fn: out[c] = log f(theta[c][0..k-1]) for c < nchains; 0 = ok (theta, out, hip_stream, user: addresses)
 LOGPOST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p)
@@ -118,6 +120,13 @@ def lib():
                                                C.c_void_p, C.c_void_p]
         L.fmcmc_gelman_finish.restype = C.c_int
         L.fmcmc_gelman_finish.argtypes = [_dp, C.c_int32, C.c_int64, _dp, _dp]
+        L.fmcmc_summary_work_len.restype = C.c_int64
+        L.fmcmc_summary_work_len.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+        L.fmcmc_summary_pooled_len.restype = C.c_int64
+        L.fmcmc_summary_pooled_len.argtypes = [C.c_int32, C.c_int32]
+        L.fmcmc_summary_dev.restype = C.c_int
+        L.fmcmc_summary_dev.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                        C.c_int32, _dp, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.fmcmc_rng_stream_dev.restype = C.c_int
         L.fmcmc_rng_stream_dev.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                            C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]

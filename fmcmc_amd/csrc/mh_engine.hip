@@ -232,6 +232,8 @@ extern "C" {
 
 int fmcmc_abi_version(void) { return FMCMC_ABI_VERSION; }
 const char* fmcmc_last_error(void) { return g_err; }
+// (not part of the C-ABI: the other translation units of the library leave their texts in the same thread-local buffer)
+__attribute__((visibility("hidden"))) void fmcmc_set_error_text_(const char* text) { set_err("%s", text); }
 static thread_local const char* g_kernel = "";
 const char* fmcmc_last_kernel(void) { return g_kernel; }
 

@@ -1,0 +1,507 @@
+// summary.hip — posterior summary of a call's kept rows, computed where the sweep left them (coda::summary.mcmc(.list),
+// coda::effectiveSize, coda::spectrum0.ar; formulas restated in fmcmc_amd/convergence.py and INTEGRATION.md).
+//
+// One chain's column is N contiguous doubles (samples + (c k + col) S + row0), so every stage walks contiguous memory:
+//   1. summary_series_kernel   one workgroup per (chain, column): mean, autocovariances r_0..r_M of the series centred on its
+//                              own mean, residual sd of the straight-line fit, count of non-finite values;
+//   2. summary_ar_kernel       one wavefront per series: Levinson-Durbin + AIC order + spectral density at zero;
+//   3. summary_pool_kernel     fixed-order sums over the chains: pooled mean / variance, mean spec0, effective size;
+//   4. select_*                exact order statistics of the pooled C N values of a column by a most-significant-digit radix
+//                              select on order-preserving 64-bit keys (8 passes of 8 bits, integer counts only).
+// Every sum has a fixed shape, so the results do not depend on the launch.  Nothing here writes `samples`.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdarg.h>
+
+#include "../../include/fmcmc_amd.h"
+#include "../../include/fmh_detmath.h"
+
+extern "C" void fmcmc_set_error_text_(const char* text);   // mh_engine.hip: the buffer behind fmcmc_last_error()
+
+namespace {
+
+constexpr int MAXM = 64;            // largest AR order (coda: floor(10 log10 N)); N < 10^6.5
+constexpr int ACS = 72;             // doubles per series in work: r[0..64], 65 mean, 66 residual sd of x ~ 1 + t, 67 non-finite count
+constexpr int SLOT_MEAN = 65, SLOT_RSD = 66, SLOT_NF = 67;
+constexpr int ST = 512;             // threads of the series kernel
+constexpr int SW = ST / 64;
+constexpr int LDS_ROWS = 19456;     // rows of a series staged in LDS at once ((19456 + 72) rows + the reduction scratch < 160 KB)
+constexpr int RED = 68;             // reduction scratch per wave
+constexpr int LG = 8;               // lags per group of the product loop
+constexpr int PAD = MAXM + LG;      // zero rows behind a tile
+constexpr int MAXPROBS = 16;
+constexpr int HT = 256;             // threads of the histogram kernel
+constexpr int HP = 4;               // 16-byte loads in flight per thread of the histogram kernel
+constexpr int TILE = 2 * HP * HT;   // rows of one chain a histogram block takes per step
+
+int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+int fail(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  fmcmc_set_error_text_(buf);
+  return code;
+}
+
+// (a pair is 8-byte aligned only: a window starts at any row of a history whose row stride may be odd; gelman.hip)
+typedef double sd2_t __attribute__((ext_vector_type(2), aligned(8)));
+
+__device__ __forceinline__ double wave_sum(double v) {   // butterfly: the same value, formed in the same order, in every lane
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// Sum over the workgroup: lanes by butterfly, then the waves in wave order.  `red` holds one double per wave.
+template <int NWAVES>
+__device__ __forceinline__ double block_sum(double v, double* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = red[0];
+#pragma unroll
+  for (int w = 1; w < NWAVES; w++) s += red[w];
+  return s;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- stage 1
+// The series is staged in LDS once when it fits (N <= tile_rows): the mean, the centring, all M + 1 lags and the line fit are
+// taken from there.  A longer series takes the mean from global memory and then walks tiles of tile_rows rows with an M-row
+// halo.  Thread t owns the rows t, t + ST, ... of a tile (conflict-free 8-byte LDS reads for every lag) and keeps one
+// accumulator per lag; the accumulators are joined over the lanes in a fixed pattern and then in wave order.
+__global__ __launch_bounds__(ST) void summary_series_kernel(const double* __restrict__ samples, long long S, int k, long long row0,
+                                                            long long N, const int* __restrict__ cols, int p, int M,
+                                                            int tile_rows, double* __restrict__ acov) {
+  extern __shared__ double smem[];
+  double* s_x = smem;                          // [tile_rows + PAD]
+  double* s_red = smem + tile_rows + PAD;      // [SW * RED]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long series = blockIdx.x, c = series / p;
+  const int j = (int)(series % p);
+  const double* __restrict__ x = samples + (c * (long long)k + cols[j]) * S + row0;
+  double* out = acov + series * ACS;
+  const bool single = N <= (long long)tile_rows;
+  const double dn = (double)N;
+
+  // mean (and the count of non-finite values); a short series is staged on the way
+  double s = 0.0, nf = 0.0;
+  constexpr int LU = 8;                        // pairs in flight per thread: the loads of a batch are issued back to back
+  for (long long base = 0; base < N; base += 2LL * LU * ST) {
+    double a[LU], b[LU];
+#pragma unroll
+    for (int u = 0; u < LU; u++) {
+      const long long i = base + 2LL * (u * ST + tid);
+      a[u] = 0.0; b[u] = 0.0;
+      if (i + 1 < N) {
+        const sd2_t v = *reinterpret_cast<const sd2_t*>(x + i);
+        a[u] = v[0]; b[u] = v[1];
+      } else if (i < N) {
+        a[u] = x[i];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < LU; u++) {
+      const long long i = base + 2LL * (u * ST + tid);
+      if (i < N) {                             // (a missing second row of the pair adds 0)
+        s += a[u]; s += b[u];
+        nf += (fmh_isfinite(a[u]) ? 0.0 : 1.0) + (fmh_isfinite(b[u]) ? 0.0 : 1.0);
+        if (single) { s_x[i] = a[u]; if (i + 1 < N) s_x[i + 1] = b[u]; }
+      }
+    }
+  }
+  const double mean = block_sum<SW>(s, s_red) / dn;
+  nf = block_sum<SW>(nf, s_red);
+
+  double acc[MAXM + 1];
+#pragma unroll
+  for (int l = 0; l <= MAXM; l++) acc[l] = 0.0;
+  double sxt = 0.0;
+  const double tbar = 0.5 * (dn - 1.0);        // rows are numbered 0 .. N - 1 (the fit's residuals do not depend on the origin)
+  for (long long t0 = 0; t0 < N; t0 += tile_rows) {
+    const int len = (int)((N - t0 < tile_rows) ? N - t0 : tile_rows);
+    const int ext = (int)((N - t0 < (long long)tile_rows + M) ? N - t0 : (long long)tile_rows + M);
+    __syncthreads();
+    if (single) {
+      for (int i = tid; i < len; i += ST) s_x[i] -= mean;
+    } else {
+      for (int i = tid; i < ext; i += ST) s_x[i] = x[t0 + i] - mean;
+    }
+    for (int i = ext + tid; i < len + PAD; i += ST) s_x[i] = 0.0;    // rows beyond the series multiply as 0
+    __syncthreads();
+    for (int i = tid; i < len; i += ST) {
+      const double xi = s_x[i];
+      sxt = __builtin_fma((double)(t0 + i) - tbar, xi, sxt);
+      // lags in groups of LG: one uniform branch per group, its LDS reads issued together (a branch per lag left every read's
+      // latency exposed: 1.0 ms instead of 0.6 at 1024 x 5 x 10^4); the lags of the last group beyond M are computed and dropped
+#pragma unroll
+      for (int g = 0; g < MAXM / LG; g++) {
+        if (LG * g <= M) {
+#pragma unroll
+          for (int u = 0; u < LG; u++) acc[LG * g + u] = __builtin_fma(xi, s_x[i + LG * g + u], acc[LG * g + u]);
+        }
+      }
+      if (M == MAXM) acc[MAXM] = __builtin_fma(xi, s_x[i + MAXM], acc[MAXM]);
+    }
+  }
+  // join.  Lanes: a transposing reduction of the lags 0..63 -- at the step of distance h a lane keeps the half of its values
+  // whose index has bit h equal to its own lane bit and adds the partner's copy of that half; after the six steps lane l holds
+  // the wave's sum of lag l (63 exchanges instead of 64 butterflies of six).  Lag 64 and the line-fit sum by butterfly.
+  __syncthreads();
+#pragma unroll
+  for (int h = 32; h >= 1; h >>= 1) {
+    const bool up = (lane & h) != 0;
+#pragma unroll
+    for (int i = 0; i < h; i++) {
+      const double keep = up ? acc[i + h] : acc[i];
+      const double send = up ? acc[i] : acc[i + h];
+      acc[i] = keep + __shfl_xor(send, h, 64);
+    }
+  }
+  s_red[wave * RED + lane] = acc[0];
+  {
+    const double v64 = wave_sum(acc[MAXM]), vt = wave_sum(sxt);
+    if (lane == 0) { s_red[wave * RED + MAXM] = v64; s_red[wave * RED + MAXM + 1] = vt; }
+  }
+  __syncthreads();
+  if (tid <= MAXM + 1) {
+    double v = s_red[tid];
+    for (int w = 1; w < SW; w++) v += s_red[w * RED + tid];
+    s_red[tid] = v;
+    if (tid <= M) out[tid] = v / dn;           // acf(type = "covariance"): divisor N
+    else if (tid <= MAXM) out[tid] = 0.0;
+  }
+  __syncthreads();
+  // residual standard deviation of x ~ 1 + t, from the residuals themselves (the closed form N r_0 - sxt^2 / stt cancels to
+  // noise of the size of the threshold for an exactly linear series)
+  const double stt = dn * (dn * dn - 1.0) / 12.0;
+  const double slope = s_red[MAXM + 1] / stt;
+  double rs = 0.0, rss = 0.0;
+  for (long long i = tid; i < N; i += ST) {
+    const double xc = single ? s_x[i] : x[i] - mean;
+    const double res = xc - slope * ((double)i - tbar);
+    rs += res;
+    rss = __builtin_fma(res, res, rss);
+  }
+  rs = block_sum<SW>(rs, s_red + SW * RED - SW);     // (the last SW doubles of the scratch: s_red[MAXM + 1] is still being read)
+  rss = block_sum<SW>(rss, s_red + SW * RED - SW);
+  if (tid == 0) {
+    const double q = rss - rs * rs / dn;
+    out[SLOT_MEAN] = mean;
+    out[SLOT_RSD] = sqrt((q > 0.0 ? q : (q == q ? 0.0 : q)) / (dn - 1.0));
+    out[SLOT_NF] = nf;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- stage 2
+// stats::ar.yw (Levinson-Durbin, AIC, first minimum) and coda::spectrum0.ar for one series per wavefront.  Lane j holds the
+// coefficient of lag j + 1 and r_{j+1}; step m needs coefficient m - i next to coefficient i and r_{m-i} next to it: both are
+// the same lane reversal over the first m - 1 lanes.
+__global__ __launch_bounds__(256) void summary_ar_kernel(const double* __restrict__ acov, long long nseries, long long N, int M,
+                                                         double* __restrict__ stats) {
+  const int lane = threadIdx.x & 63;
+  long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const bool live = w < nseries;
+  if (!live) w = nseries - 1;
+  const double* a = acov + w * ACS;
+  const double dn = (double)N;
+  const double r0 = a[0];
+  const double rj = (lane < M) ? a[lane + 1] : 0.0;
+  const double mean = a[SLOT_MEAN], rsd = a[SLOT_RSD];
+  double coef = 0.0, v = r0;
+  double best_aic = (dn * fmh_log(r0) + 0.0) + 2.0, best_v = r0, best_coef = 0.0;
+  int best_o = 0;
+  for (int m = 1; m <= M; m++) {
+    const bool below = lane < m - 1;
+    const int src = below ? m - 2 - lane : lane;
+    const double rrev = __shfl(rj, src, 64), crev = __shfl(coef, src, 64);
+    const double acc = __shfl(rj, m - 1, 64) - wave_sum(below ? coef * rrev : 0.0);
+    const double phi = acc / v;
+    coef = below ? coef - phi * crev : (lane == m - 1 ? phi : coef);
+    v = v * (1.0 - phi * phi);
+    const double aic = (dn * fmh_log(v) + 2.0 * m) + 2.0;
+    if (aic < best_aic) { best_aic = aic; best_v = v; best_coef = coef; best_o = m; }
+  }
+  const double sum_ar = wave_sum(best_coef);
+  const double var_pred = best_v * dn / (dn - (double)(best_o + 1));
+  const double one_m = 1.0 - sum_ar;
+  double spec0 = var_pred / (one_m * one_m);
+  double order = (double)best_o;
+  if (rsd < 1.5e-8) { spec0 = 0.0; order = 0.0; }       // constant or exactly linear series (coda: all.equal(sd(residuals), 0))
+  if (live && lane == 0) {
+    double* o = stats + w * 4;
+    o[0] = mean;
+    o[1] = r0 * dn / (dn - 1.0);
+    o[2] = spec0;
+    o[3] = order;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- stage 3
+// Per column: pooled mean and centred sum of squares from the chains' {N, mean, M2} (all chains have N rows), sum of spec0,
+// sum of the effective-size terms, non-finite count.  Thread g takes the chains g, g + 256, ... in chain order.
+__global__ __launch_bounds__(256) void summary_pool_kernel(const double* __restrict__ stats, const double* __restrict__ acov,
+                                                           long long C, int p, long long N, double* __restrict__ pooled) {
+  __shared__ double s_red[4];
+  const int j = blockIdx.x, tid = threadIdx.x;
+  const double dn = (double)N, dc = (double)C;
+  double s = 0.0;
+  for (long long c = tid; c < C; c += 256) s += stats[(c * p + j) * 4];
+  const double mean = block_sum<4>(s, s_red) / dc;
+  double m2 = 0.0, ssp = 0.0, sess = 0.0, snf = 0.0;
+  for (long long c = tid; c < C; c += 256) {
+    const double* o = stats + (c * p + j) * 4;
+    const double d = o[0] - mean;
+    m2 += (dn - 1.0) * o[1] + dn * d * d;
+    ssp += o[2];
+    sess += (o[2] == 0.0) ? 0.0 : dn * o[1] / o[2];
+    snf += acov[(c * p + j) * ACS + SLOT_NF];
+  }
+  m2 = block_sum<4>(m2, s_red);
+  ssp = block_sum<4>(ssp, s_red);
+  sess = block_sum<4>(sess, s_red);
+  snf = block_sum<4>(snf, s_red);
+  if (tid == 0) {
+    double* o = pooled + (long long)j * 5;
+    o[0] = mean;
+    o[1] = m2 / (dc * dn - 1.0);
+    o[2] = ssp / dc;
+    o[3] = sess;
+    o[4] = snf;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- stage 4
+// Radix select.  A target is (column, prob, lo | hi) with a 0-based rank among the C N pooled values of its column.  Pass d
+// fixes bits [56 - 8 d, 64 - 8 d) of its key: the histogram of that digit over the values whose higher bits equal the target's
+// prefix, then a walk over the 256 counts.  Targets of a column with the same prefix share one histogram (that of the first
+// of them, their "leader"): in the first passes that is one histogram for all of them.  Counts are integers, so neither the
+// arrival order of the atomic adds nor ties matter.
+struct Ranks { long long lo[MAXPROBS], hi[MAXPROBS]; };
+
+__device__ __forceinline__ unsigned long long key_of(double x) {      // order-preserving: x < y <=> key(x) < key(y)
+  const unsigned long long u = fmh_d2u(x);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double value_of(unsigned long long kx) {
+  return fmh_u2d((kx >> 63) ? (kx & 0x7fffffffffffffffull) : ~kx);
+}
+
+// state per target: prefix, rank, leader (index within the column); then the histograms [T][256]
+__global__ __launch_bounds__(256) void select_init_kernel(unsigned long long* __restrict__ state, unsigned long long* __restrict__ hist,
+                                                          int nprobs, Ranks ranks) {
+  const int t = blockIdx.x, nt = 2 * nprobs, tl = t % nt;
+  hist[(long long)t * 256 + threadIdx.x] = 0ull;
+  if (threadIdx.x == 0) {
+    state[3LL * t] = 0ull;
+    state[3LL * t + 1] = (unsigned long long)((tl & 1) ? ranks.hi[tl >> 1] : ranks.lo[tl >> 1]);
+    state[3LL * t + 2] = 0ull;
+  }
+}
+
+__global__ __launch_bounds__(HT) void select_hist_kernel(const double* __restrict__ samples, long long S, int k, long long row0,
+                                                         long long N, long long C, const int* __restrict__ cols, int nprobs,
+                                                         int pass, const unsigned long long* __restrict__ state,
+                                                         unsigned long long* __restrict__ hist) {
+  extern __shared__ unsigned int s_h[][256];           // [2 nprobs][256]
+  __shared__ unsigned long long s_prefix[2 * MAXPROBS];
+  __shared__ int s_lead[2 * MAXPROBS];
+  __shared__ int s_nlead;
+  const int j = blockIdx.y, nt = 2 * nprobs, tid = threadIdx.x;
+  const unsigned long long* st = state + 3LL * j * nt;
+  if (tid == 0) {
+    int n = 0;
+    for (int t = 0; t < nt; t++)
+      if ((int)st[3 * t + 2] == t) { s_lead[n] = t; s_prefix[n] = st[3 * t]; n++; }
+    s_nlead = n;
+  }
+  for (int e = tid; e < nt * 256; e += HT) (&s_h[0][0])[e] = 0u;
+  __syncthreads();
+  const int nlead = s_nlead;
+  const int shift = 56 - 8 * pass;
+  const long long tiles_per_chain = (N + TILE - 1) / TILE, total = C * tiles_per_chain;
+  const double* __restrict__ colbase = samples + (long long)cols[j] * S + row0;
+  for (long long tile = blockIdx.x; tile < total; tile += gridDim.x) {
+    const long long c = tile / tiles_per_chain, r0 = (tile % tiles_per_chain) * TILE;
+    const double* __restrict__ x = colbase + c * (long long)k * S;
+    double v[2 * HP];
+    bool ok[2 * HP];
+#pragma unroll
+    for (int u = 0; u < HP; u++) {
+      const long long r = r0 + u * (2 * HT) + 2 * tid;
+      ok[2 * u] = r < N; ok[2 * u + 1] = r + 1 < N;
+      if (ok[2 * u + 1]) {
+        const sd2_t q = *reinterpret_cast<const sd2_t*>(x + r);
+        v[2 * u] = q[0]; v[2 * u + 1] = q[1];
+      } else {
+        v[2 * u] = ok[2 * u] ? x[r] : 0.0; v[2 * u + 1] = 0.0;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 2 * HP; u++) {
+      if (!ok[u]) continue;
+      const unsigned long long kx = key_of(v[u]);
+      const unsigned long long high = (pass == 0) ? 0ull : (kx >> (shift + 8));
+      const unsigned int digit = (unsigned int)(kx >> shift) & 255u;
+      for (int g = 0; g < nlead; g++)
+        if (high == s_prefix[g]) atomicAdd(&s_h[s_lead[g]][digit], 1u);
+    }
+  }
+  __syncthreads();
+  for (int g = 0; g < nlead; g++) {
+    const int t = s_lead[g];
+    for (int b = tid; b < 256; b += HT) {
+      const unsigned int cnt = s_h[t][b];
+      if (cnt) atomicAdd(&hist[((long long)j * nt + t) * 256 + b], (unsigned long long)cnt);
+    }
+  }
+}
+
+// One wavefront per column.  Per target the 64 lanes take four counts each of its leader's histogram, a prefix sum over the
+// lanes finds the lane and then the bin that holds the rank; then lane = target: extend the prefix, find the new leaders,
+// clear the histograms for the next pass.  After the last pass the prefix is the key of the order statistic.
+__global__ __launch_bounds__(64) void select_scan_kernel(unsigned long long* __restrict__ state, unsigned long long* __restrict__ hist,
+                                                         int nprobs, int pass, double* __restrict__ out) {
+  __shared__ unsigned long long s_p[2 * MAXPROBS], s_cum[2 * MAXPROBS];
+  __shared__ int s_digit[2 * MAXPROBS];
+  const int j = blockIdx.x, nt = 2 * nprobs, t = threadIdx.x;
+  unsigned long long* st = state + 3LL * j * nt;
+  unsigned long long* hs = hist + (long long)j * nt * 256;
+  if (t < nt) { s_digit[t] = 255; s_cum[t] = 0ull; }
+  __syncthreads();
+  for (int g = 0; g < nt; g++) {
+    const unsigned long long rank = st[3 * g + 1];
+    const unsigned long long* h = hs + (long long)st[3 * g + 2] * 256 + 4 * t;
+    const unsigned long long c0 = h[0], c1 = h[1], c2 = h[2], c3 = h[3];
+    const unsigned long long mine = c0 + c1 + c2 + c3;
+    unsigned long long incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned long long up = __shfl_up(incl, o, 64);
+      if (t >= o) incl += up;
+    }
+    unsigned long long cum = incl - mine;
+    if (rank >= cum && rank < incl) {            // exactly one lane: the ranks are below the total count
+      int b = 0;
+      if (rank >= cum + c0) { cum += c0; b = 1;
+        if (rank >= cum + c1) { cum += c1; b = 2;
+          if (rank >= cum + c2) { cum += c2; b = 3; } } }
+      s_digit[g] = 4 * t + b;
+      s_cum[g] = cum;
+    }
+  }
+  __syncthreads();
+  unsigned long long prefix = 0ull;
+  if (t < nt) {
+    prefix = (st[3 * t] << 8) | (unsigned long long)s_digit[t];
+    s_p[t] = prefix;
+  }
+  __syncthreads();
+  for (int e = t; e < nt * 256; e += 64) hs[e] = 0ull;
+  if (t < nt) {
+    int lead = t;
+    for (int u = t - 1; u >= 0; u--)
+      if (s_p[u] == prefix) lead = u;
+    st[3 * t] = prefix;
+    st[3 * t + 1] -= s_cum[t];
+    st[3 * t + 2] = (unsigned long long)lead;
+    if (pass == 7) out[(long long)j * nt + t] = value_of(prefix);
+  }
+}
+
+long long ar_order_max(long long N) {
+  const long long m = (long long)floor(10.0 * log10((double)N));
+  return m < N - 1 ? m : N - 1;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t fmcmc_summary_pooled_len(int32_t p, int32_t nprobs) {
+  if (p < 1 || nprobs < 0) return 0;
+  return (int64_t)p * 5 + (int64_t)p * nprobs * 2;
+}
+
+int64_t fmcmc_summary_work_len(int64_t nchains, int32_t p, int32_t nprobs) {
+  if (nchains < 1 || p < 1 || nprobs < 0) return 0;
+  const int64_t series = nchains * (int64_t)p, targets = (int64_t)p * nprobs * 2;
+  return series * ACS + series * 4 + targets * (3 + 256);
+}
+
+int fmcmc_summary_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N,
+                      const int32_t* cols, int32_t p, const double* probs, int32_t nprobs, double* work,
+                      double* chain_stats, double* pooled, void* hip_stream) {
+  // every argument check comes before the first device call
+  if (!samples || !cols || !work || !pooled) return fail(FMCMC_ERR_ARG, "fmcmc_summary_dev: null argument");
+  if (nchains < 1) return fail(FMCMC_ERR_ARG, "fmcmc_summary_dev: nchains = %lld, need at least one chain", (long long)nchains);
+  if (k < 1) return fail(FMCMC_ERR_ARG, "fmcmc_summary_dev: k = %d, need at least one parameter", (int)k);
+  if (p < 1) return fail(FMCMC_ERR_ARG, "fmcmc_summary_dev: p = %d, need at least one column", (int)p);
+  if (N < 3) return fail(FMCMC_ERR_ARG, "fmcmc_summary_dev: a window of N = %lld rows is too short (spectrum0.ar needs 3)", (long long)N);
+  if (row0 < 0 || row0 + N > S)
+    return fail(FMCMC_ERR_ARG, "fmcmc_summary_dev: the window [%lld, %lld) is outside the %lld rows of a chain", (long long)row0,
+                (long long)(row0 + N), (long long)S);
+  if (nprobs < 0 || nprobs > MAXPROBS)
+    return fail(FMCMC_ERR_ARG, "fmcmc_summary_dev: nprobs = %d outside [0, %d]", (int)nprobs, MAXPROBS);
+  if (nprobs > 0 && !probs) return fail(FMCMC_ERR_ARG, "fmcmc_summary_dev: null argument");
+  for (int q = 0; q < nprobs; q++)
+    if (!(probs[q] >= 0.0 && probs[q] <= 1.0))
+      return fail(FMCMC_ERR_ARG, "fmcmc_summary_dev: probs[%d] = %g is outside [0, 1]", q, probs[q]);
+  const long long M = ar_order_max(N);
+  if (M > MAXM)
+    return fail(FMCMC_ERR_UNSUPPORTED, "fmcmc_summary_dev: N = %lld rows per chain ask for an AR order up to %lld; supported are "
+                "orders up to %d (N < 3162278)", (long long)N, M, MAXM);
+  if (nchains * (int64_t)p > 0x7fffffffLL)
+    return fail(FMCMC_ERR_UNSUPPORTED, "fmcmc_summary_dev: %lld series exceed one launch", (long long)(nchains * (int64_t)p));
+
+  hipStream_t st = (hipStream_t)hip_stream;
+  const long long series = nchains * (long long)p;
+  double* acov = work;
+  double* stats = chain_stats ? chain_stats : work + series * ACS;
+  unsigned long long* state = reinterpret_cast<unsigned long long*>(work + series * ACS + series * 4);
+  const long long targets = (long long)p * nprobs * 2;
+  unsigned long long* hist = state + 3 * targets;
+
+  const int tile_rows = (int)(N < LDS_ROWS ? N : LDS_ROWS);
+  const size_t lds = (size_t)(tile_rows + PAD + SW * RED) * sizeof(double);
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(summary_series_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)lds) != hipSuccess)
+    return fail(FMCMC_ERR_DEVICE, "fmcmc_summary_dev: %zu bytes of LDS refused", lds);
+  hipLaunchKernelGGL(summary_series_kernel, dim3((unsigned)series), dim3(ST), lds, st, samples, (long long)S, (int)k,
+                     (long long)row0, (long long)N, cols, (int)p, (int)M, tile_rows, acov);
+  hipLaunchKernelGGL(summary_ar_kernel, dim3((unsigned)((series + 3) / 4)), dim3(256), 0, st, acov, series, (long long)N, (int)M,
+                     stats);
+  hipLaunchKernelGGL(summary_pool_kernel, dim3((unsigned)p), dim3(256), 0, st, stats, acov, (long long)nchains, (int)p,
+                     (long long)N, pooled);
+  if (nprobs > 0) {
+    // R's quantile type 7: index = 1 + (n - 1) prob, the order statistics floor(index) and ceil(index) (1-based)
+    Ranks ranks;
+    const long long n = nchains * (long long)N;
+    for (int q = 0; q < MAXPROBS; q++) {
+      const double index = 1.0 + (double)(n - 1) * (q < nprobs ? probs[q] : 0.0);
+      long long lo = (long long)floor(index) - 1, hi = (long long)ceil(index) - 1;
+      ranks.lo[q] = lo < 0 ? 0 : (lo > n - 1 ? n - 1 : lo);
+      ranks.hi[q] = hi < 0 ? 0 : (hi > n - 1 ? n - 1 : hi);
+    }
+    hipLaunchKernelGGL(select_init_kernel, dim3((unsigned)targets), dim3(256), 0, st, state, hist, (int)nprobs, ranks);
+    const long long tiles = nchains * ((N + TILE - 1) / TILE);
+    long long nblk = 2048 / p;
+    if (nblk < 1) nblk = 1;
+    if (nblk > tiles) nblk = tiles;
+    for (int pass = 0; pass < 8; pass++) {
+      hipLaunchKernelGGL(select_hist_kernel, dim3((unsigned)nblk, (unsigned)p), dim3(HT), (size_t)(2 * nprobs) * 256 * sizeof(unsigned int), st, samples, (long long)S, (int)k,
+                         (long long)row0, (long long)N, (long long)nchains, cols, (int)nprobs, pass, state, hist);
+      hipLaunchKernelGGL(select_scan_kernel, dim3((unsigned)p), dim3(64), 0, st, state, hist, (int)nprobs, pass,
+                         pooled + (long long)p * 5);
+    }
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(FMCMC_ERR_DEVICE, "fmcmc_summary_dev: launch failed (%s)", hipGetErrorString(e));
+  return FMCMC_OK;
+}
+
+}  // extern "C"

@@ -252,6 +252,20 @@ class DeviceChains:
                   for c in range(s.shape[0])]
         return chains[0] if (len(chains) == 1 and self.nchains_total == 1) else McmcList(chains)
 
+    # posterior summaries reduced where the rows are (fmcmc_amd/summary.py -> csrc/summary.hip); nothing is copied to the host
+    def summary(self, quantiles=(0.025, 0.25, 0.5, 0.75, 0.975), cols=None):
+        from .summary import summary
+        return summary(self, quantiles, cols)
+
+    def effective_size(self, cols=None):
+        from .summary import effective_size
+        return effective_size(self, cols)
+
+    def geweke(self, frac1=0.1, frac2=0.5, cols=None):
+        """Geweke z-scores of every chain, [C][p] (convergence_geweke stays the single-chain checker of the reference)."""
+        from .summary import geweke
+        return geweke(self, frac1, frac2, cols)
+
 
 def _validate_common(nsteps, nchains, burnin, thin, multicore):
     if multicore and nchains == 1:

@@ -1,0 +1,222 @@
+"""summary() / effective_size() of a result, computed on the device (coda::summary.mcmc(.list), coda::effectiveSize).
+
+The first thing every example of the reference does with a result is `summary(ans)` (README.md:178-201, R/mcmc.R:212).  Here the
+kept rows stay where the sweep left them: csrc/summary.hip reduces every (chain, column) series to its mean, variance and
+spectral density at zero (coda::spectrum0.ar), pools them over the chains and selects the exact order statistics the
+quantiles need; a few hundred numbers come back.  The host finish below is the type-7 interpolation and the standard errors.
+There is no CPU fallback.
+"""
+import ctypes as C
+from types import SimpleNamespace
+
+import numpy as np
+
+from . import _abi as abi
+
+DEFAULT_QUANTILES = (0.025, 0.25, 0.5, 0.75, 0.975)
+
+
+# ------------------------------------------------------------------------------------------------ host finish (pure numpy)
+def type7_ranks(n, probs):
+    """R's quantile type 7: index = 1 + (n - 1) prob; returns (index, lo, hi) with lo = floor(index), hi = ceil(index), 1-based."""
+    index = 1.0 + np.float64(n - 1) * np.asarray(probs, dtype=np.float64)
+    return index, np.floor(index).astype(np.int64), np.ceil(index).astype(np.int64)
+
+
+def type7_quantiles(order_stats, n, probs):
+    """order_stats [..., nprobs, 2] = x_(lo), x_(hi)  ->  quantiles [..., nprobs]: x_(lo), and (1 - h) x_(lo) + h x_(hi) with
+    h = index - lo where index > lo and x_(hi) != x_(lo)."""
+    order_stats = np.asarray(order_stats, dtype=np.float64)
+    index, lo, _ = type7_ranks(n, probs)
+    h = index - lo
+    xlo, xhi = order_stats[..., 0], order_stats[..., 1]
+    with np.errstate(invalid="ignore", over="ignore"):
+        mixed = (1.0 - h) * xlo + h * xhi
+    return np.where((index > lo) & (xhi != xlo), mixed, xlo)
+
+
+def finish_statistics(pooled_stats, nchain, niter):
+    """pooled_stats [p][>= 3] = {pooled mean, pooled variance, mean spec0}  ->  [p][4] = Mean, SD, Naive SE, Time-series SE
+    (coda::summary.mcmc.list: sqrt(var / (C N)) and sqrt(mean_c(spec0) / (C N)))."""
+    ps = np.asarray(pooled_stats, dtype=np.float64)
+    n = float(nchain) * float(niter)
+    with np.errstate(invalid="ignore"):
+        return np.stack([ps[:, 0], np.sqrt(ps[:, 1]), np.sqrt(ps[:, 1] / n), np.sqrt(ps[:, 2] / n)], axis=1)
+
+
+def _fmt_column(values, digits=4):
+    """One printed column the way R lays out a matrix column: a common number of decimals that gives every entry at least
+    `digits` significant digits."""
+    values = np.asarray(values, dtype=np.float64)
+    dec = 0
+    for v in values:
+        if np.isfinite(v) and v != 0.0:
+            dec = max(dec, digits - 1 - int(np.floor(np.log10(abs(float("%.*e" % (digits - 1, v)))))))
+    dec = min(max(dec, 0), 15)
+    return ["%.*f" % (dec, v) for v in values]
+
+
+def _fmt_table(rownames, colnames, matrix):
+    cols = [[name] + _fmt_column(matrix[:, j]) for j, name in enumerate(colnames)]
+    widths = [max(len(s) for s in col) for col in cols]
+    w0 = max([len(r) for r in rownames] + [0])
+    lines = []
+    for i in range(len(rownames) + 1):
+        head = ("" if i == 0 else rownames[i - 1]).ljust(w0)
+        lines.append(head + " " + " ".join(col[i].rjust(w) for col, w in zip(cols, widths)))
+    return "\n".join(lines)
+
+
+class McmcSummary:
+    """coda's summary.mcmc object: statistics [p][4] (Mean, SD, Naive SE, Time-series SE), quantiles [p][nprobs], and
+    per_chain (mean, sd, tsse, ess, order; each [nchain][p]) -- which chains mix badly is what the pooled table cannot say."""
+    stat_names = ("Mean", "SD", "Naive SE", "Time-series SE")
+
+    def __init__(self, statistics, quantiles, probs, varnames, start, end, thin, nchain, per_chain=None, ess=None):
+        self.statistics = np.asarray(statistics, dtype=np.float64)
+        self.quantiles = np.asarray(quantiles, dtype=np.float64)
+        self.probs = tuple(float(q) for q in probs)
+        self.varnames = list(varnames)
+        self.start, self.end, self.thin, self.nchain = int(start), int(end), int(thin), int(nchain)
+        self.per_chain = per_chain
+        self.ess = ess
+
+    niter = property(lambda self: (self.end - self.start) // self.thin + 1)
+    quantile_names = property(lambda self: ["%g%%" % (100.0 * q) for q in self.probs])
+
+    def __str__(self):
+        out = ["", "Iterations = %d:%d" % (self.start, self.end), "Thinning interval = %d " % self.thin,
+               "Number of chains = %d " % self.nchain, "Sample size per chain = %d " % self.niter, "",
+               "1. Empirical mean and standard deviation for each variable,", "   plus standard error of the mean:", "",
+               _fmt_table(self.varnames, self.stat_names, self.statistics), ""]
+        if self.quantiles.size:
+            out += ["2. Quantiles for each variable:", "", _fmt_table(self.varnames, self.quantile_names, self.quantiles), ""]
+        return "\n".join(out)
+
+    def __repr__(self):
+        return "<McmcSummary nvar=%d nchain=%d niter=%d>" % (len(self.varnames), self.nchain, self.niter)
+
+
+# ------------------------------------------------------------------------------------------------ device side
+def _single_process():
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise NotImplementedError("summary() / effective_size() / geweke() reduce the chains of ONE process: under "
+                                  "torch.distributed with more than one rank the chains are sharded and a sharded summary "
+                                  "(all-reduced sums and histograms) is not implemented.")
+
+
+def _as_device_chains(x):
+    """DeviceChains as they are; an Mcmc / McmcList is uploaded first (as convergence_gelman.__call__ does)."""
+    import torch
+    from .mcmc import DeviceChains, Mcmc, McmcList
+    if isinstance(x, DeviceChains):
+        return x
+    if isinstance(x, Mcmc):
+        x = McmcList([x])
+    if not isinstance(x, McmcList) or len(x) < 1:
+        raise TypeError("expected a DeviceChains, Mcmc or McmcList object")
+    arr = np.ascontiguousarray(x.as_array().transpose(0, 2, 1))   # [C][k][S]
+    return DeviceChains(torch.as_tensor(arr).cuda(), None, None, x.iters, x.thin, x[0].varnames, 0, len(x))
+
+
+def _columns(dc, cols):
+    k = int(dc._samples.shape[1])
+    cols = np.arange(k, dtype=np.int32) if cols is None else np.atleast_1d(np.asarray(cols)).astype(np.int32)
+    if cols.size < 1 or cols.min() < 0 or cols.max() >= k:
+        raise ValueError("`cols` must name at least one of the %d parameters (0-based)." % k)
+    return cols
+
+
+def enqueue_window(dc, row0, N, cols, probs=(), want_chains=True):
+    """Enqueues one fmcmc_summary_dev call on the window [row0, row0 + N) of the kept rows of `dc` (current torch stream).
+    Returns the device tensors (pooled, chain_stats or None, work) and the columns; nothing is synchronised."""
+    import torch
+    _single_process()
+    L = abi.lib()
+    smp = dc._samples
+    Cn, k, cap = (int(v) for v in smp.shape)
+    if Cn < 1:
+        raise ValueError("no chains to summarise")
+    if row0 < 0 or row0 + N > dc.nrows:
+        raise ValueError("the window [%d, %d) is outside the %d kept rows" % (row0, row0 + N, dc.nrows))
+    if smp.dtype != torch.float64 or not smp.is_contiguous():
+        raise ValueError("samples must be a contiguous float64 [C][k][S] tensor")
+    dev = smp.device
+    cols = _columns(dc, cols)
+    p, nprobs = int(cols.size), len(probs)
+    probs_h = np.ascontiguousarray(probs, dtype=np.float64)
+    cols_d = torch.as_tensor(cols).to(dev)
+    work = torch.empty(max(int(L.fmcmc_summary_work_len(Cn, p, nprobs)), 1), dtype=torch.float64, device=dev)
+    pooled = torch.empty(int(L.fmcmc_summary_pooled_len(p, nprobs)), dtype=torch.float64, device=dev)
+    chain_stats = torch.empty((Cn, p, 4), dtype=torch.float64, device=dev) if want_chains else None
+    with torch.cuda.device(dev):
+        rc = L.fmcmc_summary_dev(smp.data_ptr(), Cn, k, cap, int(row0), int(N), cols_d.data_ptr(), p,
+                                 probs_h.ctypes.data_as(C.POINTER(C.c_double)), nprobs, work.data_ptr(),
+                                 chain_stats.data_ptr() if want_chains else None, pooled.data_ptr(),
+                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != abi.OK:
+        raise (NotImplementedError if rc == abi.ERR_UNSUPPORTED else ValueError if rc == abi.ERR_ARG else RuntimeError)(
+            abi.last_error())
+    return pooled, chain_stats, work, cols
+
+
+def window_stats(dc, row0, N, cols, probs=(), want_chains=True):
+    """One device summary of the window [row0, row0 + N), copied back:
+    (pooled_stats [p][5], order_stats [p][nprobs][2], chain_stats [C][p][4] or None) as numpy arrays."""
+    pooled, chain_stats, _work, cols = enqueue_window(dc, row0, N, cols, probs, want_chains)
+    p, nprobs = int(cols.size), len(probs)
+    ph = pooled.cpu().numpy()
+    cs = chain_stats.cpu().numpy() if want_chains else None
+    ps = ph[:5 * p].reshape(p, 5)
+    os_ = ph[5 * p:].reshape(p, nprobs, 2)
+    nbad = int(ps[:, 4].sum())
+    if nbad:
+        raise ValueError("%d non-finite value(s) among the rows to summarise (columns %s)"
+                         % (nbad, [int(c) for c, b in zip(cols, ps[:, 4]) if b]))
+    return ps, os_, cs
+
+
+def _per_chain(cs, N):
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ess = np.where(cs[:, :, 2] == 0.0, 0.0, N * cs[:, :, 1] / cs[:, :, 2])
+    return SimpleNamespace(mean=cs[:, :, 0].copy(), sd=np.sqrt(cs[:, :, 1]), tsse=np.sqrt(cs[:, :, 2] / N), ess=ess,
+                           spec0=cs[:, :, 2].copy(), order=cs[:, :, 3].astype(np.int64))
+
+
+def summary(x, quantiles=DEFAULT_QUANTILES, cols=None):
+    """coda::summary of a result: x a DeviceChains (read in place), an Mcmc or a McmcList (uploaded first)."""
+    dc = _as_device_chains(x)
+    probs = tuple(float(q) for q in np.atleast_1d(np.asarray(quantiles, dtype=np.float64)))
+    if len(probs) > abi.SUMMARY_MAX_PROBS:
+        raise ValueError("at most %d quantiles per call" % abi.SUMMARY_MAX_PROBS)
+    N, Cn = int(dc.nrows), int(dc._samples.shape[0])
+    ps, os_, cs = window_stats(dc, 0, N, cols, probs)
+    cols = _columns(dc, cols)
+    names = [dc.names[c] for c in cols] if dc.names is not None else ["par%d" % (c + 1) for c in cols]
+    return McmcSummary(finish_statistics(ps, Cn, N), type7_quantiles(os_, Cn * N, probs), probs, names,
+                       int(dc.iters[0]), int(dc.iters[-1]), dc.thin, Cn, per_chain=_per_chain(cs, N), ess=ps[:, 3].copy())
+
+
+def effective_size(x, cols=None):
+    """coda::effectiveSize: per column, the sum over the chains of N var / spec0 (0 where spec0 is 0)."""
+    dc = _as_device_chains(x)
+    ps, _, _ = window_stats(dc, 0, int(dc.nrows), cols, (), want_chains=False)
+    return ps[:, 3].copy()
+
+
+def geweke(dc, frac1=0.1, frac2=0.5, cols=None):
+    """coda::geweke.diag for every chain at once: z [C][p] from two window calls (the windows of convergence.geweke_diag)."""
+    from .convergence import _window_rows
+    dc = _as_device_chains(dc)
+    iters = np.asarray(dc.iters)
+    start, end = float(iters[0]), float(iters[-1])
+    wins = ((start, np.ceil(start + frac1 * (end - start))), (np.floor(end - frac2 * (end - start)), end))
+    means, variances = [], []
+    for s, e in wins:
+        lo, hi = _window_rows(iters, s, e)
+        _, _, cs = window_stats(dc, lo, hi - lo, cols, ())
+        means.append(cs[:, :, 0])
+        variances.append(cs[:, :, 2] / (hi - lo))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (means[0] - means[1]) / np.sqrt(variances[0] + variances[1])

@@ -283,6 +283,29 @@ int fmcmc_gelman_partial_dev(const double* samples, int64_t nchains, int32_t k, 
 int fmcmc_gelman_finish(const double* partial, int32_t p, int64_t N, double* psrf,
                         double* mpsrf);
 
+/* ---- posterior summary of the kept rows, computed on the device (coda::summary.mcmc(.list), coda::effectiveSize) -----------
+ * Window = kept rows [row0, row0 + N) of each of the `nchains` local chains, columns cols[p] (device int32, each < k); S is the
+ * row stride of `samples` (fmcmc_out.ld_rows), as for fmcmc_gelman_partial_dev.  Per chain c and column j:
+ *   mean, variance (divisor N - 1), spec0 = coda::spectrum0.ar (autocovariances with divisor N of the series centred on its
+ *   mean up to lag M = min(N - 1, floor(10 log10 N)), Levinson-Durbin, aic_m = N log(v_m) + 2 m + 2 at its first minimum o,
+ *   var.pred = v_o N / (N - (o + 1)), spec0 = var.pred / (1 - sum ar)^2; 0 for a constant or exactly linear series), order o.
+ * chain_stats (device, may be NULL): [nchains][p][4] = {mean, variance, spec0, order}.
+ * pooled (device, fmcmc_summary_pooled_len(p, nprobs) doubles): [p][5] = {mean and variance (divisor nchains N - 1) of the
+ *   pooled rows, mean over the chains of spec0, effective size = sum_c (spec0 == 0 ? 0 : N var_c / spec0), count of non-finite
+ *   values}, then [p][nprobs][2] = the order statistics x_(lo), x_(hi) of the nchains N pooled values of the column, with
+ *   index = 1 + (nchains N - 1) probs[q], lo = floor(index), hi = ceil(index) (R's quantile type 7 interpolates between them:
+ *   q = x_(lo) + (index - lo) (x_(hi) - x_(lo))).  They are exact (a radix select on the values' bits, no sort, no sketch).
+ * probs: HOST array of nprobs <= 16 probabilities in [0, 1], read during the call; nprobs = 0 skips the order statistics.
+ * work: device scratch of fmcmc_summary_work_len(nchains, p, nprobs) doubles.  The call only enqueues kernels on hip_stream and
+ * reads `samples` only.  N >= 3; N < 3162278 (AR orders up to 64), FMCMC_ERR_UNSUPPORTED beyond.  Argument errors are found
+ * before any device call (no GPU needed) and leave their text in fmcmc_last_error().  Every sum has a fixed order: the
+ * results are the same bits on every call.  With non-finite values in the window the moments are NaN and the count says so. */
+int64_t fmcmc_summary_work_len(int64_t nchains, int32_t p, int32_t nprobs);
+int64_t fmcmc_summary_pooled_len(int32_t p, int32_t nprobs);
+int fmcmc_summary_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N,
+                      const int32_t* cols, int32_t p, const double* probs, int32_t nprobs, double* work,
+                      double* chain_stats, double* pooled, void* hip_stream);
+
 /* Materialises the canonical Philox stream of a call in device memory, in the FED layout of fmcmc_run:
  * logu[C][nsteps] (entry i-1 = log accept-uniform of loop step i), z[C][nsteps][kz] (N(0,1) when student_df == 0;
  * Student-t with student_df degrees of freedom when student_df > 0 -- kernel_ram: kf for the default qfun rt(k, k),

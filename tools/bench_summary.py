@@ -1,0 +1,82 @@
+"""Time of the device-side summary (fmcmc_amd/summary.py -> csrc/summary.hip) next to the copy it makes unnecessary, on the
+output of two of bench.py's configs:
+  * headline (c2): 1024 chains x 5 parameters x 10^4 kept rows, kernel_normal(scale = 0.02)
+  * c4:            512 chains x 50 parameters x 5000 kept rows, kernel_ram()
+Per shape, one warm-up call and then the best of five of: the enqueued kernels of summary() between two HIP events; the wall
+time of summary() including the small copy back; the wall time of DeviceChains.to_host() of the same rows in the same process.
+Usage: python tools/bench_summary.py [--shapes headline,c4] [--json FILE]   (one JSON line per shape; --json also writes them, with
+the device and the date, to FILE: profiles/bench_summary.json holds the run DESIGN.md section 5.10 quotes)"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SHAPES = {"headline": ("c2", 10000), "c4": ("c4", 5000)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="headline,c4")
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    import torch
+    import fmcmc_amd as F
+    from fmcmc_amd.summary import DEFAULT_QUANTILES, enqueue_window
+    from bench import Config
+    dev = torch.device("cuda", 0)
+    lines = []
+    for shape in a.shapes.split(","):
+        cname, nsteps = SHAPES[shape]
+        cfg = Config(cname)
+        X, y, init = cfg.workload(cfg.chains, 0)
+        kern = F.kernel_normal(scale=0.02) if cname == "c2" else F.kernel_ram()
+        dc = F.MCMC(init, F.gaussian_linreg(X, y), nsteps, nchains=cfg.chains, seed=1215, kernel=kern, _return_device=True,
+                    keep_logpost=False, keep_draws=False)
+        C_, k, N = (int(v) for v in dc.samples.shape)
+
+        def events():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            keep = enqueue_window(dc, 0, N, None, DEFAULT_QUANTILES)
+            e1.record()
+            e1.synchronize()
+            del keep
+            return e0.elapsed_time(e1) * 1e-3
+
+        def wall(fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0
+
+        best = {}
+        for name, fn in (("summary_kernels_ms", events), ("summary_wall_ms", lambda: wall(dc.summary)),
+                         ("to_host_wall_ms", lambda: wall(dc.to_host))):
+            fn()
+            best[name] = round(1e3 * min(fn() for _ in range(5)), 3)
+        nbytes = C_ * k * N * 8
+        lines.append(dict(shape=shape, chains=C_, columns=k, rows=N, sample_bytes=nbytes, quantiles=len(DEFAULT_QUANTILES), **best,
+                          read_gbs_of_9_passes=round(9 * nbytes / best["summary_kernels_ms"] * 1e-6, 1)))
+        print(json.dumps(lines[-1]), flush=True)
+        del dc
+        torch.cuda.empty_cache()
+    if a.json:
+        props = torch.cuda.get_device_properties(dev)
+        with open(a.json, "w") as f:
+            json.dump({"tool": "tools/bench_summary.py", "date_utc": time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime()),
+                       "device": props.name, "arch": getattr(props, "gcnArchName", ""), "torch": torch.__version__,
+                       "timing": "per shape one warm-up call, then the best of five; kernels: HIP events around the enqueued "
+                                 "launches of one summary(); wall: perf_counter around the synchronised call",
+                       "shapes": lines}, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
