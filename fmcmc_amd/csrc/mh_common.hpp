@@ -1,6 +1,6 @@
 // mh_common.hpp -- shared device code of the sweep kernels: launch arguments, LDS-only barriers, wave reductions on
 // DPP / permlane swaps, reflection, per-chain LDS layout, streamed evaluation and the closed forms of the families.
-// Included by mh_engine.hip only (one translation unit; everything lives in its anonymous namespace).
+// Included by every translation unit of the library (mh_tu.hpp); everything lives in an anonymous namespace, a copy per unit.
 #pragma once
 // Device code for gfx950 only: MFMA lane layouts, DPP / permlane forms, LDS sizes and -- for the wide kernels -- the
 // behaviour of sc1 (write-through, L1-bypassing) accesses that the inter-workgroup hand-overs rest on are this target's.
@@ -594,7 +594,7 @@ __device__ __attribute__((noinline)) void shard_columns(ShardCols c) {
 // through C in ascending column order ARE the canonical fma chain of an observation: same bits as shard_columns, the
 // streamed kernels and the oracle.  Operand layout (lane l): A[i = l % 16][kk = l / 16], B[kk = l / 16][j = l % 16],
 // D register r = row 4 r + l / 16, column l % 16 (probed).  So a lane GROUP g = l / 16 ends up with 4 rows per M-tile for chain
-// l % 16, and the slice is laid out (shard_build_mfma, mh_engine.hip) so that those rows are CONSECUTIVE SLOTS of one
+// l % 16, and the slice is laid out (shard_build_mfma, mh_prep.hpp) so that those rows are CONSECUTIVE SLOTS of one
 // canonical lane: group g works for canonical lane q = g / H of the slice (H = 4 / LPW groups per lane), its value
 // t = 4 mt + r (M-tile mt, register r) is slot spg h + t, h = g % H, spg = ceil(nslots / H) <= 10.  The r^2 chain of a
 // canonical lane therefore runs inside a lane in slot order; with H = 2 the second half continues from the partner
