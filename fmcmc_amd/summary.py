@@ -161,6 +161,16 @@ def enqueue_window(dc, row0, N, cols, probs=(), want_chains=True):
     return pooled, chain_stats, work, cols
 
 
+# per series at the head of `work` (csrc/summary.hip: ACS, SLOT_*): r_0 .. r_64 (divisor N; exactly 0 above the window's largest
+# AR order), the mean, the residual sd of the straight-line fit, the count of non-finite values
+WORK_SERIES_LEN, WORK_MAX_ORDER, WORK_MEAN, WORK_RESID_SD, WORK_NON_FINITE = 72, 64, 65, 66, 67
+
+
+def _series_work(work, nseries):
+    """The [nseries][72] head of the `work` tensor of enqueue_window (series = chain * p + column), still on the device."""
+    return work[:nseries * WORK_SERIES_LEN].view(nseries, WORK_SERIES_LEN)
+
+
 def window_stats(dc, row0, N, cols, probs=(), want_chains=True):
     """One device summary of the window [row0, row0 + N), copied back:
     (pooled_stats [p][5], order_stats [p][nprobs][2], chain_stats [C][p][4] or None) as numpy arrays."""

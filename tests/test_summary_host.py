@@ -174,3 +174,79 @@ def test_host_spectrum0_reproduces_the_readme_standard_errors(O, readme_data):
     assert [sig(v, 4) for v in naive] == R["naive_se"]
     assert [sig(v, 4) for v in ts] == [sig(v, 4) for v in R["ts_se"]]
     assert [spectrum0_ar(s[:, j])[1] for j in range(3)] == [28, 35, 36]
+
+
+# ------------------------------------------------------------------------------------------------ the edge tests' own references
+# tests/test_gpu_summary_edges.py holds the device to references and inputs that are built there; what those tests rely on is
+# proved here from the host alone (run with -s for the distances of the float64 family from longdouble).
+@pytest.fixture(scope="module")
+def T():
+    import test_gpu_summary_edges
+    return test_gpu_summary_edges
+
+
+def test_edge_references_restate_the_yardstick(T):
+    from test_gpu_summary import LD, ar1, host_series, spec0_tolerance
+    rng = np.random.default_rng(1)
+    series = [ar1(0.7, 700, rng, mu=2.0), T.seasonal(1300, 31, rng, mu=-1.0), ar1(0.9, 5, rng), np.full(50, 2.5)]
+    for y in series:                              # the longdouble reference is host_series, bit for bit
+        a, b = T.restate(y, LD, acov=True), host_series(y, LD)
+        assert all(a[f] == b[f] for f in ("mean", "var", "spec0", "order", "gap"))
+    tol, refs = T.edge_tolerance(series, "self-check")
+    tol0, _ = spec0_tolerance(series, "self-check, two members")
+    assert tol >= tol0 > 0 and [r["order"] for r in refs] == [host_series(y, LD)["order"] for y in series]
+    # the autocovariances handed to check_acov are what their names say
+    y = series[1]
+    xc = y.astype(LD) - y.astype(LD).sum() / y.size
+    assert np.array_equal(refs[1]["xc"], xc)
+    for l in (0, 1, 30, 31):
+        assert refs[1]["r"][l] == (xc[:y.size - l] * xc[l:]).sum() / LD(y.size)
+        assert abs(refs[1]["absr"][l] - np.abs(xc[:y.size - l] * xc[l:]).sum()) <= 1e-12 * refs[1]["absr"][l]
+    # strided_sum: element i joins chain i mod 512 in row order; the 512 chains join pairwise
+    v = rng.standard_normal(512 * 300 + 77)
+    chains = np.zeros(512)
+    for i, x in enumerate(v):
+        chains[i % 512] += x
+    while chains.size > 1:
+        chains = chains[0::2] + chains[1::2]
+    assert T.strided_sum(v) == chains[0] and T.strided_sum(v[:5]) == (v[0] + v[1]) + (v[2] + v[3]) + v[4]
+    # seasonal obeys its recurrence with unit innovations; key_sort is np.sort where np.sort is defined, and splits the zeros
+    x = T.seasonal(40000, 42, np.random.default_rng(2), phi=0.6, mu=3.0) - 3.0
+    e = x[42:] - 0.6 * x[:-42]
+    assert abs(e.std() - 1.0) < 0.02 and abs(np.corrcoef(e[42:], e[:-42])[0, 1]) < 0.02 and abs(x.var() - 1 / 0.64) < 0.05
+    w = np.concatenate([rng.standard_normal(1000) * 10.0 ** rng.integers(-300, 300, 1000), [5e-324, -5e-324, 1.7e308, -1.7e308]])
+    assert np.array_equal(T.key_sort(w).view(np.uint64), np.sort(w).view(np.uint64))
+    assert [str(z) for z in T.key_sort(np.array([0.0, -0.0, 1.0, -0.0, 0.0, -1.0]))] == ["-1.0", "-0.0", "-0.0", "0.0", "0.0", "1.0"]
+    assert [T.first_n_of_order(M) for M in (16, 40, 48, 63, 64, 65)] == [40, 10000, 63096, 1995263, 2511887, 3162278]
+
+
+def _edge_cases(T, group):
+    if group == "short":
+        return [T.length_case(N, nchains=3) for N in T.SHORT + (20, 21, 40)]
+    if group == "strides":
+        return [T.length_case(N) for N in T.STRIDES]
+    if group == "group-edges":
+        return [T.length_case(n) for M in T.GROUP_EDGES for n in (T.first_n_of_order(M) - 1, T.first_n_of_order(M))]
+    if group == "tile":
+        return [T.length_case(N) for N in T.TILE_EDGES]
+    if group == "width":
+        return [(T.width_case(256), None), (T.width_case(65, seed=65), None)]
+    return [T.big_case(int(group))]
+
+
+@pytest.mark.parametrize("group", ["short", "strides", "group-edges", "tile", "width", "2511886", "2511887", "3162277"])
+def test_edge_inputs_select_their_orders_with_a_clear_gap(T, group):
+    """Every series of the series-length and width tests: the longdouble reference selects the order the input is built for
+    (lag = M and M - 2: spec0 needs every lag), with an AIC gap of at least 1e-3, so check_series leaves out no series."""
+    worst = 0.0
+    for arr, orders in _edge_cases(T, group):
+        C_, N, k = arr.shape
+        label = "%s: %d x %d x %d" % (group, C_, N, k)
+        tol, refs = T.edge_tolerance([arr[c, :, j] for c in range(C_) for j in range(k)], label, acov=False)
+        T.check_reference(refs, orders, label)
+        assert all(r["gap"] >= 1e-6 for r in refs)                 # check_series' own threshold for leaving a series out
+        if orders is None:
+            print("    AR(1) inputs: selected orders %d .. %d" % (min(r["order"] for r in refs), max(r["order"] for r in refs)))
+        assert 0 < tol < 1e-11, (label, tol)
+        worst = max(worst, tol)
+    print("[%s] largest tolerance %.3g" % (group, worst))
