@@ -27,7 +27,8 @@ EXPORTS = ["fmcmc_abi_version", "fmcmc_last_error", "fmcmc_last_kernel", "fmcmc_
            "fmcmc_gelman_work_len",
            "fmcmc_gelman_partial_dev", "fmcmc_gelman_finish", "fmcmc_detmath_dev", "fmcmc_rng_stream_dev",
            "fmcmc_validate_fun", "fmcmc_mcmc_run_fun_dev", "fmcmc_mcmc_run_fun_host",
-           "fmcmc_summary_work_len", "fmcmc_summary_pooled_len", "fmcmc_summary_dev"]
+           "fmcmc_summary_work_len", "fmcmc_summary_pooled_len", "fmcmc_summary_dev",
+           "fmcmc_heidel_work_len", "fmcmc_heidel_out_len", "fmcmc_heidel_dev"]
 SUMMARY_MAX_PROBS = 16
 
 # fmcmc_logpost_fn: out[c] = log f(theta[c][0..k-1]) for c < nchains; 0 = ok (theta, out, hip_stream, user: addresses)
@@ -127,6 +128,12 @@ def lib():
         L.fmcmc_summary_dev.restype = C.c_int
         L.fmcmc_summary_dev.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                         C.c_int32, _dp, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        for nm in ("fmcmc_heidel_work_len", "fmcmc_heidel_out_len"):
+            getattr(L, nm).restype = C.c_int64
+            getattr(L, nm).argtypes = [C.c_int64, C.c_int32, C.c_int64]
+        L.fmcmc_heidel_dev.restype = C.c_int
+        L.fmcmc_heidel_dev.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                       C.c_int32, C.c_int64, C.POINTER(C.c_int64), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.fmcmc_rng_stream_dev.restype = C.c_int
         L.fmcmc_rng_stream_dev.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                            C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -7,7 +7,9 @@
 //   2. summary_ar_kernel       one wavefront per series: Levinson-Durbin + AIC order + spectral density at zero;
 //   3. summary_pool_kernel     fixed-order sums over the chains: pooled mean / variance, mean spec0, effective size;
 //   4. select_*                exact order statistics of the pooled C N values of a column by a most-significant-digit radix
-//                              select on order-preserving 64-bit keys (8 passes of 8 bits, integer counts only).
+//                              select on order-preserving 64-bit keys (8 passes of 8 bits, integer counts only);
+//   5. summary_cvm_kernel      coda::heidel.diag: stages 1-2 on the S0 window and on every candidate tail, then one workgroup
+//                              per (series, candidate) scans the centred tail and sums the squares of its Brownian bridge.
 // Every sum has a fixed shape, so the results do not depend on the launch.  Nothing here writes `samples`.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -413,9 +415,96 @@ __global__ __launch_bounds__(64) void select_scan_kernel(unsigned long long* __r
   }
 }
 
+// ------------------------------------------------------------------------------------------------------- Heidelberger-Welch
+// Cramer-von Mises sum of the Brownian bridge of a tail (coda::heidel.diag): Q = sum_t B_t^2, B_t = sum_{u <= t} (y_u - m), for
+// the rows lo .. N - 1 of the window; m is the mean stages 1-2 left in `stats` for that tail (the same bits).  The series is
+// centred before it is scanned (cumsum(Y) - ybar t cancels).  One workgroup per (series, candidate) walks the tail in tiles
+// of CT rows, staged in LDS with coalesced loads; thread t then owns the CR consecutive rows t CR .. t CR + CR - 1 of the tile
+// (CR odd: the 8-byte LDS reads of a 32-lane half fall on 32 different bank pairs).  Scan: the thread's own sum, a shuffle
+// scan over the lanes, the waves' totals in wave order, and the carry of the tiles before; then the thread walks its rows
+// again and accumulates B^2.  The shape of every sum depends on the length of the tail alone.
+constexpr int CR = 9;               // rows per thread of a tile
+constexpr int CT = ST * CR;         // rows per tile (36 KB of LDS: four workgroups per CU)
+constexpr int CVM_CANDS = 32;       // candidates per launch (their first rows travel as kernel arguments)
+struct CvmCands { long long lo[CVM_CANDS]; };
+
+__global__ __launch_bounds__(ST) void summary_cvm_kernel(const double* __restrict__ samples, long long S, int k, long long row0,
+                                                         long long N, const int* __restrict__ cols, int p, CvmCands cands,
+                                                         const double* __restrict__ stats, long long nseries,
+                                                         double* __restrict__ q_out) {
+  __shared__ double s_x[CT];
+  __shared__ double s_w[SW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long series = blockIdx.x, c = series / p;
+  const int j = (int)(series % p), s = blockIdx.y;
+  const long long lo = cands.lo[s], n = N - lo;
+  const double* __restrict__ x = samples + (c * (long long)k + cols[j]) * S + row0 + lo;
+  const double mean = stats[((long long)s * nseries + series) * 4];
+  double carry = 0.0, q = 0.0;
+  for (long long t0 = 0; t0 < n; t0 += CT) {
+    const int len = (int)((n - t0 < CT) ? n - t0 : CT);
+    double v[CR];
+#pragma unroll
+    for (int u = 0; u < CR; u++) {
+      const int i = u * ST + tid;
+      v[u] = (i < len) ? x[t0 + i] : mean;     // (rows beyond the tail: centred to exactly 0)
+    }
+    __syncthreads();                           // the tile before has been read
+#pragma unroll
+    for (int u = 0; u < CR; u++) s_x[u * ST + tid] = v[u] - mean;
+    __syncthreads();
+    double d[CR], loc = 0.0;
+#pragma unroll
+    for (int u = 0; u < CR; u++) { d[u] = s_x[tid * CR + u]; loc += d[u]; }
+    double incl = loc;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const double up = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += up;
+    }
+    double excl = __shfl_up(incl, 1, 64);
+    if (lane == 0) excl = 0.0;
+    if (lane == 63) s_w[wave] = incl;
+    __syncthreads();
+    double before = carry, total = carry;      // the tiles before, then the waves in wave order
+#pragma unroll
+    for (int w = 0; w < SW; w++) {
+      const double tw = s_w[w];
+      total += tw;
+      if (w < wave) before += tw;
+    }
+    carry = total;
+    double B = before + excl;
+    const int first = tid * CR;
+#pragma unroll
+    for (int u = 0; u < CR; u++) {
+      B += d[u];
+      if (first + u < len) q = __builtin_fma(B, B, q);
+    }
+  }
+  __syncthreads();
+  q = block_sum<SW>(q, s_w);
+  if (tid == 0) q_out[(long long)s * nseries + series] = q;
+}
+
 long long ar_order_max(long long N) {
   const long long m = (long long)floor(10.0 * log10((double)N));
   return m < N - 1 ? m : N - 1;
+}
+
+// Stages 1 and 2 for the window [row0, row0 + N) of every series: acov [series][ACS], stats [series][4].
+int launch_series_stats(const char* who, hipStream_t st, const double* samples, long long S, int k, long long row0, long long N,
+                        const int* cols, int p, long long series, double* acov, double* stats) {
+  const int M = (int)ar_order_max(N);
+  const int tile_rows = (int)(N < LDS_ROWS ? N : LDS_ROWS);
+  const size_t lds = (size_t)(tile_rows + PAD + SW * RED) * sizeof(double);
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(summary_series_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)lds) != hipSuccess)
+    return fail(FMCMC_ERR_DEVICE, "%s: %zu bytes of LDS refused", who, lds);
+  hipLaunchKernelGGL(summary_series_kernel, dim3((unsigned)series), dim3(ST), lds, st, samples, S, k, row0, N, cols, p, M,
+                     tile_rows, acov);
+  hipLaunchKernelGGL(summary_ar_kernel, dim3((unsigned)((series + 3) / 4)), dim3(256), 0, st, acov, series, N, M, stats);
+  return FMCMC_OK;
 }
 
 }  // namespace
@@ -466,15 +555,8 @@ int fmcmc_summary_dev(const double* samples, int64_t nchains, int32_t k, int64_t
   const long long targets = (long long)p * nprobs * 2;
   unsigned long long* hist = state + 3 * targets;
 
-  const int tile_rows = (int)(N < LDS_ROWS ? N : LDS_ROWS);
-  const size_t lds = (size_t)(tile_rows + PAD + SW * RED) * sizeof(double);
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(summary_series_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)lds) != hipSuccess)
-    return fail(FMCMC_ERR_DEVICE, "fmcmc_summary_dev: %zu bytes of LDS refused", lds);
-  hipLaunchKernelGGL(summary_series_kernel, dim3((unsigned)series), dim3(ST), lds, st, samples, (long long)S, (int)k,
-                     (long long)row0, (long long)N, cols, (int)p, (int)M, tile_rows, acov);
-  hipLaunchKernelGGL(summary_ar_kernel, dim3((unsigned)((series + 3) / 4)), dim3(256), 0, st, acov, series, (long long)N, (int)M,
-                     stats);
+  const int rc = launch_series_stats("fmcmc_summary_dev", st, samples, S, k, row0, N, cols, p, series, acov, stats);
+  if (rc != FMCMC_OK) return rc;
   hipLaunchKernelGGL(summary_pool_kernel, dim3((unsigned)p), dim3(256), 0, st, stats, acov, (long long)nchains, (int)p,
                      (long long)N, pooled);
   if (nprobs > 0) {
@@ -501,6 +583,71 @@ int fmcmc_summary_dev(const double* samples, int64_t nchains, int32_t k, int64_t
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(FMCMC_ERR_DEVICE, "fmcmc_summary_dev: launch failed (%s)", hipGetErrorString(e));
+  return FMCMC_OK;
+}
+
+int64_t fmcmc_heidel_work_len(int64_t nchains, int32_t p, int64_t ncand) {
+  if (nchains < 1 || p < 1 || ncand < 1 || nchains > 0x7fffffffLL / p) return 0;
+  return nchains * (int64_t)p * ACS;
+}
+
+int64_t fmcmc_heidel_out_len(int64_t nchains, int32_t p, int64_t ncand) {
+  if (nchains < 1 || p < 1 || ncand < 1 || nchains > 0x7fffffffLL / p || ncand > 0x7fffffffLL) return 0;
+  return (1 + ncand) * nchains * (int64_t)p * 4 + ncand * nchains * (int64_t)p;
+}
+
+int fmcmc_heidel_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N,
+                     const int32_t* cols, int32_t p, int64_t half_row, const int64_t* cand_rows, int64_t ncand, double* work,
+                     double* out, void* hip_stream) {
+  // every argument check comes before the first device call
+  if (!samples || !cols || !cand_rows || !work || !out) return fail(FMCMC_ERR_ARG, "fmcmc_heidel_dev: null argument");
+  if (nchains < 1) return fail(FMCMC_ERR_ARG, "fmcmc_heidel_dev: nchains = %lld, need at least one chain", (long long)nchains);
+  if (k < 1) return fail(FMCMC_ERR_ARG, "fmcmc_heidel_dev: k = %d, need at least one parameter", (int)k);
+  if (p < 1) return fail(FMCMC_ERR_ARG, "fmcmc_heidel_dev: p = %d, need at least one column", (int)p);
+  if (ncand < 1) return fail(FMCMC_ERR_ARG, "fmcmc_heidel_dev: ncand = %lld, need at least one candidate start", (long long)ncand);
+  if (N < 3 || row0 < 0 || row0 + N > S)
+    return fail(FMCMC_ERR_ARG, "fmcmc_heidel_dev: the window [%lld, %lld) is shorter than 3 rows or outside the %lld rows of a chain",
+                (long long)row0, (long long)(row0 + N), (long long)S);
+  if (half_row < 0 || N - half_row < 3)
+    return fail(FMCMC_ERR_ARG, "fmcmc_heidel_dev: half_row = %lld leaves %lld of the %lld rows (spectrum0.ar needs 3)",
+                (long long)half_row, (long long)(N - half_row), (long long)N);
+  for (int64_t s = 0; s < ncand; s++) {
+    if (cand_rows[s] < 0 || N - cand_rows[s] < 3)
+      return fail(FMCMC_ERR_ARG, "fmcmc_heidel_dev: cand_rows[%lld] = %lld leaves %lld of the %lld rows (spectrum0.ar needs 3)",
+                  (long long)s, (long long)cand_rows[s], (long long)(N - cand_rows[s]), (long long)N);
+    if (s > 0 && cand_rows[s] < cand_rows[s - 1])
+      return fail(FMCMC_ERR_ARG, "fmcmc_heidel_dev: cand_rows must ascend (cand_rows[%lld] = %lld after %lld)", (long long)s,
+                  (long long)cand_rows[s], (long long)cand_rows[s - 1]);
+  }
+  if (half_row < cand_rows[0])
+    return fail(FMCMC_ERR_ARG, "fmcmc_heidel_dev: half_row = %lld lies before cand_rows[0] = %lld (the S0 window must be part of "
+                "the longest tail, whose non-finite count covers it)", (long long)half_row, (long long)cand_rows[0]);
+  if (ar_order_max(N) > MAXM)
+    return fail(FMCMC_ERR_UNSUPPORTED, "fmcmc_heidel_dev: N = %lld rows per chain ask for an AR order up to %lld; supported are "
+                "orders up to %d (N < 3162278)", (long long)N, ar_order_max(N), MAXM);
+  if (nchains > 0x7fffffffLL / p || ncand > 0x7fffffffLL)
+    return fail(FMCMC_ERR_UNSUPPORTED, "fmcmc_heidel_dev: %lld chains x %d columns x %lld candidates exceed what one call takes",
+                (long long)nchains, (int)p, (long long)ncand);
+
+  hipStream_t st = (hipStream_t)hip_stream;
+  const long long series = nchains * (long long)p;
+  double* q_out = out + (1 + ncand) * series * 4;
+  // the S0 window, then the tails from the shortest to the longest: `work` is left holding the series work of cand_rows[0]
+  int rc = launch_series_stats("fmcmc_heidel_dev", st, samples, S, k, row0 + half_row, N - half_row, cols, p, series, work, out);
+  for (int64_t s = ncand - 1; s >= 0 && rc == FMCMC_OK; s--)
+    rc = launch_series_stats("fmcmc_heidel_dev", st, samples, S, k, row0 + cand_rows[s], N - cand_rows[s], cols, p, series, work,
+                             out + (1 + s) * series * 4);
+  if (rc != FMCMC_OK) return rc;
+  for (int64_t s0 = 0; s0 < ncand; s0 += CVM_CANDS) {
+    const int ns = (int)(ncand - s0 < CVM_CANDS ? ncand - s0 : CVM_CANDS);
+    CvmCands cands;
+    for (int s = 0; s < CVM_CANDS; s++) cands.lo[s] = cand_rows[s0 + (s < ns ? s : 0)];
+    hipLaunchKernelGGL(summary_cvm_kernel, dim3((unsigned)series, (unsigned)ns), dim3(ST), 0, st, samples, (long long)S, (int)k,
+                       (long long)row0, (long long)N, cols, (int)p, cands, out + (1 + s0) * series * 4, series,
+                       q_out + s0 * series);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(FMCMC_ERR_DEVICE, "fmcmc_heidel_dev: launch failed (%s)", hipGetErrorString(e));
   return FMCMC_OK;
 }
 

@@ -266,6 +266,11 @@ class DeviceChains:
         from .summary import geweke
         return geweke(self, frac1, frac2, cols)
 
+    def heidel(self, eps=0.1, pvalue=0.05, cols=None):
+        """Heidelberger-Welch diagnostic of every chain (convergence_heildel stays the single-chain checker of the reference)."""
+        from .summary import heidel
+        return heidel(self, eps, pvalue, cols)
+
 
 def _validate_common(nsteps, nchains, burnin, thin, multicore):
     if multicore and nchains == 1:

@@ -1,4 +1,5 @@
-"""summary() / effective_size() of a result, computed on the device (coda::summary.mcmc(.list), coda::effectiveSize).
+"""summary() / effective_size() / geweke() / heidel() of a result, computed on the device (coda::summary.mcmc(.list),
+coda::effectiveSize, coda::geweke.diag, coda::heidel.diag).
 
 The first thing every example of the reference does with a result is `summary(ans)` (README.md:178-201, R/mcmc.R:212).  Here the
 kept rows stay where the sweep left them: csrc/summary.hip reduces every (chain, column) series to its mean, variance and
@@ -101,7 +102,7 @@ class McmcSummary:
 def _single_process():
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        raise NotImplementedError("summary() / effective_size() / geweke() reduce the chains of ONE process: under "
+        raise NotImplementedError("summary() / effective_size() / geweke() / heidel() reduce the chains of ONE process: under "
                                   "torch.distributed with more than one rank the chains are sharded and a sharded summary "
                                   "(all-reduced sums and histograms) is not implemented.")
 
@@ -230,3 +231,160 @@ def geweke(dc, frac1=0.1, frac2=0.5, cols=None):
         variances.append(cs[:, :, 2] / (hi - lo))
     with np.errstate(divide="ignore", invalid="ignore"):
         return (means[0] - means[1]) / np.sqrt(variances[0] + variances[1])
+
+
+# ------------------------------------------------------------------------------------------------ Heidelberger-Welch
+def pcramer(q, eps=1e-5):
+    """convergence._pcramer (the distribution function of the Cramer-von Mises statistic, coda's four-term series) for an
+    array of q."""
+    from scipy.special import gamma, kv
+    q = np.asarray(q, dtype=np.float64)
+    log_eps = np.log(eps)
+    total = np.zeros(q.shape)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore", under="ignore"):
+        for k in range(4):
+            zc = gamma(k + 0.5) * np.sqrt(4 * k + 1) / (gamma(k + 1) * np.pi ** 1.5 * np.sqrt(q))
+            u = (4 * k + 1) ** 2 / (16 * q)
+            total = total + np.where(u > -log_eps, 0.0, zc * np.exp(-u) * kv(0.25, u))
+    return np.where(np.isnan(q), np.nan, total)
+
+
+def heidel_candidates(iters):
+    """The windows of convergence.heidel_diag: (the candidate labels coda's seq() yields, the first row each keeps, the row of
+    label end / 2).  A candidate label need not be an iteration of the chain: the tail starts at iters[row]."""
+    from .convergence import _window_rows
+    iters = np.asarray(iters, dtype=np.float64)
+    if iters.size < 1:
+        raise ValueError("no rows to test")
+    start, end = iters[0], iters[-1]
+    labels = np.arange(start, end / 2 + 1e-9, iters.size / 10.0)
+    if labels.size < 1:
+        raise ValueError("heidel: the first iteration %g lies beyond end / 2 = %g, so there is no candidate start "
+                         "(coda::heidel.diag fails here: wrong sign in 'by' argument)" % (start, end / 2))
+    rows = np.array([_window_rows(iters, st)[0] for st in labels], dtype=np.int64)
+    return labels, rows, _window_rows(iters, end / 2)[0]
+
+
+class HeidelDiag:
+    """coda::heidel.diag of every chain: stest, start, pvalue, htest, mean, halfwidth, each [C][p] (NaN where coda prints NA);
+    table [C][p][6] in coda's column order, so table[c] is convergence.heidel_diag of chain c; cvm [C][p][ncand], the
+    Cramer-von Mises statistic of the tail from each of `candidates` (the labels coda's seq() yields; `start` is the label of
+    the first row such a tail keeps, which differs where niter / 10 is off the thinning grid)."""
+    columns = ("stest", "start", "pvalue", "htest", "mean", "halfwidth")
+
+    def __init__(self, table, cvm, candidates, varnames=None, eps=0.1, pvalue=0.05):
+        self.table = np.asarray(table, dtype=np.float64)
+        self.cvm = np.asarray(cvm, dtype=np.float64)
+        self.candidates = np.asarray(candidates, dtype=np.float64)
+        self.varnames = list(varnames) if varnames is not None else ["par%d" % (j + 1) for j in range(self.table.shape[1])]
+        self.eps, self.alpha = float(eps), float(pvalue)
+
+    stest = property(lambda self: self.table[:, :, 0])
+    start = property(lambda self: self.table[:, :, 1])
+    pvalue = property(lambda self: self.table[:, :, 2])
+    htest = property(lambda self: self.table[:, :, 3])
+    mean = property(lambda self: self.table[:, :, 4])
+    halfwidth = property(lambda self: self.table[:, :, 5])
+
+    @staticmethod
+    def _block(rownames, heads, cols):
+        cols = [list(h) + c for h, c in zip(heads, cols)]
+        rows = ["", ""] + list(rownames)
+        widths = [max(len(v) for v in col) for col in [rows] + cols]
+        return "\n".join(" ".join(col[i].ljust(w) for col, w in zip([rows] + cols, widths)) for i in range(len(rows)))
+
+    def __str__(self):
+        word = lambda v: "NA" if np.isnan(v) else ("passed" if v else "failed")
+        num = lambda v: "NA" if np.isnan(v) else "%.3g" % v
+        out = []
+        for c, t in enumerate(self.table):
+            if len(self.table) > 1:
+                out += ["[[%d]]" % (c + 1)]
+            out += [" " * 35,
+                    self._block(self.varnames, (("Stationarity", "test"), ("start", "iteration"), ("p-value", "")),
+                                ([word(v) for v in t[:, 0]], [num(v) for v in t[:, 1]], [num(v) for v in t[:, 2]])),
+                    " " * 30,
+                    self._block(self.varnames, (("Halfwidth", "test"), ("Mean", ""), ("Halfwidth", "")),
+                                ([word(v) for v in t[:, 3]], [num(v) for v in t[:, 4]], [num(v) for v in t[:, 5]])), ""]
+        return "\n".join(out)
+
+    def __repr__(self):
+        return "<HeidelDiag nchain=%d nvar=%d ncand=%d>" % (self.table.shape[0], self.table.shape[1], self.candidates.size)
+
+
+def heidel_finish(n, mean, spec0, Q, S0, starts, eps=0.1, pvalue=0.05, varnames=None, candidates=None):
+    """The host finish of heidel(): n [ncand] rows of each candidate tail; mean, spec0, Q [ncand][C][p] of the tails (Q the sum
+    of squares of the Brownian bridge); S0 [C][p], the spectral density of the window from end / 2; starts [ncand], the
+    iteration label of the first row of each tail (coda's start(Y): what `start` reports); candidates: the labels asked for.
+    Follows convergence.heidel_diag: the start is the first candidate whose statistic I = Q / (n^2 S0) has
+    pcramer(I) < 1 - pvalue (else the last one is reported), halfwidth = 1.96 sqrt(spec0 / n) of that tail."""
+    n = np.asarray(n, dtype=np.float64)[:, None, None]
+    mean, spec0, Q = (np.asarray(a, dtype=np.float64) for a in (mean, spec0, Q))
+    S0 = np.asarray(S0, dtype=np.float64)[None]
+    ncand = Q.shape[0]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        I = Q / (n * S0) / n                                            # [ncand][C][p]
+        pc = pcramer(I)
+        ok = np.isfinite(I) & (pc < 1 - pvalue)
+        converged = ok.any(axis=0)
+        pick = np.where(converged, ok.argmax(axis=0), ncand - 1)[None]   # first passing candidate, else the last examined
+        take = lambda a: np.take_along_axis(np.broadcast_to(a, Q.shape), pick, axis=0)[0]
+        I_s, pc_s, n_s, mean_s = take(I), take(pc), take(n), take(mean)
+        halfwidth = 1.96 * np.sqrt(take(spec0) / n_s)
+        passed = np.isfinite(halfwidth) & (np.abs(halfwidth / mean_s) <= eps)
+    na = ~converged | ~np.isfinite(I_s) | ~np.isfinite(halfwidth)
+    start = np.broadcast_to(np.asarray(starts, dtype=np.float64)[:, None, None], Q.shape)
+    blank = lambda a: np.where(na, np.nan, a)
+    table = np.stack([converged.astype(np.float64), blank(take(start)), np.where(np.isfinite(I_s), 1 - pc_s, np.nan),
+                      blank(passed.astype(np.float64)), blank(mean_s), blank(halfwidth)], axis=-1)
+    return HeidelDiag(table, np.moveaxis(I, 0, -1), starts if candidates is None else candidates, varnames, eps, pvalue)
+
+
+def enqueue_heidel(dc, half_row, cand_rows, cols):
+    """Enqueues one fmcmc_heidel_dev call on the kept rows of `dc` (current torch stream).  Returns the device tensors
+    (out, work) and the columns; nothing is synchronised."""
+    import torch
+    _single_process()
+    L = abi.lib()
+    smp = dc._samples
+    Cn, k, cap = (int(v) for v in smp.shape)
+    if Cn < 1:
+        raise ValueError("no chains to test")
+    if smp.dtype != torch.float64 or not smp.is_contiguous():
+        raise ValueError("samples must be a contiguous float64 [C][k][S] tensor")
+    dev = smp.device
+    cols = _columns(dc, cols)
+    p = int(cols.size)
+    cand = np.ascontiguousarray(cand_rows, dtype=np.int64)
+    cols_d = torch.as_tensor(cols).to(dev)
+    work = torch.empty(max(int(L.fmcmc_heidel_work_len(Cn, p, cand.size)), 1), dtype=torch.float64, device=dev)
+    out = torch.empty(max(int(L.fmcmc_heidel_out_len(Cn, p, cand.size)), 1), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.fmcmc_heidel_dev(smp.data_ptr(), Cn, k, cap, 0, int(dc.nrows), cols_d.data_ptr(), p, int(half_row),
+                                cand.ctypes.data_as(C.POINTER(C.c_int64)), int(cand.size), work.data_ptr(), out.data_ptr(),
+                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != abi.OK:
+        raise (NotImplementedError if rc == abi.ERR_UNSUPPORTED else ValueError if rc == abi.ERR_ARG else RuntimeError)(
+            abi.last_error())
+    return out, work, cols
+
+
+def heidel(x, eps=0.1, pvalue=0.05, cols=None):
+    """coda::heidel.diag for every chain at once: x a DeviceChains (read in place), an Mcmc or a McmcList (uploaded first).
+    The windows are those of convergence.heidel_diag; the device reduces every one of them to its mean, spec0 and the sum of
+    squares of its Brownian bridge (csrc/summary.hip), heidel_finish does the rest on a few numbers per series."""
+    dc = _as_device_chains(x)
+    labels, rows, half_row = heidel_candidates(dc.iters)
+    N, Cn, ncand = int(dc.nrows), int(dc._samples.shape[0]), int(rows.size)
+    out, work, cols = enqueue_heidel(dc, half_row, rows, cols)
+    p = int(cols.size)
+    nbad = _series_work(work, Cn * p)[:, WORK_NON_FINITE].reshape(Cn, p).sum(0).cpu().numpy()
+    if nbad.sum():
+        raise ValueError("%d non-finite value(s) among the rows to test (columns %s)"
+                         % (int(nbad.sum()), [int(c) for c, b in zip(cols, nbad) if b]))
+    oh = out.cpu().numpy()
+    stats = oh[:(1 + ncand) * Cn * p * 4].reshape(1 + ncand, Cn, p, 4)
+    Q = oh[(1 + ncand) * Cn * p * 4:].reshape(ncand, Cn, p)
+    names = [dc.names[c] for c in cols] if dc.names is not None else None
+    return heidel_finish(N - rows, stats[1:, :, :, 0], stats[1:, :, :, 2], Q, stats[0, :, :, 2], np.asarray(dc.iters)[rows], eps,
+                         pvalue, names, candidates=labels)

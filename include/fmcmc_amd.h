@@ -306,6 +306,27 @@ int fmcmc_summary_dev(const double* samples, int64_t nchains, int32_t k, int64_t
                       const int32_t* cols, int32_t p, const double* probs, int32_t nprobs, double* work,
                       double* chain_stats, double* pooled, void* hip_stream);
 
+/* ---- Heidelberger-Welch diagnostic of every chain (coda::heidel.diag), the device part ---------------------------------------
+ * Window, samples, S, cols as for fmcmc_summary_dev.  Rows are counted from row0: half_row is the first row of the window the
+ * spectral density S0 of the stationarity test comes from (coda: window(Y, start = end / 2)); cand_rows is a HOST array, read
+ * during the call, of ncand >= 1 ascending first rows of the candidate tails [cand_rows[s], N) (ncand is not capped);
+ * half_row >= cand_rows[0], so that the longest tail contains every row the call reads.
+ * out (device, fmcmc_heidel_out_len doubles): [1 + ncand][nchains][p][4] = {mean, variance, spec0, order} as fmcmc_summary_dev
+ *   defines them, entry 0 for [half_row, N), entry 1 + s for the tail of candidate s; then [ncand][nchains][p] = Q, the sum
+ *   over the rows t of the tail of B_t^2, B_t = sum_{u <= t} (y_u - mean): the tail is centred on the mean reported for it
+ *   before it is scanned.  The Cramer-von Mises statistic is Q / (n^2 S0), n = N - cand_rows[s].
+ * work: device scratch of fmcmc_heidel_work_len doubles; on return its first nchains p 72 doubles are the series work of the
+ *   tail of cand_rows[0] (per series 72 doubles, the 68th the count of non-finite values among the rows of that tail, which
+ *   are all the rows the call reads).  The `start` coda reports for candidate s is the iteration label of row cand_rows[s].
+ * Every window needs 3 rows (FMCMC_ERR_ARG); N < 3162278 (FMCMC_ERR_UNSUPPORTED).  Argument errors are found before any device
+ * call and leave their text in fmcmc_last_error().  The call only enqueues kernels on hip_stream, reads `samples` only, and
+ * every sum has a fixed shape that depends on the length of its window alone: a series gives the same bits wherever it sits. */
+int64_t fmcmc_heidel_work_len(int64_t nchains, int32_t p, int64_t ncand);
+int64_t fmcmc_heidel_out_len(int64_t nchains, int32_t p, int64_t ncand);
+int fmcmc_heidel_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N,
+                     const int32_t* cols, int32_t p, int64_t half_row, const int64_t* cand_rows, int64_t ncand, double* work,
+                     double* out, void* hip_stream);
+
 /* Materialises the canonical Philox stream of a call in device memory, in the FED layout of fmcmc_run:
  * logu[C][nsteps] (entry i-1 = log accept-uniform of loop step i), z[C][nsteps][kz] (N(0,1) when student_df == 0;
  * Student-t with student_df degrees of freedom when student_df > 0 -- kernel_ram: kf for the default qfun rt(k, k),

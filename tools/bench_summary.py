@@ -4,8 +4,11 @@ output of two of bench.py's configs:
   * c4:            512 chains x 50 parameters x 5000 kept rows, kernel_ram()
 Per shape, one warm-up call and then the best of five of: the enqueued kernels of summary() between two HIP events; the wall
 time of summary() including the small copy back; the wall time of DeviceChains.to_host() of the same rows in the same process.
+At the headline shape also heidel(): its enqueued kernels between two HIP events, its wall time, and the only other route to
+the same table: to_host() plus convergence.heidel_diag chain by chain, timed on --heidel-host-chains chains and scaled to all.
 Usage: python tools/bench_summary.py [--shapes headline,c4] [--json FILE]   (one JSON line per shape; --json also writes them, with
-the device and the date, to FILE: profiles/bench_summary.json holds the run DESIGN.md section 5.10 quotes)"""
+the device and the date, to FILE: profiles/bench_summary.json holds the run DESIGN.md section 5.10 quotes, and
+profiles/bench_summary_heidel.json the headline run with heidel())"""
 import argparse
 import json
 import os
@@ -24,10 +27,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="headline,c4")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--heidel-host-chains", type=int, default=4)
     a = ap.parse_args()
     import torch
     import fmcmc_amd as F
-    from fmcmc_amd.summary import DEFAULT_QUANTILES, enqueue_window
+    from fmcmc_amd.summary import DEFAULT_QUANTILES, enqueue_heidel, enqueue_window, heidel_candidates
     from bench import Config
     dev = torch.device("cuda", 0)
     lines = []
@@ -61,6 +65,29 @@ def main():
                          ("to_host_wall_ms", lambda: wall(dc.to_host))):
             fn()
             best[name] = round(1e3 * min(fn() for _ in range(5)), 3)
+        if shape == "headline":
+            _, rows, half = heidel_candidates(dc.iters)
+
+            def heidel_events():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                keep = enqueue_heidel(dc, half, rows, None)
+                e1.record()
+                e1.synchronize()
+                del keep
+                return e0.elapsed_time(e1) * 1e-3
+
+            for name, fn in (("heidel_kernels_ms", heidel_events), ("heidel_wall_ms", lambda: wall(dc.heidel))):
+                fn()
+                best[name] = round(1e3 * min(fn() for _ in range(5)), 3)
+            host = dc.samples[:a.heidel_host_chains].cpu().numpy()
+            t0 = time.perf_counter()
+            for c in range(host.shape[0]):
+                F.heidel_diag(host[c].T, dc.iters)
+            per_chain = (time.perf_counter() - t0) / host.shape[0]
+            best.update(heidel_candidates=int(rows.size), heidel_diag_host_ms_per_chain=round(1e3 * per_chain, 3),
+                        heidel_host_route_ms=round(best["to_host_wall_ms"] + 1e3 * per_chain * C_, 1))
+            del host
         nbytes = C_ * k * N * 8
         lines.append(dict(shape=shape, chains=C_, columns=k, rows=N, sample_bytes=nbytes, quantiles=len(DEFAULT_QUANTILES), **best,
                           read_gbs_of_9_passes=round(9 * nbytes / best["summary_kernels_ms"] * 1e-6, 1)))
