@@ -28,7 +28,7 @@ EXPORTS = ["fmcmc_abi_version", "fmcmc_last_error", "fmcmc_last_kernel", "fmcmc_
            "fmcmc_gelman_partial_dev", "fmcmc_gelman_finish", "fmcmc_detmath_dev", "fmcmc_rng_stream_dev",
            "fmcmc_validate_fun", "fmcmc_mcmc_run_fun_dev", "fmcmc_mcmc_run_fun_host",
            "fmcmc_summary_work_len", "fmcmc_summary_pooled_len", "fmcmc_summary_dev",
-           "fmcmc_heidel_work_len", "fmcmc_heidel_out_len", "fmcmc_heidel_dev"]
+           "fmcmc_heidel_work_len", "fmcmc_heidel_out_len", "fmcmc_heidel_dev", "fmcmc_plan_route"]
 SUMMARY_MAX_PROBS = 16
 
 # fmcmc_logpost_fn: out[c] = log f(theta[c][0..k-1]) for c < nchains; 0 = ok (theta, out, hip_stream, user: addresses)
@@ -139,6 +139,9 @@ def lib():
                                            C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
         L.fmcmc_detmath_dev.restype = C.c_int
         L.fmcmc_detmath_dev.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p]
+        L.fmcmc_plan_route.restype = C.c_int
+        L.fmcmc_plan_route.argtypes = [C.POINTER(Model), C.POINTER(Kernel), C.POINTER(Run), C.c_int64, C.c_int32,
+                                       C.c_char_p, C.c_size_t]
         _lib = L
     return _lib
 
@@ -150,3 +153,11 @@ def last_error():
 def last_kernel():
     """Kernel variant chosen by this thread's last sweep (diagnostic; results never depend on it)."""
     return lib().fmcmc_last_kernel().decode("utf-8", "replace")
+
+
+def plan_route(model, kernel, run, ld_rows=0, ncu=256):
+    """(code, line): the route planned for a call whose kernel holds HOST pointers, as one line of key=value fields
+    (fmcmc_plan_route; no device needed).  A refused call returns fmcmc_validate's code and an empty line."""
+    buf = C.create_string_buffer(1024)
+    rc = lib().fmcmc_plan_route(C.byref(model), C.byref(kernel), C.byref(run), ld_rows, ncu, buf, len(buf))
+    return rc, buf.value.decode("ascii")

@@ -380,19 +380,24 @@ static size_t shard_theta_doubles(int k, long long ch) { return ((size_t)k * (ch
 static size_t shard_part_doubles(long long ch) { return (size_t)(NT + SH_PAD) * ch; }
 constexpr size_t SHARD_BAR_DOUBLES = 32 * 20 / 2;
 
-// ---- step 1: the launch arguments of the normalised call (cx.m / cx.kn), the adapt history ring and the logistic sums
-static int build_sweep_args(SweepCtx& cx, fmcmc_state* st, fmcmc_out* out, int ram_bounded, SweepArgs& A) {
-  memset(&A, 0, sizeof(A));
+// The normalisation every call goes through before it is planned and launched.  Returns SweepArgs.variate (1: U(0,1) variates).
+static int normalise_call(fmcmc_model& m, fmcmc_kernel& kn) {
   // iid Normal(mu, sigma) IS the Gaussian linear model with an intercept and no covariate -- the same canonical arithmetic in
   // every kernel and in the oracle (fmcmc_oracle.c: pp = 0, icc = 1) -- so it takes that model's fast paths instead of the
   // all-family kernel (tools/option_audit.py)
-  fmcmc_model& m = cx.m;
   if (m.family == FMCMC_FAM_IID_NORMAL) { m.family = FMCMC_FAM_GAUSSIAN_LINREG; m.p = 0; m.intercept = 1; }
   // the uniform kernels ARE the normal kernels with mu = min., scale = max. - min. and U(0,1) variates
+  if (kn.kind == FMCMC_KERNEL_UNIF) { kn.kind = FMCMC_KERNEL_NORMAL; return 1; }
+  if (kn.kind == FMCMC_KERNEL_UNIF_REFLECTIVE) { kn.kind = FMCMC_KERNEL_NORMAL_REFLECTIVE; return 1; }
+  return kn.kind == FMCMC_KERNEL_UMIRROR ? 1 : 0;
+}
+
+// ---- step 1: the launch arguments of the normalised call (cx.m / cx.kn), the adapt history ring and the logistic sums
+static int build_sweep_args(SweepCtx& cx, fmcmc_state* st, fmcmc_out* out, int ram_bounded, SweepArgs& A) {
+  memset(&A, 0, sizeof(A));
+  fmcmc_model& m = cx.m;
   fmcmc_kernel& kn = cx.kn;
-  if (kn.kind == FMCMC_KERNEL_UNIF) { kn.kind = FMCMC_KERNEL_NORMAL; A.variate = 1; }
-  if (kn.kind == FMCMC_KERNEL_UNIF_REFLECTIVE) { kn.kind = FMCMC_KERNEL_NORMAL_REFLECTIVE; A.variate = 1; }
-  if (kn.kind == FMCMC_KERNEL_UMIRROR) A.variate = 1;
+  A.variate = normalise_call(m, kn);
   const bool mirror = (kn.kind == FMCMC_KERNEL_NMIRROR || kn.kind == FMCMC_KERNEL_UMIRROR);
   if (mirror && (!st->mirror_mu || !st->mirror_scale || !st->obs_arate || !st->abs_iter)) {
     set_err("mirror kernels need state->mirror_mu, mirror_scale, obs_arate and abs_iter");
@@ -903,6 +908,35 @@ int fmcmc_mcmc_run_host(const fmcmc_model* m, const fmcmc_kernel* kn, const fmcm
   stage_call(H, kn, run, st, out);
   if (H.rc == FMCMC_OK) H.rc = launch_sweep(&dm, &H.dk, &H.dr, &H.ds, &H.dout, H.kf, any_bounded(kn->fixed, kn->lb, kn->ub, H.k), H.stream);
   return fetch_call(H, kn, run, st, out);
+}
+
+// Diagnostic, no device call and no allocation: the route plan_route gives a call, as one line of key=value fields of Route.
+// `kn` holds HOST pointers, as for fmcmc_mcmc_run_host; ncu: the compute units to plan for.
+int fmcmc_plan_route(const fmcmc_model* m_in, const fmcmc_kernel* kn_in, const fmcmc_run* run, int64_t ld_rows, int32_t ncu,
+                     char* text, size_t text_len) {
+  if (!text || text_len < 1) { set_err("null argument"); return FMCMC_ERR_ARG; }
+  text[0] = 0;
+  const int rv = fmcmc_validate(m_in, kn_in, run);
+  if (rv != FMCMC_OK) return rv;
+  if (!kn_in->fixed || !kn_in->lb || !kn_in->ub) { set_err("kernel arrays lb, ub and fixed are required"); return FMCMC_ERR_ARG; }
+  const int kf = count_free(kn_in, kn_in->fixed), bounded = any_bounded(kn_in->fixed, kn_in->lb, kn_in->ub, kn_in->k);
+  fmcmc_model m = *m_in;
+  fmcmc_kernel kn = *kn_in;
+  normalise_call(m, kn);
+  const long long S = fmcmc_kept_rows(run->nsteps, run->burnin, run->thin);
+  const Route R = plan_route(&m, &kn, run, kf, bounded, variates_per_step(&kn, kf), ld_rows > 0 ? ld_rows : S, ncu > 0 ? ncu : 256, read_knobs());
+  Route B = R; B.form = R.base;
+  const int len = snprintf(text, text_len,
+      "form=%s base=%s kfn=%d kfn_base=%d lds=%zu lds_run=%zu lds_exceeded=%d no_kernel=%d cw=%d tb=%d res_p=%d nblk=%lld wide_switched=%d "
+      "pipe_opt=%d spec_cw=%d mfma_ng=%d mfma_ext=%d mfma_ad=%d kx=%d ring=%d win=%lld nb_launch=%lld ch_launch=%lld nslots=%d "
+      "kfn_fed=%d kfn_shadow=%d lds_shadow=%zu ch_shadow=%lld lpw=%d nmt=%d t10=%d mblk=%d ngrp=%d tiles=%d mfma_form=%d wide2=%d "
+      "kfn_long=%d lds_long=%zu lcg=%lld lrow=%lld",
+      kernel_name(R), kernel_name(B), R.kfn != nullptr, R.kfn_base != nullptr, R.lds, R.lds_run, (int)R.lds_exceeded, (int)R.no_kernel, R.cw, R.tb,
+      R.res_p, R.nblk, (int)R.wide_switched, R.pipe_opt, R.spec_cw, R.mfma_ng, R.mfma_ext, R.mfma_ad, R.kx, (int)R.ring, R.win, R.nb_launch,
+      R.ch_launch, R.nslots, R.kfn_fed != nullptr, R.kfn_shadow != nullptr, R.lds_shadow, R.ch_shadow, R.lpw, R.nmt, R.t10, R.mblk, R.ngrp,
+      R.tiles, (int)R.mfma_form, (int)R.wide2, R.kfn_long != nullptr, R.lds_long, R.lcg, R.lrow);
+  if (len < 0 || (size_t)len >= text_len) { set_err("fmcmc_plan_route: the text buffer holds %zu bytes, the route needs %d", text_len, len + 1); return FMCMC_ERR_ARG; }
+  return FMCMC_OK;
 }
 
 int fmcmc_validate_fun(const fmcmc_kernel* kn, const fmcmc_run* run) {

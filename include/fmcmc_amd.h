@@ -30,6 +30,7 @@
 #ifndef FMCMC_AMD_H
 #define FMCMC_AMD_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -235,6 +236,17 @@ int64_t fmcmc_kept_rows(int64_t nsteps, int64_t burnin, int64_t thin);
 /* Validates a call exactly like R/mcmc.R:501-520 and the kernel initialisers
  * (R/kernel_normal.R:134-135, R/kernel.R:9,129-132); no GPU needed. */
 int fmcmc_validate(const fmcmc_model* model, const fmcmc_kernel* kernel, const fmcmc_run* run);
+
+/* Diagnostic: the route the library plans for a call -- which kernel form would run it and in which shape -- without a device
+ * call or an allocation, so it works on a machine without a GPU.  `kernel` holds HOST pointers (lb, ub and fixed are required;
+ * the data pointers of `model` and the fed streams of `run` are never read, only tested for null by fmcmc_validate).  ld_rows:
+ * fmcmc_out.ld_rows of the call (0: its kept rows); ncu: the compute units of the device to plan for (MI355X: 256).  Reads
+ * FMCMC_AMD_DEBUG as a run does.  Writes one line of space-separated key=value fields into `text`: `form` and `base` as
+ * fmcmc_last_kernel() names them, every number and flag of the plan, and its five kernel handles as 0 (none) or 1.  A run may
+ * still step down from `form` to `base` (a refused cooperative launch), and a fed logistic call may take "logistic-shadow".
+ * Returns fmcmc_validate's code and message for a call it refuses; FMCMC_ERR_ARG when `text` is too short (1024 bytes do). */
+int fmcmc_plan_route(const fmcmc_model* model, const fmcmc_kernel* kernel, const fmcmc_run* run, int64_t ld_rows, int32_t ncu,
+                     char* text, size_t text_len);
 
 /* The hot path. Replaces R/mcmc.R:720-838 x R/kernel_*.R for all chains of the call. */
 int fmcmc_mcmc_run_dev(const fmcmc_model* model, const fmcmc_kernel* kernel,
