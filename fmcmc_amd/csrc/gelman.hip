@@ -150,6 +150,160 @@ __global__ __launch_bounds__(GT) void gelman_chain_mfma(const double* __restrict
   }
 }
 
+// 64 < p <= 256: the NCB (NCB + 1) / 2 tiles of a chain no longer fit one wave's registers (136 tiles = 544 doubles per lane
+// at p = 256), so the OUTPUT is tiled.  The columns form super-blocks of 64 (four 16-column blocks), NSB = ceil(p / 64) of
+// them; one workgroup serves one (chain, super-block pair A <= B): DIAG = true the NSB pairs A == B (10 tiles, the kernel above
+// at a column offset), DIAG = false the NSB (NSB - 1) / 2 pairs A < B (16 tiles = 128 accumulator registers, eight column blocks
+// per row group).  Everything else is the kernel above: the same instruction and lane layout, rows shifted by the chain's first
+// window row, column sums on the VALU, four waves on four contiguous row ranges joined through LDS in wave order.  The column
+// sums of a super-block are formed by every pair that holds it, by the same operations in the same order, so they agree to
+// the bit between workgroups; the diagonal pair writes xbar.  An off-diagonal pair writes its tile and the mirrored one from
+// one value, so S_c is exactly symmetric.  DEPTH row groups are buffered (DEPTH - 1 loads in flight behind the one being
+// multiplied): three, as above, at four and at eight column blocks -- 128 accumulator registers + 3 x 64 of buffers, 440 of
+// the 512 a lane has at one wave per SIMD, no scratch; two stages at eight blocks measured 5 to 7 % slower.
+// The window is read NSB times per chain (a super-block once by its diagonal pair and once by each of the NSB - 1 others).
+template <bool DIAG, int DEPTH>
+__global__ __launch_bounds__(GT) void gelman_pair_mfma(const double* __restrict__ samples, long long S, int k, long long row0,
+                                                       long long N, const int* __restrict__ cols, int p, int nsb,
+                                                       const double* __restrict__ center, double* __restrict__ work) {
+  constexpr int NB = DIAG ? 4 : 8;                  // column blocks in flight: A's four, then B's four
+  constexpr int NT = DIAG ? 10 : 16;                // tiles
+  __shared__ double s_acc[NT * 256];                // [tile][lane * 4 + r]
+  __shared__ double s_sum[NB * 16];                 // column sums of d
+  __shared__ double s_shift[NB * 16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int kk = lane >> 4, j = lane & 15;
+  const int npairs = DIAG ? nsb : nsb * (nsb - 1) / 2;
+  const long long c = blockIdx.x / npairs;
+  int sa = (int)(blockIdx.x % npairs), sb = sa;
+  if (!DIAG) {                                      // pairs in the order (0,1) (0,2) .. (0,nsb-1) (1,2) ..
+    int rem = sa;
+    sa = 0;
+    while (rem >= nsb - 1 - sa) { rem -= nsb - 1 - sa; sa++; }
+    sb = sa + 1 + rem;
+  }
+  const double* base = samples + c * (long long)k * S + row0;
+  // this lane's column of every block (a padded column reads column 0 and is multiplied by 0)
+  const double* colp[NB];
+  double shift[NB], msk[NB], csum[NB];
+#pragma unroll
+  for (int cb = 0; cb < NB; cb++) {
+    const int a = (cb < 4 ? sa : sb) * 64 + (cb & 3) * 16 + j;
+    colp[cb] = base + (long long)cols[a < p ? a : 0] * S;
+    shift[cb] = colp[cb][0];
+    msk[cb] = a < p ? 1.0 : 0.0;
+    csum[cb] = 0.0;
+  }
+  gd4_t acc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; t++) acc[t] = (gd4_t){0.0, 0.0, 0.0, 0.0};
+  // rows of this wave, the groups of 16 and the lane's four rows of a group: as in gelman_chain_mfma
+  const long long groups = (N + 15) / 16, per = (groups + 3) / 4;
+  const long long g_lo = wave * per, g_hi = (g_lo + per < groups) ? g_lo + per : groups;
+  typedef double gd2_t __attribute__((ext_vector_type(2), aligned(8)));
+  double buf[DEPTH][NB][4];
+  auto load = [&](long long gi, double (&v)[NB][4]) {
+    const long long t = 16 * gi + 4 * kk;
+    if (t + 3 < N) {
+#pragma unroll
+      for (int cb = 0; cb < NB; cb++) {
+        const gd2_t lo = *reinterpret_cast<const gd2_t*>(colp[cb] + t), hi = *reinterpret_cast<const gd2_t*>(colp[cb] + t + 2);
+        v[cb][0] = lo[0]; v[cb][1] = lo[1]; v[cb][2] = hi[0]; v[cb][3] = hi[1];
+      }
+    } else {
+#pragma unroll
+      for (int cb = 0; cb < NB; cb++)
+#pragma unroll
+        for (int u = 0; u < 4; u++) v[cb][u] = (t + u < N) ? colp[cb][t + u] : shift[cb];   // (a row beyond the window: d = 0)
+    }
+  };
+#pragma unroll
+  for (int i = 0; i < DEPTH - 1; i++)
+    if (g_lo + i < g_hi) load(g_lo + i, buf[i]);
+  for (long long gi = g_lo; gi < g_hi; gi += DEPTH) {
+#pragma unroll
+    for (int ph = 0; ph < DEPTH; ph++) {       // buffer roles rotate statically
+      if (gi + ph < g_hi) {
+        if (gi + ph + DEPTH - 1 < g_hi) load(gi + ph + DEPTH - 1, buf[(ph + DEPTH - 1) % DEPTH]);
+        double (&cur)[NB][4] = buf[ph];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+          double d[NB];
+#pragma unroll
+          for (int cb = 0; cb < NB; cb++) { d[cb] = (cur[cb][u] - shift[cb]) * msk[cb]; csum[cb] += d[cb]; }
+          if (DIAG) {
+            int t = 0;
+#pragma unroll
+            for (int ab = 0; ab < 4; ab++)
+#pragma unroll
+              for (int bb = ab; bb < 4; bb++, t++) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(d[ab], d[bb], acc[t], 0, 0, 0);
+          } else {
+#pragma unroll
+            for (int ab = 0; ab < 4; ab++)
+#pragma unroll
+              for (int bb = 0; bb < 4; bb++)
+                acc[ab * 4 + bb] = __builtin_amdgcn_mfma_f64_16x16x4f64(d[ab], d[NB - 4 + bb], acc[ab * 4 + bb], 0, 0, 0);
+          }
+        }
+      }
+    }
+  }
+  // column sums: the four kk classes of a column sit in lanes j, j + 16, j + 32, j + 48
+#pragma unroll
+  for (int cb = 0; cb < NB; cb++) {
+    double v = csum[cb];
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    csum[cb] = v;
+  }
+  // waves combine in wave order
+  for (int w = 0; w < 4; w++) {
+    if (wave == w) {
+#pragma unroll
+      for (int t = 0; t < NT; t++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          double* d = &s_acc[t * 256 + lane * 4 + r];
+          *d = (w == 0) ? acc[t][r] : *d + acc[t][r];
+        }
+      if (lane < 16) {
+#pragma unroll
+        for (int cb = 0; cb < NB; cb++) {
+          double* d = &s_sum[cb * 16 + lane];
+          *d = (w == 0) ? csum[cb] : *d + csum[cb];
+          if (w == 0) s_shift[cb * 16 + lane] = shift[cb];
+        }
+      }
+    }
+    __syncthreads();
+  }
+  // finish: D register r of lane l is row 4 r + l / 16, column l % 16 of its tile; la / lb index s_sum, a / b2 the p columns
+  double* wout = work + c * (long long)(p + p * p);
+  const double dn = (double)N;
+  if (DIAG && tid < 64 && sa * 64 + tid < p)
+    wout[sa * 64 + tid] = (s_shift[tid] + s_sum[tid] / dn) - (center ? center[sa * 64 + tid] : 0.0);
+  for (int e = tid; e < NT * 256; e += GT) {
+    const int t = e >> 8, q = e & 255, l = q >> 2, r = q & 3;
+    int ab, bb;
+    if (DIAG) {
+      int rem = t;
+      ab = 0;
+      while (rem >= 4 - ab) { rem -= 4 - ab; ab++; }
+      bb = ab + rem;
+    } else {
+      ab = t >> 2;
+      bb = t & 3;
+    }
+    const int la = ab * 16 + 4 * r + (l >> 4), lb = (NB - 4) * 16 + bb * 16 + (l & 15);
+    const int a = sa * 64 + la, b2 = sb * 64 + lb - (NB - 4) * 16;
+    if (a < p && b2 < p && (!DIAG || ab < bb || a <= b2)) {
+      const double v = (s_acc[e] - s_sum[la] * s_sum[lb] / dn) / (dn - 1.0);
+      wout[p + a * p + b2] = v;
+      wout[p + b2 * p + a] = v;
+    }
+  }
+}
+
 // Fixed-order sum over the local chains -> partial.  64 elements of the partial per block, four threads per element: thread
 // g sums the chains g, g + 4, g + 8, ... in chain order, the four sums are joined as ((g0 + g1) + g2) + g3.  (One block for
 // everything -- 21 elements per thread, each a serial walk over 512 chains -- took 2.5 of the 3.0 ms of a check at C4.)
@@ -289,21 +443,33 @@ extern "C" {
 int64_t fmcmc_gelman_partial_len(int32_t p) { return 1 + 5 * (int64_t)p + 2 * (int64_t)p * p; }
 int64_t fmcmc_gelman_work_len(int64_t nchains, int32_t p) { return nchains * ((int64_t)p + (int64_t)p * p); }
 
+// 1 <= p <= FMCMC_MAX_K.  Up to FMCMC_MAX_K_WAVE columns one workgroup holds a chain's whole covariance (gelman_chain_mfma<1..4>);
+// above, one workgroup per chain and super-block pair (gelman_pair_mfma), diagonal pairs and off-diagonal pairs in a launch each.
 int fmcmc_gelman_partial_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0,
                              int64_t N, const int32_t* cols, int32_t p, const double* center,
                              double* work, double* partial, void* hip_stream) {
-  if (!samples || !cols || !work || !partial || p < 1 || p > FMCMC_MAX_K_WAVE || nchains < 1 || N < 2 ||
+  if (!samples || !cols || !work || !partial || p < 1 || p > FMCMC_MAX_K || nchains < 1 || N < 2 ||
       row0 < 0 || row0 + N > S)
     return FMCMC_ERR_ARG;
   hipStream_t st = (hipStream_t)hip_stream;
 #define GELMAN_LAUNCH(NCBV)                                                                                         \
   hipLaunchKernelGGL(gelman_chain_mfma<NCBV>, dim3((unsigned)nchains), dim3(GT), 0, st, samples, (long long)S, (int)k, \
                      (long long)row0, (long long)N, cols, (int)p, center, work)
-  switch ((p + 15) / 16) {
-    case 1: GELMAN_LAUNCH(1); break;
-    case 2: GELMAN_LAUNCH(2); break;
-    case 3: GELMAN_LAUNCH(3); break;
-    default: GELMAN_LAUNCH(4); break;
+  if (p > FMCMC_MAX_K_WAVE) {
+    // one workgroup per (chain, pair of 64-column super-blocks): the diagonal pairs, then the off-diagonal ones
+    const int nsb = (p + 63) / 64;                 // 2, 3 or 4
+    if (nchains > 0x7fffffff / 6) return FMCMC_ERR_ARG;
+    hipLaunchKernelGGL((gelman_pair_mfma<true, 3>), dim3((unsigned)(nchains * nsb)), dim3(GT), 0, st, samples, (long long)S, (int)k,
+                       (long long)row0, (long long)N, cols, (int)p, nsb, center, work);
+    hipLaunchKernelGGL((gelman_pair_mfma<false, 3>), dim3((unsigned)(nchains * (nsb * (nsb - 1) / 2))), dim3(GT), 0, st, samples,
+                       (long long)S, (int)k, (long long)row0, (long long)N, cols, (int)p, nsb, center, work);
+  } else {
+    switch ((p + 15) / 16) {
+      case 1: GELMAN_LAUNCH(1); break;
+      case 2: GELMAN_LAUNCH(2); break;
+      case 3: GELMAN_LAUNCH(3); break;
+      default: GELMAN_LAUNCH(4); break;
+    }
   }
 #undef GELMAN_LAUNCH
   const int plen = 1 + 5 * (int)p + 2 * (int)p * (int)p;

@@ -271,6 +271,11 @@ class DeviceChains:
         from .summary import heidel
         return heidel(self, eps, pvalue, cols)
 
+    def gelman_diag(self, confidence=0.95, autoburnin=True, multivariate=True, cols=None):
+        """Gelman-Rubin factors with coda's upper confidence limit (convergence_gelman stays the auto-stop checker)."""
+        from .summary import gelman_diag
+        return gelman_diag(self, confidence, autoburnin, multivariate, cols)
+
 
 def _validate_common(nsteps, nchains, burnin, thin, multicore):
     if multicore and nchains == 1:

@@ -1,10 +1,11 @@
-"""summary() / effective_size() / geweke() / heidel() of a result, computed on the device (coda::summary.mcmc(.list),
-coda::effectiveSize, coda::geweke.diag, coda::heidel.diag).
+"""summary() / effective_size() / geweke() / heidel() / gelman_diag() of a result, computed on the device
+(coda::summary.mcmc(.list), coda::effectiveSize, coda::geweke.diag, coda::heidel.diag, coda::gelman.diag).
 
 The first thing every example of the reference does with a result is `summary(ans)` (README.md:178-201, R/mcmc.R:212).  Here the
 kept rows stay where the sweep left them: csrc/summary.hip reduces every (chain, column) series to its mean, variance and
 spectral density at zero (coda::spectrum0.ar), pools them over the chains and selects the exact order statistics the
 quantiles need; a few hundred numbers come back.  The host finish below is the type-7 interpolation and the standard errors.
+gelman_diag() is the one cross-chain diagnostic: csrc/gelman.hip reduces the window, gelman_diag_finish adds coda's upper limit.
 There is no CPU fallback.
 """
 import ctypes as C
@@ -388,3 +389,156 @@ def heidel(x, eps=0.1, pvalue=0.05, cols=None):
     names = [dc.names[c] for c in cols] if dc.names is not None else None
     return heidel_finish(N - rows, stats[1:, :, :, 0], stats[1:, :, :, 2], Q, stats[0, :, :, 2], np.asarray(dc.iters)[rows], eps,
                          pvalue, names, candidates=labels)
+
+
+# ------------------------------------------------------------------------------------------------ Gelman-Rubin
+def _fmt_column_sig(values, digits=3):
+    """One printed column the way R's print.default(digits) lays it out: the fewest decimals, common to the column, that show
+    every entry to `digits` significant digits (trailing zeros that no entry needs are dropped: 1.001 and 1.004 print as 1)."""
+    dec = 0
+    for v in np.asarray(values, dtype=np.float64).ravel():
+        if np.isfinite(v) and v != 0.0:
+            mant, exp = ("%.*e" % (digits - 1, v)).split("e")
+            nsig = len(mant.replace("-", "").replace(".", "").rstrip("0")) or 1
+            dec = max(dec, nsig - 1 - int(exp))
+    dec = min(max(dec, 0), 15)
+    return ["NA" if np.isnan(v) else "%.*f" % (dec, v) for v in np.asarray(values, dtype=np.float64).ravel()]
+
+
+class GelmanDiag:
+    """coda's gelman.diag object: psrf [p][2] ("Point est.", "Upper C.I."), mpsrf (None when it was not asked for or p == 1),
+    the window [start, end] of iteration labels the factors were computed on, and the confidence of the upper limit."""
+    columns = ("Point est.", "Upper C.I.")
+
+    def __init__(self, psrf, mpsrf, varnames=None, start=None, end=None, confidence=0.95):
+        self.psrf = np.asarray(psrf, dtype=np.float64).reshape(-1, 2)
+        self.mpsrf = None if mpsrf is None else float(mpsrf)
+        self.varnames = list(varnames) if varnames is not None else ["par%d" % (j + 1) for j in range(self.psrf.shape[0])]
+        self.start, self.end, self.confidence = start, end, float(confidence)
+
+    def __str__(self):
+        cols = [[name] + _fmt_column_sig(self.psrf[:, j]) for j, name in enumerate(self.columns)]
+        widths = [max(len(s) for s in col) for col in cols]
+        w0 = max(len(r) for r in self.varnames)
+        out = ["Potential scale reduction factors:", ""]
+        for i in range(len(self.varnames) + 1):
+            head = ("" if i == 0 else self.varnames[i - 1]).ljust(w0)
+            out.append(head + " " + " ".join(col[i].rjust(w) for col, w in zip(cols, widths)))
+        if self.mpsrf is not None:
+            out += ["", "Multivariate psrf", "", _fmt_column_sig([self.mpsrf])[0]]
+        return "\n".join(out) + "\n"
+
+    def __repr__(self):
+        return "<GelmanDiag nvar=%d mpsrf=%s>" % (self.psrf.shape[0], "None" if self.mpsrf is None else "%.4g" % self.mpsrf)
+
+
+_GELMAN_FEW_CHAINS = "Convergence test with the Gelman is only available when `nchains` > 1L."
+
+
+def gelman_diag_finish(partial, p, N, confidence=0.95, multivariate=True, varnames=None, start=None, end=None):
+    """The host finish of gelman_diag(): a pure function of the (summed) partial vector of fmcmc_gelman_partial_dev
+    (include/fmcmc_amd.h; partial[0] = number of chains m), p, the window length N and `confidence`.
+    The point estimates and mpsrf are fmcmc_gelman_finish's.  The upper limit is coda::gelman.diag's, from the terms that
+    function forms (w, b, var.w, df.adj):
+        sqrt(df.adj ((N - 1) / N + qf((1 + confidence) / 2, m - 1, 2 w^2 / var.w) (1 + 1 / m) b / (N w)));
+    where var.w is 0 (every chain has the same variance) the quantile is that of R at an infinite denominator df,
+    qchisq(., m - 1) / (m - 1)."""
+    from scipy import stats
+    P = np.ascontiguousarray(partial, dtype=np.float64)
+    p, N = int(p), int(N)
+    if P.size < 1 + 5 * p + 2 * p * p or p < 1 or N < 2:
+        raise ValueError("gelman_diag: a partial of 1 + 5p + 2p^2 numbers, p >= 1 and N >= 2 rows are needed")
+    m = float(P[0])
+    if m < 2:
+        raise ValueError(_GELMAN_FEW_CHAINS)
+    if not 0.0 < confidence < 1.0:
+        raise ValueError("`confidence` must lie in (0, 1).")
+    L = abi.lib()
+    point = np.empty(p)
+    mps = C.c_double()
+    dp = C.POINTER(C.c_double)
+    rc = L.fmcmc_gelman_finish(P.ctypes.data_as(dp), p, N, point.ctypes.data_as(dp), C.byref(mps))
+    if rc == abi.ERR_CHAIN and not (multivariate and p > 1):
+        rc = abi.OK              # (the point estimates are complete before the Cholesky factor of W is tried)
+    if rc == abi.ERR_CHAIN:
+        raise ValueError("cannot compute: W is not positive definite")
+    if rc != abi.OK:
+        raise RuntimeError("fmcmc_gelman_finish failed (%d)" % rc)
+    o = 1
+    sx = P[o:o + p]; o += p
+    sxx = P[o:o + p * p].reshape(p, p).diagonal(); o += 2 * p * p
+    sS = P[o - p * p:o].reshape(p, p).diagonal()
+    s_s2, s_s2s2, s_s2x, s_s2xx = (P[o + i * p:o + (i + 1) * p] for i in range(4))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mu = sx / m
+        w = sS / m
+        b = N * (sxx - m * mu * mu) / (m - 1)
+        ms2 = s_s2 / m
+        var_s2 = (s_s2s2 - m * ms2 * ms2) / (m - 1)
+        cov_s2_x2 = (s_s2xx - m * ms2 * (sxx / m)) / (m - 1)
+        cov_s2_x = (s_s2x - m * ms2 * mu) / (m - 1)
+        var_w = var_s2 / m
+        var_b = 2 * b * b / (m - 1)
+        cov_wb = (N / m) * (cov_s2_x2 - 2 * mu * cov_s2_x)
+        V = (N - 1) * w / N + (1 + 1 / m) * b / N
+        var_V = ((N - 1.0) ** 2 * var_w + (1 + 1 / m) ** 2 * var_b + 2.0 * (N - 1) * (1 + 1 / m) * cov_wb) / (float(N) * N)
+        df_V = 2 * V * V / var_V
+        df_adj = (df_V + 3) / (df_V + 1)
+        q = (1.0 + confidence) / 2.0
+        flat = var_w == 0.0
+        qf = np.where(flat, stats.chi2.ppf(q, m - 1) / (m - 1),
+                      stats.f.ppf(q, m - 1, np.where(flat, 1.0, 2 * w * w / np.where(flat, 1.0, var_w))))
+        upper = np.sqrt(df_adj * ((N - 1.0) / N + qf * (1 + 1 / m) * b / (N * w)))
+    mpsrf = mps.value if (multivariate and p > 1) else None
+    return GelmanDiag(np.stack([point, upper], axis=1), mpsrf, varnames, start, end, confidence)
+
+
+def enqueue_gelman(dc, row0, N, cols):
+    """Enqueues one fmcmc_gelman_partial_dev call on the window [row0, row0 + N) of the kept rows of `dc` (current torch
+    stream), centred on the window's first row of chain 0.  Returns the device tensors (partial, work) and the columns."""
+    import torch
+    _single_process()
+    L = abi.lib()
+    smp = dc._samples
+    Cn, k, cap = (int(v) for v in smp.shape)
+    if row0 < 0 or N < 2 or row0 + N > dc.nrows:
+        raise ValueError("the window [%d, %d) needs at least two of the %d kept rows" % (row0, row0 + N, dc.nrows))
+    if smp.dtype != torch.float64 or not smp.is_contiguous():
+        raise ValueError("samples must be a contiguous float64 [C][k][S] tensor")
+    dev = smp.device
+    cols = _columns(dc, cols)
+    p = int(cols.size)
+    if p > abi.MAX_K:
+        raise ValueError("at most %d columns per call" % abi.MAX_K)
+    cols_d = torch.as_tensor(cols).to(dev)
+    center = smp[0, cols_d.long(), row0].contiguous()
+    partial = torch.empty(int(L.fmcmc_gelman_partial_len(p)), dtype=torch.float64, device=dev)
+    work = torch.empty(int(L.fmcmc_gelman_work_len(Cn, p)), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.fmcmc_gelman_partial_dev(smp.data_ptr(), Cn, k, cap, int(row0), int(N), cols_d.data_ptr(), p, center.data_ptr(),
+                                        work.data_ptr(), partial.data_ptr(),
+                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != abi.OK:
+        raise RuntimeError("fmcmc_gelman_partial_dev failed (%d)" % rc)
+    return partial, work, cols
+
+
+def gelman_diag(x, confidence=0.95, autoburnin=True, multivariate=True, cols=None):
+    """coda::gelman.diag of a result: x a DeviceChains (read in place), an Mcmc or a McmcList (uploaded first).  With
+    `autoburnin` the factors are those of the second half of the rows (coda's window, the one convergence_gelman tests).
+    The device reduces every chain's window to its mean and covariance and sums them (fmcmc_gelman_partial_dev, any
+    p <= 256); gelman_diag_finish does the rest on that vector.  coda's `transform = TRUE` (log / logit of bounded
+    variables before the test) is not offered: transform the columns before the call."""
+    from .convergence import _window
+    from .mcmc import Mcmc, McmcList
+    _single_process()
+    if isinstance(x, Mcmc) or (isinstance(x, McmcList) and len(x) < 2):       # (before anything is uploaded)
+        raise ValueError(_GELMAN_FEW_CHAINS)
+    dc = _as_device_chains(x)
+    if int(dc._samples.shape[0]) < 2:
+        raise ValueError(_GELMAN_FEW_CHAINS)
+    row0, N = _window(dc.iters) if autoburnin else (0, int(dc.nrows))
+    partial, _work, cols = enqueue_gelman(dc, row0, N, cols)
+    names = [dc.names[c] for c in cols] if dc.names is not None else ["par%d" % (c + 1) for c in cols]
+    return gelman_diag_finish(partial.cpu().numpy(), int(cols.size), N, confidence, multivariate, names,
+                              int(dc.iters[row0]), int(dc.iters[-1]))

@@ -45,8 +45,9 @@ extern "C" {
  * its matrices live in LDS while they fit and in the chain's own Sigma buffer beyond (kernel_adapt from 134, kernel_ram from 184
  * free parameters).  Raised from 128 to 256 under the same FMCMC_ABI_VERSION: no struct, signature or buffer layout changed
  * (INTEGRATION.md); 256 and not more because the host oracle's stack frame grows as k^2;
- * fmcmc_gelman_partial_dev (MFMA window tiles) takes p <= FMCMC_MAX_K_WAVE columns (above it the host side forms the same partial
- * sums itself, fmcmc_amd/convergence.py), fmcmc_gelman_finish any p <= FMCMC_MAX_K. */
+ * fmcmc_gelman_partial_dev and fmcmc_gelman_finish take any p <= FMCMC_MAX_K columns (the window reduction tiles its output
+ * above FMCMC_MAX_K_WAVE: one workgroup per chain and pair of 64-column blocks; widened from FMCMC_MAX_K_WAVE under the same
+ * FMCMC_ABI_VERSION, no layout changed). */
 #define FMCMC_MAX_K_WAVE 64
 
 /* ---- log-posterior families: the `fun` argument of MCMC() (R/mcmc.R:327) ---------- */
@@ -283,7 +284,8 @@ int fmcmc_mcmc_run_fun_host(const fmcmc_kernel* kernel, const fmcmc_run* run, fm
 int64_t fmcmc_gelman_partial_len(int32_t p);
 /* doubles of scratch (device) the partial kernel needs: per chain xbar[p] and S_c[p][p] */
 int64_t fmcmc_gelman_work_len(int64_t nchains, int32_t p);
-/* cols[p]: parameter indices to test (the free parameters, R/mcmc.R:950-968), device int32.
+/* cols[p]: parameter indices to test (the free parameters, R/mcmc.R:950-968), device int32; 1 <= p <= FMCMC_MAX_K.
+ * work: fmcmc_gelman_work_len doubles, left as work[c] = {xbar[p] - center, S_c[p][p] (both triangles)} per chain.
  * center[p] (device, may be NULL): xbar sums are accumulated relative to it (all ranks must
  * pass the same vector); it only limits cancellation, R-hat is shift-invariant. */
 int fmcmc_gelman_partial_dev(const double* samples, int64_t nchains, int32_t k, int64_t S,
@@ -291,7 +293,7 @@ int fmcmc_gelman_partial_dev(const double* samples, int64_t nchains, int32_t k, 
                              const double* center, double* work, double* partial,
                              void* hip_stream);
 /* Host finish on the (all-reduced) partial: psrf[p] point estimates, *mpsrf (NaN if p == 1).
- * Returns FMCMC_ERR_CHAIN when W is not positive definite (gelman.diag would fail). */
+ * Returns FMCMC_ERR_CHAIN when W is not positive definite (gelman.diag would fail); psrf[p] is complete then too. */
 int fmcmc_gelman_finish(const double* partial, int32_t p, int64_t N, double* psrf,
                         double* mpsrf);
 

@@ -1,0 +1,203 @@
+"""GPU tests of the Gelman-Rubin window reduction above 64 columns (csrc/gelman.hip: gelman_pair_mfma, one workgroup per chain
+and pair of 64-column super-blocks), of convergence_gelman on it and of gelman_diag().
+
+Yardsticks:
+ * the partial vector against its numpy definition (test_abi.numpy_gelman_partial) within the project's own tolerance of
+   test_gelman_partial_kernel_wide: rtol 1e-9, atol 1e-11 max|ref|.  A float64 emulation of the kernel's arithmetic (shift by the
+   first row, one pass, four row quarters) sits at 1.4e-4 of that tolerance at these shapes, as numpy does against longdouble;
+ * psrf / mpsrf of fmcmc_gelman_finish on the device partial against the oracle's coda restatement, rtol 1e-9 as in
+   tests/test_k256_host.py;
+ * equalities that need no tolerance: placement in the launch, repetition, symmetry, what a call leaves of NaN-filled buffers;
+ * p <= 64 against the bits the library of the parent commit produced (tests/golden/gelman_narrow_bits.json, written by
+   tests/golden/make_gelman_narrow_bits.py).
+Every buffer is filled with NaN before a call and carries GUARD more elements than documented, which must stay NaN.
+"""
+import ctypes as C
+import functools
+import json
+import os
+
+import numpy as np
+import pytest
+
+from test_abi import numpy_gelman_partial
+
+pytestmark = pytest.mark.gpu
+GUARD = 64
+GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "gelman_narrow_bits.json")
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _gpu():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+
+
+# ------------------------------------------------------------------------------------------------ inputs
+def make_chains(Cn, k, S, seed):
+    """[C][k][S]: noise, an offset per chain and column, a slow random walk."""
+    rng = np.random.default_rng(seed)
+    return (0.5 * rng.standard_normal((Cn, k, S)) + 0.2 * rng.standard_normal((Cn, k, 1)) + 3.0
+            + 0.01 * np.cumsum(rng.standard_normal((Cn, k, S)), axis=2))
+
+
+def pick_columns(k, p, seed):
+    return (np.arange(k) if p == k else np.sort(np.random.default_rng(seed).choice(k, size=p, replace=False))).astype(np.int32)
+
+
+def device_partial(x, cols, row0, N, center=None):
+    """One fmcmc_gelman_partial_dev call on x [C][k][S]: (work [C][p + p p], partial) as numpy; buffers NaN-filled, guards
+    checked."""
+    import torch
+    from fmcmc_amd import _abi as abi
+    L = abi.lib()
+    Cn, k, S = x.shape
+    p = len(cols)
+    xd = torch.as_tensor(np.ascontiguousarray(x)).cuda()
+    cd = torch.as_tensor(np.asarray(cols, dtype=np.int32)).cuda()
+    center = x[0, cols, row0] if center is None else center
+    ctr = torch.as_tensor(np.ascontiguousarray(center)).cuda()
+    wlen, plen = int(L.fmcmc_gelman_work_len(Cn, p)), int(L.fmcmc_gelman_partial_len(p))
+    assert wlen == Cn * (p + p * p) and plen == 1 + 5 * p + 2 * p * p
+    work = torch.full((wlen + GUARD,), float("nan"), dtype=torch.float64, device="cuda")
+    part = torch.full((plen + GUARD,), float("nan"), dtype=torch.float64, device="cuda")
+    rc = L.fmcmc_gelman_partial_dev(xd.data_ptr(), Cn, k, S, row0, N, cd.data_ptr(), p, ctr.data_ptr(), work.data_ptr(),
+                                    part.data_ptr(), None)
+    assert rc == abi.OK, rc
+    torch.cuda.synchronize()
+    wh, ph = work.cpu().numpy(), part.cpu().numpy()
+    assert np.isnan(wh[wlen:]).all() and np.isnan(ph[plen:]).all()      # nothing written past the documented lengths
+    return wh[:wlen].reshape(Cn, p + p * p), ph[:plen]
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+# (chains, p, N, k, row0): the row stride S is odd and larger than the window; p = 200 is a sorted subset of 256 columns
+SHAPES = [(3, 65, 2, 65, 7), (3, 80, 17, 80, 1), (2, 129, 65, 129, 3), (3, 200, 333, 256, 101), (4, 256, 333, 256, 0),
+          (2, 128, 15, 128, 5), (2, 128, 16, 128, 5), (2, 128, 17, 128, 5), (2, 128, 63, 128, 5), (2, 128, 64, 128, 5),
+          (2, 128, 65, 128, 5)]
+
+
+@functools.lru_cache(maxsize=None)
+def case(Cn, p, N, k, row0):
+    """Input, device result and numpy reference of one shape, computed once and shared (read-only)."""
+    S = row0 + N + 2
+    S += 1 - S % 2
+    x = make_chains(Cn, k, S, 1000 * p + N)
+    cols = pick_columns(k, p, p)
+    work, part = device_partial(x, cols, row0, N)
+    win = x[:, cols, row0:row0 + N].transpose(0, 2, 1)           # [m][N][p]
+    ref = numpy_gelman_partial(win, x[0, cols, row0])
+    for a in (x, work, part, win, ref):
+        a.setflags(write=False)
+    return x, cols, work, part, win, ref
+
+
+# ------------------------------------------------------------------------------------------------ 1. the partial
+@pytest.mark.parametrize("Cn,p,N,k,row0", SHAPES)
+def test_partial_equals_its_numpy_definition(Cn, p, N, k, row0):
+    x, cols, work, part, win, ref = case(Cn, p, N, k, row0)
+    assert not np.isnan(work).any() and not np.isnan(part).any()
+    tol = 1e-9 * np.abs(ref) + 1e-11 * np.abs(ref).max()
+    print("worst |partial - ref| / tolerance: %.2e" % (np.abs(part - ref) / tol).max())
+    assert np.allclose(part, ref, rtol=1e-9, atol=1e-11 * np.abs(ref).max())
+    # the per-chain block: {xbar - center, S_c}
+    xb = win.mean(1) - x[0, cols, row0]
+    assert np.allclose(work[:, :p], xb, rtol=1e-9, atol=1e-11 * np.abs(xb).max())
+    Sc = work[:, p:].reshape(Cn, p, p)
+    assert np.array_equal(_bits(Sc), _bits(Sc.transpose(0, 2, 1)))     # exactly symmetric
+
+
+# ------------------------------------------------------------------------------------------------ 2. finish on the device partial
+@pytest.mark.parametrize("Cn,p,N,k,row0", [(4, 256, 333, 256, 0), (3, 200, 333, 256, 101)])
+def test_finish_on_the_device_partial_equals_the_oracle(O, Cn, p, N, k, row0):
+    """(Most of this test's seconds at p = 256 are the oracle's own cyclic Jacobi eigenvalue sweeps, as in
+    tests/test_k256_host.py; the device call and fmcmc_gelman_finish take milliseconds.)"""
+    from fmcmc_amd import _abi as abi
+    x, cols, work, part, win, ref = case(Cn, p, N, k, row0)
+    psrf = np.empty(p); mps = C.c_double(); dp = C.POINTER(C.c_double)
+    pc = np.array(part)
+    assert abi.lib().fmcmc_gelman_finish(pc.ctypes.data_as(dp), p, N, psrf.ctypes.data_as(dp), C.byref(mps)) == abi.OK
+    opsrf, ompsrf = O.gelman(win)
+    print("worst psrf distance %.2e, mpsrf %.2e (relative)" % (np.abs(psrf / opsrf - 1).max(), abs(mps.value / ompsrf - 1)))
+    assert np.allclose(psrf, opsrf, rtol=1e-9) and abs(mps.value - ompsrf) < 1e-9 * ompsrf
+
+
+# ------------------------------------------------------------------------------------------------ 3. equalities
+@pytest.mark.parametrize("p,N", [(200, 70), (65, 33)])
+def test_a_chain_does_not_depend_on_the_launch(p, N):
+    row0 = 3
+    x = make_chains(5, p, row0 + N + 2, p)
+    cols = np.arange(p, dtype=np.int32)
+    center = x[0, cols, row0].copy()
+    w5, p5 = device_partial(x, cols, row0, N, center)
+    w5b, p5b = device_partial(x, cols, row0, N, center)
+    assert np.array_equal(_bits(w5), _bits(w5b)) and np.array_equal(_bits(p5), _bits(p5b))       # two calls
+    wr, _ = device_partial(x[::-1], cols, row0, N, center)                                       # another place in the launch
+    assert np.array_equal(_bits(wr[::-1]), _bits(w5))
+    for c in (0, 2, 4):                                                                          # a launch of its own
+        w1, _ = device_partial(x[c:c + 1], cols, row0, N, center)
+        assert np.array_equal(_bits(w1[0]), _bits(w5[c]))
+
+
+@pytest.mark.parametrize("Cn,p,N,k,row0", [(3, 65, 2, 65, 7), (2, 129, 65, 129, 3)])
+def test_padded_super_blocks_leave_no_nan(Cn, p, N, k, row0):
+    """The last super-block holds one live column: the NaN the buffers were filled with is gone from every documented element,
+    and the padded columns (which read column 0 and multiply by 0) put none into the live ones."""
+    x, cols, work, part, win, ref = case(Cn, p, N, k, row0)
+    assert np.isfinite(work).all() and np.isfinite(part).all()
+    assert part[0] == Cn
+
+
+# ------------------------------------------------------------------------------------------------ 4. p <= 64 is untouched
+def narrow_case(p):
+    """The p <= 64 inputs of the golden fixture and the bits of the device result (work, partial)."""
+    Cn, k, S, row0, N = 5, 64, 141, 7, 131
+    x = make_chains(Cn, k, S, 64000 + p)
+    cols = pick_columns(k, p, p)
+    work, part = device_partial(x, cols, row0, N)
+    return _bits(work).ravel(), _bits(part)
+
+
+def bit_checksums(u64):
+    """Order-dependent and order-independent 64-bit checksums of a vector of bit patterns, as hex strings."""
+    u64 = np.asarray(u64, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        weighted = (u64 * (np.arange(u64.size, dtype=np.uint64) * np.uint64(2) + np.uint64(1))).sum(dtype=np.uint64)
+    return {"n": int(u64.size), "xor": "%016x" % int(np.bitwise_xor.reduce(u64)), "weighted_sum": "%016x" % int(weighted),
+            "first": "%016x" % int(u64[0]), "last": "%016x" % int(u64[-1])}
+
+
+@pytest.mark.parametrize("p", [64, 50])
+def test_at_most_64_columns_give_the_bits_of_the_parent(p):
+    fx = json.load(open(GOLDEN))["p%d" % p]
+    work, part = narrow_case(p)
+    assert bit_checksums(work) == fx["work"]
+    assert bit_checksums(part) == fx["partial"]
+
+
+# ------------------------------------------------------------------------------------------------ 5. the checker and gelman_diag
+def test_check_device_and_gelman_diag_at_200_columns(O):
+    import torch
+    import fmcmc_amd as f
+    Cn, p, S = 3, 200, 700
+    x = make_chains(Cn, p, S, 5)
+    dc = f.DeviceChains(torch.as_tensor(x).cuda(), None, None, np.arange(1, S + 1), 1, None, 0, Cn)
+    chk = f.convergence_gelman(100, threshold=1.10)
+    verdict = chk.check_device(dc, np.arange(p))
+    end, val, psrf = chk.history[-1]
+    win = x[:, :, 350:].transpose(0, 2, 1)                       # coda's autoburnin: iterations 351 .. 700
+    opsrf, ompsrf = O.gelman(win)
+    assert end == S and verdict == bool(ompsrf < 1.10)
+    assert np.allclose(psrf, opsrf, rtol=1e-9) and abs(val - ompsrf) < 1e-9 * ompsrf
+    g = f.gelman_diag(dc)
+    assert isinstance(g, f.GelmanDiag) and (g.start, g.end) == (351, 700) and g.psrf.shape == (p, 2)
+    assert np.array_equal(_bits(g.psrf[:, 0]), _bits(psrf)) and g.mpsrf == val
+    assert np.all(g.psrf[:, 1] >= g.psrf[:, 0])
+    gm = dc.gelman_diag(multivariate=False, autoburnin=False, cols=[3, 150])
+    assert gm.mpsrf is None and gm.varnames == ["par4", "par151"] and (gm.start, gm.end) == (1, 700)
+    o2, _ = O.gelman(x[:, [3, 150], :].transpose(0, 2, 1))
+    assert np.allclose(gm.psrf[:, 0], o2, rtol=1e-9)
