@@ -24,8 +24,10 @@ constexpr int GT = 256;  // threads per block
 // it is as much arithmetic as memory traffic.  So it runs on the matrix cores: v_mfma_f64_16x16x4 with M = N = a block of
 // 16 columns and K = 4 consecutive rows.  Both operands have the SAME lane layout (lane l holds row t0 + l / 16 of column
 // 16 cb + l % 16), so a K-step loads one double per lane and column block and feeds all NCB (NCB + 1) / 2 tile pairs.
-// ONE pass over the data: rows are shifted by the chain's first window row (d = x - x[row0]; the shift is within a few
-// standard deviations of the mean, which keeps sum d d' - N dbar dbar' free of cancellation), the column sums ride along on
+// ONE pass over the data: rows are shifted by the chain's first window row (d = x - x[row0]).  The shift is a row of the
+// window, so sum d_a^2 = (N - 1) E_a with E_a = S_aa + N / (N - 1) (x[row0] - mean)_a^2 <= N S_aa (the first row is at most
+// sqrt(N - 1) window standard deviations from the window mean), and sum d d' - N dbar dbar' stays within (N + 32) u sqrt(E_a E_b) of S_ab, u = 2^-53
+// (tests/gelman_ref.py derives it, tests/test_gpu_gelman_narrow.py holds the device to it).  The column sums ride along on
 // the VALU.  The four waves take four contiguous row ranges and are combined through LDS in wave order; the result does
 // not depend on the launch.  (The previous VALU version: one thread per column for the means, LDS-tiled pair products:
 // 4.8 ms = 215 GB/s at C4's width.)

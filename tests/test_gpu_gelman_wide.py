@@ -5,6 +5,8 @@ Yardsticks:
  * the partial vector against its numpy definition (test_abi.numpy_gelman_partial) within the project's own tolerance of
    test_gelman_partial_kernel_wide: rtol 1e-9, atol 1e-11 max|ref|.  A float64 emulation of the kernel's arithmetic (shift by the
    first row, one pass, four row quarters) sits at 1.4e-4 of that tolerance at these shapes, as numpy does against longdouble;
+ * `work` against longdouble and the partial against its definition from the device's `work`, within the a-priori bounds of
+   tests/gelman_ref.py (derived from the kernel's order of operations, proven sane by tests/test_gelman_narrow_host.py);
  * psrf / mpsrf of fmcmc_gelman_finish on the device partial against the oracle's coda restatement, rtol 1e-9 as in
    tests/test_k256_host.py;
  * equalities that need no tolerance: placement in the launch, repetition, symmetry, what a call leaves of NaN-filled buffers;
@@ -109,6 +111,23 @@ def test_partial_equals_its_numpy_definition(Cn, p, N, k, row0):
     assert np.allclose(work[:, :p], xb, rtol=1e-9, atol=1e-11 * np.abs(xb).max())
     Sc = work[:, p:].reshape(Cn, p, p)
     assert np.array_equal(_bits(Sc), _bits(Sc.transpose(0, 2, 1)))     # exactly symmetric
+
+
+@pytest.mark.parametrize("Cn,p,N", [(3, 65, 17), (3, 200, 70)])
+def test_work_and_partial_within_the_a_priori_bounds(Cn, p, N):
+    """The yardstick of tests/test_gpu_gelman_narrow.py on gelman_pair_mfma (the same arithmetic per element): `work` against
+    longdouble within the bounds derived in tests/gelman_ref.py, the partial against its definition evaluated in longdouble
+    from the device's own `work` within the chain-sum bound."""
+    import gelman_ref as R
+    k, row0 = p + 3, 5
+    x = make_chains(Cn, k, row0 + N + 4, 2000 * p + N)
+    cols = np.random.default_rng(p).permutation(k)[:p].astype(np.int32)
+    work, part = device_partial(x, cols, row0, N)
+    rx, rS = R.work_ratios(work, x, cols, row0, N, x[0, cols, row0])
+    rp = R.partial_ratio(part, work, p)
+    print("p = %d N = %d: worst ratio xbar %.3f, S %.3f, chain sum %.3f" % (p, N, rx, rS, rp))
+    assert rx < 1 and rS < 1 and rp < 1
+    assert part[0] == Cn
 
 
 # ------------------------------------------------------------------------------------------------ 2. finish on the device partial
