@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi as abi
+from .summary import gelman_partial_dev
 
 
 def _window(iters):
@@ -45,7 +46,6 @@ class convergence_gelman:
         L = abi.lib()
         samples = chains.samples             # view of the filled rows; the buffer's row stride is its capacity
         Cn, k, S = samples.shape
-        stride = chains.capacity
         dev = samples.device
         p = int(len(cols))
         distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
@@ -67,12 +67,7 @@ class convergence_gelman:
             dist.all_reduce(center, op=dist.ReduceOp.SUM, group=group)
         if Cn > 0:
             work = torch.empty(int(L.fmcmc_gelman_work_len(Cn, p)), dtype=torch.float64, device=dev)
-            with torch.cuda.device(dev):
-                rc = L.fmcmc_gelman_partial_dev(samples.data_ptr(), Cn, k, stride, row0, N, cols_d.data_ptr(), p,
-                                                center.data_ptr(), work.data_ptr(), partial.data_ptr(),
-                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            if rc != abi.OK:
-                raise RuntimeError("fmcmc_gelman_partial_dev failed (%d)" % rc)
+            gelman_partial_dev(samples, Cn, k, chains.capacity, row0, N, cols_d, center, work, partial)
             if self.check_invariant:  # rm_invariant: sd of ALL entries (R/convergence.R:171-173)
                 # sum and sum of squares of the whole window from the per-chain means / variances the reduction just left in
                 # `work` (an indexed copy of the window itself was 1 GB and ~1 ms per check at config C4)

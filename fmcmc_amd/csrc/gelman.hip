@@ -17,13 +17,13 @@ namespace {
 
 constexpr int GT = 256;  // threads per block
 
-// One block (4 wavefronts) per chain: work[c] = { xbar[p] - center, S_c[p*p] } of the window [row0, row0 + N).
+// Per-chain window mean and covariance: work[c] = { xbar[p] - center, S_c[p*p] } of the window [row0, row0 + N).
 //
 // The window of one chain is a column-major N x p matrix D; its covariance is the rank-N update D'D -- the one GEMM-shaped
 // piece of the whole engine besides the log-posterior, and at config C4 (512 chains x p = 50 x 5,000 rows: 1 GB, 13 GFLOP)
 // it is as much arithmetic as memory traffic.  So it runs on the matrix cores: v_mfma_f64_16x16x4 with M = N = a block of
 // 16 columns and K = 4 consecutive rows.  Both operands have the SAME lane layout (lane l holds row t0 + l / 16 of column
-// 16 cb + l % 16), so a K-step loads one double per lane and column block and feeds all NCB (NCB + 1) / 2 tile pairs.
+// 16 cb + l % 16), so a K-step loads one double per lane and column block and feeds every tile that holds the block.
 // ONE pass over the data: rows are shifted by the chain's first window row (d = x - x[row0]).  The shift is a row of the
 // window, so sum d_a^2 = (N - 1) E_a with E_a = S_aa + N / (N - 1) (x[row0] - mean)_a^2 <= N S_aa (the first row is at most
 // sqrt(N - 1) window standard deviations from the window mean), and sum d d' - N dbar dbar' stays within (N + 32) u sqrt(E_a E_b) of S_ab, u = 2^-53
@@ -31,145 +31,27 @@ constexpr int GT = 256;  // threads per block
 // the VALU.  The four waves take four contiguous row ranges and are combined through LDS in wave order; the result does
 // not depend on the launch.  (The previous VALU version: one thread per column for the means, LDS-tiled pair products:
 // 4.8 ms = 215 GB/s at C4's width.)
+//
+// The columns form super-blocks of 64 (four 16-column blocks), nsb = ceil(p / 64) of them, and one workgroup serves one
+// (chain, super-block pair A <= B): above 64 columns the tiles of a whole chain no longer fit one wave's registers (136 tiles
+// = 544 doubles per lane at p = 256), so the OUTPUT is tiled.  NA is the number of column blocks of A.  DIAG = true: the nsb
+// pairs A == B, the NA (NA + 1) / 2 tiles ab <= bb; p <= 64 is nsb = 1 with NA = ceil(p / 16).  DIAG = false (NA = 4): the
+// nsb (nsb - 1) / 2 pairs A < B, 16 tiles = 128 accumulator registers, eight column blocks per row group.  The column sums of
+// a super-block are formed by every pair that holds it, by the same operations in the same order, so they agree to the bit
+// between workgroups; the diagonal pair writes xbar.  Every tile is written with its mirror from one value, so S_c is
+// exactly symmetric.  Three row groups are buffered (two loads in flight behind the one being multiplied) at four and at
+// eight column blocks -- 128 accumulator registers + 3 x 64 of buffers, 440 of the 512 a lane has at one wave per SIMD, no
+// scratch; two stages at eight blocks measured 5 to 7 % slower.  The window is read nsb times per chain (a
+// super-block once by its diagonal pair and once by each of the nsb - 1 others).
 typedef double gd4_t __attribute__((ext_vector_type(4)));
-template <int NCB>
-__global__ __launch_bounds__(GT) void gelman_chain_mfma(const double* __restrict__ samples, long long S, int k, long long row0,
-                                                        long long N, const int* __restrict__ cols, int p,
-                                                        const double* __restrict__ center, double* __restrict__ work) {
-  constexpr int NT2 = NCB * (NCB + 1) / 2;          // tile pairs (a-block <= b-block)
-  __shared__ double s_acc[NT2 * 256];               // [tile][lane * 4 + r]
-  __shared__ double s_sum[NCB * 16];                // column sums of d
-  __shared__ double s_shift[NCB * 16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int kk = lane >> 4, j = lane & 15;
-  const long long c = blockIdx.x;
-  const double* base = samples + c * (long long)k * S + row0;
-  // this lane's column of every block (a padded column reads column 0 and is multiplied by 0)
-  const double* colp[NCB];
-  double shift[NCB], msk[NCB], csum[NCB];
-#pragma unroll
-  for (int cb = 0; cb < NCB; cb++) {
-    const int a = cb * 16 + j;
-    colp[cb] = base + (long long)cols[a < p ? a : 0] * S;
-    shift[cb] = colp[cb][0];
-    msk[cb] = a < p ? 1.0 : 0.0;
-    csum[cb] = 0.0;
-  }
-  gd4_t acc[NT2];
-#pragma unroll
-  for (int t = 0; t < NT2; t++) acc[t] = (gd4_t){0.0, 0.0, 0.0, 0.0};
-  // Rows of this wave: a contiguous quarter of the window, in groups of 16.  Lane (kk, j) loads rows 4 kk .. 4 kk + 3 of the
-  // group for its column -- 32 contiguous bytes, the four kk classes together a full 128-byte line per column -- and K-step s
-  // of the group multiplies rows {4 kk + s}: which four rows share a K-step only changes the order of a sum.  Two groups are
-  // in flight behind the one being multiplied (the loads come from HBM: ~2 us, a group's 40 MFMAs are ~1 us).
-  const long long groups = (N + 15) / 16, per = (groups + 3) / 4;
-  const long long g_lo = wave * per, g_hi = (g_lo + per < groups) ? g_lo + per : groups;
-  // (a pair is 8-byte aligned only: the window starts at any row of a history whose row stride may be odd -- the vector type
-  //  says so, the loads are still one global_load_dwordx4 each, which gfx950 serves at any 4-byte alignment)
-  typedef double gd2_t __attribute__((ext_vector_type(2), aligned(8)));
-  double buf[3][NCB][4];
-  auto load = [&](long long gi, double (&v)[NCB][4]) {
-    const long long t = 16 * gi + 4 * kk;
-    if (t + 3 < N) {
-#pragma unroll
-      for (int cb = 0; cb < NCB; cb++) {
-        const gd2_t lo = *reinterpret_cast<const gd2_t*>(colp[cb] + t), hi = *reinterpret_cast<const gd2_t*>(colp[cb] + t + 2);
-        v[cb][0] = lo[0]; v[cb][1] = lo[1]; v[cb][2] = hi[0]; v[cb][3] = hi[1];
-      }
-    } else {
-#pragma unroll
-      for (int cb = 0; cb < NCB; cb++)
-#pragma unroll
-        for (int u = 0; u < 4; u++) v[cb][u] = (t + u < N) ? colp[cb][t + u] : shift[cb];   // (a row beyond the window: d = 0)
-    }
-  };
-  if (g_lo < g_hi) load(g_lo, buf[0]);
-  if (g_lo + 1 < g_hi) load(g_lo + 1, buf[1]);
-  for (long long gi = g_lo; gi < g_hi; gi += 3) {
-#pragma unroll
-    for (int ph = 0; ph < 3; ph++) {       // buffer roles rotate statically
-      if (gi + ph < g_hi) {
-        if (gi + ph + 2 < g_hi) load(gi + ph + 2, buf[(ph + 2) % 3]);
-        double (&cur)[NCB][4] = buf[ph];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-          double d[NCB];
-#pragma unroll
-          for (int cb = 0; cb < NCB; cb++) { d[cb] = (cur[cb][u] - shift[cb]) * msk[cb]; csum[cb] += d[cb]; }
-          int t = 0;
-#pragma unroll
-          for (int ab = 0; ab < NCB; ab++)
-#pragma unroll
-            for (int bb = ab; bb < NCB; bb++, t++) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(d[ab], d[bb], acc[t], 0, 0, 0);
-        }
-      }
-    }
-  }
-  // column sums: the four kk classes of a column sit in lanes j, j + 16, j + 32, j + 48
-#pragma unroll
-  for (int cb = 0; cb < NCB; cb++) {
-    double v = csum[cb];
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    csum[cb] = v;
-  }
-  // waves combine in wave order
-  for (int w = 0; w < 4; w++) {
-    if (wave == w) {
-#pragma unroll
-      for (int t = 0; t < NT2; t++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          double* d = &s_acc[t * 256 + lane * 4 + r];
-          *d = (w == 0) ? acc[t][r] : *d + acc[t][r];
-        }
-      if (lane < 16) {
-#pragma unroll
-        for (int cb = 0; cb < NCB; cb++) {
-          double* d = &s_sum[cb * 16 + lane];
-          *d = (w == 0) ? csum[cb] : *d + csum[cb];
-          if (w == 0) s_shift[cb * 16 + lane] = shift[cb];
-        }
-      }
-    }
-    __syncthreads();
-  }
-  // finish: D register r of lane l is row 4 r + l / 16, column l % 16 of its tile
-  double* wout = work + c * (long long)(p + p * p);
-  const double dn = (double)N;
-  if (tid < p) wout[tid] = (s_shift[tid] + s_sum[tid] / dn) - (center ? center[tid] : 0.0);
-  for (int e = tid; e < NT2 * 256; e += GT) {
-    const int t = e >> 8, q = e & 255, l = q >> 2, r = q & 3;
-    int ab = 0, rem = t;
-    while (rem >= NCB - ab) { rem -= NCB - ab; ab++; }
-    const int bb = ab + rem;
-    const int a = ab * 16 + 4 * r + (l >> 4), b2 = bb * 16 + (l & 15);
-    if (a < p && b2 < p && (ab < bb || a <= b2)) {
-      const double v = (s_acc[e] - s_sum[a] * s_sum[b2] / dn) / (dn - 1.0);
-      wout[p + a * p + b2] = v;
-      wout[p + b2 * p + a] = v;
-    }
-  }
-}
-
-// 64 < p <= 256: the NCB (NCB + 1) / 2 tiles of a chain no longer fit one wave's registers (136 tiles = 544 doubles per lane
-// at p = 256), so the OUTPUT is tiled.  The columns form super-blocks of 64 (four 16-column blocks), NSB = ceil(p / 64) of
-// them; one workgroup serves one (chain, super-block pair A <= B): DIAG = true the NSB pairs A == B (10 tiles, the kernel above
-// at a column offset), DIAG = false the NSB (NSB - 1) / 2 pairs A < B (16 tiles = 128 accumulator registers, eight column blocks
-// per row group).  Everything else is the kernel above: the same instruction and lane layout, rows shifted by the chain's first
-// window row, column sums on the VALU, four waves on four contiguous row ranges joined through LDS in wave order.  The column
-// sums of a super-block are formed by every pair that holds it, by the same operations in the same order, so they agree to
-// the bit between workgroups; the diagonal pair writes xbar.  An off-diagonal pair writes its tile and the mirrored one from
-// one value, so S_c is exactly symmetric.  DEPTH row groups are buffered (DEPTH - 1 loads in flight behind the one being
-// multiplied): three, as above, at four and at eight column blocks -- 128 accumulator registers + 3 x 64 of buffers, 440 of
-// the 512 a lane has at one wave per SIMD, no scratch; two stages at eight blocks measured 5 to 7 % slower.
-// The window is read NSB times per chain (a super-block once by its diagonal pair and once by each of the NSB - 1 others).
-template <bool DIAG, int DEPTH>
-__global__ __launch_bounds__(GT) void gelman_pair_mfma(const double* __restrict__ samples, long long S, int k, long long row0,
-                                                       long long N, const int* __restrict__ cols, int p, int nsb,
-                                                       const double* __restrict__ center, double* __restrict__ work) {
-  constexpr int NB = DIAG ? 4 : 8;                  // column blocks in flight: A's four, then B's four
-  constexpr int NT = DIAG ? 10 : 16;                // tiles
+template <int NA, bool DIAG>
+__global__ __launch_bounds__(GT) void gelman_cov_mfma(const double* __restrict__ samples, long long S, int k, long long row0,
+                                                      long long N, const int* __restrict__ cols, int p, int nsb,
+                                                      const double* __restrict__ center, double* __restrict__ work) {
+  static_assert(DIAG || NA == 4, "an off-diagonal pair holds two whole super-blocks");
+  constexpr int DEPTH = 3;                          // buffered row groups
+  constexpr int NB = DIAG ? NA : 2 * NA;            // column blocks in flight: A's, then B's
+  constexpr int NT = DIAG ? NA * (NA + 1) / 2 : NA * NA;   // tiles
   __shared__ double s_acc[NT * 256];                // [tile][lane * 4 + r]
   __shared__ double s_sum[NB * 16];                 // column sums of d
   __shared__ double s_shift[NB * 16];
@@ -190,7 +72,7 @@ __global__ __launch_bounds__(GT) void gelman_pair_mfma(const double* __restrict_
   double shift[NB], msk[NB], csum[NB];
 #pragma unroll
   for (int cb = 0; cb < NB; cb++) {
-    const int a = (cb < 4 ? sa : sb) * 64 + (cb & 3) * 16 + j;
+    const int a = (cb < NA ? sa : sb) * 64 + (cb % NA) * 16 + j;
     colp[cb] = base + (long long)cols[a < p ? a : 0] * S;
     shift[cb] = colp[cb][0];
     msk[cb] = a < p ? 1.0 : 0.0;
@@ -199,9 +81,14 @@ __global__ __launch_bounds__(GT) void gelman_pair_mfma(const double* __restrict_
   gd4_t acc[NT];
 #pragma unroll
   for (int t = 0; t < NT; t++) acc[t] = (gd4_t){0.0, 0.0, 0.0, 0.0};
-  // rows of this wave, the groups of 16 and the lane's four rows of a group: as in gelman_chain_mfma
+  // Rows of this wave: a contiguous quarter of the window, in groups of 16.  Lane (kk, j) loads rows 4 kk .. 4 kk + 3 of the
+  // group for its column -- 32 contiguous bytes, the four kk classes together a full 128-byte line per column -- and K-step s
+  // of the group multiplies rows {4 kk + s}: which four rows share a K-step only changes the order of a sum.  DEPTH - 1 groups
+  // are in flight behind the one being multiplied (the loads come from HBM: ~2 us, a group's 40 MFMAs are ~1 us).
   const long long groups = (N + 15) / 16, per = (groups + 3) / 4;
   const long long g_lo = wave * per, g_hi = (g_lo + per < groups) ? g_lo + per : groups;
+  // (a pair is 8-byte aligned only: the window starts at any row of a history whose row stride may be odd -- the vector type
+  //  says so, the loads are still one global_load_dwordx4 each, which gfx950 serves at any 4-byte alignment)
   typedef double gd2_t __attribute__((ext_vector_type(2), aligned(8)));
   double buf[DEPTH][NB][4];
   auto load = [&](long long gi, double (&v)[NB][4]) {
@@ -233,19 +120,12 @@ __global__ __launch_bounds__(GT) void gelman_pair_mfma(const double* __restrict_
           double d[NB];
 #pragma unroll
           for (int cb = 0; cb < NB; cb++) { d[cb] = (cur[cb][u] - shift[cb]) * msk[cb]; csum[cb] += d[cb]; }
-          if (DIAG) {
-            int t = 0;
+          int t = 0;                           // tiles in the order of (ab, bb): B's blocks start at NB - NA
 #pragma unroll
-            for (int ab = 0; ab < 4; ab++)
+          for (int ab = 0; ab < NA; ab++)
 #pragma unroll
-              for (int bb = ab; bb < 4; bb++, t++) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(d[ab], d[bb], acc[t], 0, 0, 0);
-          } else {
-#pragma unroll
-            for (int ab = 0; ab < 4; ab++)
-#pragma unroll
-              for (int bb = 0; bb < 4; bb++)
-                acc[ab * 4 + bb] = __builtin_amdgcn_mfma_f64_16x16x4f64(d[ab], d[NB - 4 + bb], acc[ab * 4 + bb], 0, 0, 0);
-          }
+            for (int bb = DIAG ? ab : 0; bb < NA; bb++, t++)
+              acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(d[ab], d[NB - NA + bb], acc[t], 0, 0, 0);
         }
       }
     }
@@ -282,7 +162,7 @@ __global__ __launch_bounds__(GT) void gelman_pair_mfma(const double* __restrict_
   // finish: D register r of lane l is row 4 r + l / 16, column l % 16 of its tile; la / lb index s_sum, a / b2 the p columns
   double* wout = work + c * (long long)(p + p * p);
   const double dn = (double)N;
-  if (DIAG && tid < 64 && sa * 64 + tid < p)
+  if (DIAG && tid < NA * 16 && sa * 64 + tid < p)
     wout[sa * 64 + tid] = (s_shift[tid] + s_sum[tid] / dn) - (center ? center[sa * 64 + tid] : 0.0);
   for (int e = tid; e < NT * 256; e += GT) {
     const int t = e >> 8, q = e & 255, l = q >> 2, r = q & 3;
@@ -290,14 +170,14 @@ __global__ __launch_bounds__(GT) void gelman_pair_mfma(const double* __restrict_
     if (DIAG) {
       int rem = t;
       ab = 0;
-      while (rem >= 4 - ab) { rem -= 4 - ab; ab++; }
+      while (rem >= NA - ab) { rem -= NA - ab; ab++; }
       bb = ab + rem;
     } else {
-      ab = t >> 2;
-      bb = t & 3;
+      ab = (unsigned)t / NA;
+      bb = (unsigned)t % NA;
     }
-    const int la = ab * 16 + 4 * r + (l >> 4), lb = (NB - 4) * 16 + bb * 16 + (l & 15);
-    const int a = sa * 64 + la, b2 = sb * 64 + lb - (NB - 4) * 16;
+    const int la = ab * 16 + 4 * r + (l >> 4), lb = (NB - NA) * 16 + bb * 16 + (l & 15);
+    const int a = sa * 64 + la, b2 = sb * 64 + lb - (NB - NA) * 16;
     if (a < p && b2 < p && (!DIAG || ab < bb || a <= b2)) {
       const double v = (s_acc[e] - s_sum[la] * s_sum[lb] / dn) / (dn - 1.0);
       wout[p + a * p + b2] = v;
@@ -445,8 +325,8 @@ extern "C" {
 int64_t fmcmc_gelman_partial_len(int32_t p) { return 1 + 5 * (int64_t)p + 2 * (int64_t)p * p; }
 int64_t fmcmc_gelman_work_len(int64_t nchains, int32_t p) { return nchains * ((int64_t)p + (int64_t)p * p); }
 
-// 1 <= p <= FMCMC_MAX_K.  Up to FMCMC_MAX_K_WAVE columns one workgroup holds a chain's whole covariance (gelman_chain_mfma<1..4>);
-// above, one workgroup per chain and super-block pair (gelman_pair_mfma), diagonal pairs and off-diagonal pairs in a launch each.
+// 1 <= p <= FMCMC_MAX_K.  One workgroup per (chain, pair of 64-column super-blocks) of gelman_cov_mfma: the diagonal pairs (up to
+// FMCMC_MAX_K_WAVE columns there is one, with ceil(p / 16) column blocks, and nothing else), then the off-diagonal ones.
 int fmcmc_gelman_partial_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0,
                              int64_t N, const int32_t* cols, int32_t p, const double* center,
                              double* work, double* partial, void* hip_stream) {
@@ -454,25 +334,18 @@ int fmcmc_gelman_partial_dev(const double* samples, int64_t nchains, int32_t k, 
       row0 < 0 || row0 + N > S)
     return FMCMC_ERR_ARG;
   hipStream_t st = (hipStream_t)hip_stream;
-#define GELMAN_LAUNCH(NCBV)                                                                                         \
-  hipLaunchKernelGGL(gelman_chain_mfma<NCBV>, dim3((unsigned)nchains), dim3(GT), 0, st, samples, (long long)S, (int)k, \
-                     (long long)row0, (long long)N, cols, (int)p, center, work)
-  if (p > FMCMC_MAX_K_WAVE) {
-    // one workgroup per (chain, pair of 64-column super-blocks): the diagonal pairs, then the off-diagonal ones
-    const int nsb = (p + 63) / 64;                 // 2, 3 or 4
-    if (nchains > 0x7fffffff / 6) return FMCMC_ERR_ARG;
-    hipLaunchKernelGGL((gelman_pair_mfma<true, 3>), dim3((unsigned)(nchains * nsb)), dim3(GT), 0, st, samples, (long long)S, (int)k,
-                       (long long)row0, (long long)N, cols, (int)p, nsb, center, work);
-    hipLaunchKernelGGL((gelman_pair_mfma<false, 3>), dim3((unsigned)(nchains * (nsb * (nsb - 1) / 2))), dim3(GT), 0, st, samples,
-                       (long long)S, (int)k, (long long)row0, (long long)N, cols, (int)p, nsb, center, work);
-  } else {
-    switch ((p + 15) / 16) {
-      case 1: GELMAN_LAUNCH(1); break;
-      case 2: GELMAN_LAUNCH(2); break;
-      case 3: GELMAN_LAUNCH(3); break;
-      default: GELMAN_LAUNCH(4); break;
-    }
+  const int nsb = (p + 63) / 64;                   // 1 .. 4
+  if (p > FMCMC_MAX_K_WAVE && nchains > 0x7fffffff / 6) return FMCMC_ERR_ARG;
+#define GELMAN_LAUNCH(NA, DIAG, NPAIRS)                                                                                      \
+  hipLaunchKernelGGL((gelman_cov_mfma<NA, DIAG>), dim3((unsigned)(nchains * (NPAIRS))), dim3(GT), 0, st, samples, (long long)S, \
+                     (int)k, (long long)row0, (long long)N, cols, (int)p, nsb, center, work)
+  switch (nsb > 1 ? 4 : (p + 15) / 16) {
+    case 1: GELMAN_LAUNCH(1, true, nsb); break;
+    case 2: GELMAN_LAUNCH(2, true, nsb); break;
+    case 3: GELMAN_LAUNCH(3, true, nsb); break;
+    default: GELMAN_LAUNCH(4, true, nsb); break;
   }
+  if (nsb > 1) GELMAN_LAUNCH(4, false, nsb * (nsb - 1) / 2);
 #undef GELMAN_LAUNCH
   const int plen = 1 + 5 * (int)p + 2 * (int)p * (int)p;
   hipLaunchKernelGGL(gelman_sum_kernel, dim3((unsigned)((plen + 63) / 64)), dim3(GT), 0, st, work, (long long)nchains, (int)p, partial);

@@ -58,8 +58,8 @@ def _fmt_column(values, digits=4):
     return ["%.*f" % (dec, v) for v in values]
 
 
-def _fmt_table(rownames, colnames, matrix):
-    cols = [[name] + _fmt_column(matrix[:, j]) for j, name in enumerate(colnames)]
+def _fmt_table(rownames, colnames, matrix, fmt=_fmt_column):
+    cols = [[name] + fmt(matrix[:, j]) for j, name in enumerate(colnames)]
     widths = [max(len(s) for s in col) for col in cols]
     w0 = max([len(r) for r in rownames] + [0])
     lines = []
@@ -130,36 +130,57 @@ def _columns(dc, cols):
     return cols
 
 
+def _names(dc, cols):
+    return [dc.names[c] for c in cols] if dc.names is not None else ["par%d" % (c + 1) for c in cols]
+
+
+def _device_samples(dc):
+    """What every enqueue_* starts with: (library, samples [C][k][S], (C, k, S)); the caller checks its own arguments next."""
+    _single_process()
+    return abi.lib(), dc._samples, tuple(int(v) for v in dc._samples.shape)
+
+
+def _device_columns(dc, cols):
+    """... and goes on with: (device, columns, their device copy) of samples that the library can read."""
+    import torch
+    smp = dc._samples
+    if smp.dtype != torch.float64 or not smp.is_contiguous():
+        raise ValueError("samples must be a contiguous float64 [C][k][S] tensor")
+    cols = _columns(dc, cols)
+    return smp.device, cols, torch.as_tensor(cols).to(smp.device)
+
+
+def _stream(dev):
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _raise_for(rc):
+    if rc != abi.OK:
+        raise (NotImplementedError if rc == abi.ERR_UNSUPPORTED else ValueError if rc == abi.ERR_ARG else RuntimeError)(
+            abi.last_error())
+
+
 def enqueue_window(dc, row0, N, cols, probs=(), want_chains=True):
     """Enqueues one fmcmc_summary_dev call on the window [row0, row0 + N) of the kept rows of `dc` (current torch stream).
     Returns the device tensors (pooled, chain_stats or None, work) and the columns; nothing is synchronised."""
     import torch
-    _single_process()
-    L = abi.lib()
-    smp = dc._samples
-    Cn, k, cap = (int(v) for v in smp.shape)
+    L, smp, (Cn, k, cap) = _device_samples(dc)
     if Cn < 1:
         raise ValueError("no chains to summarise")
     if row0 < 0 or row0 + N > dc.nrows:
         raise ValueError("the window [%d, %d) is outside the %d kept rows" % (row0, row0 + N, dc.nrows))
-    if smp.dtype != torch.float64 or not smp.is_contiguous():
-        raise ValueError("samples must be a contiguous float64 [C][k][S] tensor")
-    dev = smp.device
-    cols = _columns(dc, cols)
+    dev, cols, cols_d = _device_columns(dc, cols)
     p, nprobs = int(cols.size), len(probs)
     probs_h = np.ascontiguousarray(probs, dtype=np.float64)
-    cols_d = torch.as_tensor(cols).to(dev)
     work = torch.empty(max(int(L.fmcmc_summary_work_len(Cn, p, nprobs)), 1), dtype=torch.float64, device=dev)
     pooled = torch.empty(int(L.fmcmc_summary_pooled_len(p, nprobs)), dtype=torch.float64, device=dev)
     chain_stats = torch.empty((Cn, p, 4), dtype=torch.float64, device=dev) if want_chains else None
     with torch.cuda.device(dev):
         rc = L.fmcmc_summary_dev(smp.data_ptr(), Cn, k, cap, int(row0), int(N), cols_d.data_ptr(), p,
                                  probs_h.ctypes.data_as(C.POINTER(C.c_double)), nprobs, work.data_ptr(),
-                                 chain_stats.data_ptr() if want_chains else None, pooled.data_ptr(),
-                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != abi.OK:
-        raise (NotImplementedError if rc == abi.ERR_UNSUPPORTED else ValueError if rc == abi.ERR_ARG else RuntimeError)(
-            abi.last_error())
+                                 chain_stats.data_ptr() if want_chains else None, pooled.data_ptr(), _stream(dev))
+    _raise_for(rc)
     return pooled, chain_stats, work, cols
 
 
@@ -204,8 +225,7 @@ def summary(x, quantiles=DEFAULT_QUANTILES, cols=None):
         raise ValueError("at most %d quantiles per call" % abi.SUMMARY_MAX_PROBS)
     N, Cn = int(dc.nrows), int(dc._samples.shape[0])
     ps, os_, cs = window_stats(dc, 0, N, cols, probs)
-    cols = _columns(dc, cols)
-    names = [dc.names[c] for c in cols] if dc.names is not None else ["par%d" % (c + 1) for c in cols]
+    names = _names(dc, _columns(dc, cols))
     return McmcSummary(finish_statistics(ps, Cn, N), type7_quantiles(os_, Cn * N, probs), probs, names,
                        int(dc.iters[0]), int(dc.iters[-1]), dc.thin, Cn, per_chain=_per_chain(cs, N), ess=ps[:, 3].copy())
 
@@ -345,28 +365,19 @@ def enqueue_heidel(dc, half_row, cand_rows, cols):
     """Enqueues one fmcmc_heidel_dev call on the kept rows of `dc` (current torch stream).  Returns the device tensors
     (out, work) and the columns; nothing is synchronised."""
     import torch
-    _single_process()
-    L = abi.lib()
-    smp = dc._samples
-    Cn, k, cap = (int(v) for v in smp.shape)
+    L, smp, (Cn, k, cap) = _device_samples(dc)
     if Cn < 1:
         raise ValueError("no chains to test")
-    if smp.dtype != torch.float64 or not smp.is_contiguous():
-        raise ValueError("samples must be a contiguous float64 [C][k][S] tensor")
-    dev = smp.device
-    cols = _columns(dc, cols)
+    dev, cols, cols_d = _device_columns(dc, cols)
     p = int(cols.size)
     cand = np.ascontiguousarray(cand_rows, dtype=np.int64)
-    cols_d = torch.as_tensor(cols).to(dev)
     work = torch.empty(max(int(L.fmcmc_heidel_work_len(Cn, p, cand.size)), 1), dtype=torch.float64, device=dev)
     out = torch.empty(max(int(L.fmcmc_heidel_out_len(Cn, p, cand.size)), 1), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         rc = L.fmcmc_heidel_dev(smp.data_ptr(), Cn, k, cap, 0, int(dc.nrows), cols_d.data_ptr(), p, int(half_row),
                                 cand.ctypes.data_as(C.POINTER(C.c_int64)), int(cand.size), work.data_ptr(), out.data_ptr(),
-                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != abi.OK:
-        raise (NotImplementedError if rc == abi.ERR_UNSUPPORTED else ValueError if rc == abi.ERR_ARG else RuntimeError)(
-            abi.last_error())
+                                _stream(dev))
+    _raise_for(rc)
     return out, work, cols
 
 
@@ -386,7 +397,7 @@ def heidel(x, eps=0.1, pvalue=0.05, cols=None):
     oh = out.cpu().numpy()
     stats = oh[:(1 + ncand) * Cn * p * 4].reshape(1 + ncand, Cn, p, 4)
     Q = oh[(1 + ncand) * Cn * p * 4:].reshape(ncand, Cn, p)
-    names = [dc.names[c] for c in cols] if dc.names is not None else None
+    names = _names(dc, cols) if dc.names is not None else None          # (None: HeidelDiag numbers them by position)
     return heidel_finish(N - rows, stats[1:, :, :, 0], stats[1:, :, :, 2], Q, stats[0, :, :, 2], np.asarray(dc.iters)[rows], eps,
                          pvalue, names, candidates=labels)
 
@@ -417,13 +428,7 @@ class GelmanDiag:
         self.start, self.end, self.confidence = start, end, float(confidence)
 
     def __str__(self):
-        cols = [[name] + _fmt_column_sig(self.psrf[:, j]) for j, name in enumerate(self.columns)]
-        widths = [max(len(s) for s in col) for col in cols]
-        w0 = max(len(r) for r in self.varnames)
-        out = ["Potential scale reduction factors:", ""]
-        for i in range(len(self.varnames) + 1):
-            head = ("" if i == 0 else self.varnames[i - 1]).ljust(w0)
-            out.append(head + " " + " ".join(col[i].rjust(w) for col, w in zip(cols, widths)))
+        out = ["Potential scale reduction factors:", "", _fmt_table(self.varnames, self.columns, self.psrf, _fmt_column_sig)]
         if self.mpsrf is not None:
             out += ["", "Multivariate psrf", "", _fmt_column_sig([self.mpsrf])[0]]
         return "\n".join(out) + "\n"
@@ -493,33 +498,34 @@ def gelman_diag_finish(partial, p, N, confidence=0.95, multivariate=True, varnam
     return GelmanDiag(np.stack([point, upper], axis=1), mpsrf, varnames, start, end, confidence)
 
 
+def gelman_partial_dev(base, Cn, k, stride, row0, N, cols_d, center, work, partial):
+    """The one call site of fmcmc_gelman_partial_dev (current torch stream): the window [row0, row0 + N) of Cn chains of k columns
+    that start at the tensor `base` with `stride` rows per column, reduced over the device columns `cols_d` around `center` into
+    `work` and the head of `partial`.  Nothing is synchronised."""
+    import torch
+    with torch.cuda.device(base.device):
+        rc = abi.lib().fmcmc_gelman_partial_dev(base.data_ptr(), int(Cn), int(k), int(stride), int(row0), int(N), cols_d.data_ptr(),
+                                                int(cols_d.numel()), center.data_ptr(), work.data_ptr(), partial.data_ptr(),
+                                                _stream(base.device))
+    if rc != abi.OK:
+        raise RuntimeError("fmcmc_gelman_partial_dev failed (%d)" % rc)
+
+
 def enqueue_gelman(dc, row0, N, cols):
     """Enqueues one fmcmc_gelman_partial_dev call on the window [row0, row0 + N) of the kept rows of `dc` (current torch
     stream), centred on the window's first row of chain 0.  Returns the device tensors (partial, work) and the columns."""
     import torch
-    _single_process()
-    L = abi.lib()
-    smp = dc._samples
-    Cn, k, cap = (int(v) for v in smp.shape)
+    L, smp, (Cn, k, cap) = _device_samples(dc)
     if row0 < 0 or N < 2 or row0 + N > dc.nrows:
         raise ValueError("the window [%d, %d) needs at least two of the %d kept rows" % (row0, row0 + N, dc.nrows))
-    if smp.dtype != torch.float64 or not smp.is_contiguous():
-        raise ValueError("samples must be a contiguous float64 [C][k][S] tensor")
-    dev = smp.device
-    cols = _columns(dc, cols)
+    dev, cols, cols_d = _device_columns(dc, cols)
     p = int(cols.size)
     if p > abi.MAX_K:
         raise ValueError("at most %d columns per call" % abi.MAX_K)
-    cols_d = torch.as_tensor(cols).to(dev)
     center = smp[0, cols_d.long(), row0].contiguous()
     partial = torch.empty(int(L.fmcmc_gelman_partial_len(p)), dtype=torch.float64, device=dev)
     work = torch.empty(int(L.fmcmc_gelman_work_len(Cn, p)), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.fmcmc_gelman_partial_dev(smp.data_ptr(), Cn, k, cap, int(row0), int(N), cols_d.data_ptr(), p, center.data_ptr(),
-                                        work.data_ptr(), partial.data_ptr(),
-                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != abi.OK:
-        raise RuntimeError("fmcmc_gelman_partial_dev failed (%d)" % rc)
+    gelman_partial_dev(smp, Cn, k, cap, row0, N, cols_d, center, work, partial)
     return partial, work, cols
 
 
@@ -539,6 +545,5 @@ def gelman_diag(x, confidence=0.95, autoburnin=True, multivariate=True, cols=Non
         raise ValueError(_GELMAN_FEW_CHAINS)
     row0, N = _window(dc.iters) if autoburnin else (0, int(dc.nrows))
     partial, _work, cols = enqueue_gelman(dc, row0, N, cols)
-    names = [dc.names[c] for c in cols] if dc.names is not None else ["par%d" % (c + 1) for c in cols]
-    return gelman_diag_finish(partial.cpu().numpy(), int(cols.size), N, confidence, multivariate, names,
+    return gelman_diag_finish(partial.cpu().numpy(), int(cols.size), N, confidence, multivariate, _names(dc, cols),
                               int(dc.iters[row0]), int(dc.iters[-1]))

@@ -11,7 +11,7 @@ and E_a = S_aa + N / (N - 1) Delta_a^2:
     |S_dev[a, b] - S_ab|                  <= (N + 32) u sqrt(E_a E_b)
     |xbar_dev[a] - (m_a - center_a)|      <= (N + 16) u sqrt(E_a) + 2 u (|m_a| + |center_a|)
 
-Derivation (first order in u; the kernel is gelman_chain_mfma, gelman_pair_mfma has the same arithmetic).  The kernel shifts
+Derivation (first order in u; the kernel is gelman_cov_mfma, the same arithmetic at every width).  The kernel shifts
 by the window's FIRST ROW, d_t = x_t - x_row0, forms sum_t d_a d_b and sum_t d_a in one pass and finishes as
 (sum d_a d_b - sum d_a sum d_b / N) / (N - 1) and (x_row0 + sum d_a / N) - center.
  * The shift is a row of the window, so sum_t d_a^2 = sum_t (x_t - m_a)^2 + N Delta_a^2 = (N - 1) E_a exactly, and by
@@ -57,7 +57,7 @@ def _check_longdouble():
 
 # ------------------------------------------------------------------------------------------------ inputs
 def make_chains(Cn, k, S, seed):
-    """[C][k][S]: noise, an offset per chain and column, a slow random walk (as in tests/test_gpu_gelman_wide.py)."""
+    """[C][k][S]: noise, an offset per chain and column, a slow random walk (as in tests/gelman_dev.py)."""
     rng = np.random.default_rng(seed)
     return (0.5 * rng.standard_normal((Cn, k, S)) + 0.2 * rng.standard_normal((Cn, k, 1)) + 3.0
             + 0.01 * np.cumsum(rng.standard_normal((Cn, k, S)), axis=2))
@@ -178,7 +178,7 @@ def work_ratios(work, x, cols, row0, N, center):
 
 
 def emulate_work(x, cols, row0, N, center):
-    """The float64 restatement of gelman_chain_mfma's order of operations: shift by the first window row, one pass, four
+    """The float64 restatement of gelman_cov_mfma's order of operations: shift by the first window row, one pass, four
     waves on four contiguous ranges of 16-row groups, a column sum per lane class joined as (0 + 1) + (2 + 3), a product
     accumulator per wave taking rows {4 kk + u} of a group for u = 0 .. 3, the waves joined in order.  work [C][p + p p]."""
     x = np.asarray(x, dtype=np.float64)

@@ -1,4 +1,4 @@
-"""GPU tests of the Gelman-Rubin window reduction at 64 columns and fewer (csrc/gelman.hip: gelman_chain_mfma<1..4>, one
+"""GPU tests of the Gelman-Rubin window reduction at 64 columns and fewer (csrc/gelman.hip: gelman_cov_mfma<1..4, true>, one
 workgroup per chain) and of gelman_sum_kernel, at their edges.
 
 Yardsticks (tests/gelman_ref.py, proven sane on the host by tests/test_gelman_narrow_host.py):
@@ -18,11 +18,10 @@ import numpy as np
 import pytest
 
 import gelman_ref as R
+from gelman_dev import FIRST_ROW, _bits, _same_bits, device_partial
 from test_gelman_diag_host import coda_gelman_ld
 
 pytestmark = pytest.mark.gpu
-GUARD = 64
-FIRST_ROW = "first row of chain 0"
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -30,41 +29,6 @@ def _gpu():
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-
-
-def device_partial(x, cols, row0, N, center=FIRST_ROW):
-    """One fmcmc_gelman_partial_dev call on x [C][k][S]: (work [C][p + p p], partial) as numpy; buffers NaN-filled, guards
-    checked.  center None passes a null pointer."""
-    import torch
-    from fmcmc_amd import _abi as abi
-    L = abi.lib()
-    Cn, k, S = x.shape
-    p = len(cols)
-    assert row0 >= 0 and row0 + N <= S and N >= 2 and min(cols) >= 0 and max(cols) < k
-    xd = torch.as_tensor(np.ascontiguousarray(x)).cuda()
-    cd = torch.as_tensor(np.ascontiguousarray(cols, dtype=np.int32)).cuda()
-    if isinstance(center, str):
-        center = x[0, cols, row0]
-    ctr = None if center is None else torch.as_tensor(np.ascontiguousarray(center, dtype=np.float64)).cuda()
-    wlen, plen = int(L.fmcmc_gelman_work_len(Cn, p)), int(L.fmcmc_gelman_partial_len(p))
-    assert wlen == Cn * (p + p * p) and plen == 1 + 5 * p + 2 * p * p
-    work = torch.full((wlen + GUARD,), float("nan"), dtype=torch.float64, device="cuda")
-    part = torch.full((plen + GUARD,), float("nan"), dtype=torch.float64, device="cuda")
-    rc = L.fmcmc_gelman_partial_dev(xd.data_ptr(), Cn, k, S, row0, N, cd.data_ptr(), p, None if ctr is None else ctr.data_ptr(),
-                                    work.data_ptr(), part.data_ptr(), None)
-    assert rc == abi.OK, rc
-    torch.cuda.synchronize()
-    wh, ph = work.cpu().numpy(), part.cpu().numpy()
-    assert np.isnan(wh[wlen:]).all() and np.isnan(ph[plen:]).all()      # nothing written past the documented lengths
-    return wh[:wlen].reshape(Cn, p + p * p), ph[:plen]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _same_bits(a, b):
-    return np.array_equal(_bits(a), _bits(b))
 
 
 def _S(work, p):
@@ -191,7 +155,7 @@ def test_a_window_of_a_long_history_equals_its_rows_uploaded_alone(p, N, row0):
 
 def test_a_pair_of_columns_does_not_depend_on_the_other_columns():
     """xbar[a] and S_c[a, b] of a call with cols = [a, b] carry the bits of the p = 64 call, of a p = 17 call that holds a and b
-    at other positions (b before a) and of a p = 200 call on gelman_pair_mfma: the row-to-lane and row-to-wave assignment
+    at other positions (b before a) and of a p = 200 call on four super-blocks: the row-to-lane and row-to-wave assignment
     depends on N alone, every product and the dbar_a dbar_b correction commute, nothing of another column enters an element."""
     k, N, row0 = 256, 81, 3
     x = R.make_chains(3, k, row0 + N + 4, 99)

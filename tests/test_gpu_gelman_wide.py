@@ -1,4 +1,4 @@
-"""GPU tests of the Gelman-Rubin window reduction above 64 columns (csrc/gelman.hip: gelman_pair_mfma, one workgroup per chain
+"""GPU tests of the Gelman-Rubin window reduction above 64 columns (csrc/gelman.hip: gelman_cov_mfma, one workgroup per chain
 and pair of 64-column super-blocks), of convergence_gelman on it and of gelman_diag().
 
 Yardsticks:
@@ -10,8 +10,8 @@ Yardsticks:
  * psrf / mpsrf of fmcmc_gelman_finish on the device partial against the oracle's coda restatement, rtol 1e-9 as in
    tests/test_k256_host.py;
  * equalities that need no tolerance: placement in the launch, repetition, symmetry, what a call leaves of NaN-filled buffers;
- * p <= 64 against the bits the library of the parent commit produced (tests/golden/gelman_narrow_bits.json, written by
-   tests/golden/make_gelman_narrow_bits.py).
+ * p <= 64 against the bits the library of the commit before p > 64 produced (tests/golden/gelman_narrow_bits.json), and every
+   width against the bits of the commit before the two kernels became one (tests/golden/gelman_bits.json); tests/golden/make_gelman_bits.py wrote both.
 Every buffer is filled with NaN before a call and carries GUARD more elements than documented, which must stay NaN.
 """
 import ctypes as C
@@ -22,11 +22,11 @@ import os
 import numpy as np
 import pytest
 
+from gelman_dev import BITS_SHAPES, _bits, bit_checksums, bits_case, device_partial, make_chains, narrow_case, pick_columns
 from test_abi import numpy_gelman_partial
 
 pytestmark = pytest.mark.gpu
-GUARD = 64
-GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "gelman_narrow_bits.json")
+GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -34,47 +34,6 @@ def _gpu():
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-
-
-# ------------------------------------------------------------------------------------------------ inputs
-def make_chains(Cn, k, S, seed):
-    """[C][k][S]: noise, an offset per chain and column, a slow random walk."""
-    rng = np.random.default_rng(seed)
-    return (0.5 * rng.standard_normal((Cn, k, S)) + 0.2 * rng.standard_normal((Cn, k, 1)) + 3.0
-            + 0.01 * np.cumsum(rng.standard_normal((Cn, k, S)), axis=2))
-
-
-def pick_columns(k, p, seed):
-    return (np.arange(k) if p == k else np.sort(np.random.default_rng(seed).choice(k, size=p, replace=False))).astype(np.int32)
-
-
-def device_partial(x, cols, row0, N, center=None):
-    """One fmcmc_gelman_partial_dev call on x [C][k][S]: (work [C][p + p p], partial) as numpy; buffers NaN-filled, guards
-    checked."""
-    import torch
-    from fmcmc_amd import _abi as abi
-    L = abi.lib()
-    Cn, k, S = x.shape
-    p = len(cols)
-    xd = torch.as_tensor(np.ascontiguousarray(x)).cuda()
-    cd = torch.as_tensor(np.asarray(cols, dtype=np.int32)).cuda()
-    center = x[0, cols, row0] if center is None else center
-    ctr = torch.as_tensor(np.ascontiguousarray(center)).cuda()
-    wlen, plen = int(L.fmcmc_gelman_work_len(Cn, p)), int(L.fmcmc_gelman_partial_len(p))
-    assert wlen == Cn * (p + p * p) and plen == 1 + 5 * p + 2 * p * p
-    work = torch.full((wlen + GUARD,), float("nan"), dtype=torch.float64, device="cuda")
-    part = torch.full((plen + GUARD,), float("nan"), dtype=torch.float64, device="cuda")
-    rc = L.fmcmc_gelman_partial_dev(xd.data_ptr(), Cn, k, S, row0, N, cd.data_ptr(), p, ctr.data_ptr(), work.data_ptr(),
-                                    part.data_ptr(), None)
-    assert rc == abi.OK, rc
-    torch.cuda.synchronize()
-    wh, ph = work.cpu().numpy(), part.cpu().numpy()
-    assert np.isnan(wh[wlen:]).all() and np.isnan(ph[plen:]).all()      # nothing written past the documented lengths
-    return wh[:wlen].reshape(Cn, p + p * p), ph[:plen]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 # (chains, p, N, k, row0): the row stride S is odd and larger than the window; p = 200 is a sorted subset of 256 columns
@@ -115,7 +74,7 @@ def test_partial_equals_its_numpy_definition(Cn, p, N, k, row0):
 
 @pytest.mark.parametrize("Cn,p,N", [(3, 65, 17), (3, 200, 70)])
 def test_work_and_partial_within_the_a_priori_bounds(Cn, p, N):
-    """The yardstick of tests/test_gpu_gelman_narrow.py on gelman_pair_mfma (the same arithmetic per element): `work` against
+    """The yardstick of tests/test_gpu_gelman_narrow.py above 64 columns (the same arithmetic per element): `work` against
     longdouble within the bounds derived in tests/gelman_ref.py, the partial against its definition evaluated in longdouble
     from the device's own `work` within the chain-sum bound."""
     import gelman_ref as R
@@ -172,28 +131,20 @@ def test_padded_super_blocks_leave_no_nan(Cn, p, N, k, row0):
 
 
 # ------------------------------------------------------------------------------------------------ 4. p <= 64 is untouched
-def narrow_case(p):
-    """The p <= 64 inputs of the golden fixture and the bits of the device result (work, partial)."""
-    Cn, k, S, row0, N = 5, 64, 141, 7, 131
-    x = make_chains(Cn, k, S, 64000 + p)
-    cols = pick_columns(k, p, p)
-    work, part = device_partial(x, cols, row0, N)
-    return _bits(work).ravel(), _bits(part)
-
-
-def bit_checksums(u64):
-    """Order-dependent and order-independent 64-bit checksums of a vector of bit patterns, as hex strings."""
-    u64 = np.asarray(u64, dtype=np.uint64)
-    with np.errstate(over="ignore"):
-        weighted = (u64 * (np.arange(u64.size, dtype=np.uint64) * np.uint64(2) + np.uint64(1))).sum(dtype=np.uint64)
-    return {"n": int(u64.size), "xor": "%016x" % int(np.bitwise_xor.reduce(u64)), "weighted_sum": "%016x" % int(weighted),
-            "first": "%016x" % int(u64[0]), "last": "%016x" % int(u64[-1])}
-
-
 @pytest.mark.parametrize("p", [64, 50])
 def test_at_most_64_columns_give_the_bits_of_the_parent(p):
-    fx = json.load(open(GOLDEN))["p%d" % p]
+    fx = json.load(open(os.path.join(GOLDEN, "gelman_narrow_bits.json")))["p%d" % p]
     work, part = narrow_case(p)
+    assert bit_checksums(work) == fx["work"]
+    assert bit_checksums(part) == fx["partial"]
+
+
+@pytest.mark.parametrize("p,N", BITS_SHAPES)
+def test_every_width_gives_the_bits_of_the_two_kernels_before_the_merge(p, N):
+    """gelman_cov_mfma against what gelman_chain_mfma (p <= 64) and gelman_pair_mfma (above) left, written by the library of the
+    commit before the merge (tests/golden/make_gelman_bits.py): every NA at both ends of its range, 2 to 4 super-blocks."""
+    fx = json.load(open(os.path.join(GOLDEN, "gelman_bits.json")))["p%d_N%d" % (p, N)]
+    work, part = bits_case(p, N)
     assert bit_checksums(work) == fx["work"]
     assert bit_checksums(part) == fx["partial"]
 

@@ -58,7 +58,7 @@ pm = collections.defaultdict(lambda: collections.defaultdict(list))
 for f in glob.glob(out + "/pmc_*/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         name = r["Kernel_Name"]
-        key = "mh_sweep" if "mh_sweep" in name else ("rng_fill" if "rng_fill" in name else ("gelman_chain" if "gelman_chain" in name else None))
+        key = "mh_sweep" if "mh_sweep" in name else ("rng_fill" if "rng_fill" in name else ("gelman_cov" if "gelman_cov" in name else None))
         if key:
             pm[key][r["Counter_Name"]].append(float(r["Counter_Value"]))
 summary["pmc_per_launch_mean"] = {k: {c: sum(v) / len(v) for c, v in d.items()} for k, d in pm.items()}

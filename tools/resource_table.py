@@ -37,7 +37,7 @@ PRODUCT = [("C2 headline", r"mh_sweep_mfma<1, 1, 20, false, false, false>"),
            ("kernel_adapt, 8 <= p <= 11 (owners' matrices in LDS)", r"mh_sweep_mfma_ad<3, 3, -1, false>"),
            ("64 < k <= 256, matrices in LDS", r"mh_sweep_bigk<false>"),
            ("kernel_adapt k > 133 / kernel_ram k > 183, matrices in HBM", r"mh_sweep_bigk<true>"), ("rng stream", r"rng_fill_kernel"),
-           ("Gelman window covariance", r"gelman_chain_mfma"), ("Gelman chain sum", r"gelman_sum_kernel")]
+           ("Gelman window covariance", r"gelman_cov_mfma"), ("Gelman chain sum", r"gelman_sum_kernel")]
 
 
 def demangle(names):
