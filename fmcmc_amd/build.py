@@ -2,7 +2,7 @@
 
 The library is several translation units (csrc/mh_engine.hip = C-ABI + launches, with its own headers mh_route.hpp = kernel
 selection, mh_prep.hpp = data-preparation kernels, mh_host.hpp = host-pointer staging; csrc/k_*.hip = one kernel family
-each, csrc/gelman.hip, csrc/summary.hip) compiled in parallel into build/*.o and linked by hipcc; only the units whose sources changed are
+each, csrc/gelman.hip, csrc/summary.hip, csrc/raftery.hip) compiled in parallel into build/*.o and linked by hipcc; only the units whose sources changed are
 recompiled."""
 import concurrent.futures
 import glob

@@ -230,6 +230,60 @@ def heidel_diag(data, iters, eps=0.1, pvalue=0.05):
     return out
 
 
+def raftery_threshold(data, q):
+    """u [p]: R's type-7 quantile at q of every column of data [n][p] on its own (the arithmetic of summary.type7_quantiles)."""
+    from .summary import type7_order_ranks, type7_quantiles
+    data = np.asarray(data, dtype=np.float64)
+    n = data.shape[0]
+    order = np.sort(data, axis=0)[type7_order_ranks(n, [q])[0]]            # [2][p] = x_(lo), x_(hi)
+    return type7_quantiles(order.T[:, None, :], n, [q])[:, 0]
+
+
+def raftery_counts(Z, j0, nj):
+    """The integers raftery.diag needs of an indicator Z [n][p] (0 / 1) for the thinnings j = j0 .. j0 + nj - 1: the rows
+    0, j, 2 j, ... (m of them) give tri [p][nj][8], the counts of the consecutive triples (a, b, c) at 4 a + 2 b + c (all 0 when
+    m < 3), and last_pair [p][nj][2] = (Z_{m-2}, Z_{m-1}) of the thinned series (Z_{m-2} given as 0 when m == 1)."""
+    Z = np.asarray(Z, dtype=np.int64)
+    p = Z.shape[1]
+    tri, last = np.zeros((p, nj, 8), dtype=np.int64), np.zeros((p, nj, 2), dtype=np.int64)
+    for a, j in enumerate(range(j0, j0 + nj)):
+        z = Z[::j]
+        m = z.shape[0]
+        for col in range(p):
+            if m >= 3:
+                tri[col, a] = np.bincount(4 * z[:-2, col] + 2 * z[1:-1, col] + z[2:, col], minlength=8)
+            last[col, a] = (z[m - 2, col] if m >= 2 else 0, z[m - 1, col])
+    return tri, last
+
+
+def raftery_diag(data, iters, q=0.025, r=0.005, s=0.95, converge_eps=0.001):
+    """coda::raftery.diag of one chain: data [n][p] -> rows (M, N, Nmin, I) per variable, I unrounded (coda prints signif(I, 3)).
+    nmin = ceiling(q (1 - q) qnorm((1 + s) / 2)^2 / r^2); with fewer rows every entry but Nmin is NaN (coda: c("Error", nmin)).
+    Per variable: u = the type-7 quantile of the series at q, Z = (x <= u); for kthin = thin, 2 thin, ... the series is thinned
+    to the rows 0, j, 2 j, ..., the 2x2x2 table of its consecutive triples gives G2 against the second-order fit and
+    BIC = G2 - 2 log(m - 2); at the first kthin with BIC < 0 the 2x2 table of consecutive pairs gives alpha and beta, and
+    M, N = M + nkeep and I = N / nmin follow (summary.raftery_finish, shared with the device path).  A constant series (an empty
+    row of the pair table) and a search that runs out of rows (m < 3) give NaN except Nmin."""
+    from types import SimpleNamespace
+    from .summary import raftery_bound, raftery_search, raftery_table
+    data = np.asarray(data, dtype=np.float64)
+    iters = np.asarray(iters)
+    if data.ndim != 2 or data.shape[0] != iters.size:
+        raise ValueError("raftery_diag: data [n][p] and the n iteration labels are needed")
+    n, p = data.shape
+    bad = ~np.isfinite(data)
+    if bad.any():
+        raise ValueError("%d non-finite value(s) among the rows to test (columns %s)"
+                         % (int(bad.sum()), [j for j in range(p) if bad[:, j].any()]))
+    _, nmin = raftery_bound(q, r, s)
+    if nmin > n:
+        return raftery_table(SimpleNamespace(nmin=nmin), (p,))
+    thin = int(iters[1] - iters[0]) if n > 1 else 1
+    Z = data <= raftery_threshold(data, q)[None, :]
+    fin = raftery_search(lambda j0, nj: raftery_counts(Z, j0, nj), n, thin, q, r, s, converge_eps)
+    return raftery_table(fin, (p,))
+
+
 class _SingleChainChecker:
     """Common plumbing of the single-chain checkers: LAST_CONV_CHECK-style history, rm_invariant, device entry."""
     name = ""

@@ -1,0 +1,393 @@
+// raftery.hip — order statistics of every (chain, column) series on its own, and the device part of coda::raftery.diag
+// (the algorithm is restated in fmcmc_amd/convergence.py: raftery_diag, and in INTEGRATION.md).
+//
+// One chain's column is N contiguous doubles (samples + (c k + col) S + row0), as in summary.hip.  One workgroup per series:
+//   1. stage        the series is read once with 8-byte-aligned pair loads, its non-finite values are counted, and while it fits
+//                   (N <= 19456 rows, the tile of summary_series_kernel) its order-preserving keys are kept in LDS;
+//   2. select       exact order statistics at up to 32 ranks by a most-significant-digit radix select on the keys: 8 passes of
+//                   8 bits, the histograms in LDS.  Targets with the same prefix share one histogram (that of their "leader"),
+//                   HG leaders are counted per walk over the series; a series too long for LDS is re-read every walk;
+//   3. raftery      u = type-7 quantile from the two order statistics (two rounded products, one rounded sum), the indicator
+//                   Z_t = (x_t <= u) bit-packed into `work` by wave ballots, then per thinning j (one wavefront each) the
+//                   2x2x2 table of the consecutive triples of Z at rows 0, j, 2j, ... and its last pair.
+// Every count is an integer, so neither the arrival order of the LDS atomics nor the launch changes a result.  Nothing here
+// writes `samples`.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdarg.h>
+
+#include "../../include/fmcmc_amd.h"
+#include "../../include/fmh_detmath.h"
+
+extern "C" void fmcmc_set_error_text_(const char* text);   // mh_engine.hip: the buffer behind fmcmc_last_error()
+
+namespace {
+
+constexpr int OT = 512;             // threads of a series workgroup
+constexpr int OW = OT / 64;
+constexpr int LDS_ROWS = 19456;     // rows of a series whose keys are staged in LDS (152 KB; summary.hip: the same tile)
+constexpr int MAXRANKS = 32;        // targets per call: 2 x SUMMARY_MAX_PROBS
+constexpr int HG = 4;               // histograms (leaders) per walk over the series
+constexpr int MAXNJ = 32;           // thinnings per launch
+constexpr int LU = 4;               // pairs in flight per thread
+constexpr int MAXM = 64;            // summary.hip: the AR order that bounds the rows of a window there, and so here
+constexpr int HEAD = 4;             // doubles per series at the head of the raftery output: u, x_(lo), x_(hi), non-finite count
+constexpr int CNT = 10;             // integers per (series, thinning): T[a][b][c] at 4 a + 2 b + c, then Z_{m-2}, Z_{m-1}
+
+int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+int fail(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  fmcmc_set_error_text_(buf);
+  return code;
+}
+
+typedef double sd2_t __attribute__((ext_vector_type(2), aligned(8)));   // (a pair is 8-byte aligned only: summary.hip)
+
+// the key mapping of summary.hip: x < y <=> key(x) < key(y), and value_of(key_of(x)) has the bits of x
+__device__ __forceinline__ unsigned long long key_of(double x) {
+  const unsigned long long u = fmh_d2u(x);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double value_of(unsigned long long kx) {
+  return fmh_u2d((kx >> 63) ? (kx & 0x7fffffffffffffffull) : ~kx);
+}
+
+struct OrderRanks { unsigned int r[MAXRANKS]; };    // 0-based, each < N < 2^32
+
+struct SelectLds {
+  unsigned int hist[HG][256];                       // counts of a walk, then their exclusive prefix sums
+  unsigned long long prefix[MAXRANKS];              // per target: the key bits fixed so far
+  unsigned int rank[MAXRANKS];                      // per target: its rank among the values that share its prefix
+  int slot[MAXRANKS];                               // per target: the position of its leader in `list`
+  int list[MAXRANKS];                               // the leaders of this pass
+  int nlead;
+  unsigned int nf;                                  // non-finite values of the series
+};
+
+// Reads the series once: counts its non-finite values into L.nf and, when `staged`, leaves key_of(x[i]) in s_k[i].
+__device__ __forceinline__ void stage_series(const double* __restrict__ x, long long N, bool staged, unsigned long long* s_k,
+                                             SelectLds& L) {
+  const int tid = threadIdx.x;
+  if (tid == 0) L.nf = 0u;
+  __syncthreads();
+  unsigned int nf = 0u;
+  for (long long base = 0; base < N; base += 2LL * LU * OT) {
+    double a[LU], b[LU];
+#pragma unroll
+    for (int u = 0; u < LU; u++) {
+      const long long i = base + 2LL * (u * OT + tid);
+      a[u] = 0.0; b[u] = 0.0;
+      if (i + 1 < N) {
+        const sd2_t v = *reinterpret_cast<const sd2_t*>(x + i);
+        a[u] = v[0]; b[u] = v[1];
+      } else if (i < N) {
+        a[u] = x[i];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < LU; u++) {
+      const long long i = base + 2LL * (u * OT + tid);
+      if (i < N) {
+        nf += fmh_isfinite(a[u]) ? 0u : 1u;
+        if (staged) s_k[i] = key_of(a[u]);
+        if (i + 1 < N) {
+          nf += fmh_isfinite(b[u]) ? 0u : 1u;
+          if (staged) s_k[i + 1] = key_of(b[u]);
+        }
+      }
+    }
+  }
+  if (nf) atomicAdd(&L.nf, nf);
+  __syncthreads();
+}
+
+// Radix select of the nt targets whose ranks are in L.rank (L.prefix zeroed): on return L.prefix[t] is the key of the order
+// statistic of target t.  Every thread of the workgroup calls it; it starts and ends with a barrier.
+__device__ __forceinline__ void select_series(const double* __restrict__ x, long long N, bool staged,
+                                              const unsigned long long* s_k, int nt, SelectLds& L) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int pass = 0; pass < 8; pass++) {
+    const int shift = 56 - 8 * pass;
+    __syncthreads();
+    if (tid == 0) {                                  // leaders: the first target of every distinct prefix
+      int n = 0;
+      for (int t = 0; t < nt; t++) {
+        int l = t;
+        for (int u = 0; u < t; u++)
+          if (L.prefix[u] == L.prefix[t]) { l = u; break; }
+        if (l == t) { L.slot[t] = n; L.list[n] = t; n++; }
+        else L.slot[t] = L.slot[l];
+      }
+      L.nlead = n;
+    }
+    __syncthreads();
+    const int nlead = L.nlead;
+    for (int g0 = 0; g0 < nlead; g0 += HG) {
+      const int ng = nlead - g0 < HG ? nlead - g0 : HG;
+      unsigned long long pg[HG];
+#pragma unroll
+      for (int g = 0; g < HG; g++) pg[g] = L.prefix[L.list[g0 + (g < ng ? g : 0)]];
+      for (int e = tid; e < HG * 256; e += OT) (&L.hist[0][0])[e] = 0u;
+      __syncthreads();
+      auto count = [&](unsigned long long kx) {
+        const unsigned long long high = (pass == 0) ? 0ull : (kx >> (shift + 8));
+        const unsigned int digit = (unsigned int)(kx >> shift) & 255u;
+#pragma unroll
+        for (int g = 0; g < HG; g++)
+          if (g < ng && high == pg[g]) atomicAdd(&L.hist[g][digit], 1u);
+      };
+      if (staged) {
+        for (int i = tid; i < (int)N; i += OT) count(s_k[i]);
+      } else {
+        for (long long base = 0; base < N; base += 2LL * LU * OT) {
+          double a[LU], b[LU];
+#pragma unroll
+          for (int u = 0; u < LU; u++) {
+            const long long i = base + 2LL * (u * OT + tid);
+            a[u] = 0.0; b[u] = 0.0;
+            if (i + 1 < N) {
+              const sd2_t v = *reinterpret_cast<const sd2_t*>(x + i);
+              a[u] = v[0]; b[u] = v[1];
+            } else if (i < N) {
+              a[u] = x[i];
+            }
+          }
+#pragma unroll
+          for (int u = 0; u < LU; u++) {
+            const long long i = base + 2LL * (u * OT + tid);
+            if (i < N) count(key_of(a[u]));
+            if (i + 1 < N) count(key_of(b[u]));
+          }
+        }
+      }
+      __syncthreads();
+      if (wave < ng) {                               // one wavefront per histogram: exclusive prefix sums, four bins a lane
+        unsigned int* h = &L.hist[wave][4 * lane];
+        const unsigned int c0 = h[0], c1 = h[1], c2 = h[2], c3 = h[3];
+        const unsigned int mine = c0 + c1 + c2 + c3;
+        unsigned int incl = mine;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const unsigned int up = __shfl_up(incl, o, 64);
+          if (lane >= o) incl += up;
+        }
+        const unsigned int excl = incl - mine;
+        h[0] = excl; h[1] = excl + c0; h[2] = excl + c0 + c1; h[3] = excl + c0 + c1 + c2;
+      }
+      __syncthreads();
+      if (tid < nt && L.slot[tid] >= g0 && L.slot[tid] < g0 + ng) {
+        // the bin that holds the rank: the largest b whose exclusive sum is <= rank (the rank is below the total, so that
+        // bin is not empty).  Only targets of this group change, and no later group of the pass reads their prefixes.
+        const unsigned int* cum = L.hist[L.slot[tid] - g0];
+        const unsigned int r = L.rank[tid];
+        int b = 0;
+#pragma unroll
+        for (int step = 128; step >= 1; step >>= 1)
+          if (cum[b + step] <= r) b += step;
+        L.prefix[tid] = (L.prefix[tid] << 8) | (unsigned long long)b;
+        L.rank[tid] = r - cum[b];
+      }
+      __syncthreads();
+    }
+  }
+}
+
+__global__ __launch_bounds__(OT) void chain_order_kernel(const double* __restrict__ samples, long long S, int k, long long row0,
+                                                         long long N, const int* __restrict__ cols, int p, int nt,
+                                                         OrderRanks ranks, int staged, double* __restrict__ nf_out,
+                                                         double* __restrict__ out) {
+  extern __shared__ unsigned long long s_k[];        // [N] when staged
+  __shared__ SelectLds L;
+  const int tid = threadIdx.x;
+  const long long series = blockIdx.x, c = series / p;
+  const int j = (int)(series % p);
+  const double* __restrict__ x = samples + (c * (long long)k + cols[j]) * S + row0;
+  stage_series(x, N, staged != 0, s_k, L);
+  if (tid < nt) { L.prefix[tid] = 0ull; L.rank[tid] = ranks.r[tid]; }
+  select_series(x, N, staged != 0, s_k, nt, L);
+  if (tid < nt) out[series * nt + tid] = value_of(L.prefix[tid]);
+  if (tid == 0) nf_out[series] = (double)L.nf;
+}
+
+__device__ __forceinline__ unsigned int bit_at(const unsigned long long* bits, long long row) {
+  return (unsigned int)(bits[row >> 6] >> (row & 63)) & 1u;
+}
+
+__global__ __launch_bounds__(OT) void raftery_kernel(const double* __restrict__ samples, long long S, int k, long long row0,
+                                                     long long N, const int* __restrict__ cols, int p, unsigned int rank_lo,
+                                                     unsigned int rank_hi, int interpolate, double h, long long j0, int nj,
+                                                     int staged, unsigned long long* bits_all, long long words,
+                                                     double* __restrict__ head, long long* __restrict__ counts) {
+  extern __shared__ unsigned long long s_k[];        // [N] when staged
+  __shared__ SelectLds L;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long series = blockIdx.x, c = series / p;
+  const int col = (int)(series % p);
+  const double* __restrict__ x = samples + (c * (long long)k + cols[col]) * S + row0;
+  stage_series(x, N, staged != 0, s_k, L);
+  if (tid < 2) { L.prefix[tid] = 0ull; L.rank[tid] = tid ? rank_hi : rank_lo; }
+  select_series(x, N, staged != 0, s_k, 2, L);
+  // the threshold: summary.type7_quantiles, operation for operation (two rounded products, one rounded sum)
+  const double xlo = value_of(L.prefix[0]), xhi = value_of(L.prefix[1]);
+  const double u = (interpolate && xhi != xlo) ? __dadd_rn(__dmul_rn(1.0 - h, xlo), __dmul_rn(h, xhi)) : xlo;
+  // the indicator, 64 rows a word: the ballot of a wavefront over 64 consecutive rows (the IEEE comparison on the values)
+  unsigned long long* bits = bits_all + series * words;   // (written, then read by other wavefronts: no __restrict__)
+  for (long long base = (long long)wave * 64; base < N; base += OT) {
+    const long long i = base + lane;
+    double v = 0.0;
+    if (i < N) v = staged ? value_of(s_k[i]) : x[i];
+    const unsigned long long w = __ballot(i < N && v <= u);
+    if (lane == 0) bits[base >> 6] = w;
+  }
+  if (tid == 0) {
+    double* o = head + series * HEAD;
+    o[0] = u; o[1] = xlo; o[2] = xhi; o[3] = (double)L.nf;
+  }
+  __threadfence_block();
+  __syncthreads();
+  // counts: one wavefront per thinning; lane l takes the triples l, l + 64, ... and keeps the eight counts in 16-bit fields
+  // (a lane sees fewer than N / 64 < 2^16 triples)
+  for (int jj = wave; jj < nj; jj += OW) {
+    const long long j = j0 + jj, m = (N + j - 1) / j, ntri = m >= 3 ? m - 2 : 0;
+    unsigned long long lo = 0ull, hi = 0ull;
+    for (long long i = lane; i < ntri; i += 64) {
+      const unsigned int a = bit_at(bits, i * j), b = bit_at(bits, (i + 1) * j), cc = bit_at(bits, (i + 2) * j);
+      const unsigned long long inc = 1ull << (16 * (2 * b + cc));
+      lo += a ? 0ull : inc;
+      hi += a ? inc : 0ull;
+    }
+    unsigned int cnt[8];
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      cnt[e] = (unsigned int)(lo >> (16 * e)) & 0xffffu;
+      cnt[4 + e] = (unsigned int)(hi >> (16 * e)) & 0xffffu;
+    }
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) cnt[e] += __shfl_xor(cnt[e], o, 64);
+    }
+    if (lane == 0) {
+      long long* o = counts + (series * nj + jj) * CNT;
+#pragma unroll
+      for (int e = 0; e < 8; e++) o[e] = (long long)cnt[e];
+      o[8] = m >= 2 ? (long long)bit_at(bits, (m - 2) * j) : 0LL;
+      o[9] = (long long)bit_at(bits, (m - 1) * j);
+    }
+  }
+}
+
+long long ar_order_max(long long N) {
+  const long long m = (long long)floor(10.0 * log10((double)N));
+  return m < N - 1 ? m : N - 1;
+}
+
+// The checks fmcmc_summary_dev makes of its window, for both entries; every one comes before the first device call.
+int check_window(const char* who, const void* samples, const void* cols, const void* work, const void* out, int64_t nchains,
+                 int32_t k, int64_t S, int64_t row0, int64_t N, int32_t p) {
+  if (!samples || !cols || !work || !out) return fail(FMCMC_ERR_ARG, "%s: null argument", who);
+  if (nchains < 1) return fail(FMCMC_ERR_ARG, "%s: nchains = %lld, need at least one chain", who, (long long)nchains);
+  if (k < 1) return fail(FMCMC_ERR_ARG, "%s: k = %d, need at least one parameter", who, (int)k);
+  if (p < 1) return fail(FMCMC_ERR_ARG, "%s: p = %d, need at least one column", who, (int)p);
+  if (N < 3) return fail(FMCMC_ERR_ARG, "%s: a window of N = %lld rows is too short (3 are needed)", who, (long long)N);
+  if (row0 < 0 || row0 + N > S)
+    return fail(FMCMC_ERR_ARG, "%s: the window [%lld, %lld) is outside the %lld rows of a chain", who, (long long)row0,
+                (long long)(row0 + N), (long long)S);
+  if (ar_order_max(N) > MAXM)
+    return fail(FMCMC_ERR_UNSUPPORTED, "%s: N = %lld rows per chain; supported are N < 3162278 (the limit of fmcmc_summary_dev)",
+                who, (long long)N);
+  if (nchains > 0x7fffffffLL / p)
+    return fail(FMCMC_ERR_UNSUPPORTED, "%s: %lld chains x %d columns exceed one launch", who, (long long)nchains, (int)p);
+  return FMCMC_OK;
+}
+
+template <typename Kernel>
+int allow_lds(const char* who, Kernel kernel, size_t lds) {
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+      hipSuccess)
+    return fail(FMCMC_ERR_DEVICE, "%s: %zu bytes of LDS refused", who, lds);
+  return FMCMC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t fmcmc_chain_order_work_len(int64_t nchains, int32_t p, int32_t nranks) {
+  if (nchains < 1 || p < 1 || nranks < 1 || nchains > 0x7fffffffLL / p) return 0;
+  return nchains * (int64_t)p;
+}
+
+int fmcmc_chain_order_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N,
+                          const int32_t* cols, int32_t p, const int64_t* ranks, int32_t nranks, double* work, double* out,
+                          void* hip_stream) {
+  const char* who = "fmcmc_chain_order_dev";
+  int rc = check_window(who, samples, cols, work, out, nchains, k, S, row0, N, p);
+  if (rc != FMCMC_OK) return rc;
+  if (!ranks) return fail(FMCMC_ERR_ARG, "%s: null argument", who);
+  if (nranks < 1 || nranks > MAXRANKS) return fail(FMCMC_ERR_ARG, "%s: nranks = %d outside [1, %d]", who, (int)nranks, MAXRANKS);
+  OrderRanks r;
+  for (int t = 0; t < MAXRANKS; t++) {
+    if (t < nranks && (ranks[t] < 0 || ranks[t] >= N))
+      return fail(FMCMC_ERR_ARG, "%s: ranks[%d] = %lld is outside [0, %lld)", who, t, (long long)ranks[t], (long long)N);
+    r.r[t] = (unsigned int)(t < nranks ? ranks[t] : 0);
+  }
+  hipStream_t st = (hipStream_t)hip_stream;
+  const int staged = N <= LDS_ROWS;
+  const size_t lds = staged ? (size_t)N * sizeof(unsigned long long) : 0;
+  rc = allow_lds(who, chain_order_kernel, lds);
+  if (rc != FMCMC_OK) return rc;
+  hipLaunchKernelGGL(chain_order_kernel, dim3((unsigned)(nchains * p)), dim3(OT), lds, st, samples, (long long)S, (int)k,
+                     (long long)row0, (long long)N, cols, (int)p, (int)nranks, r, staged, work, out);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(FMCMC_ERR_DEVICE, "%s: launch failed (%s)", who, hipGetErrorString(e));
+  return FMCMC_OK;
+}
+
+int64_t fmcmc_raftery_work_len(int64_t nchains, int32_t p, int64_t N) {
+  if (nchains < 1 || p < 1 || N < 1 || nchains > 0x7fffffffLL / p) return 0;
+  return nchains * (int64_t)p * ((N + 63) / 64);
+}
+
+int64_t fmcmc_raftery_out_len(int64_t nchains, int32_t p, int32_t nj) {
+  if (nchains < 1 || p < 1 || nj < 1 || nj > MAXNJ || nchains > 0x7fffffffLL / p) return 0;
+  return nchains * (int64_t)p * (HEAD + (int64_t)nj * CNT);
+}
+
+int fmcmc_raftery_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N,
+                      const int32_t* cols, int32_t p, double q, int64_t j0, int32_t nj, double* work, double* out,
+                      void* hip_stream) {
+  const char* who = "fmcmc_raftery_dev";
+  int rc = check_window(who, samples, cols, work, out, nchains, k, S, row0, N, p);
+  if (rc != FMCMC_OK) return rc;
+  if (!(q >= 0.0 && q <= 1.0)) return fail(FMCMC_ERR_ARG, "%s: q = %g is outside [0, 1]", who, q);
+  if (nj < 1 || nj > MAXNJ) return fail(FMCMC_ERR_ARG, "%s: nj = %d outside [1, %d]", who, (int)nj, MAXNJ);
+  if (j0 < 1 || j0 > 0x7fffffffLL) return fail(FMCMC_ERR_ARG, "%s: j0 = %lld, the thinnings start at 1", who, (long long)j0);
+  // R's quantile type 7 on the N rows of one series: index = 1 + (N - 1) q, the order statistics floor and ceil of it (1-based)
+  const double index = 1.0 + (double)(N - 1) * q;
+  const double flo = floor(index);
+  long long lo = (long long)flo - 1, hi = (long long)ceil(index) - 1;
+  lo = lo < 0 ? 0 : (lo > N - 1 ? N - 1 : lo);
+  hi = hi < 0 ? 0 : (hi > N - 1 ? N - 1 : hi);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const long long series = nchains * (long long)p;
+  const int staged = N <= LDS_ROWS;
+  const size_t lds = staged ? (size_t)N * sizeof(unsigned long long) : 0;
+  rc = allow_lds(who, raftery_kernel, lds);
+  if (rc != FMCMC_OK) return rc;
+  hipLaunchKernelGGL(raftery_kernel, dim3((unsigned)series), dim3(OT), lds, st, samples, (long long)S, (int)k, (long long)row0,
+                     (long long)N, cols, (int)p, (unsigned int)lo, (unsigned int)hi, (int)(index > flo), index - flo,
+                     (long long)j0, (int)nj, staged, reinterpret_cast<unsigned long long*>(work), (long long)((N + 63) / 64),
+                     out, reinterpret_cast<long long*>(out + series * HEAD));
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(FMCMC_ERR_DEVICE, "%s: launch failed (%s)", who, hipGetErrorString(e));
+  return FMCMC_OK;
+}
+
+}  // extern "C"

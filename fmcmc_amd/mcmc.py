@@ -271,6 +271,16 @@ class DeviceChains:
         from .summary import heidel
         return heidel(self, eps, pvalue, cols)
 
+    def raftery_diag(self, q=0.025, r=0.005, s=0.95, converge_eps=0.001, cols=None):
+        """Raftery-Lewis run-length diagnostic of every chain: burn-in M, total N, lower bound Nmin, dependence factor I."""
+        from .summary import raftery_diag
+        return raftery_diag(self, q, r, s, converge_eps, cols)
+
+    def chain_quantiles(self, probs=(0.025, 0.25, 0.5, 0.75, 0.975), cols=None):
+        """Type-7 quantiles of every chain on its own, [C][p][nprobs] (summary() pools the chains)."""
+        from .summary import chain_quantiles
+        return chain_quantiles(self, probs, cols)
+
     def gelman_diag(self, confidence=0.95, autoburnin=True, multivariate=True, cols=None):
         """Gelman-Rubin factors with coda's upper confidence limit (convergence_gelman stays the auto-stop checker)."""
         from .summary import gelman_diag

@@ -1,5 +1,6 @@
-"""summary() / effective_size() / geweke() / heidel() / gelman_diag() of a result, computed on the device
-(coda::summary.mcmc(.list), coda::effectiveSize, coda::geweke.diag, coda::heidel.diag, coda::gelman.diag).
+"""summary() / effective_size() / geweke() / heidel() / raftery_diag() / gelman_diag() / chain_quantiles() of a result, computed
+on the device (coda::summary.mcmc(.list), coda::effectiveSize, coda::geweke.diag, coda::heidel.diag, coda::raftery.diag,
+coda::gelman.diag).
 
 The first thing every example of the reference does with a result is `summary(ans)` (README.md:178-201, R/mcmc.R:212).  Here the
 kept rows stay where the sweep left them: csrc/summary.hip reduces every (chain, column) series to its mean, variance and
@@ -400,6 +401,270 @@ def heidel(x, eps=0.1, pvalue=0.05, cols=None):
     names = _names(dc, cols) if dc.names is not None else None          # (None: HeidelDiag numbers them by position)
     return heidel_finish(N - rows, stats[1:, :, :, 0], stats[1:, :, :, 2], Q, stats[0, :, :, 2], np.asarray(dc.iters)[rows], eps,
                          pvalue, names, candidates=labels)
+
+
+# ------------------------------------------------------------------------------------------------ Raftery-Lewis, per-chain quantiles
+RAFTERY_BATCH = 16          # thinnings per device launch (and per step of the host restatement): j = 1 .. 16, then 17 .. 32, ...
+RAFTERY_DEFAULTS = dict(q=0.025, r=0.005, s=0.95, converge_eps=0.001)
+
+
+def raftery_bound(q, r, s):
+    """coda::raftery.diag: (phi, nmin) = qnorm((1 + s) / 2), ceiling(q (1 - q) phi^2 / r^2): 3746 rows for the defaults."""
+    from scipy.special import ndtri
+    q, r, s = float(q), float(r), float(s)
+    if not (0.0 < q < 1.0 and r > 0.0 and 0.0 < s < 1.0):
+        raise ValueError("raftery_diag: need 0 < q < 1, r > 0 and 0 < s < 1")
+    phi = float(ndtri(0.5 * (1.0 + s)))
+    return phi, int(np.ceil((q * (1.0 - q) * (phi * phi)) / (r * r)))
+
+
+def raftery_finish(tri, last_pair, m, thin, q=0.025, r=0.005, s=0.95, converge_eps=0.001, j=None):
+    """The finish of raftery_diag(), from integer counts only, for any leading shape [...] (a series, [p], [C][p]):
+    tri [...][nj][8]: per thinning j the counts T[a][b][c] (at 4 a + 2 b + c) of the consecutive triples (Z_i, Z_{i+1}, Z_{i+2}),
+    i = 0 .. m - 3, of the indicator thinned to the rows 0, j, 2 j, ...; last_pair [...][nj][2] = (Z_{m-2}, Z_{m-1}) of that
+    thinned series; m [nj] = ceil(n / j), its length; j [nj]: the thinnings (default 1 .. nj); thin: the spacing of the labels.
+    Per thinning G2 = sum over the non-empty cells, a outermost, of T log(T / fit) 2 with fit = T_ab. T_.bc / T_.b., and
+    BIC = G2 - log(m - 2) 2; the thinning taken is the first with BIC < 0.  The pairs F[a][b] of that thinning are sum_c T[a][b][c]
+    plus the last pair; alpha = F01 / (F00 + F01), beta = F10 / (F10 + F11); M, N, I as coda forms them.
+    Returns a namespace of [...] arrays: M, N, I, kthin (NaN where there is no result), j (0 there), alpha, beta, and the flags
+    `failed` (a thinning with m < 3 was reached before any BIC < 0) and `undecided` (every thinning tried had m >= 3 and
+    BIC >= 0: more are needed), then bic [...][nj] and nmin.  Equal counts give equal bits."""
+    phi, nmin = raftery_bound(q, r, s)
+    tri = np.asarray(tri, dtype=np.int64)
+    last_pair = np.asarray(last_pair, dtype=np.int64)
+    m = np.atleast_1d(np.asarray(m, dtype=np.int64))
+    nj = m.size
+    j = np.arange(1, nj + 1, dtype=np.int64) if j is None else np.atleast_1d(np.asarray(j, dtype=np.int64))
+    if tri.shape[-2:] != (nj, 8) or last_pair.shape != tri.shape[:-1] + (2,) or j.size != nj:
+        raise ValueError("raftery_finish: tri [...][nj][8], last_pair [...][nj][2], m [nj] and j [nj] are needed")
+    lead = tri.shape[:-2]
+    T = np.ascontiguousarray(tri, dtype=np.float64).reshape(lead + (nj, 2, 2, 2))
+    with np.errstate(all="ignore"):
+        ab = T[..., 0] + T[..., 1]                                   # [..][nj][a][b]
+        bc = T[..., 0, :, :] + T[..., 1, :, :]                       # [..][nj][b][c]
+        mid = ab[..., 0, :] + ab[..., 1, :]                          # [..][nj][b]
+        fit = (ab[..., :, :, None] * bc[..., None, :, :]) / mid[..., None, :, None]
+        term = T * np.log(np.ascontiguousarray(T / fit)) * 2.0
+        term = np.where(T != 0.0, term, 0.0).reshape(lead + (nj, 8))
+        g2 = np.zeros(lead + (nj,))
+        for cell in range(8):                                        # (coda's loop order; an empty cell adds nothing)
+            g2 = g2 + term[..., cell]
+        valid = m >= 3
+        bic = np.where(valid, g2 - np.log(np.where(valid, m - 2, 1).astype(np.float64)) * 2.0, np.nan)
+        passing = valid & (bic < 0.0)
+        # m falls as j grows: a thinning with m < 3 is behind every valid one
+        found = passing.any(axis=-1)
+        pick = passing.argmax(axis=-1)
+        failed = ~found & (~valid).any()
+        undecided = ~found & bool(valid.all())
+        sel = pick[..., None, None]
+        Tj = np.take_along_axis(tri, sel, axis=-2)[..., 0, :].reshape(lead + (2, 2, 2))
+        lp = np.take_along_axis(last_pair, sel, axis=-2)[..., 0, :]
+        F = Tj[..., 0] + Tj[..., 1]                                  # [..][a][b], integers
+        F = F + ((lp[..., 0, None, None] == np.arange(2)[:, None]) & (lp[..., 1, None, None] == np.arange(2)[None, :]))
+        F = F.astype(np.float64)
+        alpha = F[..., 0, 1] / (F[..., 0, 0] + F[..., 0, 1])
+        beta = F[..., 1, 0] / (F[..., 1, 0] + F[..., 1, 1])
+        kthin = (j[pick] * int(thin)).astype(np.float64)
+        ab_ = alpha + beta
+        tempburn = np.log((converge_eps * ab_) / np.maximum(alpha, beta)) / np.log(np.abs(1.0 - alpha - beta))
+        M = np.ceil(tempburn) * kthin
+        tempprec = ((2.0 - alpha - beta) * alpha * beta * (phi * phi)) / ((ab_ * ab_ * ab_) * (r * r))
+        nkeep = np.ceil(tempprec) * kthin
+        N = M + nkeep
+        I = N / nmin
+    bad = ~found | ~np.isfinite(M) | ~np.isfinite(N)
+    blank = lambda a: np.where(bad, np.nan, a)
+    return SimpleNamespace(M=blank(M), N=blank(N), I=blank(I), kthin=np.where(found, kthin, np.nan), j=np.where(found, j[pick], 0),
+                           alpha=np.where(found, alpha, np.nan), beta=np.where(found, beta, np.nan), failed=failed,
+                           undecided=undecided, bic=bic, nmin=nmin)
+
+
+def raftery_search(counts, n, thin, q=0.025, r=0.005, s=0.95, converge_eps=0.001):
+    """The thinning search both raftery_diag()s share: counts(j0, nj) -> (tri [...][nj][8], last_pair [...][nj][2]) of the
+    thinnings j0 .. j0 + nj - 1 is asked for one batch after the other while some series has no thinning with BIC < 0 yet and
+    the next one still has m = ceil(n / j) >= 3 rows.  Returns raftery_finish of everything counted."""
+    tris, lasts, j0 = [], [], 1
+    while True:
+        t, l = counts(j0, RAFTERY_BATCH)
+        tris.append(np.asarray(t, dtype=np.int64))
+        lasts.append(np.asarray(l, dtype=np.int64))
+        j0 += RAFTERY_BATCH
+        j = np.arange(1, j0, dtype=np.int64)
+        fin = raftery_finish(np.concatenate(tris, axis=-2), np.concatenate(lasts, axis=-2), -(-int(n) // j), thin, q, r, s,
+                             converge_eps, j=j)
+        if not fin.undecided.any() or -(-int(n) // j0) < 3:       # (an undecided series fails at the next thinning: NaN already)
+            return fin
+
+
+def host_chain_order(series, ranks):
+    """The order statistics fmcmc_chain_order_dev selects, from a sort: series [..., n], 0-based ranks -> [..., nranks]."""
+    return np.sort(np.asarray(series, dtype=np.float64), axis=-1)[..., np.asarray(ranks, dtype=np.int64)]
+
+
+def type7_order_ranks(n, probs):
+    """The 0-based ranks [nprobs][2] of x_(lo), x_(hi) that type7_quantiles(., n, probs) needs."""
+    _, lo, hi = type7_ranks(n, probs)
+    return np.clip(np.stack([lo, hi], axis=-1) - 1, 0, n - 1)
+
+
+def host_chain_quantiles(series, probs):
+    """chain_quantiles() without the device: series [..., n] -> type-7 quantiles [..., nprobs] of every series on its own."""
+    series = np.asarray(series, dtype=np.float64)
+    n = series.shape[-1]
+    ranks = type7_order_ranks(n, probs)
+    return type7_quantiles(host_chain_order(series, ranks.ravel()).reshape(series.shape[:-1] + ranks.shape), n, probs)
+
+
+class RafteryDiag:
+    """coda::raftery.diag of every chain: M (burn-in), N (total), I = N / nmin (unrounded; coda prints signif(I, 3)) and kthin,
+    each [C][p], NaN where coda has no number (a constant series; fewer than nmin rows: `nmin` is set all the same);
+    table [C][p][4] in coda's column order (M, N, Nmin, I), so table[c] is convergence.raftery_diag of chain c;
+    u [C][p]: the per-series threshold, the type-7 quantile at q; alpha, beta [C][p]: the transition rates of the indicator."""
+    columns = ("M", "N", "Nmin", "I")
+
+    def __init__(self, table, kthin, nmin, nrows, q, r, s, converge_eps, varnames=None, u=None, alpha=None, beta=None):
+        self.table = np.asarray(table, dtype=np.float64)
+        self.kthin = np.asarray(kthin, dtype=np.float64)
+        self.nmin, self.nrows = int(nmin), int(nrows)
+        self.q, self.r, self.s, self.converge_eps = float(q), float(r), float(s), float(converge_eps)
+        self.varnames = list(varnames) if varnames is not None else ["par%d" % (j + 1) for j in range(self.table.shape[1])]
+        self.u, self.alpha, self.beta = u, alpha, beta
+
+    M = property(lambda self: self.table[:, :, 0])
+    N = property(lambda self: self.table[:, :, 1])
+    I = property(lambda self: self.table[:, :, 3])
+
+    def __str__(self):
+        whole = lambda v: "NA" if np.isnan(v) else "%d" % v
+        out = []
+        for c, t in enumerate(self.table):
+            if len(self.table) > 1:
+                out += ["[[%d]]" % (c + 1)]
+            out += ["", "Quantile (q) = %g" % self.q, "Accuracy (r) = +/- %g" % self.r, "Probability (s) = %g " % self.s, ""]
+            if self.nmin > self.nrows:
+                out += ["You need a sample size of at least %d with these values of q, r and s" % self.nmin, ""]
+                continue
+            out += [HeidelDiag._block(self.varnames, (("Burn-in", "(M)"), ("Total", "(N)"), ("Lower bound", "(Nmin)"),
+                                                      ("Dependence", "factor (I)")),
+                                      ([whole(v) for v in t[:, 0]], [whole(v) for v in t[:, 1]], [whole(v) for v in t[:, 2]],
+                                       ["NA" if np.isnan(v) else "%.3g" % v for v in t[:, 3]])), ""]
+        return "\n".join(out)
+
+    def __repr__(self):
+        return "<RafteryDiag nchain=%d nvar=%d nmin=%d>" % (self.table.shape[0], self.table.shape[1], self.nmin)
+
+
+def raftery_table(fin, shape):
+    """[...][4] = M, N, Nmin, I from raftery_finish's namespace (or all NaN but Nmin when fin is the bound alone)."""
+    table = np.full(tuple(shape) + (4,), np.nan)
+    table[..., 2] = fin.nmin
+    if hasattr(fin, "M"):
+        table[..., 0], table[..., 1], table[..., 3] = fin.M, fin.N, fin.I
+    return table
+
+
+def _raise_non_finite(nbad, cols, what):
+    """nbad [C][p] counts of non-finite values per series."""
+    per_col = np.asarray(nbad).sum(axis=0)
+    if per_col.sum():
+        raise ValueError("%d non-finite value(s) among the rows to %s (columns %s)"
+                         % (int(per_col.sum()), what, [int(c) for c, b in zip(cols, per_col) if b]))
+
+
+def enqueue_chain_order(dc, ranks, cols):
+    """Enqueues one fmcmc_chain_order_dev call on the kept rows of `dc` (current torch stream): the values at the 0-based
+    `ranks` of every (chain, column) series.  Returns the device tensors (out [C][p][nranks], non-finite counts [C][p]) and the
+    columns; nothing is synchronised."""
+    import torch
+    L, smp, (Cn, k, cap) = _device_samples(dc)
+    if Cn < 1:
+        raise ValueError("no chains to order")
+    dev, cols, cols_d = _device_columns(dc, cols)
+    p = int(cols.size)
+    ranks = np.ascontiguousarray(ranks, dtype=np.int64).ravel()
+    work = torch.empty(max(int(L.fmcmc_chain_order_work_len(Cn, p, ranks.size)), 1), dtype=torch.float64, device=dev)
+    out = torch.empty((Cn, p, max(int(ranks.size), 1)), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.fmcmc_chain_order_dev(smp.data_ptr(), Cn, k, cap, 0, int(dc.nrows), cols_d.data_ptr(), p,
+                                     ranks.ctypes.data_as(C.POINTER(C.c_int64)), int(ranks.size), work.data_ptr(), out.data_ptr(),
+                                     _stream(dev))
+    _raise_for(rc)
+    return out, work[:Cn * p].view(Cn, p), cols
+
+
+def chain_quantiles(x, probs=DEFAULT_QUANTILES, cols=None):
+    """R's type-7 quantiles of every chain on its own, [C][p][nprobs] (summary() pools the chains): x a DeviceChains (read in
+    place), an Mcmc or a McmcList (uploaded first); at most 16 probs.  The order statistics are selected exactly on the device
+    (csrc/raftery.hip, one workgroup per series); the interpolation is type7_quantiles."""
+    dc = _as_device_chains(x)
+    probs = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+    if probs.size < 1 or probs.size > abi.SUMMARY_MAX_PROBS:
+        raise ValueError("between 1 and %d probs per call" % abi.SUMMARY_MAX_PROBS)
+    if not np.all((probs >= 0.0) & (probs <= 1.0)):
+        raise ValueError("`probs` must lie in [0, 1]")
+    n = int(dc.nrows)
+    ranks = type7_order_ranks(n, probs)
+    out, nbad, cols = enqueue_chain_order(dc, ranks.ravel(), cols)
+    _raise_non_finite(nbad.cpu().numpy(), cols, "order")
+    os_ = out.cpu().numpy()
+    return type7_quantiles(os_.reshape(os_.shape[:2] + ranks.shape), n, probs)
+
+
+def enqueue_raftery(dc, q, j0, nj, cols):
+    """Enqueues one fmcmc_raftery_dev call on the kept rows of `dc` (current torch stream) for the thinnings j0 .. j0 + nj - 1.
+    Returns the device tensors (head [C][p][4] = u, x_(lo), x_(hi), non-finite count; counts [C][p][nj][10] int64; work) and the
+    columns; nothing is synchronised."""
+    import torch
+    L, smp, (Cn, k, cap) = _device_samples(dc)
+    if Cn < 1:
+        raise ValueError("no chains to test")
+    dev, cols, cols_d = _device_columns(dc, cols)
+    p, n = int(cols.size), int(dc.nrows)
+    work = torch.empty(max(int(L.fmcmc_raftery_work_len(Cn, p, n)), 1), dtype=torch.float64, device=dev)
+    out = torch.empty(max(int(L.fmcmc_raftery_out_len(Cn, p, nj)), 1), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.fmcmc_raftery_dev(smp.data_ptr(), Cn, k, cap, 0, n, cols_d.data_ptr(), p, float(q), int(j0), int(nj),
+                                 work.data_ptr(), out.data_ptr(), _stream(dev))
+    _raise_for(rc)
+    series = Cn * p
+    return (out[:series * 4].view(Cn, p, 4), out[series * 4:series * (4 + 10 * nj)].view(torch.int64).view(Cn, p, nj, 10),
+            work, cols)
+
+
+def raftery_diag(x, q=0.025, r=0.005, s=0.95, converge_eps=0.001, cols=None):
+    """coda::raftery.diag for every chain at once: x a DeviceChains (read in place), an Mcmc or a McmcList (uploaded first).
+    The device selects every series' own type-7 quantile at q, packs the indicator x <= u and counts its triples for a batch of
+    thinnings (csrc/raftery.hip); raftery_finish does the rest on those integers, the same function convergence.raftery_diag
+    ends in, so the two agree bit for bit.  A second batch is launched only while some series has no thinning with BIC < 0."""
+    dc = _as_device_chains(x)
+    n, Cn = int(dc.nrows), int(dc._samples.shape[0])
+    cols_ = _columns(dc, cols)
+    names = _names(dc, cols_) if dc.names is not None else None
+    _single_process()
+    phi, nmin = raftery_bound(q, r, s)
+    shape = (Cn, int(cols_.size))
+    if nmin > n:
+        return RafteryDiag(raftery_table(SimpleNamespace(nmin=nmin), shape), np.full(shape, np.nan), nmin, n, q, r, s,
+                           converge_eps, names)
+    heads = []
+
+    def counts(j0, nj):
+        head, cnt, _work, _ = enqueue_raftery(dc, q, j0, nj, cols)
+        ch = cnt.cpu().numpy()
+        if not heads:
+            heads.append(head.cpu().numpy())
+            _raise_non_finite(heads[0][:, :, 3], cols_, "test")
+        return ch[..., :8], ch[..., 8:]
+
+    iters = np.asarray(dc.iters)
+    thin = int(iters[1] - iters[0]) if iters.size > 1 else int(dc.thin)
+    fin = raftery_search(counts, n, thin, q, r, s, converge_eps)
+    return RafteryDiag(raftery_table(fin, shape), fin.kthin, nmin, n, q, r, s, converge_eps, names, u=heads[0][:, :, 0].copy(),
+                       alpha=fin.alpha, beta=fin.beta)
+
+
+raftery = raftery_diag      # (the name the package exports it under: fmcmc_amd.raftery_diag is the host restatement)
 
 
 # ------------------------------------------------------------------------------------------------ Gelman-Rubin

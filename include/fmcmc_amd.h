@@ -341,6 +341,43 @@ int fmcmc_heidel_dev(const double* samples, int64_t nchains, int32_t k, int64_t 
                      const int32_t* cols, int32_t p, int64_t half_row, const int64_t* cand_rows, int64_t ncand, double* work,
                      double* out, void* hip_stream);
 
+/* ---- order statistics of every chain on its own ------------------------------------------------------------------------------
+ * Window, samples, S, cols as for fmcmc_summary_dev, and its row limits (3 <= N < 3162278).  ranks is a HOST array, read during
+ * the call, of 1 <= nranks <= 32 0-based ranks in [0, N), the same for every series (repeats allowed).
+ * out (device, nchains p nranks doubles): [nchains][p][nranks], out[c][j][t] = the value with ranks[t] values of the N rows of
+ *   chain c, column cols[j] before it in ascending order (-0.0 before +0.0).  They are exact: a radix select on the values' bits,
+ *   one workgroup per series, the series held in LDS up to 19456 rows and re-read from global memory every pass beyond.
+ * work (device, fmcmc_chain_order_work_len doubles): [nchains][p], left as the count of non-finite values of each series (a NaN
+ *   sorts below -Inf or above +Inf by its sign bit).
+ * Argument errors are found before any device call and leave their text in fmcmc_last_error().  The call only enqueues one
+ * kernel on hip_stream and reads `samples` only; all counts are integers: a series gives the same bits wherever it sits. */
+int64_t fmcmc_chain_order_work_len(int64_t nchains, int32_t p, int32_t nranks);
+int fmcmc_chain_order_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N,
+                          const int32_t* cols, int32_t p, const int64_t* ranks, int32_t nranks, double* work, double* out,
+                          void* hip_stream);
+
+/* ---- Raftery-Lewis run-length diagnostic of every chain (coda::raftery.diag), the device part ---------------------------------
+ * Window, samples, S, cols and row limits as for fmcmc_summary_dev.  Per series (chain c, column cols[j]):
+ *   u = R's type-7 quantile of the N rows of the series at q (0 <= q <= 1): index = 1 + (N - 1) q, lo = floor(index),
+ *   hi = ceil(index) (1-based), u = x_(lo) when index == lo or x_(hi) == x_(lo), else (1 - h) x_(lo) + h x_(hi) with h = index - lo
+ *   (two rounded products, one rounded sum); Z_t = (x_t <= u), t = 0 .. N - 1.
+ *   For each thinning j = j0 .. j0 + nj - 1 (j0 >= 1, 1 <= nj <= 32): rows 0, j, 2 j, ... (m = ceil(N / j) of them), the counts
+ *   T[a][b][c] of the triples (Z_i, Z_{i+1}, Z_{i+2}) = (a, b, c), i = 0 .. m - 3, of the thinned series (all 0 when m < 3), and
+ *   its last pair (Z_{m-2}, Z_{m-1}) (Z_{m-2} reported as 0 when m == 1).
+ * out (device, fmcmc_raftery_out_len(nchains, p, nj) 8-byte words): [nchains][p][4] doubles = {u, x_(lo), x_(hi), count of
+ *   non-finite values of the series}, then [nchains][p][nj][10] 64-bit INTEGERS = {T at 4 a + 2 b + c, Z_{m-2}, Z_{m-1}}.
+ * work (device, fmcmc_raftery_work_len(nchains, p, N) doubles): [nchains][p][ceil(N / 64)] 64-bit words, left as the
+ *   indicator, bit t % 64 of word t / 64 = Z_t.  A call does not depend on what an earlier call left there.
+ * BIC, the first thinning that passes, alpha, beta, M, N and I follow from these integers on the host
+ * (fmcmc_amd/summary.py: raftery_finish).  Argument errors are found before any device call and leave their text in
+ * fmcmc_last_error().  The call only enqueues one kernel on hip_stream and reads `samples` only; everything but u is an
+ * integer and u has a fixed arithmetic: a series gives the same bits wherever it sits. */
+int64_t fmcmc_raftery_work_len(int64_t nchains, int32_t p, int64_t N);
+int64_t fmcmc_raftery_out_len(int64_t nchains, int32_t p, int32_t nj);
+int fmcmc_raftery_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N,
+                      const int32_t* cols, int32_t p, double q, int64_t j0, int32_t nj, double* work, double* out,
+                      void* hip_stream);
+
 /* Materialises the canonical Philox stream of a call in device memory, in the FED layout of fmcmc_run:
  * logu[C][nsteps] (entry i-1 = log accept-uniform of loop step i), z[C][nsteps][kz] (N(0,1) when student_df == 0;
  * Student-t with student_df degrees of freedom when student_df > 0 -- kernel_ram: kf for the default qfun rt(k, k),

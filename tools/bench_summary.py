@@ -6,9 +6,13 @@ Per shape, one warm-up call and then the best of five of: the enqueued kernels o
 time of summary() including the small copy back; the wall time of DeviceChains.to_host() of the same rows in the same process.
 At the headline shape also heidel(): its enqueued kernels between two HIP events, its wall time, and the only other route to
 the same table: to_host() plus convergence.heidel_diag chain by chain, timed on --heidel-host-chains chains and scaled to all.
+And raftery_diag() (the `raftery` leg): the one kernel of fmcmc_raftery_dev for the first batch of thinnings between two HIP
+events, the wall time of the whole call with its copy back and numpy finish, the number of launches it took, the kernel and wall
+of chain_quantiles() at the default five probs, and convergence.raftery_diag on the host for --heidel-host-chains chains.
 Usage: python tools/bench_summary.py [--shapes headline,c4] [--json FILE]   (one JSON line per shape; --json also writes them, with
 the device and the date, to FILE: profiles/bench_summary.json holds the run DESIGN.md section 5.10 quotes, and
-profiles/bench_summary_heidel.json the headline run with heidel())"""
+profiles/bench_summary_heidel.json the headline run with heidel(), profiles/bench_summary_raftery.json the one with the
+raftery leg)"""
 import argparse
 import json
 import os
@@ -31,6 +35,8 @@ def main():
     a = ap.parse_args()
     import torch
     import fmcmc_amd as F
+    import importlib
+    S = importlib.import_module("fmcmc_amd.summary")     # (fmcmc_amd.summary is the function)
     from fmcmc_amd.summary import DEFAULT_QUANTILES, enqueue_heidel, enqueue_window, heidel_candidates
     from bench import Config
     dev = torch.device("cuda", 0)
@@ -87,6 +93,40 @@ def main():
             per_chain = (time.perf_counter() - t0) / host.shape[0]
             best.update(heidel_candidates=int(rows.size), heidel_diag_host_ms_per_chain=round(1e3 * per_chain, 3),
                         heidel_host_route_ms=round(best["to_host_wall_ms"] + 1e3 * per_chain * C_, 1))
+            # the raftery leg
+            def between_events(enqueue):
+                def run():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    keep = enqueue()
+                    e1.record()
+                    e1.synchronize()
+                    del keep
+                    return e0.elapsed_time(e1) * 1e-3
+                return run
+
+            ranks = S.type7_order_ranks(N, DEFAULT_QUANTILES).ravel()
+            launches = []
+            real = S.enqueue_raftery
+            S.enqueue_raftery = lambda *args: launches.append(args[2]) or real(*args)
+            try:
+                rd = dc.raftery_diag()
+            finally:
+                S.enqueue_raftery = real
+            for name, fn in (("raftery_kernel_ms", between_events(lambda: S.enqueue_raftery(dc, 0.025, 1, S.RAFTERY_BATCH, None))),
+                             ("raftery_wall_ms", lambda: wall(dc.raftery_diag)),
+                             ("chain_order_kernel_ms", between_events(lambda: S.enqueue_chain_order(dc, ranks, None))),
+                             ("chain_quantiles_wall_ms", lambda: wall(dc.chain_quantiles))):
+                fn()
+                best[name] = round(1e3 * min(fn() for _ in range(5)), 3)
+            t0 = time.perf_counter()
+            for c in range(host.shape[0]):
+                F.raftery_diag(host[c].T, dc.iters)
+            per_chain = (time.perf_counter() - t0) / host.shape[0]
+            best.update(raftery_launches=len(launches), raftery_thinnings_per_launch=S.RAFTERY_BATCH,
+                        raftery_kthin_max=float(np.nanmax(rd.kthin)), raftery_I_median=round(float(np.nanmedian(rd.I)), 3),
+                        raftery_diag_host_ms_per_chain=round(1e3 * per_chain, 3),
+                        raftery_host_route_ms=round(best["to_host_wall_ms"] + 1e3 * per_chain * C_, 1))
             del host
         nbytes = C_ * k * N * 8
         lines.append(dict(shape=shape, chains=C_, columns=k, rows=N, sample_bytes=nbytes, quantiles=len(DEFAULT_QUANTILES), **best,
