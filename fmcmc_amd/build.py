@@ -2,8 +2,9 @@
 
 The library is several translation units (csrc/mh_engine.hip = C-ABI + launches, with its own headers mh_route.hpp = kernel
 selection, mh_prep.hpp = data-preparation kernels, mh_host.hpp = host-pointer staging; csrc/k_*.hip = one kernel family
-each, csrc/gelman.hip, csrc/summary.hip, csrc/raftery.hip) compiled in parallel into build/*.o and linked by hipcc; only the units whose sources changed are
-recompiled."""
+each; the diagnostics csrc/gelman.hip, csrc/summary.hip, csrc/raftery.hip with the header they share, csrc/diag_common.hpp)
+compiled in parallel into build/*.o and linked by hipcc; only the units whose sources (unit_deps: the unit and the headers it
+includes) changed are recompiled."""
 import concurrent.futures
 import glob
 import os

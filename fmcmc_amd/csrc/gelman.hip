@@ -6,12 +6,9 @@
 // local chains into a small "partial" vector.  Partials of different GPUs ADD, so the only
 // collective of the whole engine is one all-reduce(sum) of 1 + 5p + 2p^2 doubles per check.
 // Host side: fmcmc_gelman_finish turns the reduced partial into psrf / mpsrf.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <math.h>
 #include <vector>
 
-#include "../../include/fmcmc_amd.h"
+#include "diag_common.hpp"
 
 namespace {
 
@@ -87,16 +84,13 @@ __global__ __launch_bounds__(GT) void gelman_cov_mfma(const double* __restrict__
   // are in flight behind the one being multiplied (the loads come from HBM: ~2 us, a group's 40 MFMAs are ~1 us).
   const long long groups = (N + 15) / 16, per = (groups + 3) / 4;
   const long long g_lo = wave * per, g_hi = (g_lo + per < groups) ? g_lo + per : groups;
-  // (a pair is 8-byte aligned only: the window starts at any row of a history whose row stride may be odd -- the vector type
-  //  says so, the loads are still one global_load_dwordx4 each, which gfx950 serves at any 4-byte alignment)
-  typedef double gd2_t __attribute__((ext_vector_type(2), aligned(8)));
   double buf[DEPTH][NB][4];
   auto load = [&](long long gi, double (&v)[NB][4]) {
     const long long t = 16 * gi + 4 * kk;
     if (t + 3 < N) {
 #pragma unroll
       for (int cb = 0; cb < NB; cb++) {
-        const gd2_t lo = *reinterpret_cast<const gd2_t*>(colp[cb] + t), hi = *reinterpret_cast<const gd2_t*>(colp[cb] + t + 2);
+        const dpair_t lo = *reinterpret_cast<const dpair_t*>(colp[cb] + t), hi = *reinterpret_cast<const dpair_t*>(colp[cb] + t + 2);
         v[cb][0] = lo[0]; v[cb][1] = lo[1]; v[cb][2] = hi[0]; v[cb][3] = hi[1];
       }
     } else {
@@ -391,7 +385,7 @@ int fmcmc_gelman_finish(const double* P, int32_t p, int64_t N, double* psrf, dou
   }
   *mpsrf = NAN;
   if (p > 1) {
-    // L = chol(W) lower; Z = L^-1 B L^-T; largest eigenvalue by cyclic Jacobi
+    // L = chol(W) lower; Z = L^-1 B L^-T; largest eigenvalue by Householder tridiagonalisation and QL (top_eigenvalue_sym)
     std::vector<double> L(p * p, 0.0), Y(p * p), Z(p * p);
     for (int j = 0; j < p; j++) {
       double d = W[j * p + j];

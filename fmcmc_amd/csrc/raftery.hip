@@ -3,7 +3,7 @@
 //
 // One chain's column is N contiguous doubles (samples + (c k + col) S + row0), as in summary.hip.  One workgroup per series:
 //   1. stage        the series is read once with 8-byte-aligned pair loads, its non-finite values are counted, and while it fits
-//                   (N <= 19456 rows, the tile of summary_series_kernel) its order-preserving keys are kept in LDS;
+//                   (N <= LDS_ROWS, the tile of summary_series_kernel) its order-preserving keys are kept in LDS;
 //   2. select       exact order statistics at up to 32 ranks by a most-significant-digit radix select on the keys: 8 passes of
 //                   8 bits, the histograms in LDS.  Targets with the same prefix share one histogram (that of their "leader"),
 //                   HG leaders are counted per walk over the series; a series too long for LDS is re-read every walk;
@@ -12,51 +12,18 @@
 //                   2x2x2 table of the consecutive triples of Z at rows 0, j, 2j, ... and its last pair.
 // Every count is an integer, so neither the arrival order of the LDS atomics nor the launch changes a result.  Nothing here
 // writes `samples`.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <math.h>
-#include <stdio.h>
-#include <stdarg.h>
-
-#include "../../include/fmcmc_amd.h"
-#include "../../include/fmh_detmath.h"
-
-extern "C" void fmcmc_set_error_text_(const char* text);   // mh_engine.hip: the buffer behind fmcmc_last_error()
+#include "diag_common.hpp"
 
 namespace {
 
 constexpr int OT = 512;             // threads of a series workgroup
 constexpr int OW = OT / 64;
-constexpr int LDS_ROWS = 19456;     // rows of a series whose keys are staged in LDS (152 KB; summary.hip: the same tile)
 constexpr int MAXRANKS = 32;        // targets per call: 2 x SUMMARY_MAX_PROBS
 constexpr int HG = 4;               // histograms (leaders) per walk over the series
 constexpr int MAXNJ = 32;           // thinnings per launch
 constexpr int LU = 4;               // pairs in flight per thread
-constexpr int MAXM = 64;            // summary.hip: the AR order that bounds the rows of a window there, and so here
 constexpr int HEAD = 4;             // doubles per series at the head of the raftery output: u, x_(lo), x_(hi), non-finite count
 constexpr int CNT = 10;             // integers per (series, thinning): T[a][b][c] at 4 a + 2 b + c, then Z_{m-2}, Z_{m-1}
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  fmcmc_set_error_text_(buf);
-  return code;
-}
-
-typedef double sd2_t __attribute__((ext_vector_type(2), aligned(8)));   // (a pair is 8-byte aligned only: summary.hip)
-
-// the key mapping of summary.hip: x < y <=> key(x) < key(y), and value_of(key_of(x)) has the bits of x
-__device__ __forceinline__ unsigned long long key_of(double x) {
-  const unsigned long long u = fmh_d2u(x);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double value_of(unsigned long long kx) {
-  return fmh_u2d((kx >> 63) ? (kx & 0x7fffffffffffffffull) : ~kx);
-}
 
 struct OrderRanks { unsigned int r[MAXRANKS]; };    // 0-based, each < N < 2^32
 
@@ -73,36 +40,17 @@ struct SelectLds {
 // Reads the series once: counts its non-finite values into L.nf and, when `staged`, leaves key_of(x[i]) in s_k[i].
 __device__ __forceinline__ void stage_series(const double* __restrict__ x, long long N, bool staged, unsigned long long* s_k,
                                              SelectLds& L) {
-  const int tid = threadIdx.x;
-  if (tid == 0) L.nf = 0u;
+  if (threadIdx.x == 0) L.nf = 0u;
   __syncthreads();
   unsigned int nf = 0u;
-  for (long long base = 0; base < N; base += 2LL * LU * OT) {
-    double a[LU], b[LU];
-#pragma unroll
-    for (int u = 0; u < LU; u++) {
-      const long long i = base + 2LL * (u * OT + tid);
-      a[u] = 0.0; b[u] = 0.0;
-      if (i + 1 < N) {
-        const sd2_t v = *reinterpret_cast<const sd2_t*>(x + i);
-        a[u] = v[0]; b[u] = v[1];
-      } else if (i < N) {
-        a[u] = x[i];
-      }
+  walk_pairs<OT, LU>(x, N, [&](long long i, double a, double b, bool has_b) {
+    nf += fmh_isfinite(a) ? 0u : 1u;
+    if (staged) s_k[i] = key_of(a);
+    if (has_b) {
+      nf += fmh_isfinite(b) ? 0u : 1u;
+      if (staged) s_k[i + 1] = key_of(b);
     }
-#pragma unroll
-    for (int u = 0; u < LU; u++) {
-      const long long i = base + 2LL * (u * OT + tid);
-      if (i < N) {
-        nf += fmh_isfinite(a[u]) ? 0u : 1u;
-        if (staged) s_k[i] = key_of(a[u]);
-        if (i + 1 < N) {
-          nf += fmh_isfinite(b[u]) ? 0u : 1u;
-          if (staged) s_k[i + 1] = key_of(b[u]);
-        }
-      }
-    }
-  }
+  });
   if (nf) atomicAdd(&L.nf, nf);
   __syncthreads();
 }
@@ -113,7 +61,6 @@ __device__ __forceinline__ void select_series(const double* __restrict__ x, long
                                               const unsigned long long* s_k, int nt, SelectLds& L) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int pass = 0; pass < 8; pass++) {
-    const int shift = 56 - 8 * pass;
     __syncthreads();
     if (tid == 0) {                                  // leaders: the first target of every distinct prefix
       int n = 0;
@@ -136,8 +83,8 @@ __device__ __forceinline__ void select_series(const double* __restrict__ x, long
       for (int e = tid; e < HG * 256; e += OT) (&L.hist[0][0])[e] = 0u;
       __syncthreads();
       auto count = [&](unsigned long long kx) {
-        const unsigned long long high = (pass == 0) ? 0ull : (kx >> (shift + 8));
-        const unsigned int digit = (unsigned int)(kx >> shift) & 255u;
+        const unsigned long long high = radix_high(kx, pass);
+        const unsigned int digit = radix_digit(kx, pass);
 #pragma unroll
         for (int g = 0; g < HG; g++)
           if (g < ng && high == pg[g]) atomicAdd(&L.hist[g][digit], 1u);
@@ -145,26 +92,7 @@ __device__ __forceinline__ void select_series(const double* __restrict__ x, long
       if (staged) {
         for (int i = tid; i < (int)N; i += OT) count(s_k[i]);
       } else {
-        for (long long base = 0; base < N; base += 2LL * LU * OT) {
-          double a[LU], b[LU];
-#pragma unroll
-          for (int u = 0; u < LU; u++) {
-            const long long i = base + 2LL * (u * OT + tid);
-            a[u] = 0.0; b[u] = 0.0;
-            if (i + 1 < N) {
-              const sd2_t v = *reinterpret_cast<const sd2_t*>(x + i);
-              a[u] = v[0]; b[u] = v[1];
-            } else if (i < N) {
-              a[u] = x[i];
-            }
-          }
-#pragma unroll
-          for (int u = 0; u < LU; u++) {
-            const long long i = base + 2LL * (u * OT + tid);
-            if (i < N) count(key_of(a[u]));
-            if (i + 1 < N) count(key_of(b[u]));
-          }
-        }
+        walk_pairs<OT, LU>(x, N, [&](long long, double a, double b, bool has_b) { count(key_of(a)); if (has_b) count(key_of(b)); });
       }
       __syncthreads();
       if (wave < ng) {                               // one wavefront per histogram: exclusive prefix sums, four bins a lane
@@ -283,38 +211,6 @@ __global__ __launch_bounds__(OT) void raftery_kernel(const double* __restrict__ 
   }
 }
 
-long long ar_order_max(long long N) {
-  const long long m = (long long)floor(10.0 * log10((double)N));
-  return m < N - 1 ? m : N - 1;
-}
-
-// The checks fmcmc_summary_dev makes of its window, for both entries; every one comes before the first device call.
-int check_window(const char* who, const void* samples, const void* cols, const void* work, const void* out, int64_t nchains,
-                 int32_t k, int64_t S, int64_t row0, int64_t N, int32_t p) {
-  if (!samples || !cols || !work || !out) return fail(FMCMC_ERR_ARG, "%s: null argument", who);
-  if (nchains < 1) return fail(FMCMC_ERR_ARG, "%s: nchains = %lld, need at least one chain", who, (long long)nchains);
-  if (k < 1) return fail(FMCMC_ERR_ARG, "%s: k = %d, need at least one parameter", who, (int)k);
-  if (p < 1) return fail(FMCMC_ERR_ARG, "%s: p = %d, need at least one column", who, (int)p);
-  if (N < 3) return fail(FMCMC_ERR_ARG, "%s: a window of N = %lld rows is too short (3 are needed)", who, (long long)N);
-  if (row0 < 0 || row0 + N > S)
-    return fail(FMCMC_ERR_ARG, "%s: the window [%lld, %lld) is outside the %lld rows of a chain", who, (long long)row0,
-                (long long)(row0 + N), (long long)S);
-  if (ar_order_max(N) > MAXM)
-    return fail(FMCMC_ERR_UNSUPPORTED, "%s: N = %lld rows per chain; supported are N < 3162278 (the limit of fmcmc_summary_dev)",
-                who, (long long)N);
-  if (nchains > 0x7fffffffLL / p)
-    return fail(FMCMC_ERR_UNSUPPORTED, "%s: %lld chains x %d columns exceed one launch", who, (long long)nchains, (int)p);
-  return FMCMC_OK;
-}
-
-template <typename Kernel>
-int allow_lds(const char* who, Kernel kernel, size_t lds) {
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-      hipSuccess)
-    return fail(FMCMC_ERR_DEVICE, "%s: %zu bytes of LDS refused", who, lds);
-  return FMCMC_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -369,12 +265,7 @@ int fmcmc_raftery_dev(const double* samples, int64_t nchains, int32_t k, int64_t
   if (!(q >= 0.0 && q <= 1.0)) return fail(FMCMC_ERR_ARG, "%s: q = %g is outside [0, 1]", who, q);
   if (nj < 1 || nj > MAXNJ) return fail(FMCMC_ERR_ARG, "%s: nj = %d outside [1, %d]", who, (int)nj, MAXNJ);
   if (j0 < 1 || j0 > 0x7fffffffLL) return fail(FMCMC_ERR_ARG, "%s: j0 = %lld, the thinnings start at 1", who, (long long)j0);
-  // R's quantile type 7 on the N rows of one series: index = 1 + (N - 1) q, the order statistics floor and ceil of it (1-based)
-  const double index = 1.0 + (double)(N - 1) * q;
-  const double flo = floor(index);
-  long long lo = (long long)flo - 1, hi = (long long)ceil(index) - 1;
-  lo = lo < 0 ? 0 : (lo > N - 1 ? N - 1 : lo);
-  hi = hi < 0 ? 0 : (hi > N - 1 ? N - 1 : hi);
+  const Type7 r = type7_ranks(N, q);                 // on the N rows of one series
   hipStream_t st = (hipStream_t)hip_stream;
   const long long series = nchains * (long long)p;
   const int staged = N <= LDS_ROWS;
@@ -382,7 +273,7 @@ int fmcmc_raftery_dev(const double* samples, int64_t nchains, int32_t k, int64_t
   rc = allow_lds(who, raftery_kernel, lds);
   if (rc != FMCMC_OK) return rc;
   hipLaunchKernelGGL(raftery_kernel, dim3((unsigned)series), dim3(OT), lds, st, samples, (long long)S, (int)k, (long long)row0,
-                     (long long)N, cols, (int)p, (unsigned int)lo, (unsigned int)hi, (int)(index > flo), index - flo,
+                     (long long)N, cols, (int)p, (unsigned int)r.lo, (unsigned int)r.hi, r.between, r.h,
                      (long long)j0, (int)nj, staged, reinterpret_cast<unsigned long long*>(work), (long long)((N + 63) / 64),
                      out, reinterpret_cast<long long*>(out + series * HEAD));
   const hipError_t e = hipGetLastError();

@@ -11,46 +11,21 @@
 //   5. summary_cvm_kernel      coda::heidel.diag: stages 1-2 on the S0 window and on every candidate tail, then one workgroup
 //                              per (series, candidate) scans the centred tail and sums the squares of its Brownian bridge.
 // Every sum has a fixed shape, so the results do not depend on the launch.  Nothing here writes `samples`.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <math.h>
-#include <stdio.h>
-#include <stdarg.h>
-
-#include "../../include/fmcmc_amd.h"
-#include "../../include/fmh_detmath.h"
-
-extern "C" void fmcmc_set_error_text_(const char* text);   // mh_engine.hip: the buffer behind fmcmc_last_error()
+#include "diag_common.hpp"
 
 namespace {
 
-constexpr int MAXM = 64;            // largest AR order (coda: floor(10 log10 N)); N < 10^6.5
 constexpr int ACS = 72;             // doubles per series in work: r[0..64], 65 mean, 66 residual sd of x ~ 1 + t, 67 non-finite count
 constexpr int SLOT_MEAN = 65, SLOT_RSD = 66, SLOT_NF = 67;
 constexpr int ST = 512;             // threads of the series kernel
 constexpr int SW = ST / 64;
-constexpr int LDS_ROWS = 19456;     // rows of a series staged in LDS at once ((19456 + 72) rows + the reduction scratch < 160 KB)
-constexpr int RED = 68;             // reduction scratch per wave
+constexpr int RED = 68;             // reduction scratch per wave ((LDS_ROWS + 72) rows of a tile + SW of these < 160 KB)
 constexpr int LG = 8;               // lags per group of the product loop
 constexpr int PAD = MAXM + LG;      // zero rows behind a tile
 constexpr int MAXPROBS = 16;
 constexpr int HT = 256;             // threads of the histogram kernel
 constexpr int HP = 4;               // 16-byte loads in flight per thread of the histogram kernel
 constexpr int TILE = 2 * HP * HT;   // rows of one chain a histogram block takes per step
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  fmcmc_set_error_text_(buf);
-  return code;
-}
-
-// (a pair is 8-byte aligned only: a window starts at any row of a history whose row stride may be odd; gelman.hip)
-typedef double sd2_t __attribute__((ext_vector_type(2), aligned(8)));
 
 __device__ __forceinline__ double wave_sum(double v) {   // butterfly: the same value, formed in the same order, in every lane
 #pragma unroll
@@ -92,6 +67,8 @@ __global__ __launch_bounds__(ST) void summary_series_kernel(const double* __rest
 
   // mean (and the count of non-finite values); a short series is staged on the way
   double s = 0.0, nf = 0.0;
+  // (written out, not walk_pairs of diag_common.hpp: through the template the same operations compile to another block layout
+  //  of this loop, which measured 0.05 ms = 1 % more at 512 x 50 x 5000)
   constexpr int LU = 8;                        // pairs in flight per thread: the loads of a batch are issued back to back
   for (long long base = 0; base < N; base += 2LL * LU * ST) {
     double a[LU], b[LU];
@@ -100,7 +77,7 @@ __global__ __launch_bounds__(ST) void summary_series_kernel(const double* __rest
       const long long i = base + 2LL * (u * ST + tid);
       a[u] = 0.0; b[u] = 0.0;
       if (i + 1 < N) {
-        const sd2_t v = *reinterpret_cast<const sd2_t*>(x + i);
+        const dpair_t v = *reinterpret_cast<const dpair_t*>(x + i);
         a[u] = v[0]; b[u] = v[1];
       } else if (i < N) {
         a[u] = x[i];
@@ -285,14 +262,6 @@ __global__ __launch_bounds__(256) void summary_pool_kernel(const double* __restr
 // arrival order of the atomic adds nor ties matter.
 struct Ranks { long long lo[MAXPROBS], hi[MAXPROBS]; };
 
-__device__ __forceinline__ unsigned long long key_of(double x) {      // order-preserving: x < y <=> key(x) < key(y)
-  const unsigned long long u = fmh_d2u(x);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double value_of(unsigned long long kx) {
-  return fmh_u2d((kx >> 63) ? (kx & 0x7fffffffffffffffull) : ~kx);
-}
-
 // state per target: prefix, rank, leader (index within the column); then the histograms [T][256]
 __global__ __launch_bounds__(256) void select_init_kernel(unsigned long long* __restrict__ state, unsigned long long* __restrict__ hist,
                                                           int nprobs, Ranks ranks) {
@@ -324,7 +293,6 @@ __global__ __launch_bounds__(HT) void select_hist_kernel(const double* __restric
   for (int e = tid; e < nt * 256; e += HT) (&s_h[0][0])[e] = 0u;
   __syncthreads();
   const int nlead = s_nlead;
-  const int shift = 56 - 8 * pass;
   const long long tiles_per_chain = (N + TILE - 1) / TILE, total = C * tiles_per_chain;
   const double* __restrict__ colbase = samples + (long long)cols[j] * S + row0;
   for (long long tile = blockIdx.x; tile < total; tile += gridDim.x) {
@@ -337,7 +305,7 @@ __global__ __launch_bounds__(HT) void select_hist_kernel(const double* __restric
       const long long r = r0 + u * (2 * HT) + 2 * tid;
       ok[2 * u] = r < N; ok[2 * u + 1] = r + 1 < N;
       if (ok[2 * u + 1]) {
-        const sd2_t q = *reinterpret_cast<const sd2_t*>(x + r);
+        const dpair_t q = *reinterpret_cast<const dpair_t*>(x + r);
         v[2 * u] = q[0]; v[2 * u + 1] = q[1];
       } else {
         v[2 * u] = ok[2 * u] ? x[r] : 0.0; v[2 * u + 1] = 0.0;
@@ -347,8 +315,8 @@ __global__ __launch_bounds__(HT) void select_hist_kernel(const double* __restric
     for (int u = 0; u < 2 * HP; u++) {
       if (!ok[u]) continue;
       const unsigned long long kx = key_of(v[u]);
-      const unsigned long long high = (pass == 0) ? 0ull : (kx >> (shift + 8));
-      const unsigned int digit = (unsigned int)(kx >> shift) & 255u;
+      const unsigned long long high = radix_high(kx, pass);
+      const unsigned int digit = radix_digit(kx, pass);
       for (int g = 0; g < nlead; g++)
         if (high == s_prefix[g]) atomicAdd(&s_h[s_lead[g]][digit], 1u);
     }
@@ -487,20 +455,14 @@ __global__ __launch_bounds__(ST) void summary_cvm_kernel(const double* __restric
   if (tid == 0) q_out[(long long)s * nseries + series] = q;
 }
 
-long long ar_order_max(long long N) {
-  const long long m = (long long)floor(10.0 * log10((double)N));
-  return m < N - 1 ? m : N - 1;
-}
-
 // Stages 1 and 2 for the window [row0, row0 + N) of every series: acov [series][ACS], stats [series][4].
 int launch_series_stats(const char* who, hipStream_t st, const double* samples, long long S, int k, long long row0, long long N,
                         const int* cols, int p, long long series, double* acov, double* stats) {
   const int M = (int)ar_order_max(N);
   const int tile_rows = (int)(N < LDS_ROWS ? N : LDS_ROWS);
   const size_t lds = (size_t)(tile_rows + PAD + SW * RED) * sizeof(double);
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(summary_series_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)lds) != hipSuccess)
-    return fail(FMCMC_ERR_DEVICE, "%s: %zu bytes of LDS refused", who, lds);
+  const int rc = allow_lds(who, summary_series_kernel, lds);
+  if (rc != FMCMC_OK) return rc;
   hipLaunchKernelGGL(summary_series_kernel, dim3((unsigned)series), dim3(ST), lds, st, samples, S, k, row0, N, cols, p, M,
                      tile_rows, acov);
   hipLaunchKernelGGL(summary_ar_kernel, dim3((unsigned)((series + 3) / 4)), dim3(256), 0, st, acov, series, N, M, stats);
@@ -525,27 +487,13 @@ int64_t fmcmc_summary_work_len(int64_t nchains, int32_t p, int32_t nprobs) {
 int fmcmc_summary_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N,
                       const int32_t* cols, int32_t p, const double* probs, int32_t nprobs, double* work,
                       double* chain_stats, double* pooled, void* hip_stream) {
-  // every argument check comes before the first device call
-  if (!samples || !cols || !work || !pooled) return fail(FMCMC_ERR_ARG, "fmcmc_summary_dev: null argument");
-  if (nchains < 1) return fail(FMCMC_ERR_ARG, "fmcmc_summary_dev: nchains = %lld, need at least one chain", (long long)nchains);
-  if (k < 1) return fail(FMCMC_ERR_ARG, "fmcmc_summary_dev: k = %d, need at least one parameter", (int)k);
-  if (p < 1) return fail(FMCMC_ERR_ARG, "fmcmc_summary_dev: p = %d, need at least one column", (int)p);
-  if (N < 3) return fail(FMCMC_ERR_ARG, "fmcmc_summary_dev: a window of N = %lld rows is too short (spectrum0.ar needs 3)", (long long)N);
-  if (row0 < 0 || row0 + N > S)
-    return fail(FMCMC_ERR_ARG, "fmcmc_summary_dev: the window [%lld, %lld) is outside the %lld rows of a chain", (long long)row0,
-                (long long)(row0 + N), (long long)S);
-  if (nprobs < 0 || nprobs > MAXPROBS)
-    return fail(FMCMC_ERR_ARG, "fmcmc_summary_dev: nprobs = %d outside [0, %d]", (int)nprobs, MAXPROBS);
-  if (nprobs > 0 && !probs) return fail(FMCMC_ERR_ARG, "fmcmc_summary_dev: null argument");
+  const char* who = "fmcmc_summary_dev";
+  int rc = check_window(who, samples, cols, work, pooled, nchains, k, S, row0, N, p);
+  if (rc != FMCMC_OK) return rc;
+  if (nprobs < 0 || nprobs > MAXPROBS) return fail(FMCMC_ERR_ARG, "%s: nprobs = %d outside [0, %d]", who, (int)nprobs, MAXPROBS);
+  if (nprobs > 0 && !probs) return fail(FMCMC_ERR_ARG, "%s: null argument", who);
   for (int q = 0; q < nprobs; q++)
-    if (!(probs[q] >= 0.0 && probs[q] <= 1.0))
-      return fail(FMCMC_ERR_ARG, "fmcmc_summary_dev: probs[%d] = %g is outside [0, 1]", q, probs[q]);
-  const long long M = ar_order_max(N);
-  if (M > MAXM)
-    return fail(FMCMC_ERR_UNSUPPORTED, "fmcmc_summary_dev: N = %lld rows per chain ask for an AR order up to %lld; supported are "
-                "orders up to %d (N < 3162278)", (long long)N, M, MAXM);
-  if (nchains * (int64_t)p > 0x7fffffffLL)
-    return fail(FMCMC_ERR_UNSUPPORTED, "fmcmc_summary_dev: %lld series exceed one launch", (long long)(nchains * (int64_t)p));
+    if (!(probs[q] >= 0.0 && probs[q] <= 1.0)) return fail(FMCMC_ERR_ARG, "%s: probs[%d] = %g is outside [0, 1]", who, q, probs[q]);
 
   hipStream_t st = (hipStream_t)hip_stream;
   const long long series = nchains * (long long)p;
@@ -555,19 +503,15 @@ int fmcmc_summary_dev(const double* samples, int64_t nchains, int32_t k, int64_t
   const long long targets = (long long)p * nprobs * 2;
   unsigned long long* hist = state + 3 * targets;
 
-  const int rc = launch_series_stats("fmcmc_summary_dev", st, samples, S, k, row0, N, cols, p, series, acov, stats);
+  rc = launch_series_stats(who, st, samples, S, k, row0, N, cols, p, series, acov, stats);
   if (rc != FMCMC_OK) return rc;
   hipLaunchKernelGGL(summary_pool_kernel, dim3((unsigned)p), dim3(256), 0, st, stats, acov, (long long)nchains, (int)p,
                      (long long)N, pooled);
   if (nprobs > 0) {
-    // R's quantile type 7: index = 1 + (n - 1) prob, the order statistics floor(index) and ceil(index) (1-based)
-    Ranks ranks;
-    const long long n = nchains * (long long)N;
+    Ranks ranks;                                 // among the pooled values of a column
     for (int q = 0; q < MAXPROBS; q++) {
-      const double index = 1.0 + (double)(n - 1) * (q < nprobs ? probs[q] : 0.0);
-      long long lo = (long long)floor(index) - 1, hi = (long long)ceil(index) - 1;
-      ranks.lo[q] = lo < 0 ? 0 : (lo > n - 1 ? n - 1 : lo);
-      ranks.hi[q] = hi < 0 ? 0 : (hi > n - 1 ? n - 1 : hi);
+      const Type7 r = type7_ranks(nchains * (long long)N, q < nprobs ? probs[q] : 0.0);
+      ranks.lo[q] = r.lo; ranks.hi[q] = r.hi;
     }
     hipLaunchKernelGGL(select_init_kernel, dim3((unsigned)targets), dim3(256), 0, st, state, hist, (int)nprobs, ranks);
     const long long tiles = nchains * ((N + TILE - 1) / TILE);
@@ -582,7 +526,7 @@ int fmcmc_summary_dev(const double* samples, int64_t nchains, int32_t k, int64_t
     }
   }
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(FMCMC_ERR_DEVICE, "fmcmc_summary_dev: launch failed (%s)", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(FMCMC_ERR_DEVICE, "%s: launch failed (%s)", who, hipGetErrorString(e));
   return FMCMC_OK;
 }
 
@@ -599,43 +543,34 @@ int64_t fmcmc_heidel_out_len(int64_t nchains, int32_t p, int64_t ncand) {
 int fmcmc_heidel_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N,
                      const int32_t* cols, int32_t p, int64_t half_row, const int64_t* cand_rows, int64_t ncand, double* work,
                      double* out, void* hip_stream) {
-  // every argument check comes before the first device call
-  if (!samples || !cols || !cand_rows || !work || !out) return fail(FMCMC_ERR_ARG, "fmcmc_heidel_dev: null argument");
-  if (nchains < 1) return fail(FMCMC_ERR_ARG, "fmcmc_heidel_dev: nchains = %lld, need at least one chain", (long long)nchains);
-  if (k < 1) return fail(FMCMC_ERR_ARG, "fmcmc_heidel_dev: k = %d, need at least one parameter", (int)k);
-  if (p < 1) return fail(FMCMC_ERR_ARG, "fmcmc_heidel_dev: p = %d, need at least one column", (int)p);
-  if (ncand < 1) return fail(FMCMC_ERR_ARG, "fmcmc_heidel_dev: ncand = %lld, need at least one candidate start", (long long)ncand);
-  if (N < 3 || row0 < 0 || row0 + N > S)
-    return fail(FMCMC_ERR_ARG, "fmcmc_heidel_dev: the window [%lld, %lld) is shorter than 3 rows or outside the %lld rows of a chain",
-                (long long)row0, (long long)(row0 + N), (long long)S);
+  const char* who = "fmcmc_heidel_dev";
+  int rc = check_window(who, samples, cols, work, out, nchains, k, S, row0, N, p);
+  if (rc != FMCMC_OK) return rc;
+  if (!cand_rows) return fail(FMCMC_ERR_ARG, "%s: null argument", who);
+  if (ncand < 1) return fail(FMCMC_ERR_ARG, "%s: ncand = %lld, need at least one candidate start", who, (long long)ncand);
+  if (ncand > 0x7fffffffLL) return fail(FMCMC_ERR_UNSUPPORTED, "%s: %lld candidates exceed what one call takes", who, (long long)ncand);
   if (half_row < 0 || N - half_row < 3)
-    return fail(FMCMC_ERR_ARG, "fmcmc_heidel_dev: half_row = %lld leaves %lld of the %lld rows (spectrum0.ar needs 3)",
+    return fail(FMCMC_ERR_ARG, "%s: half_row = %lld leaves %lld of the %lld rows (spectrum0.ar needs 3)", who,
                 (long long)half_row, (long long)(N - half_row), (long long)N);
   for (int64_t s = 0; s < ncand; s++) {
     if (cand_rows[s] < 0 || N - cand_rows[s] < 3)
-      return fail(FMCMC_ERR_ARG, "fmcmc_heidel_dev: cand_rows[%lld] = %lld leaves %lld of the %lld rows (spectrum0.ar needs 3)",
+      return fail(FMCMC_ERR_ARG, "%s: cand_rows[%lld] = %lld leaves %lld of the %lld rows (spectrum0.ar needs 3)", who,
                   (long long)s, (long long)cand_rows[s], (long long)(N - cand_rows[s]), (long long)N);
     if (s > 0 && cand_rows[s] < cand_rows[s - 1])
-      return fail(FMCMC_ERR_ARG, "fmcmc_heidel_dev: cand_rows must ascend (cand_rows[%lld] = %lld after %lld)", (long long)s,
+      return fail(FMCMC_ERR_ARG, "%s: cand_rows must ascend (cand_rows[%lld] = %lld after %lld)", who, (long long)s,
                   (long long)cand_rows[s], (long long)cand_rows[s - 1]);
   }
   if (half_row < cand_rows[0])
-    return fail(FMCMC_ERR_ARG, "fmcmc_heidel_dev: half_row = %lld lies before cand_rows[0] = %lld (the S0 window must be part of "
-                "the longest tail, whose non-finite count covers it)", (long long)half_row, (long long)cand_rows[0]);
-  if (ar_order_max(N) > MAXM)
-    return fail(FMCMC_ERR_UNSUPPORTED, "fmcmc_heidel_dev: N = %lld rows per chain ask for an AR order up to %lld; supported are "
-                "orders up to %d (N < 3162278)", (long long)N, ar_order_max(N), MAXM);
-  if (nchains > 0x7fffffffLL / p || ncand > 0x7fffffffLL)
-    return fail(FMCMC_ERR_UNSUPPORTED, "fmcmc_heidel_dev: %lld chains x %d columns x %lld candidates exceed what one call takes",
-                (long long)nchains, (int)p, (long long)ncand);
+    return fail(FMCMC_ERR_ARG, "%s: half_row = %lld lies before cand_rows[0] = %lld (the S0 window must be part of "
+                "the longest tail, whose non-finite count covers it)", who, (long long)half_row, (long long)cand_rows[0]);
 
   hipStream_t st = (hipStream_t)hip_stream;
   const long long series = nchains * (long long)p;
   double* q_out = out + (1 + ncand) * series * 4;
   // the S0 window, then the tails from the shortest to the longest: `work` is left holding the series work of cand_rows[0]
-  int rc = launch_series_stats("fmcmc_heidel_dev", st, samples, S, k, row0 + half_row, N - half_row, cols, p, series, work, out);
+  rc = launch_series_stats(who, st, samples, S, k, row0 + half_row, N - half_row, cols, p, series, work, out);
   for (int64_t s = ncand - 1; s >= 0 && rc == FMCMC_OK; s--)
-    rc = launch_series_stats("fmcmc_heidel_dev", st, samples, S, k, row0 + cand_rows[s], N - cand_rows[s], cols, p, series, work,
+    rc = launch_series_stats(who, st, samples, S, k, row0 + cand_rows[s], N - cand_rows[s], cols, p, series, work,
                              out + (1 + s) * series * 4);
   if (rc != FMCMC_OK) return rc;
   for (int64_t s0 = 0; s0 < ncand; s0 += CVM_CANDS) {
@@ -647,7 +582,7 @@ int fmcmc_heidel_dev(const double* samples, int64_t nchains, int32_t k, int64_t 
                        q_out + s0 * series);
   }
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(FMCMC_ERR_DEVICE, "fmcmc_heidel_dev: launch failed (%s)", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(FMCMC_ERR_DEVICE, "%s: launch failed (%s)", who, hipGetErrorString(e));
   return FMCMC_OK;
 }
 

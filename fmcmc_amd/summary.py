@@ -70,6 +70,19 @@ def _fmt_table(rownames, colnames, matrix, fmt=_fmt_column):
     return "\n".join(lines)
 
 
+def _fmt_block(rownames, heads, cols):
+    """coda's diagnostic tables: left-aligned columns under two-line headings."""
+    cols = [list(h) + c for h, c in zip(heads, cols)]
+    rows = ["", ""] + list(rownames)
+    widths = [max(len(v) for v in col) for col in [rows] + cols]
+    return "\n".join(" ".join(col[i].ljust(w) for col, w in zip([rows] + cols, widths)) for i in range(len(rows)))
+
+
+def _par_names(index):
+    """The names of unnamed parameters: par1, par2, ... for the 0-based `index`."""
+    return ["par%d" % (j + 1) for j in index]
+
+
 class McmcSummary:
     """coda's summary.mcmc object: statistics [p][4] (Mean, SD, Naive SE, Time-series SE), quantiles [p][nprobs], and
     per_chain (mean, sd, tsse, ess, order; each [nchain][p]) -- which chains mix badly is what the pooled table cannot say."""
@@ -132,23 +145,29 @@ def _columns(dc, cols):
 
 
 def _names(dc, cols):
-    return [dc.names[c] for c in cols] if dc.names is not None else ["par%d" % (c + 1) for c in cols]
+    return [dc.names[c] for c in cols] if dc.names is not None else _par_names(cols)
 
 
-def _device_samples(dc):
-    """What every enqueue_* starts with: (library, samples [C][k][S], (C, k, S)); the caller checks its own arguments next."""
-    _single_process()
-    return abi.lib(), dc._samples, tuple(int(v) for v in dc._samples.shape)
-
-
-def _device_columns(dc, cols):
-    """... and goes on with: (device, columns, their device copy) of samples that the library can read."""
+def _open(dc, cols, verb):
+    """What every enqueue_* starts with: the library L, the samples smp [C][k][S] that it can read, Cn, k, cap = S, their device
+    dev, the columns cols, their device copy cols_d and their number p; the caller checks its own arguments next."""
     import torch
+    _single_process()
     smp = dc._samples
+    Cn, k, cap = (int(v) for v in smp.shape)
+    if Cn < 1:
+        raise ValueError("no chains to %s" % verb)
     if smp.dtype != torch.float64 or not smp.is_contiguous():
         raise ValueError("samples must be a contiguous float64 [C][k][S] tensor")
     cols = _columns(dc, cols)
-    return smp.device, cols, torch.as_tensor(cols).to(smp.device)
+    return SimpleNamespace(L=abi.lib(), smp=smp, Cn=Cn, k=k, cap=cap, dev=smp.device, cols=cols,
+                           cols_d=torch.as_tensor(cols).to(smp.device), p=int(cols.size))
+
+
+def _doubles(o, n):
+    """n doubles (at least one) on the device of what _open returned."""
+    import torch
+    return torch.empty(max(int(n), 1), dtype=torch.float64, device=o.dev)
 
 
 def _stream(dev):
@@ -156,7 +175,11 @@ def _stream(dev):
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
-def _raise_for(rc):
+def _windowed(o, entry, row0, N, *rest):
+    """The one C call of an enqueue_*: entry(samples, C, k, S, row0, N, cols, p, *rest, stream) on the current torch stream."""
+    import torch
+    with torch.cuda.device(o.dev):
+        rc = entry(o.smp.data_ptr(), o.Cn, o.k, o.cap, int(row0), int(N), o.cols_d.data_ptr(), o.p, *rest, _stream(o.dev))
     if rc != abi.OK:
         raise (NotImplementedError if rc == abi.ERR_UNSUPPORTED else ValueError if rc == abi.ERR_ARG else RuntimeError)(
             abi.last_error())
@@ -165,24 +188,16 @@ def _raise_for(rc):
 def enqueue_window(dc, row0, N, cols, probs=(), want_chains=True):
     """Enqueues one fmcmc_summary_dev call on the window [row0, row0 + N) of the kept rows of `dc` (current torch stream).
     Returns the device tensors (pooled, chain_stats or None, work) and the columns; nothing is synchronised."""
-    import torch
-    L, smp, (Cn, k, cap) = _device_samples(dc)
-    if Cn < 1:
-        raise ValueError("no chains to summarise")
+    o = _open(dc, cols, "summarise")
     if row0 < 0 or row0 + N > dc.nrows:
         raise ValueError("the window [%d, %d) is outside the %d kept rows" % (row0, row0 + N, dc.nrows))
-    dev, cols, cols_d = _device_columns(dc, cols)
-    p, nprobs = int(cols.size), len(probs)
     probs_h = np.ascontiguousarray(probs, dtype=np.float64)
-    work = torch.empty(max(int(L.fmcmc_summary_work_len(Cn, p, nprobs)), 1), dtype=torch.float64, device=dev)
-    pooled = torch.empty(int(L.fmcmc_summary_pooled_len(p, nprobs)), dtype=torch.float64, device=dev)
-    chain_stats = torch.empty((Cn, p, 4), dtype=torch.float64, device=dev) if want_chains else None
-    with torch.cuda.device(dev):
-        rc = L.fmcmc_summary_dev(smp.data_ptr(), Cn, k, cap, int(row0), int(N), cols_d.data_ptr(), p,
-                                 probs_h.ctypes.data_as(C.POINTER(C.c_double)), nprobs, work.data_ptr(),
-                                 chain_stats.data_ptr() if want_chains else None, pooled.data_ptr(), _stream(dev))
-    _raise_for(rc)
-    return pooled, chain_stats, work, cols
+    work = _doubles(o, o.L.fmcmc_summary_work_len(o.Cn, o.p, len(probs)))
+    pooled = _doubles(o, o.L.fmcmc_summary_pooled_len(o.p, len(probs)))
+    chain_stats = _doubles(o, o.Cn * o.p * 4).view(o.Cn, o.p, 4) if want_chains else None
+    _windowed(o, o.L.fmcmc_summary_dev, row0, N, probs_h.ctypes.data_as(C.POINTER(C.c_double)), len(probs), work.data_ptr(),
+              chain_stats.data_ptr() if want_chains else None, pooled.data_ptr())
+    return pooled, chain_stats, work, o.cols
 
 
 # per series at the head of `work` (csrc/summary.hip: ACS, SLOT_*): r_0 .. r_64 (divisor N; exactly 0 above the window's largest
@@ -204,10 +219,7 @@ def window_stats(dc, row0, N, cols, probs=(), want_chains=True):
     cs = chain_stats.cpu().numpy() if want_chains else None
     ps = ph[:5 * p].reshape(p, 5)
     os_ = ph[5 * p:].reshape(p, nprobs, 2)
-    nbad = int(ps[:, 4].sum())
-    if nbad:
-        raise ValueError("%d non-finite value(s) among the rows to summarise (columns %s)"
-                         % (nbad, [int(c) for c, b in zip(cols, ps[:, 4]) if b]))
+    _raise_non_finite(ps[None, :, 4], cols, "summarise")
     return ps, os_, cs
 
 
@@ -298,7 +310,7 @@ class HeidelDiag:
         self.table = np.asarray(table, dtype=np.float64)
         self.cvm = np.asarray(cvm, dtype=np.float64)
         self.candidates = np.asarray(candidates, dtype=np.float64)
-        self.varnames = list(varnames) if varnames is not None else ["par%d" % (j + 1) for j in range(self.table.shape[1])]
+        self.varnames = list(varnames) if varnames is not None else _par_names(range(self.table.shape[1]))
         self.eps, self.alpha = float(eps), float(pvalue)
 
     stest = property(lambda self: self.table[:, :, 0])
@@ -308,13 +320,6 @@ class HeidelDiag:
     mean = property(lambda self: self.table[:, :, 4])
     halfwidth = property(lambda self: self.table[:, :, 5])
 
-    @staticmethod
-    def _block(rownames, heads, cols):
-        cols = [list(h) + c for h, c in zip(heads, cols)]
-        rows = ["", ""] + list(rownames)
-        widths = [max(len(v) for v in col) for col in [rows] + cols]
-        return "\n".join(" ".join(col[i].ljust(w) for col, w in zip([rows] + cols, widths)) for i in range(len(rows)))
-
     def __str__(self):
         word = lambda v: "NA" if np.isnan(v) else ("passed" if v else "failed")
         num = lambda v: "NA" if np.isnan(v) else "%.3g" % v
@@ -323,11 +328,11 @@ class HeidelDiag:
             if len(self.table) > 1:
                 out += ["[[%d]]" % (c + 1)]
             out += [" " * 35,
-                    self._block(self.varnames, (("Stationarity", "test"), ("start", "iteration"), ("p-value", "")),
-                                ([word(v) for v in t[:, 0]], [num(v) for v in t[:, 1]], [num(v) for v in t[:, 2]])),
+                    _fmt_block(self.varnames, (("Stationarity", "test"), ("start", "iteration"), ("p-value", "")),
+                               ([word(v) for v in t[:, 0]], [num(v) for v in t[:, 1]], [num(v) for v in t[:, 2]])),
                     " " * 30,
-                    self._block(self.varnames, (("Halfwidth", "test"), ("Mean", ""), ("Halfwidth", "")),
-                                ([word(v) for v in t[:, 3]], [num(v) for v in t[:, 4]], [num(v) for v in t[:, 5]])), ""]
+                    _fmt_block(self.varnames, (("Halfwidth", "test"), ("Mean", ""), ("Halfwidth", "")),
+                               ([word(v) for v in t[:, 3]], [num(v) for v in t[:, 4]], [num(v) for v in t[:, 5]])), ""]
         return "\n".join(out)
 
     def __repr__(self):
@@ -365,21 +370,13 @@ def heidel_finish(n, mean, spec0, Q, S0, starts, eps=0.1, pvalue=0.05, varnames=
 def enqueue_heidel(dc, half_row, cand_rows, cols):
     """Enqueues one fmcmc_heidel_dev call on the kept rows of `dc` (current torch stream).  Returns the device tensors
     (out, work) and the columns; nothing is synchronised."""
-    import torch
-    L, smp, (Cn, k, cap) = _device_samples(dc)
-    if Cn < 1:
-        raise ValueError("no chains to test")
-    dev, cols, cols_d = _device_columns(dc, cols)
-    p = int(cols.size)
+    o = _open(dc, cols, "test")
     cand = np.ascontiguousarray(cand_rows, dtype=np.int64)
-    work = torch.empty(max(int(L.fmcmc_heidel_work_len(Cn, p, cand.size)), 1), dtype=torch.float64, device=dev)
-    out = torch.empty(max(int(L.fmcmc_heidel_out_len(Cn, p, cand.size)), 1), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.fmcmc_heidel_dev(smp.data_ptr(), Cn, k, cap, 0, int(dc.nrows), cols_d.data_ptr(), p, int(half_row),
-                                cand.ctypes.data_as(C.POINTER(C.c_int64)), int(cand.size), work.data_ptr(), out.data_ptr(),
-                                _stream(dev))
-    _raise_for(rc)
-    return out, work, cols
+    work = _doubles(o, o.L.fmcmc_heidel_work_len(o.Cn, o.p, cand.size))
+    out = _doubles(o, o.L.fmcmc_heidel_out_len(o.Cn, o.p, cand.size))
+    _windowed(o, o.L.fmcmc_heidel_dev, 0, dc.nrows, int(half_row), cand.ctypes.data_as(C.POINTER(C.c_int64)), int(cand.size),
+              work.data_ptr(), out.data_ptr())
+    return out, work, o.cols
 
 
 def heidel(x, eps=0.1, pvalue=0.05, cols=None):
@@ -391,10 +388,8 @@ def heidel(x, eps=0.1, pvalue=0.05, cols=None):
     N, Cn, ncand = int(dc.nrows), int(dc._samples.shape[0]), int(rows.size)
     out, work, cols = enqueue_heidel(dc, half_row, rows, cols)
     p = int(cols.size)
-    nbad = _series_work(work, Cn * p)[:, WORK_NON_FINITE].reshape(Cn, p).sum(0).cpu().numpy()
-    if nbad.sum():
-        raise ValueError("%d non-finite value(s) among the rows to test (columns %s)"
-                         % (int(nbad.sum()), [int(c) for c, b in zip(cols, nbad) if b]))
+    _raise_non_finite(_series_work(work, Cn * p)[:, WORK_NON_FINITE].reshape(Cn, p).sum(0, keepdim=True).cpu().numpy(), cols,
+                      "test")
     oh = out.cpu().numpy()
     stats = oh[:(1 + ncand) * Cn * p * 4].reshape(1 + ncand, Cn, p, 4)
     Q = oh[(1 + ncand) * Cn * p * 4:].reshape(ncand, Cn, p)
@@ -528,7 +523,7 @@ class RafteryDiag:
         self.kthin = np.asarray(kthin, dtype=np.float64)
         self.nmin, self.nrows = int(nmin), int(nrows)
         self.q, self.r, self.s, self.converge_eps = float(q), float(r), float(s), float(converge_eps)
-        self.varnames = list(varnames) if varnames is not None else ["par%d" % (j + 1) for j in range(self.table.shape[1])]
+        self.varnames = list(varnames) if varnames is not None else _par_names(range(self.table.shape[1]))
         self.u, self.alpha, self.beta = u, alpha, beta
 
     M = property(lambda self: self.table[:, :, 0])
@@ -545,10 +540,10 @@ class RafteryDiag:
             if self.nmin > self.nrows:
                 out += ["You need a sample size of at least %d with these values of q, r and s" % self.nmin, ""]
                 continue
-            out += [HeidelDiag._block(self.varnames, (("Burn-in", "(M)"), ("Total", "(N)"), ("Lower bound", "(Nmin)"),
-                                                      ("Dependence", "factor (I)")),
-                                      ([whole(v) for v in t[:, 0]], [whole(v) for v in t[:, 1]], [whole(v) for v in t[:, 2]],
-                                       ["NA" if np.isnan(v) else "%.3g" % v for v in t[:, 3]])), ""]
+            out += [_fmt_block(self.varnames, (("Burn-in", "(M)"), ("Total", "(N)"), ("Lower bound", "(Nmin)"),
+                                               ("Dependence", "factor (I)")),
+                               ([whole(v) for v in t[:, 0]], [whole(v) for v in t[:, 1]], [whole(v) for v in t[:, 2]],
+                                ["NA" if np.isnan(v) else "%.3g" % v for v in t[:, 3]])), ""]
         return "\n".join(out)
 
     def __repr__(self):
@@ -565,7 +560,7 @@ def raftery_table(fin, shape):
 
 
 def _raise_non_finite(nbad, cols, what):
-    """nbad [C][p] counts of non-finite values per series."""
+    """nbad [C][p] counts of non-finite values per series: the one error every diagnostic raises for them."""
     per_col = np.asarray(nbad).sum(axis=0)
     if per_col.sum():
         raise ValueError("%d non-finite value(s) among the rows to %s (columns %s)"
@@ -576,21 +571,13 @@ def enqueue_chain_order(dc, ranks, cols):
     """Enqueues one fmcmc_chain_order_dev call on the kept rows of `dc` (current torch stream): the values at the 0-based
     `ranks` of every (chain, column) series.  Returns the device tensors (out [C][p][nranks], non-finite counts [C][p]) and the
     columns; nothing is synchronised."""
-    import torch
-    L, smp, (Cn, k, cap) = _device_samples(dc)
-    if Cn < 1:
-        raise ValueError("no chains to order")
-    dev, cols, cols_d = _device_columns(dc, cols)
-    p = int(cols.size)
+    o = _open(dc, cols, "order")
     ranks = np.ascontiguousarray(ranks, dtype=np.int64).ravel()
-    work = torch.empty(max(int(L.fmcmc_chain_order_work_len(Cn, p, ranks.size)), 1), dtype=torch.float64, device=dev)
-    out = torch.empty((Cn, p, max(int(ranks.size), 1)), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.fmcmc_chain_order_dev(smp.data_ptr(), Cn, k, cap, 0, int(dc.nrows), cols_d.data_ptr(), p,
-                                     ranks.ctypes.data_as(C.POINTER(C.c_int64)), int(ranks.size), work.data_ptr(), out.data_ptr(),
-                                     _stream(dev))
-    _raise_for(rc)
-    return out, work[:Cn * p].view(Cn, p), cols
+    work = _doubles(o, o.L.fmcmc_chain_order_work_len(o.Cn, o.p, ranks.size))
+    out = _doubles(o, o.Cn * o.p * max(int(ranks.size), 1)).view(o.Cn, o.p, -1)
+    _windowed(o, o.L.fmcmc_chain_order_dev, 0, dc.nrows, ranks.ctypes.data_as(C.POINTER(C.c_int64)), int(ranks.size),
+              work.data_ptr(), out.data_ptr())
+    return out, work[:o.Cn * o.p].view(o.Cn, o.p), o.cols
 
 
 def chain_quantiles(x, probs=DEFAULT_QUANTILES, cols=None):
@@ -616,20 +603,13 @@ def enqueue_raftery(dc, q, j0, nj, cols):
     Returns the device tensors (head [C][p][4] = u, x_(lo), x_(hi), non-finite count; counts [C][p][nj][10] int64; work) and the
     columns; nothing is synchronised."""
     import torch
-    L, smp, (Cn, k, cap) = _device_samples(dc)
-    if Cn < 1:
-        raise ValueError("no chains to test")
-    dev, cols, cols_d = _device_columns(dc, cols)
-    p, n = int(cols.size), int(dc.nrows)
-    work = torch.empty(max(int(L.fmcmc_raftery_work_len(Cn, p, n)), 1), dtype=torch.float64, device=dev)
-    out = torch.empty(max(int(L.fmcmc_raftery_out_len(Cn, p, nj)), 1), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.fmcmc_raftery_dev(smp.data_ptr(), Cn, k, cap, 0, n, cols_d.data_ptr(), p, float(q), int(j0), int(nj),
-                                 work.data_ptr(), out.data_ptr(), _stream(dev))
-    _raise_for(rc)
-    series = Cn * p
-    return (out[:series * 4].view(Cn, p, 4), out[series * 4:series * (4 + 10 * nj)].view(torch.int64).view(Cn, p, nj, 10),
-            work, cols)
+    o = _open(dc, cols, "test")
+    work = _doubles(o, o.L.fmcmc_raftery_work_len(o.Cn, o.p, int(dc.nrows)))
+    out = _doubles(o, o.L.fmcmc_raftery_out_len(o.Cn, o.p, nj))
+    _windowed(o, o.L.fmcmc_raftery_dev, 0, dc.nrows, float(q), int(j0), int(nj), work.data_ptr(), out.data_ptr())
+    series = o.Cn * o.p
+    return (out[:series * 4].view(o.Cn, o.p, 4),
+            out[series * 4:series * (4 + 10 * nj)].view(torch.int64).view(o.Cn, o.p, nj, 10), work, o.cols)
 
 
 def raftery_diag(x, q=0.025, r=0.005, s=0.95, converge_eps=0.001, cols=None):
@@ -689,7 +669,7 @@ class GelmanDiag:
     def __init__(self, psrf, mpsrf, varnames=None, start=None, end=None, confidence=0.95):
         self.psrf = np.asarray(psrf, dtype=np.float64).reshape(-1, 2)
         self.mpsrf = None if mpsrf is None else float(mpsrf)
-        self.varnames = list(varnames) if varnames is not None else ["par%d" % (j + 1) for j in range(self.psrf.shape[0])]
+        self.varnames = list(varnames) if varnames is not None else _par_names(range(self.psrf.shape[0]))
         self.start, self.end, self.confidence = start, end, float(confidence)
 
     def __str__(self):
@@ -779,19 +759,16 @@ def gelman_partial_dev(base, Cn, k, stride, row0, N, cols_d, center, work, parti
 def enqueue_gelman(dc, row0, N, cols):
     """Enqueues one fmcmc_gelman_partial_dev call on the window [row0, row0 + N) of the kept rows of `dc` (current torch
     stream), centred on the window's first row of chain 0.  Returns the device tensors (partial, work) and the columns."""
-    import torch
-    L, smp, (Cn, k, cap) = _device_samples(dc)
+    o = _open(dc, cols, "compare")
     if row0 < 0 or N < 2 or row0 + N > dc.nrows:
         raise ValueError("the window [%d, %d) needs at least two of the %d kept rows" % (row0, row0 + N, dc.nrows))
-    dev, cols, cols_d = _device_columns(dc, cols)
-    p = int(cols.size)
-    if p > abi.MAX_K:
+    if o.p > abi.MAX_K:
         raise ValueError("at most %d columns per call" % abi.MAX_K)
-    center = smp[0, cols_d.long(), row0].contiguous()
-    partial = torch.empty(int(L.fmcmc_gelman_partial_len(p)), dtype=torch.float64, device=dev)
-    work = torch.empty(int(L.fmcmc_gelman_work_len(Cn, p)), dtype=torch.float64, device=dev)
-    gelman_partial_dev(smp, Cn, k, cap, row0, N, cols_d, center, work, partial)
-    return partial, work, cols
+    center = o.smp[0, o.cols_d.long(), row0].contiguous()
+    partial = _doubles(o, o.L.fmcmc_gelman_partial_len(o.p))
+    work = _doubles(o, o.L.fmcmc_gelman_work_len(o.Cn, o.p))
+    gelman_partial_dev(o.smp, o.Cn, o.k, o.cap, row0, N, o.cols_d, center, work, partial)
+    return partial, work, o.cols
 
 
 def gelman_diag(x, confidence=0.95, autoburnin=True, multivariate=True, cols=None):

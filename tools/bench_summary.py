@@ -50,14 +50,17 @@ def main():
                     keep_logpost=False, keep_draws=False)
         C_, k, N = (int(v) for v in dc.samples.shape)
 
-        def events():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            keep = enqueue_window(dc, 0, N, None, DEFAULT_QUANTILES)
-            e1.record()
-            e1.synchronize()
-            del keep
-            return e0.elapsed_time(e1) * 1e-3
+        def between_events(enqueue):
+            """seconds between two HIP events around what `enqueue` launches (its tensors live until the second has passed)"""
+            def run():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                keep = enqueue()
+                e1.record()
+                e1.synchronize()
+                del keep
+                return e0.elapsed_time(e1) * 1e-3
+            return run
 
         def wall(fn):
             torch.cuda.synchronize()
@@ -67,23 +70,15 @@ def main():
             return time.perf_counter() - t0
 
         best = {}
-        for name, fn in (("summary_kernels_ms", events), ("summary_wall_ms", lambda: wall(dc.summary)),
+        for name, fn in (("summary_kernels_ms", between_events(lambda: enqueue_window(dc, 0, N, None, DEFAULT_QUANTILES))),
+                         ("summary_wall_ms", lambda: wall(dc.summary)),
                          ("to_host_wall_ms", lambda: wall(dc.to_host))):
             fn()
             best[name] = round(1e3 * min(fn() for _ in range(5)), 3)
         if shape == "headline":
             _, rows, half = heidel_candidates(dc.iters)
-
-            def heidel_events():
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                keep = enqueue_heidel(dc, half, rows, None)
-                e1.record()
-                e1.synchronize()
-                del keep
-                return e0.elapsed_time(e1) * 1e-3
-
-            for name, fn in (("heidel_kernels_ms", heidel_events), ("heidel_wall_ms", lambda: wall(dc.heidel))):
+            for name, fn in (("heidel_kernels_ms", between_events(lambda: enqueue_heidel(dc, half, rows, None))),
+                             ("heidel_wall_ms", lambda: wall(dc.heidel))):
                 fn()
                 best[name] = round(1e3 * min(fn() for _ in range(5)), 3)
             host = dc.samples[:a.heidel_host_chains].cpu().numpy()
@@ -94,17 +89,6 @@ def main():
             best.update(heidel_candidates=int(rows.size), heidel_diag_host_ms_per_chain=round(1e3 * per_chain, 3),
                         heidel_host_route_ms=round(best["to_host_wall_ms"] + 1e3 * per_chain * C_, 1))
             # the raftery leg
-            def between_events(enqueue):
-                def run():
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    keep = enqueue()
-                    e1.record()
-                    e1.synchronize()
-                    del keep
-                    return e0.elapsed_time(e1) * 1e-3
-                return run
-
             ranks = S.type7_order_ranks(N, DEFAULT_QUANTILES).ravel()
             launches = []
             real = S.enqueue_raftery
