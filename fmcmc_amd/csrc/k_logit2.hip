@@ -1,13 +1,20 @@
-// k_logit2.hip -- logistic-only instantiations of mh_sweep_kernel (mh_streamed.hpp), g table in LDS: the observation-sharded form (logit_shard) and the long-data form,
-// variates from a materialised stream only (FEDONLY: what config C5 runs on)
+// k_logit2.hip -- mh_sweep_logit2<KIND> (mh_logit2.hpp): the observation-sharded logistic sweep of the normal / uniform proposal kernels,
+// owners in the shadow of the grid-wide hand-overs (config C5)
+// (one part, which only names the object: build/k_logit2.o is the logit2 part of k_streamed.hip)
+#define FMH_PARTS(X) X(logit3)
 #include "mh_tu.hpp"
-#include "mh_streamed.hpp"
+#include "mh_spec.hpp"
+#include "mh_logit2.hpp"
 
 namespace fmh {
-FMH_HIDDEN const void* k_logit_2(int cw, int kind) {
-#define LK(CWV) ((kind == 1) ? (const void*)mh_sweep_kernel<CWV, -1, 2, 1, FMCMC_FAM_LOGISTIC, 1, true> : (kind == 2) ? (const void*)mh_sweep_kernel<CWV, -1, 2, 2, FMCMC_FAM_LOGISTIC, 1, true> \
-               : (kind == 3) ? (const void*)mh_sweep_kernel<CWV, -1, 2, 3, FMCMC_FAM_LOGISTIC, 1, true> : (kind == 4) ? (const void*)mh_sweep_kernel<CWV, -1, 2, 4, FMCMC_FAM_LOGISTIC, 1, true> : nullptr)
-  return cw == 1 ? LK(1) : cw == 2 ? LK(2) : cw == 4 ? LK(4) : nullptr;
-#undef LK
+FMH_HIDDEN const void* k_logit2(int kind) {
+  return kind == FMCMC_KERNEL_NORMAL ? (const void*)mh_sweep_logit2<FMCMC_KERNEL_NORMAL>
+       : kind == FMCMC_KERNEL_NORMAL_REFLECTIVE ? (const void*)mh_sweep_logit2<FMCMC_KERNEL_NORMAL_REFLECTIVE> : nullptr;
 }
+FMH_HIDDEN size_t k_logit2_lds(int k) { return logit2_lds_bytes(k); }
+FMH_HIDDEN const void* k_logit2a(int kind) {
+  return kind == FMCMC_KERNEL_ADAPT ? (const void*)mh_sweep_logit2a<FMCMC_KERNEL_ADAPT>
+       : kind == FMCMC_KERNEL_RAM ? (const void*)mh_sweep_logit2a<FMCMC_KERNEL_RAM> : nullptr;
+}
+FMH_HIDDEN size_t k_logit2a_lds() { return logit2a_lds_bytes(); }
 }  // namespace fmh

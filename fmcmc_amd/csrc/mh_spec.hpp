@@ -1129,7 +1129,7 @@ __device__ __forceinline__ void spec_compute_logit(const SweepArgs& A, const dou
 // OPTMAX: the most observation slots a compute lane holds (x in VGPRs: OPTMAX P doubles); the launch's (even) slot count
 // A.spec_opt <= OPTMAX selects the compute loop.  FAM: the Gaussian linear model, or (round 5) the logistic one -- the g table in LDS
 // where the linear model keeps y, the closed form sum_j b_j hs_j - total - prior in the owners.
-// RING: kernel_adapt(freq = 2 .. 8) -- its own kernel (k_spec_r.hip): as one more owner inside the freq = 1 kernel it cost that
+// RING: kernel_adapt(freq = 2 .. 8) -- its own kernel (part spec_r of k_spec.hip): as one more owner inside the freq = 1 kernel it cost that
 // kernel's owner loop scalar-register spills (kernel_adapt in the latency form at n = 10,000: 2.20 -> 2.33 us per step).
 template <int P, int OPTMAX, int KIND, int FAM = FMCMC_FAM_GAUSSIAN_LINREG, bool RING = false>
 __global__ __launch_bounds__(SPEC_NT) void mh_sweep_spec(const SweepArgs A) {

@@ -1,6 +1,7 @@
-// mh_tu.hpp -- what every translation unit of libfmcmc_amd.so starts with.  The device code is split over several .hip files so
+// mh_tu.hpp -- what every translation unit of libfmcmc_amd.so starts with.  The device code is split over several objects so
 // that they compile in parallel (fmcmc_amd/build.py): mh_engine.hip holds the C-ABI, validation and launches (selection: mh_route.hpp), every
-// k_*.hip instantiates one kernel family and hands its kernels out by (run-time) shape through the look-ups of mh_kernels.hpp.
+// k_*.hip instantiates one kernel template and hands its kernels out by (run-time) shape through the look-ups of mh_kernels.hpp; a
+// template with many instantiations is one source compiled once per part of its table (mh_parts.hpp).
 // All device helpers live in anonymous namespaces: each translation unit has its own copy, nothing device-side is linked.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -45,15 +45,16 @@ def demangle(names):
     return [re.sub(r"\(anonymous namespace\)::", "", s).split("(")[0].replace("void ", "") for s in out.splitlines()]
 
 
-def _one_unit(src, extra_flags):
-    """remarks and ISA of one translation unit (the product's own flags + --cuda-device-only)"""
-    base = [B.HIPCC] + list(B.FLAGS) + list(extra_flags) + ["--cuda-device-only"]
+def _one_unit(unit, extra_flags):
+    """remarks and ISA of one translation unit of B.units() (the product's own flags + --cuda-device-only)"""
+    src, _part, obj, unit_flags = unit
+    base = [B.HIPCC] + list(B.FLAGS) + list(extra_flags) + unit_flags + ["--cuda-device-only"]
     t0 = time.time()
     err = subprocess.run(base + ["-c", "-Rpass-analysis=kernel-resource-usage", src, "-o", "/dev/null"], capture_output=True, text=True).stderr
     secs = time.time() - t0
-    asm = "/tmp/fmcmc_amd_%s.s" % os.path.splitext(os.path.basename(src))[0]
+    asm = "/tmp/fmcmc_amd_%s.s" % B.unit_name(obj)
     subprocess.run(base + ["-S", src, "-o", asm], capture_output=True, text=True)
-    return src, err, secs, asm
+    return B.unit_name(obj), err, secs, asm
 
 
 _UNITS = None
@@ -65,7 +66,7 @@ def units(extra_flags=()):
         from concurrent.futures import ThreadPoolExecutor
         t0 = time.time()
         with ThreadPoolExecutor(min(8, os.cpu_count() or 1)) as ex:
-            res = list(ex.map(lambda s_: _one_unit(s_, extra_flags), B.sources()))
+            res = list(ex.map(lambda u: _one_unit(u, extra_flags), B.units()))
         _UNITS = (res, time.time() - t0)
     return _UNITS
 
@@ -73,12 +74,12 @@ def units(extra_flags=()):
 def collect(extra_flags=()):
     rows = []
     res, wall = units(extra_flags)
-    for src, err, secs, _asm in res:
+    for unit, err, secs, _asm in res:
         cur = None
         for line in err.splitlines():
             m = re.search(r"remark: Function Name: (\S+)", line)
             if m:
-                cur = {"mangled": m.group(1), "source": os.path.basename(src)}
+                cur = {"mangled": m.group(1), "unit": unit}
                 rows.append(cur)
                 continue
             m = re.search(r"remark:\s+([A-Za-z][^:]*): (\S+) \[-Rpass", line)
@@ -87,7 +88,7 @@ def collect(extra_flags=()):
     for r, d in zip(rows, demangle([r["mangled"] for r in rows])):
         r["name"] = d
     return rows, {"wall_8_jobs": round(wall, 1), "sum_of_units": round(sum(u[2] for u in res), 1),
-                  "per_unit": {os.path.basename(u[0]): round(u[2], 1) for u in res}}
+                  "per_unit": {u[0]: round(u[2], 1) for u in res}}
 
 
 # real (noinline) device functions that carry the hot loops of a product kernel: the remark pass reports kernels only, so
@@ -101,7 +102,7 @@ DEVICE_FUNCS = [("C5 observation loop (observation-sharded)", "logit_shard<5, 2,
 def isa_functions(extra_flags=()):
     out = []
     funcs, cur = {}, None
-    for _src, _err, _secs, asm in units(extra_flags)[0]:
+    for _unit, _err, _secs, asm in units(extra_flags)[0]:
         cur = None
         for line in open(asm):
             m = re.match(r"^(_Z\w+):", line)
