@@ -30,10 +30,12 @@ EXPORTS = ["fmcmc_abi_version", "fmcmc_last_error", "fmcmc_last_kernel", "fmcmc_
            "fmcmc_summary_work_len", "fmcmc_summary_pooled_len", "fmcmc_summary_dev",
            "fmcmc_heidel_work_len", "fmcmc_heidel_out_len", "fmcmc_heidel_dev", "fmcmc_plan_route",
            "fmcmc_chain_order_work_len", "fmcmc_chain_order_dev", "fmcmc_raftery_work_len", "fmcmc_raftery_out_len",
-           "fmcmc_raftery_dev"]
+           "fmcmc_raftery_dev", "fmcmc_hpd_work_len", "fmcmc_hpd_dev", "fmcmc_autocov_out_len", "fmcmc_autocov_dev"]
 SUMMARY_MAX_PROBS = 16
 CHAIN_ORDER_MAX_RANKS = 2 * SUMMARY_MAX_PROBS
 RAFTERY_MAX_THINNINGS = 32     # thinnings per fmcmc_raftery_dev call
+HPD_MAX_TAIL = 8192            # rows N - gap of each tail fmcmc_hpd_dev holds in LDS
+AUTOCOV_MAX_LAGS = 32          # lags per fmcmc_autocov_dev call
 
 # fmcmc_logpost_fn: out[c] = log f(theta[c][0..k-1]) for c < nchains; 0 = ok (theta, out, hip_stream, user: addresses)
 LOGPOST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p)
@@ -150,6 +152,16 @@ def lib():
         L.fmcmc_raftery_dev.restype = C.c_int
         L.fmcmc_raftery_dev.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                         C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fmcmc_hpd_work_len.restype = C.c_int64
+        L.fmcmc_hpd_work_len.argtypes = [C.c_int64, C.c_int32]
+        L.fmcmc_hpd_dev.restype = C.c_int
+        L.fmcmc_hpd_dev.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
+                                    C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fmcmc_autocov_out_len.restype = C.c_int64
+        L.fmcmc_autocov_out_len.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+        L.fmcmc_autocov_dev.restype = C.c_int
+        L.fmcmc_autocov_dev.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
+                                        C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.fmcmc_rng_stream_dev.restype = C.c_int
         L.fmcmc_rng_stream_dev.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                            C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -10,6 +10,9 @@
 //   3. raftery      u = type-7 quantile from the two order statistics (two rounded products, one rounded sum), the indicator
 //                   Z_t = (x_t <= u) bit-packed into `work` by wave ballots, then per thinning j (one wavefront each) the
 //                   2x2x2 table of the consecutive triples of Z at rows 0, j, 2j, ... and its last pair.
+//   4. hpd         coda::HPDinterval of a series (chain_hpd_kernel): the shortest interval between x_(i) and x_(i + gap) uses the
+//                   T = N - gap smallest and the T largest values alone; the two order statistics that bound them are selected,
+//                   both tails are compacted into LDS, sorted there, and the T widths are reduced to their first minimum.
 // Every count is an integer, so neither the arrival order of the LDS atomics nor the launch changes a result.  Nothing here
 // writes `samples`.
 #include "diag_common.hpp"
@@ -24,6 +27,8 @@ constexpr int MAXNJ = 32;           // thinnings per launch
 constexpr int LU = 4;               // pairs in flight per thread
 constexpr int HEAD = 4;             // doubles per series at the head of the raftery output: u, x_(lo), x_(hi), non-finite count
 constexpr int CNT = 10;             // integers per (series, thinning): T[a][b][c] at 4 a + 2 b + c, then Z_{m-2}, Z_{m-1}
+constexpr int HPD_MAX_TAIL = 8192;  // rows of each tail of chain_hpd_kernel held in LDS (two tails of 64 KB)
+constexpr int HPD_OUT = 4;          // doubles per series of the hpd output: lower, upper, i*, non-finite count
 
 struct OrderRanks { unsigned int r[MAXRANKS]; };    // 0-based, each < N < 2^32
 
@@ -211,6 +216,93 @@ __global__ __launch_bounds__(OT) void raftery_kernel(const double* __restrict__ 
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------- HPD
+// coda::HPDinterval of one series: with x_(0) <= .. <= x_(N-1), the first minimum over i = 0 .. T - 1 (T = N - gap) of
+// x_(i + gap) - x_(i).  Only x_(0) .. x_(T-1) (the low tail) and x_(gap) .. x_(N-1) (the high tail) enter, T values each; where
+// gap < T the two overlap.  The keys of x_(T-1) and x_(gap) are selected; one more walk copies into each tail the keys strictly
+// beyond its threshold (fewer than T: the threshold itself has a rank inside the tail) in the order they arrive, the rest of the
+// T slots take the threshold key (ties are equal values), the slots up to the power of two P the maximum key; both tails are
+// sorted by a bitonic network over P keys, which ends the dependence on the arrival order.  Then thread t forms the widths
+// t, t + OT, ... (one float64 subtraction each) and keeps its first minimum; (width, index) pairs are joined lexicographically.
+__global__ __launch_bounds__(OT) void chain_hpd_kernel(const double* __restrict__ samples, long long S, int k, long long row0,
+                                                       long long N, const int* __restrict__ cols, int p, unsigned int gap,
+                                                       int P, double* __restrict__ thresholds, double* __restrict__ out) {
+  extern __shared__ unsigned long long s_k[];        // [2][P]: the low tail, the high tail
+  __shared__ SelectLds L;
+  __shared__ unsigned int s_n[2];                    // keys strictly beyond the threshold copied so far, per tail
+  __shared__ double s_w[OW];
+  __shared__ unsigned int s_i[OW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long series = blockIdx.x, c = series / p;
+  const int col = (int)(series % p);
+  const double* __restrict__ x = samples + (c * (long long)k + cols[col]) * S + row0;
+  const unsigned int T = (unsigned int)N - gap;      // 1 <= T <= P <= HPD_MAX_TAIL
+  unsigned long long* lo = s_k;
+  unsigned long long* hi = s_k + P;
+  stage_series(x, N, false, s_k, L);
+  if (tid < 2) { L.prefix[tid] = 0ull; L.rank[tid] = tid ? gap : T - 1u; s_n[tid] = 0u; }
+  select_series(x, N, false, s_k, 2, L);
+  const unsigned long long klo = L.prefix[0], khi = L.prefix[1];
+  walk_pairs<OT, LU>(x, N, [&](long long, double a, double b, bool has_b) {
+    auto put = [&](unsigned long long kx) {
+      if (kx < klo) { const unsigned int at = atomicAdd(&s_n[0], 1u); if (at < T) lo[at] = kx; }
+      if (kx > khi) { const unsigned int at = atomicAdd(&s_n[1], 1u); if (at < T) hi[at] = kx; }
+    };
+    put(key_of(a));
+    if (has_b) put(key_of(b));
+  });
+  __syncthreads();
+  {
+    const unsigned int nlo = s_n[0] < T ? s_n[0] : T, nhi = s_n[1] < T ? s_n[1] : T;
+    for (unsigned int i = tid; i < (unsigned int)P; i += OT) {
+      if (i >= nlo) lo[i] = i < T ? klo : ~0ull;
+      if (i >= nhi) hi[i] = i < T ? khi : ~0ull;
+    }
+  }
+  __syncthreads();
+  // bitonic sort of both tails, ascending: P / 2 compare-exchanges per tail and step, pair q of a step = the q-th index with
+  // bit j clear and its partner with bit j set
+  for (int kk = 2; kk <= P; kk <<= 1) {
+    for (int j = kk >> 1; j >= 1; j >>= 1) {
+      for (int q = tid; q < P; q += OT) {            // q < P / 2: the low tail; beyond: the high tail
+        unsigned long long* t = q < (P >> 1) ? lo : hi;
+        const int r = q & ((P >> 1) - 1);
+        const int i = ((r & ~(j - 1)) << 1) | (r & (j - 1)), l = i | j;
+        const unsigned long long a = t[i], b = t[l];
+        const bool up = (i & kk) == 0;
+        if ((a > b) == up) { t[i] = b; t[l] = a; }
+      }
+      __syncthreads();
+    }
+  }
+  // widths and their first minimum.  (Infinite widths compare equal: the first of them wins, as which.min has it.)
+  double bw = 0.0;
+  unsigned int bi = 0xffffffffu;
+  for (unsigned int i = tid; i < T; i += OT) {
+    const double w = value_of(hi[i]) - value_of(lo[i]);
+    if (bi == 0xffffffffu || w < bw) { bw = w; bi = i; }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const double ow = __shfl_xor(bw, o, 64);
+    const unsigned int oi = __shfl_xor(bi, o, 64);
+    if (oi != 0xffffffffu && (bi == 0xffffffffu || ow < bw || (ow == bw && oi < bi))) { bw = ow; bi = oi; }
+  }
+  if (lane == 0) { s_w[wave] = bw; s_i[wave] = bi; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < OW; w++) {
+      const double ow = s_w[w];
+      const unsigned int oi = s_i[w];
+      if (oi != 0xffffffffu && (bi == 0xffffffffu || ow < bw || (ow == bw && oi < bi))) { bw = ow; bi = oi; }
+    }
+    if (bi >= T) bi = 0u;                            // (a NaN width in every slot: the call is refused for its non-finite rows)
+    double* o = out + series * HPD_OUT;
+    o[0] = value_of(lo[bi]); o[1] = value_of(hi[bi]); o[2] = (double)bi; o[3] = (double)L.nf;
+    thresholds[2 * series] = value_of(klo); thresholds[2 * series + 1] = value_of(khi);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -276,6 +368,34 @@ int fmcmc_raftery_dev(const double* samples, int64_t nchains, int32_t k, int64_t
                      (long long)N, cols, (int)p, (unsigned int)r.lo, (unsigned int)r.hi, r.between, r.h,
                      (long long)j0, (int)nj, staged, reinterpret_cast<unsigned long long*>(work), (long long)((N + 63) / 64),
                      out, reinterpret_cast<long long*>(out + series * HEAD));
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(FMCMC_ERR_DEVICE, "%s: launch failed (%s)", who, hipGetErrorString(e));
+  return FMCMC_OK;
+}
+
+int64_t fmcmc_hpd_work_len(int64_t nchains, int32_t p) {
+  if (nchains < 1 || p < 1 || nchains > 0x7fffffffLL / p) return 0;
+  return nchains * (int64_t)p * 2;
+}
+
+int fmcmc_hpd_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N, const int32_t* cols,
+                  int32_t p, int64_t gap, double* work, double* out, void* hip_stream) {
+  const char* who = "fmcmc_hpd_dev";
+  int rc = check_window(who, samples, cols, work, out, nchains, k, S, row0, N, p);
+  if (rc != FMCMC_OK) return rc;
+  if (gap < 1 || gap > N - 1) return fail(FMCMC_ERR_ARG, "%s: gap = %lld is outside [1, %lld]", who, (long long)gap, (long long)(N - 1));
+  const int64_t T = N - gap;
+  if (T > HPD_MAX_TAIL)
+    return fail(FMCMC_ERR_UNSUPPORTED, "%s: N - gap = %lld rows in each tail of a series; at most %d are held in LDS", who,
+                (long long)T, HPD_MAX_TAIL);
+  int P = 2;                                         // (the sort's pair index needs P / 2 >= 1)
+  while (P < T) P <<= 1;
+  hipStream_t st = (hipStream_t)hip_stream;
+  const size_t lds = (size_t)2 * P * sizeof(unsigned long long);
+  rc = allow_lds(who, chain_hpd_kernel, lds);
+  if (rc != FMCMC_OK) return rc;
+  hipLaunchKernelGGL(chain_hpd_kernel, dim3((unsigned)(nchains * p)), dim3(OT), lds, st, samples, (long long)S, (int)k,
+                     (long long)row0, (long long)N, cols, (int)p, (unsigned int)gap, P, work, out);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(FMCMC_ERR_DEVICE, "%s: launch failed (%s)", who, hipGetErrorString(e));
   return FMCMC_OK;

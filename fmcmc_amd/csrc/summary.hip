@@ -10,6 +10,8 @@
 //                              select on order-preserving 64-bit keys (8 passes of 8 bits, integer counts only);
 //   5. summary_cvm_kernel      coda::heidel.diag: stages 1-2 on the S0 window and on every candidate tail, then one workgroup
 //                              per (series, candidate) scans the centred tail and sums the squares of its Brownian bridge.
+//   6. summary_lag_kernel      coda::autocorr: autocovariances at up to 32 freely chosen row lags (stage 1 stops at lag M), one
+//                              workgroup per series: the mean as in stage 1, then one walk per eight lags that reads x_{t+h} from global memory.
 // Every sum has a fixed shape, so the results do not depend on the launch.  Nothing here writes `samples`.
 #include "diag_common.hpp"
 
@@ -455,6 +457,69 @@ __global__ __launch_bounds__(ST) void summary_cvm_kernel(const double* __restric
   if (tid == 0) q_out[(long long)s * nseries + series] = q;
 }
 
+// ------------------------------------------------------------------------------------------------------------ free lags
+// c_h = (1 / N) sum_{t < N - h} (x_t - m)(x_{t+h} - m) at the row lags h of the call (stats::acf, type "covariance"), and c_0.
+// The mean is the sum of stage 1 (the same order, so the same bits).  Thread t then owns the rows t, t + ST, ... and keeps one
+// accumulator per lag: xc_t is formed once, x_{t+h} is read from global memory (L2 serves it: a thread's rows were loaded by
+// its neighbours h rows ago) and centred again; a partner beyond the series multiplies as 0.  The lags travel as a kernel
+// argument and are taken in groups of LG, one walk per group with the loads of a row issued together.  The sum of a lag is the
+// thread's rows in ascending order, then block_sum: it depends on (N, h) alone, not on the other lags of the call.
+constexpr int MAXLAGS = 32;
+constexpr int LAG_HEAD = 3;         // doubles per series before the lags: mean, c_0, non-finite count
+struct LagList { int h[MAXLAGS]; };  // each < N < 2^22; slots beyond nlags hold N (no partner row)
+
+__global__ __launch_bounds__(ST) void summary_lag_kernel(const double* __restrict__ samples, long long S, int k, long long row0,
+                                                         long long N, const int* __restrict__ cols, int p, int nlags,
+                                                         LagList lags, double* __restrict__ nf_out, double* __restrict__ out) {
+  __shared__ double s_red[SW];
+  const int tid = threadIdx.x;
+  const long long series = blockIdx.x, c = series / p;
+  const int j = (int)(series % p);
+  const double* __restrict__ x = samples + (c * (long long)k + cols[j]) * S + row0;
+  const double dn = (double)N;
+  double s = 0.0, nf = 0.0;
+  walk_pairs<ST, 8>(x, N, [&](long long, double a, double b, bool) {      // (a missing second row of the pair adds 0)
+    s += a; s += b;
+    nf += (fmh_isfinite(a) ? 0.0 : 1.0) + (fmh_isfinite(b) ? 0.0 : 1.0);
+  });
+  const double mean = block_sum<SW>(s, s_red) / dn;
+  nf = block_sum<SW>(nf, s_red);
+
+  // one walk per group of LG lags (a call with the default five lags walks once); the first also sums c_0
+  double* o = out + series * (LAG_HEAD + nlags);
+#pragma unroll
+  for (int g = 0; g < MAXLAGS / LG; g++) {
+    if (LG * g < nlags) {
+      double acc0 = 0.0, acc[LG];
+#pragma unroll
+      for (int u = 0; u < LG; u++) acc[u] = 0.0;
+      for (long long i = tid; i < N; i += ST) {
+        const double xi = x[i] - mean;
+        double v[LG];
+#pragma unroll
+        for (int u = 0; u < LG; u++) {
+          const long long at = i + lags.h[LG * g + u];
+          v[u] = at < N ? x[at] - mean : 0.0;
+        }
+        if (g == 0) acc0 = __builtin_fma(xi, xi, acc0);
+#pragma unroll
+        for (int u = 0; u < LG; u++) acc[u] = __builtin_fma(xi, v[u], acc[u]);
+      }
+      if (g == 0) {
+        acc0 = block_sum<SW>(acc0, s_red);
+        if (tid == 0) { o[0] = mean; o[1] = acc0 / dn; o[2] = nf; nf_out[series] = nf; }
+      }
+#pragma unroll
+      for (int u = 0; u < LG; u++) {
+        if (LG * g + u < nlags) {
+          const double v = block_sum<SW>(acc[u], s_red);
+          if (tid == 0) o[LAG_HEAD + LG * g + u] = v / dn;
+        }
+      }
+    }
+  }
+}
+
 // Stages 1 and 2 for the window [row0, row0 + N) of every series: acov [series][ACS], stats [series][4].
 int launch_series_stats(const char* who, hipStream_t st, const double* samples, long long S, int k, long long row0, long long N,
                         const int* cols, int p, long long series, double* acov, double* stats) {
@@ -581,6 +646,36 @@ int fmcmc_heidel_dev(const double* samples, int64_t nchains, int32_t k, int64_t 
                        (long long)row0, (long long)N, cols, (int)p, cands, out + (1 + s0) * series * 4, series,
                        q_out + s0 * series);
   }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(FMCMC_ERR_DEVICE, "%s: launch failed (%s)", who, hipGetErrorString(e));
+  return FMCMC_OK;
+}
+
+int64_t fmcmc_autocov_out_len(int64_t nchains, int32_t p, int32_t nlags) {
+  if (nchains < 1 || p < 1 || nlags < 1 || nlags > MAXLAGS || nchains > 0x7fffffffLL / p) return 0;
+  return nchains * (int64_t)p * (LAG_HEAD + (int64_t)nlags);
+}
+
+int fmcmc_autocov_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N, const int32_t* cols,
+                      int32_t p, const int64_t* lags, int32_t nlags, double* work, double* out, void* hip_stream) {
+  const char* who = "fmcmc_autocov_dev";
+  int rc = check_window(who, samples, cols, work, out, nchains, k, S, row0, N, p);
+  if (rc != FMCMC_OK) return rc;
+  if (!lags) return fail(FMCMC_ERR_ARG, "%s: null argument", who);
+  if (nlags < 1 || nlags > MAXLAGS) return fail(FMCMC_ERR_ARG, "%s: nlags = %d outside [1, %d]", who, (int)nlags, MAXLAGS);
+  LagList ll;
+  for (int l = 0; l < MAXLAGS; l++) {
+    if (l < nlags) {
+      if (lags[l] < 0 || lags[l] >= N)
+        return fail(FMCMC_ERR_ARG, "%s: lags[%d] = %lld is outside [0, %lld)", who, l, (long long)lags[l], (long long)N);
+      for (int u = 0; u < l; u++)
+        if (lags[u] == lags[l]) return fail(FMCMC_ERR_ARG, "%s: lags[%d] = %lld repeats lags[%d]", who, l, (long long)lags[l], u);
+    }
+    ll.h[l] = (int)(l < nlags ? lags[l] : N);
+  }
+  hipStream_t st = (hipStream_t)hip_stream;
+  hipLaunchKernelGGL(summary_lag_kernel, dim3((unsigned)(nchains * p)), dim3(ST), 0, st, samples, (long long)S, (int)k,
+                     (long long)row0, (long long)N, cols, (int)p, (int)nlags, ll, work, out);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(FMCMC_ERR_DEVICE, "%s: launch failed (%s)", who, hipGetErrorString(e));
   return FMCMC_OK;

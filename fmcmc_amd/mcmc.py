@@ -286,6 +286,21 @@ class DeviceChains:
         from .summary import gelman_diag
         return gelman_diag(self, confidence, autoburnin, multivariate, cols)
 
+    def hpd_interval(self, prob=0.95, cols=None):
+        """Highest-posterior-density interval of every chain on its own (coda::HPDinterval): lower, upper [C][p]."""
+        from .summary import hpd_interval
+        return hpd_interval(self, prob, cols)
+
+    def autocorr_diag(self, lags=(0, 1, 5, 10, 50), relative=True, cols=None):
+        """Autocorrelations at the given lags (coda::autocorr.diag): acf [C][nlags][p] and its mean over the chains."""
+        from .summary import autocorr_diag
+        return autocorr_diag(self, lags, relative, cols)
+
+    def crosscorr(self, cols=None):
+        """Correlation matrix [p][p] of the pooled rows (coda::crosscorr)."""
+        from .summary import crosscorr
+        return crosscorr(self, cols)
+
 
 def _validate_common(nsteps, nchains, burnin, thin, multicore):
     if multicore and nchains == 1:

@@ -1,6 +1,7 @@
-"""summary() / effective_size() / geweke() / heidel() / raftery_diag() / gelman_diag() / chain_quantiles() of a result, computed
-on the device (coda::summary.mcmc(.list), coda::effectiveSize, coda::geweke.diag, coda::heidel.diag, coda::raftery.diag,
-coda::gelman.diag).
+"""summary() / effective_size() / geweke() / heidel() / raftery_diag() / gelman_diag() / chain_quantiles() / hpd_interval() /
+autocorr_diag() / crosscorr() of a result, computed on the device (coda::summary.mcmc(.list), coda::effectiveSize,
+coda::geweke.diag, coda::heidel.diag, coda::raftery.diag, coda::gelman.diag, coda::HPDinterval, coda::autocorr.diag,
+coda::crosscorr).
 
 The first thing every example of the reference does with a result is `summary(ans)` (README.md:178-201, R/mcmc.R:212).  Here the
 kept rows stay where the sweep left them: csrc/summary.hip reduces every (chain, column) series to its mean, variance and
@@ -789,3 +790,211 @@ def gelman_diag(x, confidence=0.95, autoburnin=True, multivariate=True, cols=Non
     partial, _work, cols = enqueue_gelman(dc, row0, N, cols)
     return gelman_diag_finish(partial.cpu().numpy(), int(cols.size), N, confidence, multivariate, _names(dc, cols),
                               int(dc.iters[row0]), int(dc.iters[-1]))
+
+
+# ------------------------------------------------------------------------------------------------ HPD intervals
+def hpd_gap(n, prob):
+    """coda::HPDinterval: the rows an interval spans, max(1, min(n - 1, round(n prob))) with R's round (half to even)."""
+    prob = float(prob)
+    if not 0.0 < prob < 1.0:
+        raise ValueError("`prob` must lie in (0, 1).")
+    return int(max(1, min(int(n) - 1, int(np.rint(np.float64(n) * np.float64(prob))))))
+
+
+def host_hpd_interval(series, prob=0.95, gap=None):
+    """hpd_interval() without the device, from np.sort: series [..., n] -> (lower [...], upper [...], index [...]) of every
+    series on its own: the first minimum over i of x_(i + gap) - x_(i), gap = hpd_gap(n, prob) unless it is given."""
+    srt = np.sort(np.asarray(series, dtype=np.float64), axis=-1)
+    n = srt.shape[-1]
+    gap = hpd_gap(n, prob) if gap is None else int(gap)
+    if not 1 <= gap <= n - 1:
+        raise ValueError("gap = %d is outside [1, %d]" % (gap, n - 1))
+    with np.errstate(over="ignore", invalid="ignore"):
+        width = srt[..., gap:] - srt[..., :n - gap]
+    index = np.argmin(width, axis=-1)                              # (the first of equal widths, as which.min)
+    take = lambda a: np.take_along_axis(a, index[..., None], axis=-1)[..., 0]
+    return take(srt[..., :n - gap]), take(srt[..., gap:]), index.astype(np.int64)
+
+
+class HpdInterval:
+    """coda::HPDinterval of every chain: lower, upper [C][p], index [C][p] (the 0-based rank of `lower` among the sorted rows of
+    its series; `upper` is `gap` ranks above it), table [C][p][2] so that table[c] is coda's matrix of chain c, and the
+    attribute probability = gap / nrows."""
+    columns = ("lower", "upper")
+
+    def __init__(self, lower, upper, index, gap, nrows, varnames=None):
+        self.lower, self.upper = np.asarray(lower, dtype=np.float64), np.asarray(upper, dtype=np.float64)
+        self.index = np.asarray(index, dtype=np.int64)
+        self.gap, self.nrows = int(gap), int(nrows)
+        self.varnames = list(varnames) if varnames is not None else _par_names(range(self.lower.shape[1]))
+
+    table = property(lambda self: np.stack([self.lower, self.upper], axis=-1))
+    probability = property(lambda self: self.gap / self.nrows)
+
+    def __str__(self):
+        out = []
+        for c, t in enumerate(self.table):
+            out += ["[[%d]]" % (c + 1), _fmt_table(self.varnames, self.columns, t), 'attr(,"Probability")',
+                    "[1] %.7g" % self.probability, ""]
+        return "\n".join(out)
+
+    def __repr__(self):
+        return "<HpdInterval nchain=%d nvar=%d probability=%.4g>" % (self.lower.shape[0], self.lower.shape[1], self.probability)
+
+
+def enqueue_hpd(dc, gap, cols):
+    """Enqueues one fmcmc_hpd_dev call on the kept rows of `dc` (current torch stream) for intervals that span `gap` rows.
+    Returns the device tensors (out [C][p][4] = lower, upper, i*, non-finite count; work [C][p][2], the two thresholds) and the
+    columns; nothing is synchronised."""
+    o = _open(dc, cols, "order")
+    work = _doubles(o, o.L.fmcmc_hpd_work_len(o.Cn, o.p))
+    out = _doubles(o, o.Cn * o.p * 4).view(o.Cn, o.p, 4)
+    _windowed(o, o.L.fmcmc_hpd_dev, 0, dc.nrows, int(gap), work.data_ptr(), out.data_ptr())
+    return out, work[:o.Cn * o.p * 2].view(o.Cn, o.p, 2), o.cols
+
+
+def hpd_interval(x, prob=0.95, cols=None):
+    """coda::HPDinterval of every chain on its own (HPDinterval.mcmc.list): x a DeviceChains (read in place), an Mcmc or a
+    McmcList (uploaded first).  The device selects the two tails of every series that can hold an end of the interval, sorts
+    them in LDS and finds the first shortest interval (csrc/raftery.hip: chain_hpd_kernel); the result has the bits of
+    host_hpd_interval.  A tail holds at most 8192 rows: 163840 rows per chain at prob = 0.95."""
+    dc = _as_device_chains(x)
+    n = int(dc.nrows)
+    gap = hpd_gap(n, prob)
+    out, _work, cols = enqueue_hpd(dc, gap, cols)
+    oh = out.cpu().numpy()
+    _raise_non_finite(oh[:, :, 3], cols, "order")
+    return HpdInterval(oh[:, :, 0].copy(), oh[:, :, 1].copy(), oh[:, :, 2].astype(np.int64), gap, n,
+                       _names(dc, cols) if dc.names is not None else None)
+
+
+# ------------------------------------------------------------------------------------------------ autocorrelation
+DEFAULT_LAGS = (0, 1, 5, 10, 50)
+
+
+def autocorr_lags(lags, niter, thin, relative=True):
+    """coda::autocorr's lags: (labels, row lags).  With `relative` the lags count kept rows (label = lag thin); without, they are
+    iteration labels and must be multiples of the thinning.  Labels that are not below niter thin are dropped."""
+    lags = np.atleast_1d(np.asarray(lags, dtype=np.int64))
+    thin = int(thin)
+    if relative:
+        labels = lags * thin
+    elif np.any(lags % thin != 0):
+        raise ValueError("Lags do not conform to thinning interval")
+    else:
+        labels = lags
+    labels = labels[labels < int(niter) * thin]
+    if labels.size < 1:
+        raise ValueError("no lag below the %d rows of a chain" % int(niter))
+    return labels, labels // thin
+
+
+def host_autocov(series, lags):
+    """series [..., n], row lags [nlags] -> (mean [...], c_0 [...], c_h [..., nlags]) as stats::acf(type = "covariance") forms
+    them in float64: the series centred on its mean, sum of products, divisor n."""
+    x = np.asarray(series, dtype=np.float64)
+    n = x.shape[-1]
+    mean = x.sum(axis=-1) / n
+    xc = x - mean[..., None]
+    c = np.stack([(xc[..., :n - h] * xc[..., h:]).sum(axis=-1) / n for h in (int(h) for h in lags)], axis=-1)
+    return mean, (xc * xc).sum(axis=-1) / n, c
+
+
+def host_autocorr(series, lags):
+    """autocorr_diag() without the device: series [..., n], row lags [nlags] -> acf [..., nlags] = c_h / c_0 (NaN for a
+    constant series)."""
+    _, c0, c = host_autocov(series, lags)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return c / c0[..., None]
+
+
+class AutocorrDiag:
+    """coda::autocorr.diag: acov and acf [C][nlags][p] (c_h and c_h / c_0 of every chain), mean [nlags][p] (the chains' acf
+    summed in chain order and divided by C: what coda reports for an mcmc.list), lags [nlags] (iteration labels; `rows`: the
+    same lags in kept rows), c0 and chain_mean [C][p].  print(): the table of `mean` with coda's row names."""
+
+    def __init__(self, acov, c0, lags, rows, varnames=None, chain_mean=None):
+        self.acov = np.asarray(acov, dtype=np.float64)
+        self.c0 = np.asarray(c0, dtype=np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.acf = self.acov / self.c0[:, None, :]
+        total = self.acf[0].copy()
+        for c in range(1, self.acf.shape[0]):
+            total = total + self.acf[c]
+        self.mean = total / self.acf.shape[0]
+        self.lags, self.rows = np.asarray(lags, dtype=np.int64), np.asarray(rows, dtype=np.int64)
+        self.chain_mean = chain_mean
+        self.varnames = list(varnames) if varnames is not None else _par_names(range(self.acov.shape[2]))
+
+    rownames = property(lambda self: ["Lag %d" % l for l in self.lags])
+
+    def __str__(self):
+        return _fmt_table(self.rownames, self.varnames, self.mean)
+
+    def __repr__(self):
+        return "<AutocorrDiag nchain=%d nvar=%d lags=%s>" % (self.acov.shape[0], self.acov.shape[2], self.lags.tolist())
+
+
+def enqueue_autocov(dc, lags, cols):
+    """Enqueues one fmcmc_autocov_dev call on the kept rows of `dc` (current torch stream) at the row `lags` (1 to 32, distinct,
+    each below the rows of a chain).  Returns the device tensors (out [C][p][3 + nlags] = mean, c_0, non-finite count, then c_h
+    per lag; work [C][p], the non-finite counts) and the columns; nothing is synchronised."""
+    o = _open(dc, cols, "correlate")
+    lags = np.ascontiguousarray(lags, dtype=np.int64).ravel()
+    nl = int(lags.size)
+    work = _doubles(o, o.Cn * o.p)
+    out = _doubles(o, max(o.L.fmcmc_autocov_out_len(o.Cn, o.p, nl), o.Cn * o.p * (3 + nl)))
+    _windowed(o, o.L.fmcmc_autocov_dev, 0, dc.nrows, lags.ctypes.data_as(C.POINTER(C.c_int64)), nl, work.data_ptr(), out.data_ptr())
+    return out[:o.Cn * o.p * (3 + nl)].view(o.Cn, o.p, 3 + nl), work.view(o.Cn, o.p), o.cols
+
+
+def autocorr_diag(x, lags=DEFAULT_LAGS, relative=True, cols=None):
+    """coda::autocorr.diag of a result: x a DeviceChains (read in place), an Mcmc or a McmcList (uploaded first).  The device
+    forms every chain's autocovariances at the lags asked for (csrc/summary.hip: summary_lag_kernel; summary() keeps them up to
+    the AR order only); the division by c_0 and the mean over the chains are done here.  At most 32 lags per call."""
+    dc = _as_device_chains(x)
+    labels, rows = autocorr_lags(lags, dc.nrows, dc.thin, relative)
+    out, _work, cols = enqueue_autocov(dc, rows, cols)
+    oh = out.cpu().numpy()
+    _raise_non_finite(oh[:, :, 2], cols, "correlate")
+    return AutocorrDiag(np.ascontiguousarray(oh[:, :, 3:].transpose(0, 2, 1)), oh[:, :, 1].copy(), labels, rows,
+                        _names(dc, cols) if dc.names is not None else None, chain_mean=oh[:, :, 0].copy())
+
+
+# ------------------------------------------------------------------------------------------------ cross-correlation
+def crosscorr_finish(partial, p, N):
+    """The host finish of crosscorr(): a pure function of the partial vector of fmcmc_gelman_partial_dev (include/fmcmc_amd.h:
+    m, sum xbar [p], sum xbar xbar^T [p][p], sum S_c [p][p], ...), p and the rows N of a chain.  The covariance of the m N pooled
+    rows is ((N - 1) sum S_c + N (sum xbar xbar^T - m mu mu^T)) / (m N - 1) with mu = sum xbar / m (the means may be relative to
+    any centre: a covariance does not move with it); the correlation is cov_ij / sqrt(cov_ii cov_jj), its diagonal exactly 1,
+    and NaN in the row and column of a variable whose variance is 0 (R: NA, "the standard deviation is zero")."""
+    P = np.ascontiguousarray(partial, dtype=np.float64)
+    p, N = int(p), int(N)
+    if p < 1 or N < 2 or P.size < 1 + p + 2 * p * p:
+        raise ValueError("crosscorr: a partial of at least 1 + p + 2p^2 numbers, p >= 1 and N >= 2 rows are needed")
+    m = float(P[0])
+    if m < 1:
+        raise ValueError("crosscorr: the partial holds no chain")
+    sx = P[1:1 + p]
+    sxx = P[1 + p:1 + p + p * p].reshape(p, p)
+    sS = P[1 + p + p * p:1 + p + 2 * p * p].reshape(p, p)
+    mu = sx / m
+    cov = ((N - 1.0) * sS + N * (sxx - m * np.outer(mu, mu))) / (m * N - 1.0)
+    var = cov.diagonal().copy()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cor = cov / np.sqrt(np.outer(var, var))
+    flat = ~(var > 0.0)
+    cor[flat, :] = np.nan
+    cor[:, flat] = np.nan
+    cor[np.arange(p), np.arange(p)] = np.where(flat, np.nan, 1.0)
+    return cor
+
+
+def crosscorr(x, cols=None):
+    """coda::crosscorr: the correlation matrix [p][p] of the pooled rows of all chains (p <= 256): x a DeviceChains (read in
+    place), an Mcmc or a McmcList (uploaded first).  One fmcmc_gelman_partial_dev call over all kept rows sums every chain's
+    mean and covariance; crosscorr_finish pools them.  One chain is enough."""
+    dc = _as_device_chains(x)
+    N = int(dc.nrows)
+    partial, _work, cols = enqueue_gelman(dc, 0, N, cols)
+    return crosscorr_finish(partial.cpu().numpy(), int(cols.size), N)

@@ -378,6 +378,38 @@ int fmcmc_raftery_dev(const double* samples, int64_t nchains, int32_t k, int64_t
                       const int32_t* cols, int32_t p, double q, int64_t j0, int32_t nj, double* work, double* out,
                       void* hip_stream);
 
+/* ---- highest-posterior-density interval of every chain on its own (coda::HPDinterval), the device part ---------------------
+ * Window, samples, S, cols and row limits as for fmcmc_summary_dev.  gap is the number of rows the interval spans, formed by the
+ * caller (coda: max(1, min(N - 1, round(N prob))), R's round being half-to-even); 1 <= gap <= N - 1 (FMCMC_ERR_ARG).  Per series,
+ * with x_(0) <= .. <= x_(N-1) its rows in ascending order (-0.0 before +0.0): i* = the FIRST index of the minimum over
+ * i = 0 .. N - gap - 1 of x_(i+gap) - x_(i) (one float64 subtraction each; equal widths, infinite ones included, tie).
+ * out (device, nchains p 4 doubles): [nchains][p][4] = {lower = x_(i*), upper = x_(i*+gap), i*, count of non-finite values of
+ *   the series}.  coda's attribute Probability is gap / N.
+ * work (device, fmcmc_hpd_work_len(nchains, p) doubles): [nchains][p][2], left as {x_(N-gap-1), x_(gap)}, the largest value of
+ *   the low tail and the smallest of the high tail.
+ * Only the T = N - gap smallest and the T largest rows enter; both tails are held and sorted in LDS, T <= 8192 rows each
+ * (FMCMC_ERR_UNSUPPORTED beyond, before any device call: N <= 163840 rows per chain at prob = 0.95).  The call only enqueues one
+ * kernel on hip_stream and reads `samples` only; everything is a comparison but the one subtraction per width: a series gives
+ * the same bits wherever it sits, and the bits of a sort on the host. */
+int64_t fmcmc_hpd_work_len(int64_t nchains, int32_t p);
+int fmcmc_hpd_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N, const int32_t* cols,
+                  int32_t p, int64_t gap, double* work, double* out, void* hip_stream);
+
+/* ---- autocovariances of every chain at freely chosen lags (coda::autocorr, stats::acf), the device part ----------------------
+ * Window, samples, S, cols and row limits as for fmcmc_summary_dev (which keeps r_0 .. r_M up to the AR order only).  lags is a
+ * HOST array, read during the call, of 1 <= nlags <= 32 distinct row lags in [0, N) (FMCMC_ERR_ARG otherwise), the same for
+ * every series.
+ * out (device, fmcmc_autocov_out_len(nchains, p, nlags) doubles): [nchains][p][3 + nlags] = {mean, c_0, count of non-finite
+ *   values of the series, c_{lags[0]}, .., c_{lags[nlags-1]}}, c_h = (1 / N) sum_{t < N - h} (x_t - mean)(x_{t+h} - mean), the
+ *   series centred on its own float64 mean (the bits fmcmc_summary_dev reports), the products summed with fma.  The
+ *   autocorrelation is c_h / c_0 (NaN for a constant series, as acf has it).
+ * work (device, nchains p doubles): [nchains][p], left as the count of non-finite values of each series.
+ * The call only enqueues one kernel on hip_stream and reads `samples` only.  The sum of a lag has a fixed shape that depends on
+ * (N, h) alone: not on the other lags of the call, nor on where the series sits. */
+int64_t fmcmc_autocov_out_len(int64_t nchains, int32_t p, int32_t nlags);
+int fmcmc_autocov_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N, const int32_t* cols,
+                      int32_t p, const int64_t* lags, int32_t nlags, double* work, double* out, void* hip_stream);
+
 /* Materialises the canonical Philox stream of a call in device memory, in the FED layout of fmcmc_run:
  * logu[C][nsteps] (entry i-1 = log accept-uniform of loop step i), z[C][nsteps][kz] (N(0,1) when student_df == 0;
  * Student-t with student_df degrees of freedom when student_df > 0 -- kernel_ram: kf for the default qfun rt(k, k),

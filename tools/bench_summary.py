@@ -9,10 +9,12 @@ the same table: to_host() plus convergence.heidel_diag chain by chain, timed on 
 And raftery_diag() (the `raftery` leg): the one kernel of fmcmc_raftery_dev for the first batch of thinnings between two HIP
 events, the wall time of the whole call with its copy back and numpy finish, the number of launches it took, the kernel and wall
 of chain_quantiles() at the default five probs, and convergence.raftery_diag on the host for --heidel-host-chains chains.
+And the posterior leg: the kernel and the wall time of hpd_interval() at prob 0.95, of autocorr_diag() at coda's five default
+lags and of crosscorr() (the Gelman reduction over all rows), beside the same to_host().
 Usage: python tools/bench_summary.py [--shapes headline,c4] [--json FILE]   (one JSON line per shape; --json also writes them, with
 the device and the date, to FILE: profiles/bench_summary.json holds the run DESIGN.md section 5.10 quotes, and
 profiles/bench_summary_heidel.json the headline run with heidel(), profiles/bench_summary_raftery.json the one with the
-raftery leg)"""
+raftery leg, profiles/bench_summary_posterior.json the one with the posterior leg)"""
 import argparse
 import json
 import os
@@ -111,6 +113,15 @@ def main():
                         raftery_kthin_max=float(np.nanmax(rd.kthin)), raftery_I_median=round(float(np.nanmedian(rd.I)), 3),
                         raftery_diag_host_ms_per_chain=round(1e3 * per_chain, 3),
                         raftery_host_route_ms=round(best["to_host_wall_ms"] + 1e3 * per_chain * C_, 1))
+            # the posterior leg: hpd_interval(), autocorr_diag() and crosscorr(), kernels between two HIP events and the calls' wall
+            for name, fn in (("hpd_kernel_ms", between_events(lambda: S.enqueue_hpd(dc, S.hpd_gap(N, 0.95), None))),
+                             ("hpd_wall_ms", lambda: wall(dc.hpd_interval)),
+                             ("autocov_kernel_ms", between_events(lambda: S.enqueue_autocov(dc, S.DEFAULT_LAGS, None))),
+                             ("autocorr_wall_ms", lambda: wall(dc.autocorr_diag)),
+                             ("crosscorr_kernels_ms", between_events(lambda: S.enqueue_gelman(dc, 0, N, None))),
+                             ("crosscorr_wall_ms", lambda: wall(dc.crosscorr))):
+                fn()
+                best[name] = round(1e3 * min(fn() for _ in range(5)), 3)
             del host
         nbytes = C_ * k * N * 8
         lines.append(dict(shape=shape, chains=C_, columns=k, rows=N, sample_bytes=nbytes, quantiles=len(DEFAULT_QUANTILES), **best,
