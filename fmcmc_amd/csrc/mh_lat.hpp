@@ -1,5 +1,6 @@
 // mh_lat.hpp -- mh_sweep_lat<KIND, P>: the LATENCY form of the sweep for fewer than four chains per compute unit (round 5).
 #pragma once
+#include "mh_owner.hpp"
 
 namespace {
 
@@ -248,20 +249,6 @@ __device__ __forceinline__ void lat_steps(const SweepArgs& A, double* smem) {
       if (g == 0 && vn >= 2) candidates(vn);   // (version 1's come from the prologue; behind the last step they go nowhere)
     }
   };
-  auto logpost_of = [&](double tot, double sigma) -> double {
-    double f;
-    if (sigma < 0.0 || fmh_isnan(sigma)) {
-      f = fmh_nan();
-    } else if (sigma == 0.0) {
-      f = -fmh_inf();
-    } else {
-      double t1 = fmh_log(sigma) + FMH_K(FMH_LN_SQRT_2PI);
-      double q = (0.5 * tot) / (sigma * sigma);
-      f = -(dn * t1) - q;
-    }
-    if (A.guard && !fmh_isfinite(f)) f = -fmh_inf();
-    return f;
-  };
   // one chain's lane partial: the canonical fma chains of this lane's OPT observations, four slots in flight
   auto eval_chain = [&](int c, auto&& stage) -> double {
     const int l0 = 16 * c;
@@ -391,7 +378,7 @@ __device__ __forceinline__ void lat_steps(const SweepArgs& A, double* smem) {
         f1 = -nt1 - h / ss;
         if (A.guard && !fmh_isfinite(f1)) f1 = -fmh_inf();
       } else {
-        f1 = logpost_of(tot, sigma);
+        f1 = linreg_logpost(tot, sigma, dn, A.guard);
       }
       if (v == 1) {
         f0 = f1;

@@ -1,5 +1,6 @@
 // mh_mfma.hpp -- mh_sweep_mfma<KIND, NG, NS, DBG>: the headline kernel, bit-exact fp64 MFMA evaluation.
 #pragma once
+#include "mh_owner.hpp"
 
 namespace {
 
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(NT) void mh_sweep_mfma(const SweepArgs A) {
     s_th1[tid] = (c < ncw && j < k) ? A.theta0[(cg0 + c) * k + j] : 0.0;
   }
 
-  // ---- owner state (waves 0..3), as in mh_sweep_spec
+  // ---- owner state (waves 0..3), as the normal owner of mh_spec.hpp; the closed form is mh_owner.hpp's
   const int myc = wave;
   const bool owner = (myc < ncw);
   const int cl = __builtin_amdgcn_readfirstlane((int)cg0 + (owner ? myc : 0));
@@ -158,20 +159,6 @@ __global__ __launch_bounds__(NT) void mh_sweep_mfma(const SweepArgs A) {
   const double mu_l = A.mu[jl], sc_l = A.scale[jl];
   double z_nx = (owner && kz > 0) ? ld_z(nsteps >= 2 ? 1 : 0) : 0.0;
   double lu_nx = owner ? lu_row[nsteps >= 2 ? 1 : 0] : 0.0;
-  auto logpost_of = [&](double tot, double sigma) -> double {
-    double f;
-    if (sigma < 0.0 || fmh_isnan(sigma)) {
-      f = fmh_nan();
-    } else if (sigma == 0.0) {
-      f = -fmh_inf();
-    } else {
-      double t1 = fmh_log(sigma) + FMH_K(FMH_LN_SQRT_2PI);
-      double q = (0.5 * tot) / (sigma * sigma);
-      f = -(dn * t1) - q;
-    }
-    if (A.guard && !fmh_isfinite(f)) f = -fmh_inf();
-    return f;
-  };
   auto flush_bits = [&](int i) {
     if (A.accept_bits && lane == 0) {   // (bits_stride: words per chain of the whole call's bitmap, set by launch_sweep for every launch)
       unsigned int* w = A.accept_bits + ((long long)cl * A.bits_stride + ((i - 1) >> 5));
@@ -371,7 +358,7 @@ __global__ __launch_bounds__(NT) void mh_sweep_mfma(const SweepArgs A) {
           f1 = -nt1_fast - h / ss_fast;
           if (A.guard && !fmh_isfinite(f1)) f1 = -fmh_inf();
         } else {
-          f1 = logpost_of(tot, sigma);
+          f1 = linreg_logpost(tot, sigma, dn, A.guard);
         }
         if (v == 1) {
           f0 = f1;

@@ -1,6 +1,7 @@
 // mh_spec.hpp -- mh_sweep_spec<P, OPT, KIND>: 8 compute + 4 owner wavefronts meeting on LDS sequence words; owner roles
 // for the normal kernels, kernel_adapt and kernel_ram (matrix rows in LDS or in registers).
 #pragma once
+#include "mh_owner.hpp"
 
 namespace {
 
@@ -38,8 +39,6 @@ __device__ __forceinline__ double lds_ld_f64(const double* p) {   // ordered aft
   asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"((unsigned)(size_t)p) : "memory");
   return v;
 }
-
-
 
 constexpr int SPEC_ALD = PIPE_KMAX + 1;                       // row stride of the k x k matrices in LDS
 constexpr int SPEC_ADS = 7 * PIPE_KMAX + 2 * PIPE_KMAX * SPEC_ALD;  // doubles of adaptive state per chain
@@ -93,9 +92,9 @@ __device__ __forceinline__ void spec_owner_adaptive(const SweepArgs& A, int myc,
   }
   wave_sync_lds();
   const int jl = (lane < k) ? lane : 0;
-  // (row stores and variates: wave-uniform 64-bit bases of the chain's own blocks + 32-bit offsets -- 32-bit offsets from the
-  //  BUFFER bases capped a call at 4 GiB)
-  // (wave-uniform 64-bit bases -- the chain's block -- plus a 32-bit byte offset per lane: one scalar-base store each)
+  // (row stores: wave-uniform 64-bit bases of the chain's own blocks plus a 32-bit byte offset per lane -- one scalar-base store each;
+  //  32-bit offsets from the BUFFER bases capped a call at 4 GiB.  The variate stream of roles that keep it here is addressed the same
+  //  way: ChainStream, mh_owner.hpp.  These locals and the accept bitmap stay in the role: see the note at the top of mh_owner.hpp)
   char* const s_base = reinterpret_cast<char*>(A.samples) + ((long long)cl * k) * A.ldS * 8;
   char* const d_base = A.draws ? reinterpret_cast<char*>(A.draws) + ((long long)cl * k) * A.ldS * 8 : nullptr;
   char* const l_base = A.logpost ? reinterpret_cast<char*>(A.logpost) + (long long)cl * A.ldS * 8 : nullptr;
@@ -330,10 +329,8 @@ __device__ __forceinline__ void spec_owner_adaptive(const SweepArgs& A, int myc,
   // ---- write state back
   wave_sync_lds();
   if (lane < k) A.theta0[(long long)cl * k + lane] = th0[lane];
+  owner_writeback(A, cl, lane, f0, nacc, status);
   if (lane == 0) {
-    A.f0[cl] = f0;
-    A.accept_count[cl] = nacc;
-    if (status == FMCMC_CHAIN_OK) { A.status[cl] = FMCMC_CHAIN_OK; A.status_step[cl] = 0; }
     A.abs_iter[cl] = abs_iter;
     if (A.nerrors) A.nerrors[cl] = nerr;
     if (KIND == FMCMC_KERNEL_ADAPT) A.have_mean[cl] = have_mean;
@@ -366,12 +363,8 @@ struct SpecSync {
   static constexpr bool PREP_EARLY = false;
   unsigned* s_ready; unsigned* s_done; const double* s_tr; int myc;
   template <class F> __device__ __forceinline__ double total(int v, F&&) const {
-    const int lane = threadIdx.x & 63;
     while (lds_ld_u32(&s_done[myc]) < 8u * (unsigned)v) __builtin_amdgcn_s_sleep(1);
-    const double* src = s_tr + myc * (8 * PIPE_TRS) + lane;
-    const double v0 = src[0 * PIPE_TRS], v1 = src[1 * PIPE_TRS], v2 = src[2 * PIPE_TRS], v3 = src[3 * PIPE_TRS];
-    const double v4 = src[4 * PIPE_TRS], v5 = src[5 * PIPE_TRS], v6 = src[6 * PIPE_TRS], v7 = src[7 * PIPE_TRS];
-    return wave_xor_sum(((v0 + v1) + (v2 + v3)) + ((v4 + v5) + (v6 + v7)));
+    return fold_partials(s_tr, myc);
   }
   __device__ __forceinline__ void publish(int vn) const {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -390,12 +383,8 @@ struct SpecSyncB {
   unsigned* s_ready; unsigned* s_done; const double* s_tr; int myc;
   mutable unsigned nreq = 1u;          // (request 1: the initial vector, published by the kernel's set-up)
   __device__ __forceinline__ double served() const {
-    const int lane = threadIdx.x & 63;
     while (lds_ld_u32(&s_done[myc]) < 8u * nreq) __builtin_amdgcn_s_sleep(1);
-    const double* src = s_tr + myc * (8 * PIPE_TRS) + lane;
-    const double v0 = src[0 * PIPE_TRS], v1 = src[1 * PIPE_TRS], v2 = src[2 * PIPE_TRS], v3 = src[3 * PIPE_TRS];
-    const double v4 = src[4 * PIPE_TRS], v5 = src[5 * PIPE_TRS], v6 = src[6 * PIPE_TRS], v7 = src[7 * PIPE_TRS];
-    return wave_xor_sum(((v0 + v1) + (v2 + v3)) + ((v4 + v5) + (v6 + v7)));
+    return fold_partials(s_tr, myc);
   }
   __device__ __forceinline__ void ask() const {
     nreq += 1u;
@@ -467,9 +456,9 @@ __device__ __forceinline__ void spec_owner_adaptive_reg(const SweepArgs& A, int 
   double f0 = 0.0, mean_prev = 0.0, run_sum = 0.0, zcur = 0.0;
   double Dl = 0.0;                          // adapt: D_lane of the factor (kept between the steps that form it)
   long long abs_iter = 0;
-  // (continuation windows of a long call: see spec_owner_adaptive)
-  int nacc = 0, status = A.win_cont ? A.status[cl] : FMCMC_CHAIN_OK, thin_ctr = A.thin_ctr0, have_mean = 0, nerr = 0;
-  const int ioff = (int)A.step_off;
+  const WindowCarry w0 = window_carry(A, cl);   // (and A.win_sum, the step-dependent rules: see spec_owner_adaptive)
+  int nacc = 0, status = w0.status, thin_ctr = w0.thin_ctr, have_mean = 0, nerr = 0;
+  const int ioff = w0.ioff;
   unsigned int bitword = 0;
   if (!A.fresh) {
     abs_iter = A.abs_iter[cl];
@@ -479,9 +468,6 @@ __device__ __forceinline__ void spec_owner_adaptive_reg(const SweepArgs& A, int 
       if (fl) mean_prev = A.mean_prev[(long long)cl * kf + lane];
     }
   }
-  // (row stores and variates: wave-uniform 64-bit bases of the chain's own blocks + 32-bit offsets -- 32-bit offsets from the
-  //  BUFFER bases capped a call at 4 GiB)
-  // (wave-uniform 64-bit bases -- the chain's block -- plus a 32-bit byte offset per lane: one scalar-base store each)
   char* const s_base = reinterpret_cast<char*>(A.samples) + ((long long)cl * k) * A.ldS * 8;
   char* const d_base = A.draws ? reinterpret_cast<char*>(A.draws) + ((long long)cl * k) * A.ldS * 8 : nullptr;
   char* const l_base = A.logpost ? reinterpret_cast<char*>(A.logpost) + (long long)cl * A.ldS * 8 : nullptr;
@@ -504,23 +490,11 @@ __device__ __forceinline__ void spec_owner_adaptive_reg(const SweepArgs& A, int 
     }
     bitword = 0;
   };
-  auto logpost_of = [&](double tot, double sigma) -> double {   // Gaussian linreg closed form (same as the normal owners)
-    double f;
-    if (sigma < 0.0 || fmh_isnan(sigma)) f = fmh_nan();
-    else if (sigma == 0.0) f = -fmh_inf();
-    else {
-      double t1 = fmh_log(sigma) + FMH_K(FMH_LN_SQRT_2PI);
-      double q = (0.5 * tot) / (sigma * sigma);
-      f = -(dn * t1) - q;
-    }
-    if (A.guard && !fmh_isfinite(f)) f = -fmh_inf();
-    return f;
-  };
 
   // What the decision of a step needs and f(theta1) does not enter is prepared while the compute waves evaluate the
   // pending proposal (this wave would only poll): the sigma-only part of the closed form -- n (log sigma + ln sqrt 2 pi),
   // sigma^2 and the reciprocal half of the division (div_recip / div_finish: bit for bit the plain quotient in the safe
-  // range, anything else takes logpost_of) -- and for kernel_ram eta(i, k) and the prefix sums of z^2.
+  // range, anything else takes linreg_logpost) -- and for kernel_ram eta(i, k) and the prefix sums of z^2.
   double pre_nt1 = 0.0, pre_ss = 1.0, pre_rs = 1.0, pre_eta = 0.0, pre_Pj = 0.0, pre_Pj1 = 0.0, pre_nrm2 = 1.0;
   double pre_c1 = 0.0, pre_c2 = 0.0;   // kernel_adapt: (t - 1) / t and 1 / t of the NEXT covariance update (t = abs_iter - 1: the step's own)
   double pre_lin = 0.0, pre_pri = 0.0; // logistic: sum_j b_j hs_j and sum_j b_j^2 / prior_div of the pending proposal
@@ -587,7 +561,7 @@ __device__ __forceinline__ void spec_owner_adaptive_reg(const SweepArgs& A, int 
       if (A.prior_div != 0.0) f1 = f1 - pre_pri;
       if (A.guard && !fmh_isfinite(f1)) f1 = -fmh_inf();
     } else if (pre_ok && mfr_div_safe(h)) f1 = -pre_nt1 - div_finish(h, pre_ss, pre_rs);   // (finite: the guard has nothing to do)
-    else f1 = logpost_of(tot, readlane_d(th1, sig_lane));
+    else f1 = linreg_logpost(tot, readlane_d(th1, sig_lane), dn, A.guard);
     bool st_row = false;
     double st_th0 = 0.0;
     double st_dr = th1;
@@ -646,7 +620,7 @@ __device__ __forceinline__ void spec_owner_adaptive_reg(const SweepArgs& A, int 
               if (A.prior_div != 0.0) f1 = f1 - ss / A.prior_div;
               if (A.guard && !fmh_isfinite(f1)) f1 = -fmh_inf();
             } else {
-              f1 = logpost_of(tot2, readlane_d(th1, sig_lane));
+              f1 = linreg_logpost(tot2, readlane_d(th1, sig_lane), dn, A.guard);
             }
           }
         }
@@ -796,10 +770,8 @@ __device__ __forceinline__ void spec_owner_adaptive_reg(const SweepArgs& A, int 
 #undef SPEC_ST
   // ---- write state back
   if (rl) A.theta0[(long long)cl * k + pj] = th0;
+  owner_writeback(A, cl, lane, f0, nacc, status);
   if (lane == 0) {
-    A.f0[cl] = f0;
-    A.accept_count[cl] = nacc;
-    if (status == FMCMC_CHAIN_OK) { A.status[cl] = FMCMC_CHAIN_OK; A.status_step[cl] = 0; }
     A.abs_iter[cl] = abs_iter;
     if (A.nerrors) A.nerrors[cl] = nerr;
     if (KIND == FMCMC_KERNEL_ADAPT) A.have_mean[cl] = have_mean;
@@ -836,28 +808,13 @@ __device__ __forceinline__ void mfma_owner_mirror(const SweepArgs& A, int myc, i
   char* const l_base = A.logpost ? reinterpret_cast<char*>(A.logpost) + (long long)cl * A.ldS * 8 : nullptr;
   const unsigned int lane_off = (unsigned int)((long long)jl * A.ldS * 8);
   unsigned int srow8 = 0;
-  const char* const z_base = reinterpret_cast<const char*>(A.fed_z) + ((long long)cl * nsteps) * kz * 8;
-  const unsigned int z_lane = (unsigned int)(jl) * 8u;
-  const double* const lu_row = A.fed_logu + (long long)cl * nsteps;
+  const ChainStream fed = chain_stream(A, cl, kz, jl);
   const double dn = uniform_d((double)A.n);
-  auto ld_z = [&](int row) -> double { return *reinterpret_cast<const double*>(z_base + (z_lane + (unsigned int)row * (unsigned int)(kz * 8))); };
-  double z_nx = (rl && nsteps >= 2) ? ld_z(1) : 0.0;
-  double lu_nx = (nsteps >= 2) ? lu_row[1] : 0.0;
+  double z_nx = (rl && nsteps >= 2) ? fed.z(1) : 0.0;
+  double lu_nx = (nsteps >= 2) ? fed.logu(1) : 0.0;
   auto flush_bits = [&](int i) {
     if (A.accept_bits && lane == 0) A.accept_bits[(long long)cl * ((nsteps + 31) >> 5) + ((i - 1) >> 5)] = bitword;
     bitword = 0;
-  };
-  auto logpost_of = [&](double tot, double sigma) -> double {   // Gaussian linreg closed form (as the other owners')
-    double f;
-    if (sigma < 0.0 || fmh_isnan(sigma)) f = fmh_nan();
-    else if (sigma == 0.0) f = -fmh_inf();
-    else {
-      double t1 = fmh_log(sigma) + FMH_K(FMH_LN_SQRT_2PI);
-      double q = (0.5 * tot) / (sigma * sigma);
-      f = -(dn * t1) - q;
-    }
-    if (A.guard && !fmh_isfinite(f)) f = -fmh_inf();
-    return f;
   };
   // What a step needs and the evaluation does not enter, formed while the owner waits for the total (round 5, as the register owner's
   // prepare()): the sigma-only half of the closed form with the reciprocal of sigma^2 (div_finish: bit for bit the division), and the
@@ -884,7 +841,7 @@ __device__ __forceinline__ void mfma_owner_mirror(const SweepArgs& A, int myc, i
   for (int v = 1; v <= nsteps; v++) {
     const double tot = sync.total(v, [&]() { prepare(); });
     const double hq = 0.5 * tot;
-    const double f1 = (pre_ok && mfr_div_safe(hq)) ? (-pre_nt1 - div_finish(hq, pre_ss, pre_rs)) : logpost_of(tot, readlane_d(th1, k - 1));
+    const double f1 = (pre_ok && mfr_div_safe(hq)) ? (-pre_nt1 - div_finish(hq, pre_ss, pre_rs)) : linreg_logpost(tot, readlane_d(th1, k - 1), dn, A.guard);
     bool st_row = false;
     double st_th0 = 0.0;
     const double st_dr = th1;
@@ -902,7 +859,7 @@ __device__ __forceinline__ void mfma_owner_mirror(const SweepArgs& A, int myc, i
         flush_bits(i);
       } else {
         const double lu = lu_nx;
-        lu_nx = lu_row[v < nsteps ? v : nsteps - 1];
+        lu_nx = fed.logu(v);
         bool moved = false;
         th_prev = th0;                          // (row i - 1, the row before the one decided now)
         if (lu < ratio) {
@@ -923,7 +880,7 @@ __device__ __forceinline__ void mfma_owner_mirror(const SweepArgs& A, int myc, i
       if (status == FMCMC_CHAIN_OK) {
         const int i = v + 1;
         const double z = z_nx;
-        z_nx = rl ? ld_z(v + 1 < nsteps ? v + 1 : nsteps - 1) : 0.0;
+        z_nx = rl ? fed.z(v + 1) : 0.0;
         if (abs_iter >= 1 && abs_iter <= A.warmup) mmu = over_den(mmu * (double)abs_iter + th0);   // mean_recursive(ans[i-1, ], mu, abs_iter)
         if (abs_iter == A.nadapt) {   // the one-off scale adaptation (the closure reads its argument `nadapt`)
           obs_arate = 1.0 - (double)nzero / (double)(i - 2);
@@ -968,12 +925,8 @@ __device__ __forceinline__ void mfma_owner_mirror(const SweepArgs& A, int myc, i
     A.mirror_scale[(long long)cl * k + lane] = msc;
     A.obs_arate[(long long)cl * k + lane] = obs_arate;
   }
-  if (lane == 0) {
-    A.f0[cl] = f0;
-    A.accept_count[cl] = nacc;
-    if (status == FMCMC_CHAIN_OK) { A.status[cl] = FMCMC_CHAIN_OK; A.status_step[cl] = 0; }
-    A.abs_iter[cl] = abs_iter;
-  }
+  owner_writeback(A, cl, lane, f0, nacc, status);
+  if (lane == 0) A.abs_iter[cl] = abs_iter;
 }
 
 // The compute role of mh_sweep_spec for OPT (even) observation slots of P covariates per lane: one instantiation per slot count,
@@ -1276,42 +1229,19 @@ __global__ __launch_bounds__(SPEC_NT) void mh_sweep_spec(const SweepArgs A) {
   double th0 = plane ? A.theta0[(long long)cl * k + lane] : 0.0;
   double th1 = th0;
   double f0 = 0.0;
-  // (a continuation window of a long call takes over what the windows before it left: SweepArgs.win_cont, mh_common.hpp)
-  int nacc = 0;                               // (per launch: launch_sweep adds the windows up)
-  int status = A.win_cont ? A.status[cl] : FMCMC_CHAIN_OK, thin_ctr = A.thin_ctr0;
+  const WindowCarry w0 = window_carry(A, cl);
+  int nacc = 0, status = w0.status, thin_ctr = w0.thin_ctr;
   unsigned int bitword = 0;
-  // (row stores and variates: wave-uniform 64-bit bases of the chain's own blocks + 32-bit offsets -- 32-bit offsets from the
-  //  BUFFER bases capped a call at 4 GiB)
-  // (wave-uniform 64-bit bases -- the chain's block -- plus a 32-bit byte offset per lane: one scalar-base store each)
   char* const s_base = reinterpret_cast<char*>(A.samples) + ((long long)cl * k) * A.ldS * 8;
   char* const d_base = A.draws ? reinterpret_cast<char*>(A.draws) + ((long long)cl * k) * A.ldS * 8 : nullptr;
   char* const l_base = A.logpost ? reinterpret_cast<char*>(A.logpost) + (long long)cl * A.ldS * 8 : nullptr;
   const unsigned int lane_off = (unsigned int)((long long)jl * A.ldS * 8);
   unsigned int srow8 = 0;
-  const char* const z_base = reinterpret_cast<const char*>(A.fed_z) + ((long long)cl * nsteps) * kz * 8;   // wave-uniform
-  const unsigned int z_lane = (unsigned int)(zidx) * 8u;
-  const double* const lu_row = A.fed_logu + (long long)cl * nsteps;
+  const ChainStream fed = chain_stream(A, cl, kz, zidx);
   const double dn = uniform_d((double)A.n);
-  auto ld_z = [&](int row) -> double {
-    return *reinterpret_cast<const double*>(z_base + (z_lane + (unsigned int)row * (unsigned int)(kz * 8)));
-  };
-  double z_nx = (plane && !fixed_l && nsteps >= 2) ? ld_z(1) : 0.0;   // variates of the NEXT proposal / decision
-  double lu_nx = (nsteps >= 2) ? lu_row[1] : 0.0;
+  double z_nx = (plane && !fixed_l && nsteps >= 2) ? fed.z(1) : 0.0;   // variates of the NEXT proposal / decision
+  double lu_nx = (nsteps >= 2) ? fed.logu(1) : 0.0;
 
-  auto logpost_of = [&](double tot, double sigma) -> double {
-    double f;
-    if (sigma < 0.0 || fmh_isnan(sigma)) {
-      f = fmh_nan();
-    } else if (sigma == 0.0) {
-      f = -fmh_inf();
-    } else {
-      double t1 = fmh_log(sigma) + FMH_K(FMH_LN_SQRT_2PI);
-      double q = (0.5 * tot) / (sigma * sigma);
-      f = -(dn * t1) - q;
-    }
-    if (A.guard && !fmh_isfinite(f)) f = -fmh_inf();
-    return f;
-  };
   auto flush_bits = [&](int i) {
     if (A.accept_bits && lane == 0) {   // (bits_stride: words per chain of the whole call's bitmap, set by launch_sweep for every launch)
       unsigned int* w = A.accept_bits + ((long long)cl * A.bits_stride + ((i - 1) >> 5));
@@ -1351,7 +1281,7 @@ __global__ __launch_bounds__(SPEC_NT) void mh_sweep_spec(const SweepArgs A) {
       if (A.prior_div != 0.0) f1 = f1 - pri1;
       if (A.guard && !fmh_isfinite(f1)) f1 = -fmh_inf();
     } else {
-      f1 = logpost_of(tot, readlane_d(th1, k - 1));
+      f1 = linreg_logpost(tot, readlane_d(th1, k - 1), dn, A.guard);
     }
     const double th1_eval = th1;
     bool keep_row = false;
@@ -1367,7 +1297,7 @@ __global__ __launch_bounds__(SPEC_NT) void mh_sweep_spec(const SweepArgs A) {
         flush_bits(v);
       } else {
         const double lu = lu_nx;
-        lu_nx = lu_row[v < nsteps ? v : nsteps - 1];   // log u of step v + 1 (clamped), consumed a step later
+        lu_nx = fed.logu(v);   // log u of step v + 1 (clamped), consumed a step later
         if (lu < ratio) {
           th0 = th1;
           f0 = uniform_d(f1);
@@ -1385,7 +1315,7 @@ __global__ __launch_bounds__(SPEC_NT) void mh_sweep_spec(const SweepArgs A) {
         if (!fixed_l) {
           t = th0 + (s_par[0 * PIPE_KMAX + lane] + s_par[1 * PIPE_KMAX + lane] * z_nx);
           if (KIND == FMCMC_KERNEL_NORMAL_REFLECTIVE) t = reflect1(t, s_par[2 * PIPE_KMAX + lane], s_par[3 * PIPE_KMAX + lane]);
-          z_nx = ld_z(v + 1 < nsteps ? v + 1 : nsteps - 1);   // row of step v + 2 (clamped), awaited a step later
+          z_nx = fed.z(v + 1);   // row of step v + 2 (clamped), awaited a step later
         }
         th1 = t;
         s_th1[myc * PIPE_KMAX + lane] = t;
@@ -1416,11 +1346,7 @@ __global__ __launch_bounds__(SPEC_NT) void mh_sweep_spec(const SweepArgs A) {
   }
   // ---- write state back
   if (plane) A.theta0[(long long)cl * k + lane] = th0;
-  if (lane == 0) {
-    A.f0[cl] = f0;
-    A.accept_count[cl] = nacc;   // (of THIS launch: launch_sweep adds the windows up)
-    if (status == FMCMC_CHAIN_OK) { A.status[cl] = FMCMC_CHAIN_OK; A.status_step[cl] = 0; }
-  }
+  owner_writeback(A, cl, lane, f0, nacc, status);
 }
 
 size_t spec_logit_lds_bytes(bool adaptive) {

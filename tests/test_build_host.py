@@ -98,6 +98,21 @@ def test_a_header_newer_than_the_objects_compiles_the_units_that_include_it(tmp_
     assert build(tmp_path, monkeypatch, fake, ["-DA"]) == sorted(includes_it)
 
 
+def test_a_header_included_by_a_header_is_a_dependency_of_every_unit_behind_it():
+    # mh_owner.hpp is included by headers only: a unit reaches it through mh_spec.hpp, mh_mfma.hpp or mh_lat.hpp
+    hdr = os.path.join(B.CSRC, "mh_owner.hpp")
+    assert hdr in B.deps()
+    through = {os.path.join(B.CSRC, h) for h in ("mh_spec.hpp", "mh_mfma.hpp", "mh_lat.hpp")}
+    reached = set()
+    for src in B.sources():
+        d = B.unit_deps(src)
+        assert (hdr in d) == bool(through & d), src
+        if hdr in d:
+            reached.add(os.path.basename(src))
+    assert {"k_spec.hip", "k_mfma_ad.hip", "k_logit2.hip", "k_mfma.hip", "k_lat.hip"} <= reached
+    assert "k_fun.hip" not in reached and "gelman.hip" not in reached
+
+
 def test_heavy_orders_the_compiles_and_a_stale_name_in_it_raises(tmp_path, monkeypatch, fake):
     build(tmp_path, monkeypatch, fake, ["-DA"])
     monkeypatch.setattr(B, "HEAVY", ("k_fun", "k_spec_m", "gelman"))
