@@ -30,7 +30,8 @@ EXPORTS = ["fmcmc_abi_version", "fmcmc_last_error", "fmcmc_last_kernel", "fmcmc_
            "fmcmc_summary_work_len", "fmcmc_summary_pooled_len", "fmcmc_summary_dev",
            "fmcmc_heidel_work_len", "fmcmc_heidel_out_len", "fmcmc_heidel_dev", "fmcmc_plan_route",
            "fmcmc_chain_order_work_len", "fmcmc_chain_order_dev", "fmcmc_raftery_work_len", "fmcmc_raftery_out_len",
-           "fmcmc_raftery_dev", "fmcmc_hpd_work_len", "fmcmc_hpd_dev", "fmcmc_autocov_out_len", "fmcmc_autocov_dev"]
+           "fmcmc_raftery_dev", "fmcmc_hpd_work_len", "fmcmc_hpd_dev", "fmcmc_autocov_out_len", "fmcmc_autocov_dev",
+           "fmcmc_logpost_dev", "fmcmc_validate_user", "fmcmc_mcmc_run_user_dev"]
 SUMMARY_MAX_PROBS = 16
 CHAIN_ORDER_MAX_RANKS = 2 * SUMMARY_MAX_PROBS
 RAFTERY_MAX_THINNINGS = 32     # thinnings per fmcmc_raftery_dev call
@@ -39,6 +40,18 @@ AUTOCOV_MAX_LAGS = 32          # lags per fmcmc_autocov_dev call
 
 # fmcmc_logpost_fn: out[c] = log f(theta[c][0..k-1]) for c < nchains; 0 = ok (theta, out, hip_stream, user: addresses)
 LOGPOST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p)
+
+
+class StepEnv(C.Structure):
+    """fmcmc_step_env: what a user-defined kernel's callbacks see of a loop step (device addresses)."""
+    _fields_ = [("i", C.c_int64), ("nsteps", C.c_int64), ("nchains", C.c_int64), ("chain_base", C.c_int64),
+                ("step_base", C.c_int64), ("k", C.c_int32), ("theta0", C.c_void_p), ("theta1", C.c_void_p),
+                ("f0", C.c_void_p), ("f1", C.c_void_p), ("status", C.c_void_p)]
+
+
+# fmcmc_proposal_fn / fmcmc_logratio_fn: (env, out, hip_stream, user) -> 0 = ok
+STEP_FN = C.CFUNCTYPE(C.c_int, C.POINTER(StepEnv), C.c_void_p, C.c_void_p, C.c_void_p)
+PROPOSAL_FN = LOGRATIO_FN = STEP_FN
 
 
 class Model(C.Structure):
@@ -117,6 +130,13 @@ def lib():
         L.fmcmc_mcmc_run_fun_host.restype = C.c_int
         L.fmcmc_mcmc_run_fun_host.argtypes = [C.POINTER(Kernel), C.POINTER(Run), C.POINTER(State), C.POINTER(Out),
                                               LOGPOST_FN, C.c_void_p, C.c_int]
+        L.fmcmc_logpost_dev.restype = C.c_int
+        L.fmcmc_logpost_dev.argtypes = [C.POINTER(Model), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.fmcmc_validate_user.restype = C.c_int
+        L.fmcmc_validate_user.argtypes = [C.POINTER(Run), C.c_int32]
+        L.fmcmc_mcmc_run_user_dev.restype = C.c_int
+        L.fmcmc_mcmc_run_user_dev.argtypes = [C.POINTER(Model), LOGPOST_FN, PROPOSAL_FN, LOGRATIO_FN, C.c_void_p, C.c_int32,
+                                              C.POINTER(Run), C.POINTER(State), C.POINTER(Out), C.c_void_p]
         L.fmcmc_gelman_partial_len.restype = C.c_int64
         L.fmcmc_gelman_partial_len.argtypes = [C.c_int32]
         L.fmcmc_gelman_partial_dev.restype = C.c_int

@@ -1,5 +1,5 @@
 // mh_engine.hip — gfx950 (MI355X) many-chain Metropolis-Hastings engine: the C-ABI (include/fmcmc_amd.h), validation, the
-// launcher (launch_sweep: executes the plan of mh_route.hpp's plan_route, one function per form) and the callback sweep (run_fun).
+// launcher (launch_sweep: executes the plan of mh_route.hpp's plan_route, one function per form) and the callback sweeps (run_fun; run_user).
 // Two headers belong to this unit alone: mh_prep.hpp (the data-preparation kernels launch_sweep enqueues) and mh_host.hpp (the
 // staging of the host-pointer entry points).  The sweep kernels are instantiated in the k_*.hip translation units (compiled in
 // parallel, fmcmc_amd/build.py) and reached through the look-ups of mh_kernels.hpp; their source is in the headers:
@@ -39,6 +39,7 @@
 #include "mh_bigk.hpp"
 #include "mh_route.hpp"   // (kernel selection: plan_route)
 #include "mh_fun.hpp"     // (the callback path: FunArgs, its LDS size; mh_fun_step is instantiated in k_fun.hip)
+#include "mh_user.hpp"    // (a caller-defined transition kernel: UserArgs, EvalArgs; the kernels are instantiated in k_fun.hip)
 #include "mh_prep.hpp"    // (the data-preparation kernels the launcher enqueues in front of a sweep)
 
 static thread_local const char* g_kernel = "";
@@ -192,13 +193,8 @@ int fmcmc_validate(const fmcmc_model* m, const fmcmc_kernel* kn, const fmcmc_run
       return FMCMC_ERR_UNSUPPORTED;
     }
   }
-  int kexp = -1;
-  switch (m->family) {
-    case FMCMC_FAM_GAUSSIAN_LINREG: kexp = (m->intercept ? 1 : 0) + m->p + 1; break;
-    case FMCMC_FAM_LOGISTIC: kexp = (m->intercept ? 1 : 0) + m->p; break;
-    case FMCMC_FAM_IID_NORMAL: kexp = 2; break;
-    default: set_err("unknown log-posterior family %d", m->family); return FMCMC_ERR_ARG;
-  }
+  const int kexp = eval_params(m->family, m->p, m->intercept);
+  if (kexp < 0) { set_err("unknown log-posterior family %d", m->family); return FMCMC_ERR_ARG; }
   if (kexp != kn->k) {
     set_err("Incorrect length of -initial-: the model has %d parameters, the kernel %d.", kexp, kn->k);
     return FMCMC_ERR_ARG;
@@ -825,6 +821,136 @@ static int run_fun(const fmcmc_kernel* kn, const uint8_t* fx, const double* lb, 
 }
 
 
+// ==============================================================================================
+// user-defined transition kernels: the step cut at the proposal as well (fmcmc_proposal_fn / fmcmc_logratio_fn; mh_user.hpp)
+// ==============================================================================================
+// the model of an evaluation: its family, its shape and the pointers logpost_eval_kernel reads
+static int check_eval_model(const fmcmc_model* m) {
+  const int k = eval_params(m->family, m->p, m->intercept);
+  if (k < 0) { set_err("unknown log-posterior family %d", m->family); return FMCMC_ERR_ARG; }
+  if (m->p < 0 || k < 1 || k > FMCMC_MAX_K) { set_err("number of parameters k=%d outside [1, %d]", k, FMCMC_MAX_K); return FMCMC_ERR_UNSUPPORTED; }
+  if (m->n < 1) { set_err("the model needs at least one observation"); return FMCMC_ERR_ARG; }
+  if (!m->y || (m->p > 0 && m->family != FMCMC_FAM_IID_NORMAL && !m->X)) { set_err("the model's data pointers are null"); return FMCMC_ERR_ARG; }
+  return FMCMC_OK;
+}
+
+// The families' evaluator at caller-given points: prepare() once per call of an entry point (the logistic sums, into the call's
+// scratch), enqueue() per batch of C parameter vectors.
+struct EvalCall {
+  EvalArgs E;
+  const void* kfn = nullptr;
+  int prepare(const fmcmc_model* m, ScratchList& scratch, hipStream_t stream) {
+    memset(&E, 0, sizeof(E));
+    E.family = m->family; E.p = m->p; E.intercept = m->intercept ? 1 : 0; E.guard = m->guard ? 1 : 0;
+    E.n = m->n; E.prior_div = m->prior_div; E.X = m->X; E.y = m->y;
+    kfn = fmh::k_logpost_eval();
+    if (!kfn) { set_err("no device kernel for the batched evaluation"); return FMCMC_ERR_DEVICE; }
+    if (m->family == FMCMC_FAM_LOGISTIC) {
+      double* hs = nullptr;
+      const int rh = scratch.grab(&hs, sizeof(double) * (size_t)(2 * MAXK + 2), "logistic sums");
+      if (rh != FMCMC_OK) return rh;
+      hipLaunchKernelGGL(logit_hs_kernel, dim3(1), dim3(NT), 0, stream, m->X, m->y, (long long)m->n, m->p, m->intercept ? 1 : 0, hs);
+      E.hs = hs;
+    }
+    return FMCMC_OK;
+  }
+  hipError_t enqueue(const double* theta, long long C, double* out, hipStream_t stream) {
+    E.theta = theta; E.nchains = C; E.out = out;
+    void* kargs[] = {(void*)&E};
+    hipError_t e = hipLaunchKernel(kfn, dim3((unsigned)C), dim3(NT), kargs, 0, stream);
+    return e == hipSuccess ? hipGetLastError() : e;
+  }
+};
+
+// run_fun's loop with the proposal outside (R/mcmc.R:737-783).  Every pointer of run / st / out is a DEVICE pointer.
+static int run_user(const fmcmc_model* m, fmcmc_logpost_fn fun, fmcmc_proposal_fn proposal, fmcmc_logratio_fn logratio, void* user,
+                    int k, const fmcmc_run* run, fmcmc_state* st, fmcmc_out* out, hipStream_t stream) {
+  const long long C = run->nchains, nsteps = run->nsteps;
+  UserArgs A;
+  memset(&A, 0, sizeof(A));
+  A.k = k; A.rng_mode = run->rng_mode; A.nchains = C; A.nsteps = nsteps; A.burnin = run->burnin; A.thin = run->thin;
+  const long long S = fmcmc_kept_rows(run->nsteps, run->burnin, run->thin);
+  A.ldS = out->ld_rows > 0 ? out->ld_rows : S;
+  if (A.ldS < S) { set_err("fmcmc_out.ld_rows (%lld) is smaller than the %lld kept rows of this call", (long long)out->ld_rows, S); return FMCMC_ERR_ARG; }
+  A.chain_base = run->chain_base; A.step_base = run->step_base; A.seed = run->seed; A.fed_logu = run->fed_logu;
+  A.theta0 = st->theta0; A.f0 = st->f0;
+  A.samples = out->samples; A.logpost = out->logpost; A.draws = out->draws; A.accept_count = (long long*)out->accept_count;
+  A.accept_bits = (unsigned int*)out->accept_bits; A.status = out->status; A.status_step = (long long*)out->status_step;
+  A.status_theta = out->status_theta;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  int rc = require_gfx950(dev);
+  if (rc != FMCMC_OK) return rc;
+  // scratch of the call: two theta1 [C][k] (the proposal callback reads the last proposal while it writes the new one),
+  // f(theta1) [C], the caller's log-ratio [C]
+  const size_t n_th = (size_t)C * k, bytes = sizeof(double) * (2 * n_th + (size_t)C * (logratio ? 2 : 1));
+  ScratchList scratch(stream);
+  double* thb[2] = {nullptr, nullptr};
+  if (scratch.grab(&thb[0], bytes, nullptr) != FMCMC_OK) {
+    set_err("hipMallocAsync(%zu) for the user-kernel sweep failed", bytes);
+    return FMCMC_ERR_DEVICE;
+  }
+  thb[1] = thb[0] + n_th;
+  double* f1 = thb[1] + n_th;
+  double* lr = logratio ? f1 + C : nullptr;
+  EvalCall ev;
+  if (m) {
+    rc = ev.prepare(m, scratch, stream);
+    if (rc != FMCMC_OK) return rc;
+  }
+  const int nth = (k <= FMCMC_MAX_K_WAVE) ? 64 : 256;
+  const void* kfn = fmh::k_user(nth);
+  if (!kfn) { set_err("no device kernel for the user-kernel sweep (k=%d)", k); return FMCMC_ERR_DEVICE; }
+  g_kernel = (nth == 64) ? "user" : "user-wg";
+  auto evaluate = [&](const double* th, long long step) -> int {
+    if (m) {
+      const hipError_t e = ev.enqueue(th, C, f1, stream);
+      if (e != hipSuccess) { set_err("HIP launch failed at loop step i = %lld: %s", step, hipGetErrorString(e)); return FMCMC_ERR_DEVICE; }
+      return FMCMC_OK;
+    }
+    const int rf = fun(th, (int64_t)C, (int32_t)k, f1, (void*)stream, user);
+    if (rf != 0) {
+      set_err("the log-posterior callback returned %d at loop step i = %lld%s", rf, step, step == 1 ? " (row 1: the initial values)" : "");
+      return FMCMC_ERR_FUN;
+    }
+    return FMCMC_OK;
+  };
+  auto launch = [&](const double* th, long long step, int phase) -> int {
+    A.th1 = th; A.f1 = f1; A.logratio = (phase == UPH_ACCEPT) ? lr : nullptr; A.step = step; A.phase = phase;
+    void* kargs[] = {(void*)&A};
+    hipError_t e = hipLaunchKernel(kfn, dim3((unsigned)C), dim3((unsigned)nth), kargs, 0, stream);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) { set_err("HIP launch failed at loop step i = %lld: %s", step, hipGetErrorString(e)); return FMCMC_ERR_DEVICE; }
+    return FMCMC_OK;
+  };
+  // row 1: f0 = f(initial), theta1 = theta0 and f1 = f0, as the reference initialises them
+  (void)hipMemcpyAsync(thb[0], st->theta0, sizeof(double) * n_th, hipMemcpyDeviceToDevice, stream);
+  rc = evaluate(thb[0], 1);
+  if (rc == FMCMC_OK) rc = launch(thb[0], 1, UPH_START);
+  fmcmc_step_env env;
+  memset(&env, 0, sizeof(env));
+  env.nsteps = nsteps; env.nchains = C; env.chain_base = run->chain_base; env.step_base = run->step_base; env.k = k;
+  env.theta0 = st->theta0; env.f0 = st->f0; env.f1 = f1; env.status = out->status;
+  int cur = 0;   // the buffer that holds the last proposal
+  for (long long i = 2; i <= nsteps && rc == FMCMC_OK; i++) {
+    double* next = thb[cur ^ 1];
+    env.i = i; env.theta1 = thb[cur];
+    int rp = proposal(&env, next, (void*)stream, user);
+    if (rp != 0) { set_err("the proposal callback returned %d at loop step i = %lld", rp, i); return FMCMC_ERR_FUN; }
+    cur ^= 1;
+    env.theta1 = next;
+    rc = evaluate(next, i);
+    if (rc != FMCMC_OK) break;
+    if (logratio) {
+      rp = logratio(&env, lr, (void*)stream, user);
+      if (rp != 0) { set_err("the logratio callback returned %d at loop step i = %lld", rp, i); return FMCMC_ERR_FUN; }
+    }
+    rc = launch(next, i, UPH_ACCEPT);
+  }
+  return rc;
+}
+
+
 #include "mh_host.hpp"   // (the staging of the two *_host entry points)
 
 extern "C" {
@@ -985,6 +1111,53 @@ int fmcmc_mcmc_run_fun_host(const fmcmc_kernel* kn, const fmcmc_run* run, fmcmc_
   stage_call(H, kn, run, st, out);
   if (H.rc == FMCMC_OK) H.rc = run_fun(&H.dk, kn->fixed, kn->lb, kn->ub, &H.dr, &H.ds, &H.dout, fun, user, H.stream, true);
   return fetch_call(H, kn, run, st, out);
+}
+
+int fmcmc_logpost_dev(const fmcmc_model* m, const double* theta, int64_t nchains, double* out, void* hip_stream) {
+  if (!m || !theta || !out) { set_err("null argument"); return FMCMC_ERR_ARG; }
+  if (nchains < 1) { set_err("`nchains` must be an integer greater than 1."); return FMCMC_ERR_ARG; }
+  int rc = check_eval_model(m);
+  if (rc != FMCMC_OK) return rc;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  rc = require_gfx950(dev);
+  if (rc != FMCMC_OK) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  ScratchList scratch(stream);
+  EvalCall ev;
+  rc = ev.prepare(m, scratch, stream);
+  if (rc != FMCMC_OK) return rc;
+  const hipError_t e = ev.enqueue(theta, nchains, out, stream);
+  if (e != hipSuccess) { set_err("HIP launch failed: %s", hipGetErrorString(e)); return FMCMC_ERR_DEVICE; }
+  return FMCMC_OK;
+}
+
+int fmcmc_validate_user(const fmcmc_run* run, int32_t k) {
+  if (!run) { set_err("null argument"); return FMCMC_ERR_ARG; }
+  fmcmc_kernel kn;
+  memset(&kn, 0, sizeof(kn));
+  kn.k = k;
+  const int rr = validate_run(&kn, run);
+  if (rr != FMCMC_OK) return rr;
+  if (run->rng_mode == FMCMC_RNG_FED && !run->fed_logu) { set_err("rng_mode = FED needs fed_logu"); return FMCMC_ERR_ARG; }
+  return FMCMC_OK;
+}
+
+int fmcmc_mcmc_run_user_dev(const fmcmc_model* m, fmcmc_logpost_fn fun, fmcmc_proposal_fn proposal, fmcmc_logratio_fn logratio,
+                            void* user, int32_t k, const fmcmc_run* run, fmcmc_state* st, fmcmc_out* out, void* hip_stream) {
+  if (!run || !st || !out) { set_err("null argument"); return FMCMC_ERR_ARG; }
+  if (!proposal) { set_err("null proposal callback"); return FMCMC_ERR_ARG; }
+  if (!m && !fun) { set_err("null log-posterior callback"); return FMCMC_ERR_ARG; }
+  if (!st->theta0 || !st->f0) { set_err("a user-defined kernel needs state->theta0 and f0"); return FMCMC_ERR_ARG; }
+  int rc = fmcmc_validate_user(run, k);
+  if (rc != FMCMC_OK) return rc;
+  if (m) {
+    rc = check_eval_model(m);
+    if (rc != FMCMC_OK) return rc;
+    const int kexp = eval_params(m->family, m->p, m->intercept);
+    if (kexp != k) { set_err("Incorrect length of -initial-: the model has %d parameters, the kernel %d.", kexp, k); return FMCMC_ERR_ARG; }
+  }
+  return run_user(m, fun, proposal, logratio, user, k, run, st, out, (hipStream_t)hip_stream);
 }
 
 }  // extern "C"

@@ -50,4 +50,8 @@ FMH_HIDDEN const void* k_wide2(int kind, int nmt);
 FMH_HIDDEN const void* k_bigk(int hbm);
 // k_fun.hip: mh_fun_step<NTH> (mh_fun.hpp), the steps around a caller-evaluated log-posterior: nth = 64 (k <= 64), 256 (k > 64)
 FMH_HIDDEN const void* k_fun(int nth);
+// k_fun.hip: mh_user_step<NTH> (mh_user.hpp), the accept / store step of a caller-defined transition kernel, at the same widths;
+// logpost_eval_kernel, the families' log-posterior at caller-given points (one workgroup of 512 threads per chain)
+FMH_HIDDEN const void* k_user(int nth);
+FMH_HIDDEN const void* k_logpost_eval();
 }  // namespace fmh

@@ -1,0 +1,183 @@
+// mh_user.hpp -- the device half of a USER-DEFINED transition kernel (fmcmc_mcmc_run_user_dev; R/kernel.R:136-317, kernel_new):
+//   mh_user_step<NTH>     the accept / store half of mh_fun_step (mh_fun.hpp) and nothing else.  The callback path cuts the step
+//                         at the evaluation; a user kernel cuts it once more, at the proposal: theta1 [C][k] comes from the
+//                         caller's proposal callback, f1 [C] from the evaluation, the log-ratio [C] from the caller's logratio
+//                         callback (none: f1 - f0 formed here, the decision of the built-in kernels bit for bit).
+//                           [START]   row 1: f0 = f(initial), theta1 = theta0, the row stored, status / accept bits reset
+//                           [ACCEPT]  step i: NaN checks, log u < ratio, theta0 / f0, the kept row, draws, logpost, accept bit
+//                                     (R/mcmc.R:754-778)
+//                         No proposal, no adaptation, no Sigma.  Layout of mh_fun_step: one workgroup per chain, thread r =
+//                         parameter r; NTH = 64 (k <= 64, "user") or 256 ("user-wg").  Nothing is kept in LDS: a thread holds its
+//                         parameter of theta0 / theta1, the chain's scalars are uniform.
+//   logpost_eval_kernel   the three families' canonical log-posterior of C caller-given parameter vectors, out[c] = f(theta[c, ]):
+//                         the oracle's logpost_canon (fmcmc_oracle.c) bit for bit.  One workgroup of NT = 512 threads per chain,
+//                         thread = canonical lane: lane l accumulates the observations i = l, l + 512, .. in index order, the
+//                         lanes combine by the xor butterfly (wave_xor_sum, then the eight waves' values pairwise), thread 0
+//                         evaluates the closed form.  X column-major [p][n]: a wavefront reads 64 consecutive doubles of a
+//                         column; the coefficients are broadcast from LDS.
+// Compiled into k_fun.hip only (FMH_WITH_FUN_KERNEL); mh_engine.hip includes the argument structs.
+#pragma once
+
+namespace {
+
+struct UserArgs {
+  int k, rng_mode;
+  long long nchains, nsteps, burnin, thin, ldS, chain_base, step_base;
+  unsigned long long seed;
+  const double* fed_logu;
+  // state
+  double* theta0;
+  double* f0;
+  // out
+  double* samples;
+  double* logpost;
+  double* draws;
+  long long* accept_count;
+  unsigned int* accept_bits;
+  int* status;
+  long long* status_step;
+  double* status_theta;
+  // the caller's proposal [C][k], its evaluation [C] and the caller's log-ratio [C] (nullptr: f1 - f0)
+  const double* th1;
+  const double* f1;
+  const double* logratio;
+  // this launch
+  long long step;            // the loop step whose proposal has been evaluated (1: row 1)
+  int phase;                 // UPH_*
+};
+
+enum { UPH_START = 1, UPH_ACCEPT = 2 };
+
+struct EvalArgs {
+  int family, p, intercept, guard;
+  long long n, nchains;
+  double prior_div;
+  const double* X;           // [p][n]
+  const double* y;           // [n]
+  const double* hs;          // logistic: the data-only sums of logit_hs_kernel (mh_prep.hpp)
+  const double* theta;       // [C][k]
+  double* out;               // [C]
+};
+
+__host__ __device__ inline int eval_params(int family, int p, int intercept) {   // k of a family
+  return family == FMCMC_FAM_GAUSSIAN_LINREG ? (intercept ? 1 : 0) + p + 1 : family == FMCMC_FAM_LOGISTIC ? (intercept ? 1 : 0) + p
+       : family == FMCMC_FAM_IID_NORMAL ? 2 : -1;
+}
+
+#ifdef FMH_WITH_FUN_KERNEL   /* compiled into k_fun.hip only */
+template <int NTH>
+__global__ __launch_bounds__(NTH) void mh_user_step(const UserArgs A) {
+  const int r = threadIdx.x, k = A.k;
+  const long long c = blockIdx.x;            // one chain per workgroup (grid = nchains)
+  const long long i = A.step;
+  const bool par = r < k, start = A.phase == UPH_START;
+  const double th1 = par ? A.th1[c * k + r] : 0.0;
+  double th0 = par ? A.theta0[c * k + r] : 0.0;
+  // ---- the chain's carried values (uniform: every thread keeps them)
+  int status = start ? FMCMC_CHAIN_OK : A.status[c];
+  double f0 = start ? A.f1[c] : A.f0[c];
+  long long nacc = start ? 0 : A.accept_count[c];
+  const long long nwords = (A.nsteps + 31) >> 5;
+  auto store_row = [&](long long ir, double lpv) {   // row ir of ans: kept when ir > burnin and (ir - burnin) mod thin == 0
+    if (ir > A.burnin && (ir - A.burnin) % A.thin == 0) {
+      const long long s = (ir - A.burnin) / A.thin - 1;
+      if (par) {
+        A.samples[(c * k + r) * A.ldS + s] = th0;
+        if (A.draws) A.draws[(c * k + r) * A.ldS + s] = th1;
+      }
+      if (A.logpost && r == 0) A.logpost[c * A.ldS + s] = lpv;
+    }
+  };
+  __syncthreads();   // (every wave has read the status before thread 0 writes it)
+
+  if (start) {   // row 1 (R/mcmc.R:728-735)
+    if (A.accept_bits)
+      for (long long w = r; w < nwords; w += NTH) A.accept_bits[c * nwords + w] = 0u;
+    if (r == 0) { A.status[c] = FMCMC_CHAIN_OK; A.status_step[c] = 0; }
+    store_row(1, f0);
+  } else if (status == FMCMC_CHAIN_OK) {   // accept / store of step i (R/mcmc.R:754-778)
+    const double f1 = A.f1[c];
+    if (fmh_isnan(f1)) status = FMCMC_CHAIN_NAN_LOGPOST;
+    const double ratio = A.logratio ? A.logratio[c] : f1 - f0;
+    if (status == FMCMC_CHAIN_OK && fmh_isnan(ratio)) status = FMCMC_CHAIN_NAN_RATIO;
+    if (status != FMCMC_CHAIN_OK) {
+      if (r == 0) { A.status[c] = status; A.status_step[c] = i; }
+      if (par) A.status_theta[c * k + r] = th1;
+    } else {
+      const double lu = (A.rng_mode == FMCMC_RNG_FED) ? A.fed_logu[c * A.nsteps + (i - 1)]
+                                                      : fmh_log_accept_u(A.seed, (unsigned int)(A.step_base + i), (unsigned int)(A.chain_base + c));
+      if (lu < ratio) {
+        th0 = th1;
+        f0 = f1;
+        nacc += 1;
+        if (A.accept_bits && r == 0) A.accept_bits[c * nwords + ((i - 1) >> 5)] |= (1u << ((i - 1) & 31));
+      }
+      store_row(i, f1);
+    }
+  }
+
+  // ---- carried values back to HBM
+  if (par) A.theta0[c * k + r] = th0;
+  if (r == 0) {
+    A.f0[c] = f0;
+    A.accept_count[c] = nacc;
+  }
+}
+
+__global__ __launch_bounds__(NT) void logpost_eval_kernel(const EvalArgs A) {
+  __shared__ double s_th[MAXK], s_w[NW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long c = blockIdx.x, n = A.n;   // one chain per workgroup (grid = nchains)
+  const bool logit = A.family == FMCMC_FAM_LOGISTIC;
+  const int pp = (A.family == FMCMC_FAM_IID_NORMAL) ? 0 : A.p;
+  const int ic = (A.family == FMCMC_FAM_IID_NORMAL) ? 1 : A.intercept;
+  const int k = eval_params(A.family, A.p, A.intercept);
+  const double* th = A.theta + c * k;
+  // the coefficients the observation loop reads: the logistic ones scaled by 64 (exact), so that the table's reduced argument
+  // falls out of eta (include/fmh_detmath.h, fmh_logit_g_scaled)
+  for (int j = tid; j < ic + pp; j += NT) s_th[j] = logit ? th[j] * FMH_LG_SCALE : th[j];
+  __syncthreads();
+  double acc = 0.0;
+  for (long long i = tid; i < n; i += NT) {
+    double m = ic ? s_th[0] : 0.0;
+    for (int j = 0; j < pp; j++) m = fmh_fma(A.X[(long long)j * n + i], s_th[ic + j], m);
+    if (logit) {
+      acc = acc + fmh_logit_g_scaled(fmh_abs(m));
+    } else {
+      const double r = A.y[i] - m;
+      acc = fmh_fma(r, r, acc);
+    }
+  }
+  const double v = wave_xor_sum(acc);
+  if (lane == 0) s_w[wave] = v;
+  __syncthreads();
+  if (tid != 0) return;
+  const double tot = ((s_w[0] + s_w[1]) + (s_w[2] + s_w[3])) + ((s_w[4] + s_w[5]) + (s_w[6] + s_w[7]));
+  double f;
+  if (logit) {   // logl = sum_j b_j hs_j - sum_i g(|eta_i|) - sum_j b_j^2 / prior_div
+    double lin = 0.0;
+    for (int j = 0; j < k; j++) lin = fmh_fma(th[j], A.hs[j], lin);
+    f = lin - tot;
+    if (A.prior_div != 0.0) {
+      double ss = 0.0;
+      for (int j = 0; j < k; j++) ss = fmh_fma(th[j], th[j], ss);
+      f = f - ss / A.prior_div;
+    }
+  } else {
+    const double sigma = th[ic + pp];
+    if (sigma < 0.0 || fmh_isnan(sigma)) {
+      f = fmh_nan();
+    } else if (sigma == 0.0) {
+      f = -fmh_inf();
+    } else {
+      const double t1 = fmh_log(sigma) + FMH_LN_SQRT_2PI;
+      const double q = (0.5 * tot) / (sigma * sigma);
+      f = -((double)n * t1) - q;
+    }
+  }
+  if (A.guard && !fmh_isfinite(f)) f = -fmh_inf();
+  A.out[c] = f;
+}
+#endif  // FMH_WITH_FUN_KERNEL
+
+}  // namespace

@@ -66,6 +66,30 @@ class DeviceModel:
         return abi.Model(self.family, self.p, self.n, self.Xc.data_ptr() if self.Xc is not None else None,
                          self.y.data_ptr(), self.intercept, self.guard, self.prior_div)
 
+    def logpost(self, theta, out=None, stream=None):
+        """The family's canonical log-posterior of every row of theta [C, k] (a float64 tensor on this device) -> [C]
+        (fmcmc_logpost_dev): the value the sweeps evaluate, bit for bit, enqueued on `stream` (torch's current one)."""
+        if not torch.is_tensor(theta) or theta.dtype != torch.float64 or theta.ndim != 2 or theta.shape[1] != self.k or \
+                not _on(theta, self.device):
+            raise ValueError("DeviceModel.logpost: theta must be a float64 tensor of shape [C, %d] on %s; got %s" % (
+                self.k, self.device, _describe(theta)))
+        theta = theta.contiguous()
+        if out is None:
+            out = torch.empty(theta.shape[0], dtype=torch.float64, device=self.device)
+        if theta.shape[0] == 0:
+            return out
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        cm = self.c()
+        with torch.cuda.device(self.device):
+            rc = abi.lib().fmcmc_logpost_dev(C.byref(cm), theta.data_ptr(), theta.shape[0], out.data_ptr(),
+                                             C.c_void_p(stream.cuda_stream))
+        if rc in (abi.ERR_ARG, abi.ERR_UNSUPPORTED):
+            raise ValueError(abi.last_error())
+        if rc != abi.OK:
+            raise RuntimeError("fmcmc_logpost_dev failed (%d): %s" % (rc, abi.last_error()))
+        return out
+
 
 class DeviceFun:
     """A batched user-defined log-posterior (models.BatchedFun) bound to a device: what sweep() hands to
@@ -86,19 +110,33 @@ class _DevArray:
                                          "strides": None}
 
 
-def _run_fun_dev(model, ck, crun, cs, cout, stream):
-    """fmcmc_mcmc_run_fun_dev with model.fun.fn behind a ctypes trampoline: an exception raised in fn is kept, the trampoline
-    returns non-zero (the engine abandons the call, FMCMC_ERR_FUN) and the exception is raised again here.  fn runs with the
-    engine's stream as torch's current stream, so its work is ordered with the engine's launches whatever stream sweep() got."""
-    L = abi.lib()
-    dev, fn = model.device, model.fun.fn
-    caught, views = [], {}
+def _describe(t):
+    return ("%s %s on %s" % (t.dtype, tuple(t.shape), t.device)) if torch.is_tensor(t) else type(t).__name__
 
-    def view(ptr, shape):
+
+def _on(t, dev):
+    """is the tensor on `dev` (an un-indexed "cuda" names every GPU's tensors)"""
+    return t.device.type == dev.type and (dev.index is None or t.device.index == dev.index)
+
+
+class _Views:
+    """The engine's device buffers as torch tensors, one per (address, shape) of a call."""
+
+    def __init__(self, dev):
+        self.dev, self.made = dev, {}
+
+    def __call__(self, ptr, shape):
         key = (ptr, shape)
-        if key not in views:
-            views[key] = torch.as_tensor(_DevArray(ptr, shape), device=dev)
-        return views[key]
+        if key not in self.made:
+            self.made[key] = torch.as_tensor(_DevArray(ptr, shape), device=self.dev)
+        return self.made[key]
+
+
+def _logpost_trampoline(model, stream, view, caught):
+    """model.fun.fn as a fmcmc_logpost_fn: an exception raised in fn is kept in `caught` and the trampoline returns non-zero
+    (the engine abandons the call, FMCMC_ERR_FUN).  fn runs with the engine's stream as torch's current stream, so its work is
+    ordered with the engine's launches whatever stream the call got."""
+    dev, fn = model.device, model.fun.fn
 
     def trampoline(theta_p, nchains, k, out_p, stream_p, user):
         try:
@@ -107,15 +145,23 @@ def _run_fun_dev(model, ck, crun, cs, cout, stream):
                 f = fn(th)
                 if not torch.is_tensor(f) or f.dtype != torch.float64 or f.device != dev or tuple(f.shape) != (nchains,):
                     raise ValueError("batched_fun: fn(theta) must return a float64 tensor of shape [%d] on %s; got %s" % (
-                        nchains, dev, ("%s %s on %s" % (f.dtype, tuple(f.shape), f.device)) if torch.is_tensor(f)
-                        else type(f).__name__))
+                        nchains, dev, _describe(f)))
                 view(out_p, (nchains,)).copy_(f)
             return 0
         except BaseException as e:   # (nothing may unwind through the C frames)
             caught.append(e)
             return 1
 
-    cb = abi.LOGPOST_FN(trampoline)
+    return abi.LOGPOST_FN(trampoline)
+
+
+def _run_fun_dev(model, ck, crun, cs, cout, stream):
+    """fmcmc_mcmc_run_fun_dev with model.fun.fn behind a ctypes trampoline; an exception raised in fn is raised again here,
+    after the C call has returned."""
+    L = abi.lib()
+    dev = model.device
+    caught = []
+    cb = _logpost_trampoline(model, stream, _Views(dev), caught)
     with torch.cuda.device(dev):
         rc = L.fmcmc_mcmc_run_fun_dev(C.byref(ck), C.byref(crun), C.byref(cs), C.byref(cout), cb, None,
                                       C.c_void_p(stream.cuda_stream))
@@ -232,6 +278,34 @@ def sweep(model, kernel, state, nsteps, burnin=0, thin=1, seed=0, chain_base=0,
     RuntimeError for chain errors ("fun(par) is undefined", R/mcmc.R:758-765)."""
     L = abi.lib()
     dev = state.device
+    out, crun, cout = _call_buffers(state, nsteps, burnin, thin, seed, chain_base, want_logpost, want_draws, want_bits,
+                                    fed_logu, fed_z, into, row0)
+    Cn, k = state.theta0.shape
+    rng_mode = crun.rng_mode
+    if kernel.kind in abi.SIMPLE_KERNELS and kernel.scheme == abi.SCHEME_RANDOM and state.scheme_cols is None:
+        if rng_mode == abi.RNG_FED:
+            raise ValueError("rng_mode = FED with scheme = 'random' needs state.scheme_cols (the plan R drew)")
+        state.scheme_cols = torch.zeros((Cn, nsteps), dtype=torch.int32, device=dev)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev)
+    if isinstance(model, DeviceFun):
+        if k != model.k:
+            raise ValueError("Incorrect length of -initial-: the model has %d parameters, got %d." % (model.k, k))
+        # (the output buffers above were made on the current stream: the engine's stream starts behind them)
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        rc = _run_fun_dev(model, kernel.c(), crun, state.c(nsteps), cout, stream)
+    else:
+        cm, ck, cs = model.c(), kernel.c(), state.c(nsteps)
+        with torch.cuda.device(dev):
+            rc = L.fmcmc_mcmc_run_dev(C.byref(cm), C.byref(ck), C.byref(crun), C.byref(cs), C.byref(cout),
+                                      C.c_void_p(stream.cuda_stream))
+    return _finish_call(out, state, rc, "fmcmc_mcmc_run_fun_dev" if isinstance(model, DeviceFun) else "fmcmc_mcmc_run_dev",
+                        nsteps, burnin, thin, chain_base, check)
+
+
+def _call_buffers(state, nsteps, burnin, thin, seed, chain_base, want_logpost, want_draws, want_bits, fed_logu, fed_z, into, row0):
+    """The output tensors of one call (or the views of `into` it writes) with the fmcmc_run and fmcmc_out that point at them."""
+    dev = state.device
     Cn, k = state.theta0.shape
     S = kept_rows(nsteps, burnin, thin)
     if S < 0:
@@ -267,31 +341,18 @@ def sweep(model, kernel, state, nsteps, burnin=0, thin=1, seed=0, chain_base=0,
                    out.draws.data_ptr() if want_draws else None, out.accept_count.data_ptr(),
                    out.accept_bits.data_ptr() if want_bits else None, out.status.data_ptr(),
                    out.status_step.data_ptr(), out.status_theta.data_ptr(), ld)
-    if kernel.kind in abi.SIMPLE_KERNELS and kernel.scheme == abi.SCHEME_RANDOM and state.scheme_cols is None:
-        if rng_mode == abi.RNG_FED:
-            raise ValueError("rng_mode = FED with scheme = 'random' needs state.scheme_cols (the plan R drew)")
-        state.scheme_cols = torch.zeros((Cn, nsteps), dtype=torch.int32, device=dev)
-    if stream is None:
-        stream = torch.cuda.current_stream(dev)
-    if isinstance(model, DeviceFun):
-        if k != model.k:
-            raise ValueError("Incorrect length of -initial-: the model has %d parameters, got %d." % (model.k, k))
-        # (the output buffers above were made on the current stream: the engine's stream starts behind them)
-        stream.wait_stream(torch.cuda.current_stream(dev))
-        rc = _run_fun_dev(model, kernel.c(), crun, state.c(nsteps), cout, stream)
-    else:
-        cm, ck, cs = model.c(), kernel.c(), state.c(nsteps)
-        with torch.cuda.device(dev):
-            rc = L.fmcmc_mcmc_run_dev(C.byref(cm), C.byref(ck), C.byref(crun), C.byref(cs), C.byref(cout),
-                                      C.c_void_p(stream.cuda_stream))
+    return out, crun, cout
+
+
+def _finish_call(out, state, rc, entry, nsteps, burnin, thin, chain_base, check):
+    """The return code of an entry point raised as sweep() documents it; the state advanced, the result labelled."""
     if rc in (abi.ERR_ARG, abi.ERR_UNSUPPORTED):
         raise ValueError(abi.last_error())
     if rc != abi.OK:
-        entry = "fmcmc_mcmc_run_fun_dev" if isinstance(model, DeviceFun) else "fmcmc_mcmc_run_dev"
         raise RuntimeError("%s failed (%d): %s" % (entry, rc, abi.last_error()))
     state.fresh = 0
     state.step_base += nsteps
-    out.iters = burnin + thin * np.arange(1, S + 1)
+    out.iters = burnin + thin * np.arange(1, max(kept_rows(nsteps, burnin, thin), 0) + 1)
     out.thin, out.nsteps, out.burnin = thin, nsteps, burnin
     if check:
         raise_on_chain_error(out, chain_base)
@@ -325,6 +386,128 @@ def rng_stream(state, kernel, nsteps, seed=0, chain_base=0, logu=None, z=None, s
     if rc != abi.OK:
         raise RuntimeError("fmcmc_rng_stream_dev failed (%d): %s" % (rc, abi.last_error()))
     return logu, z
+
+
+RNG_BLOCK = 256   # loop steps per fill of UserEnv's variates
+
+
+class UserEnv:
+    """What proposal(env) and logratio(env) of a kernel_new() kernel see of a loop step, for ALL local chains at once
+    (R/kernel.R:169-184); one object per call, updated in place.
+
+      i, nsteps, k       R's 1-based loop index (2 .. nsteps), the steps and the parameters of the call
+      theta0, f0         [C, k], [C]: the current states and their values
+      theta1, f1         [C, k], [C]: in proposal(), the LAST proposal and its value; in logratio(), the new ones
+      chain_ids          [C] int64: the global chain ids, chain_base + c
+      kernel             the kernel object (its kernel_new(**state) are attributes, assignable)
+      f(theta)           the model at [C, k] -> [C]
+      rnorm(n) / runif(n) / rt(n, df)   [C, n]: the engine's counter-based variates of THIS step -- variate a of (seed,
+                         step_base + i, global chain) is what a built-in kernel draws in slot a, whatever the split of the
+                         chains over calls or ranks
+
+    The tensors are float64 views of the engine's device buffers: read them, never write them.  There is no env.ans (kept
+    rows are not R's rows): a kernel that needs its history keeps it in its own state."""
+
+    def __init__(self, kernel, model, state, nsteps, seed, chain_base, stream, fed):
+        self.kernel, self.nsteps, self.i = kernel, int(nsteps), 1
+        self.theta0, self.f0 = state.theta0, state.f0
+        self.theta1, self.f1 = state.theta0, state.f0
+        Cn, self.k = state.theta0.shape
+        self.chain_ids = chain_base + torch.arange(Cn, dtype=torch.int64, device=state.device)
+        self._model, self._stream, self._fed = model, stream, fed
+        self._seed, self._chain_base, self._step_base = seed & 0xFFFFFFFFFFFFFFFF, chain_base, state.step_base
+        self._blocks = {}   # (variate family, n) -> (first step of the block, z [C][1 + RNG_BLOCK][n])
+
+    def f(self, theta):
+        if isinstance(self._model, DeviceFun):
+            return self._model.fun.fn(theta)
+        return self._model.logpost(theta, stream=self._stream)
+
+    def _variates(self, n, df):
+        if self._fed:
+            raise RuntimeError("env.rnorm / env.runif / env.rt are the engine's own stream: a call with fed_logu has none.")
+        n = int(n)
+        if n < 1:
+            raise ValueError("the number of variates must be >= 1.")
+        blk = self._blocks.get((df, n))
+        if blk is None or not blk[0] <= self.i < blk[0] + RNG_BLOCK:
+            # fmcmc_rng_stream_dev fills the steps 1 .. nsteps behind a step_base and leaves step 1 (row 1 draws nothing) zero:
+            # a block that starts at loop step b0 >= 2 is the fill behind step_base + b0 - 2, its row 0 unused
+            b0 = max(self.i, 2)
+            rows = min(RNG_BLOCK, self.nsteps - b0 + 1) + 1
+            dev, Cn = self.theta0.device, self.theta0.shape[0]
+            logu = torch.empty((Cn, rows), dtype=torch.float64, device=dev)
+            z = torch.empty((Cn, rows, n), dtype=torch.float64, device=dev)
+            with torch.cuda.device(dev):
+                rc = abi.lib().fmcmc_rng_stream_dev(self._seed, self._step_base + b0 - 2, self._chain_base, Cn, rows, n, float(df),
+                                                    logu.data_ptr(), z.data_ptr(), C.c_void_p(self._stream.cuda_stream))
+            if rc != abi.OK:
+                raise RuntimeError("fmcmc_rng_stream_dev failed (%d): %s" % (rc, abi.last_error()))
+            blk = self._blocks[(df, n)] = (b0, z)
+        return blk[1][:, self.i - blk[0] + 1, :]
+
+    def rnorm(self, n):
+        return self._variates(n, 0.0)
+
+    def runif(self, n):
+        return self._variates(n, -1.0)
+
+    def rt(self, n, df):
+        df = float(df)
+        if not 0.0 < df < float("inf"):
+            raise ValueError("-df- must be finite and positive.")
+        return self._variates(n, df)
+
+
+def sweep_user(model, kernel, state, nsteps, burnin=0, thin=1, seed=0, chain_base=0, want_logpost=True, want_draws=True,
+               want_bits=True, fed_logu=None, stream=None, check=True, into=None, row0=0):
+    """sweep() under a user-defined transition kernel (kernels.kernel_new; fmcmc_mcmc_run_user_dev): per loop step
+    kernel.proposal(env) -> theta1 [C, k], the evaluation (model: a DeviceModel, evaluated by the engine, or a DeviceFun),
+    kernel.logratio(env) -> [C] when the kernel has one, and one launch of the engine's accept / store step.  The keywords and
+    the result are sweep()'s; fed_logu feeds the accept uniforms (env.rnorm / runif / rt then raise).  The callbacks run with
+    `stream` as torch's current stream; an exception raised in one ends the call and is raised again here."""
+    L = abi.lib()
+    dev = state.device
+    Cn, k = state.theta0.shape
+    if k != model.k:
+        raise ValueError("Incorrect length of -initial-: the model has %d parameters, got %d." % (model.k, k))
+    out, crun, cout = _call_buffers(state, nsteps, burnin, thin, seed, chain_base, want_logpost, want_draws, want_bits,
+                                    fed_logu, None, into, row0)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev)
+    # (the output buffers above were made on the current stream: the engine's stream starts behind them)
+    stream.wait_stream(torch.cuda.current_stream(dev))
+    env = UserEnv(kernel, model, state, nsteps, seed, chain_base, stream, fed_logu is not None)
+    caught, view = [], _Views(dev)
+
+    def step_fn(user_fn, what, shape):
+        def trampoline(env_p, out_p, stream_p, user):
+            try:
+                with torch.cuda.stream(stream):
+                    e = env_p.contents
+                    env.i, env.theta1, env.f1 = int(e.i), view(e.theta1, (Cn, k)), view(e.f1, (Cn,))
+                    t = user_fn(env)
+                    if not torch.is_tensor(t) or t.dtype != torch.float64 or not _on(t, dev) or tuple(t.shape) != shape:
+                        raise ValueError("kernel_new: %s(env) must return a float64 tensor of shape %s on %s; got %s" % (
+                            what, list(shape), dev, _describe(t)))
+                    view(out_p, shape).copy_(t)
+                return 0
+            except BaseException as ex:   # (nothing may unwind through the C frames)
+                caught.append(ex)
+                return 1
+        return abi.STEP_FN(trampoline)
+
+    fun_cb = _logpost_trampoline(model, stream, view, caught) if isinstance(model, DeviceFun) else abi.LOGPOST_FN()
+    prop_cb = step_fn(kernel.proposal, "proposal", (Cn, k))
+    ratio_cb = step_fn(kernel.logratio, "logratio", (Cn,)) if kernel.logratio is not None else abi.STEP_FN()
+    cm = None if isinstance(model, DeviceFun) else model.c()
+    cs = state.c(nsteps)
+    with torch.cuda.device(dev):
+        rc = L.fmcmc_mcmc_run_user_dev(C.byref(cm) if cm is not None else None, fun_cb, prop_cb, ratio_cb, None, k,
+                                       C.byref(crun), C.byref(cs), C.byref(cout), C.c_void_p(stream.cuda_stream))
+    if caught:
+        raise caught[0]
+    return _finish_call(out, state, rc, "fmcmc_mcmc_run_user_dev", nsteps, burnin, thin, chain_base, check)
 
 
 def raise_on_chain_error(out, chain_base=0):

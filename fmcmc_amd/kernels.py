@@ -6,6 +6,7 @@
   kernel_ram               R/kernel_ram.R:65-181
   kernel_unif / kernel_unif_reflective   R/kernel_unif.R:42-91, :96-170
   kernel_nmirror / kernel_umirror        R/kernel_mirror.R:3-138, :140-283
+  kernel_new               R/kernel.R:136-317 (proposal / logratio are the user's, batched over the local chains)
   plan_update_sequence     R/kernel.R:66-133 (scheme = "joint" | "ordered" | "random" | integer sequence)
   check_dimensions / process_bounds   R/kernel.R:3-41
 
@@ -228,6 +229,64 @@ class fmcmc_kernel:
         names = {1: "kernel_normal", 2: "kernel_normal_reflective", 3: "kernel_adapt", 4: "kernel_ram",
                  5: "kernel_unif", 6: "kernel_unif_reflective", 7: "kernel_nmirror", 8: "kernel_umirror"}
         return "<fmcmc_kernel %s k=%s>" % (names[self.kind], self.k)
+
+
+KERNEL_USER = 0   # (no fmcmc_kernel.kind of the C-ABI: a user-defined kernel runs through fmcmc_mcmc_run_user_dev)
+
+
+def _single_argument(fn):
+    """length(formals(fn)) == 1 (R/kernel.R:291-300)"""
+    import inspect
+    if not callable(fn):
+        return False
+    try:
+        ps = list(inspect.signature(fn).parameters.values())
+    except (TypeError, ValueError):   # (a builtin without a signature: it is called with one argument)
+        return True
+    return len(ps) == 1 and ps[0].kind in (ps[0].POSITIONAL_ONLY, ps[0].POSITIONAL_OR_KEYWORD)
+
+
+class fmcmc_user_kernel(fmcmc_kernel):
+    """kernel_new(): proposal(env) and logratio(env) are the user's, batched over the local chains (engine.sweep_user).  The
+    keyword arguments of kernel_new() are attributes of this object, which the callbacks reach as env.kernel.<name>, may assign
+    to, and find again in the next call and in the next bulk of a conv_checker run -- the kernel environment of R/kernel.R:305-313."""
+
+    def __init__(self, proposal, logratio, fixed, state):
+        fmcmc_kernel.__init__(self, KERNEL_USER, fixed=fixed)
+        self.proposal, self.logratio = proposal, logratio
+        for n, v in state.items():
+            setattr(self, n, v)
+
+    def _init(self, k):
+        if self.k is not None and self._k_total == k:
+            return
+        self._k_total = self.k = k
+        self.fixed = check_dimensions(self.fixed, k, "fixed").astype(bool)   # (read by the auto-stop loop only)
+        self.which_ = np.nonzero(~self.fixed)[0]
+        self._kf = int(self.which_.size)
+
+    def spec(self, device):
+        raise TypeError("a kernel_new() kernel has no fmcmc_kernel of the C-ABI: it runs through engine.sweep_user")
+
+    def __repr__(self):
+        return "<fmcmc_kernel kernel_new k=%s>" % (self.k,)
+
+
+def kernel_new(proposal, logratio=None, fixed=False, **state):
+    """R/kernel.R:283-317.  proposal(env) -> theta1, a float64 device tensor [C_local, k]; logratio(env) -> the log of the
+    Hastings ratio, a float64 device tensor [C_local] (None: env.f1 - env.f0, a symmetric kernel).  Both take ONE argument, the
+    environment of the step, for ALL local chains at once (engine.UserEnv: i, nsteps, k, theta0, theta1, f0, f1, chain_ids,
+    kernel, f(theta), rnorm / runif / rt).  **state: further objects stored with the kernel, reached as env.kernel.<name>.
+    fixed: read by the auto-stop loop only, to drop fixed columns before the checker.  env$ans is not offered: a kernel that
+    needs its history keeps it in its own state."""
+    if not _single_argument(proposal):
+        raise ValueError("The `proposal` function should receive a single argument (an environment).")
+    if logratio is not None and not _single_argument(logratio):
+        raise ValueError("The `logratio` function should receive a single argument (an environment) ")
+    taken = [n for n in state if n.startswith("_") or n in ("kind", "k", "which_", "proposal", "logratio", "abs_iter")]
+    if taken:
+        raise ValueError("kernel_new: %s cannot name an object stored with the kernel." % ", ".join("-%s-" % n for n in taken))
+    return fmcmc_user_kernel(proposal, logratio, fixed, state)
 
 
 def kernel_normal(mu=0.0, scale=1.0, fixed=False, scheme="joint"):

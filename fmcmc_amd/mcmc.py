@@ -13,6 +13,7 @@ the call already run concurrently); `fun` is a closed-form family or a batched_f
 engine calls between its kernels' steps); with torch.distributed initialised the chains are sharded over
 the ranks in contiguous blocks (one process per GPU) and RCCL is used only by the Gelman check.
 """
+import functools
 import time
 import warnings
 
@@ -20,7 +21,7 @@ import numpy as np
 
 from . import _abi as abi
 from . import engine
-from .kernels import fmcmc_kernel, kernel_normal
+from .kernels import fmcmc_kernel, fmcmc_user_kernel, kernel_normal
 from .models import BatchedFun, LogPosterior
 
 
@@ -321,8 +322,12 @@ def _run_call(initial_local, fun, nsteps, burnin, thin, kernel, seed, chain_base
     import torch
     gm = fun.device_model(device)
     kernel._init(initial_local.shape[1])
-    if kernel._spec is None or kernel._spec.device != gm.device:
+    user = isinstance(kernel, fmcmc_user_kernel)   # kernel_new(): the proposal is the caller's (engine.sweep_user)
+    if user and fed is not None:
+        raise ValueError("-fed- supplies the variates of the built-in kernels: a kernel_new() kernel draws its own.")
+    if not user and (kernel._spec is None or kernel._spec.device != gm.device):
         kernel._spec = kernel.spec(gm.device)
+    sweep = functools.partial(engine.sweep_user, gm, kernel) if user else functools.partial(engine.sweep, gm, kernel._spec)
     if initial_local.shape[0] == 0:
         # a rank without chains (nchains < number of ranks): nothing to launch, but it still takes part in the checker's
         # all-reduce with an empty partial
@@ -345,14 +350,13 @@ def _run_call(initial_local, fun, nsteps, burnin, thin, kernel, seed, chain_base
         fkw = dict(fed_logu=torch.as_tensor(np.ascontiguousarray(logu, dtype=np.float64)).to(gm.device),
                    fed_z=torch.as_tensor(np.ascontiguousarray(z, dtype=np.float64)).to(gm.device))
     if history is not None:
-        out = engine.sweep(gm, kernel._spec, st, nsteps, burnin=burnin, thin=thin, seed=seed, chain_base=chain_base,
-                           want_bits=False, into=(history._samples, history._logpost, history._draws), row0=history.nrows,
-                           **fkw)
+        out = sweep(st, nsteps, burnin=burnin, thin=thin, seed=seed, chain_base=chain_base, want_bits=False,
+                    into=(history._samples, history._logpost, history._draws), row0=history.nrows, **fkw)
         history.extend(out.iters)
         history.accept_count = out.accept_count
         return history
-    out = engine.sweep(gm, kernel._spec, st, nsteps, burnin=burnin, thin=thin, seed=seed, chain_base=chain_base,
-                       want_logpost=want_logpost, want_draws=want_draws, want_bits=False, **fkw)
+    out = sweep(st, nsteps, burnin=burnin, thin=thin, seed=seed, chain_base=chain_base,
+                want_logpost=want_logpost, want_draws=want_draws, want_bits=False, **fkw)
     dc = DeviceChains(out.samples, out.logpost, out.draws, out.iters, thin, names, chain_base, nchains_total)
     dc.accept_count = out.accept_count
     return dc

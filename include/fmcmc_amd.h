@@ -277,6 +277,45 @@ int fmcmc_mcmc_run_fun_dev(const fmcmc_kernel* kernel, const fmcmc_run* run, fmc
 int fmcmc_mcmc_run_fun_host(const fmcmc_kernel* kernel, const fmcmc_run* run, fmcmc_state* state, fmcmc_out* out,
                             fmcmc_logpost_fn fun, void* user, int device);      /* theta/out of `fun`: host pointers */
 
+/* ---- the families' log-posterior at caller-given points -------------------------------------------------------------------
+ * out[c] = f(theta[c][0..k-1]) for c < nchains, k the family's parameter count: the canonical form the sweeps evaluate (the 512
+ * canonical lanes, their xor tree, the closed form), bit for bit.  One workgroup per parameter vector; theta and out are device
+ * pointers, the work is enqueued on hip_stream.  Any n >= 1 and any k <= FMCMC_MAX_K. */
+int fmcmc_logpost_dev(const fmcmc_model* model, const double* theta /* [C][k], device */, int64_t nchains,
+                      double* out /* [C], device */, void* hip_stream);
+
+/* ---- user-defined transition kernels: kernel_new(proposal, logratio) as batched callbacks (R/kernel.R:136-317) --------------
+ * What R/kernel.R:169-184 lists, for all chains of the call; device pointers, read-only.  `proposal` sees in theta1 / f1 the LAST
+ * proposal and its value, `logratio` the new ones.  env$ans is not offered (kept rows are not R's rows). */
+typedef struct {
+  int64_t i;               /* R's 1-based loop index, 2 .. nsteps */
+  int64_t nsteps, nchains, chain_base, step_base;
+  int32_t k;
+  const double* theta0;    /* [C][k] */
+  const double* theta1;    /* [C][k] */
+  const double* f0;        /* [C] */
+  const double* f1;        /* [C] */
+  const int32_t* status;   /* [C] FMCMC_CHAIN_*: a chain whose status is not OK no longer moves */
+} fmcmc_step_env;
+/* Called on the calling host thread, once per loop step each.  Work is enqueued on hip_stream, or the function synchronises
+ * before returning.  0 = ok; anything else aborts the call. */
+typedef int (*fmcmc_proposal_fn)(const fmcmc_step_env* env, double* theta1_out /* [C][k] */, void* hip_stream, void* user);
+typedef int (*fmcmc_logratio_fn)(const fmcmc_step_env* env, double* logratio_out /* [C] */, void* hip_stream, void* user);
+
+/* The loop of fmcmc_mcmc_run_fun_dev with the proposal outside (R/mcmc.R:737-783).  Row 1: f0 = f(initial), theta1 = theta0,
+ * f1 = f0.  Then for i = 2 .. nsteps: proposal(env) writes theta1; f1 = f(theta1), through `fun` or, when `model` is given,
+ * through the evaluator of fmcmc_logpost_dev; logratio(env) when given (NULL: f1 - f0, the decision of the built-in kernels);
+ * one launch of the accept / store step: NaN f1 -> FMCMC_CHAIN_NAN_LOGPOST, NaN ratio -> FMCMC_CHAIN_NAN_RATIO, accept iff
+ * log u < ratio with the engine's accept uniform of (seed, step_base + i, chain_base + c) (FED mode: run->fed_logu; fed_z is
+ * not read).  The same run / out layouts, statuses and outputs as fmcmc_mcmc_run_fun_dev; of `state` theta0 and f0 only.
+ * Everything is enqueued on hip_stream, no host synchronisation.  A non-zero return of a callback ends the call with
+ * FMCMC_ERR_FUN (fmcmc_last_error() names the callback, the step and the code).  1 <= k <= FMCMC_MAX_K; fmcmc_last_kernel():
+ * "user" (k <= FMCMC_MAX_K_WAVE) or "user-wg".  fmcmc_validate_user: the run checks of fmcmc_validate with their messages. */
+int fmcmc_validate_user(const fmcmc_run* run, int32_t k);
+int fmcmc_mcmc_run_user_dev(const fmcmc_model* model /* or NULL */, fmcmc_logpost_fn fun /* used when model is NULL */,
+                            fmcmc_proposal_fn proposal, fmcmc_logratio_fn logratio /* NULL: f1 - f0 */, void* user,
+                            int32_t k, const fmcmc_run* run, fmcmc_state* state, fmcmc_out* out, void* hip_stream);
+
 /* Gelman-Rubin partial sums over local chains (R/convergence.R:191-246 -> coda::gelman.diag).
  * Window = kept rows [row0, row0+N) of each chain. partial has fmcmc_gelman_partial_len(p)
  * doubles: {m, sum xbar[p], sum xbar xbar^T[p*p], sum S_c[p*p], sum s2[p], sum s2^2[p],
