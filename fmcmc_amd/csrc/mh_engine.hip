@@ -274,11 +274,28 @@ static int require_gfx950(int dev) {
   return FMCMC_OK;
 }
 
-// The kernel / run / state / out fields that SweepArgs and FunArgs both have (they name them alike), and what is derived from
-// them: kernel_ram's qfun / eta families, the variates per step, the row stride.  `kn`: the kernel as the device code sees it.
+// The run / state / out fields that SweepArgs, FunArgs and UserArgs all have (they name them alike), and the row stride
+template <class Args>
+static int fill_run_args(Args& A, int k, const fmcmc_run* run, const fmcmc_state* st, const fmcmc_out* out) {
+  A.k = k;
+  A.nchains = run->nchains; A.nsteps = run->nsteps; A.burnin = run->burnin; A.thin = run->thin;
+  const long long S = fmcmc_kept_rows(run->nsteps, run->burnin, run->thin);
+  A.ldS = out->ld_rows > 0 ? out->ld_rows : S;
+  if (A.ldS < S) { set_err("fmcmc_out.ld_rows (%lld) is smaller than the %lld kept rows of this call", (long long)out->ld_rows, S); return FMCMC_ERR_ARG; }
+  A.chain_base = run->chain_base; A.step_base = run->step_base; A.seed = run->seed;
+  A.rng_mode = run->rng_mode; A.fed_logu = run->fed_logu;
+  A.theta0 = st->theta0; A.f0 = st->f0;
+  A.samples = out->samples; A.logpost = out->logpost; A.draws = out->draws;
+  A.accept_count = (long long*)out->accept_count; A.accept_bits = out->accept_bits;
+  A.status = out->status; A.status_step = (long long*)out->status_step; A.status_theta = out->status_theta;
+  return FMCMC_OK;
+}
+
+// On top of them, the kernel fields and the adaptive state that SweepArgs and FunArgs both have, and what is derived from them:
+// kernel_ram's qfun / eta families, the variates per step.  `kn`: the kernel as the device code sees it.
 template <class Args>
 static int fill_call_args(Args& A, const fmcmc_kernel* kn, const fmcmc_run* run, const fmcmc_state* st, const fmcmc_out* out, int kf) {
-  A.kind = kn->kind; A.k = kn->k; A.scheme = kn->scheme; A.warmup = kn->warmup;
+  A.kind = kn->kind; A.scheme = kn->scheme; A.warmup = kn->warmup;
   A.freq = kn->freq < 1 ? 1 : kn->freq; A.scheme_seq = kn->scheme_seq; A.scheme_len = kn->scheme_len;
   A.constr = (kn->kind == FMCMC_KERNEL_RAM) ? kn->constr : nullptr;
   A.until = kn->until; A.eps = kn->eps; A.arate = kn->arate;
@@ -286,19 +303,39 @@ static int fill_call_args(Args& A, const fmcmc_kernel* kn, const fmcmc_run* run,
   A.ram_df = (kn->ram_qfun == FMCMC_RAM_QFUN_NORMAL) ? 0.0 : (kn->ram_qfun == FMCMC_RAM_QFUN_T_DF ? kn->ram_df : (double)kf);
   A.ram_neg_exp = (kn->ram_eta_exp != 0.0) ? -kn->ram_eta_exp : (-2.0 / 3.0);
   A.mu = kn->mu; A.scale = kn->scale; A.lb = kn->lb; A.ub = kn->ub;
-  A.nchains = run->nchains; A.nsteps = run->nsteps; A.burnin = run->burnin; A.thin = run->thin;
-  const long long S = fmcmc_kept_rows(run->nsteps, run->burnin, run->thin);
-  A.ldS = out->ld_rows > 0 ? out->ld_rows : S;
-  if (A.ldS < S) { set_err("fmcmc_out.ld_rows (%lld) is smaller than the %lld kept rows of this call", (long long)out->ld_rows, S); return FMCMC_ERR_ARG; }
-  A.chain_base = run->chain_base; A.step_base = run->step_base; A.seed = run->seed;
-  A.rng_mode = run->rng_mode; A.fresh = st->fresh;
+  A.fresh = st->fresh;
   A.kz = variates_per_step(kn, kf);
-  A.fed_logu = run->fed_logu; A.fed_z = run->fed_z;
-  A.theta0 = st->theta0; A.f0 = st->f0; A.abs_iter = (long long*)st->abs_iter; A.Sigma = st->Sigma;
+  A.fed_z = run->fed_z;
+  A.abs_iter = (long long*)st->abs_iter; A.Sigma = st->Sigma;
   A.mean_prev = st->mean_prev; A.have_mean = st->have_mean; A.nerrors = st->nerrors; A.scheme_cols = st->scheme_cols;
-  A.samples = out->samples; A.logpost = out->logpost; A.draws = out->draws;
-  A.accept_count = (long long*)out->accept_count; A.accept_bits = out->accept_bits;
-  A.status = out->status; A.status_step = (long long*)out->status_step; A.status_theta = out->status_theta;
+  return fill_run_args(A, kn->k, run, st, out);
+}
+
+// the logistic family's data-only sums of the linear part and the columns' largest |x| (logit_hs_kernel), into the call's scratch
+static int enqueue_logit_sums(const fmcmc_model& m, ScratchList& scratch, hipStream_t stream, const double** hs_out) {
+  double* hs = nullptr;
+  const int rh = scratch.grab(&hs, sizeof(double) * (size_t)(2 * MAXK + 2), "logistic sums");
+  if (rh != FMCMC_OK) return rh;
+  hipLaunchKernelGGL(logit_hs_kernel, dim3(1), dim3(NT), 0, stream, m.X, m.y, (long long)m.n, m.p, m.intercept ? 1 : 0, hs);
+  *hs_out = hs;
+  return FMCMC_OK;
+}
+
+// ---- the two callback sweeps (run_fun, run_user): one step kernel launch per evaluation
+// the caller's log-posterior at theta [C][k] -> f [C]; a non-zero return is the call's error, with the loop step in its text
+static int call_logpost(fmcmc_logpost_fn fun, const double* theta, long long C, int k, double* f, hipStream_t stream, void* user, long long step) {
+  const int rc = fun(theta, (int64_t)C, (int32_t)k, f, (void*)stream, user);
+  if (rc == 0) return FMCMC_OK;
+  set_err("the log-posterior callback returned %d at loop step i = %lld%s", rc, step, step == 1 ? " (row 1: the initial values)" : "");
+  return FMCMC_ERR_FUN;
+}
+// the step kernel of loop step `step`, one workgroup of nth threads per chain
+template <class Args>
+static int launch_step(const void* kfn, long long C, int nth, size_t lds, hipStream_t stream, const Args& A, long long step) {
+  void* kargs[] = {(void*)&A};
+  hipError_t e = hipLaunchKernel(kfn, dim3((unsigned)C), dim3((unsigned)nth), kargs, lds, stream);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) { set_err("HIP launch failed at loop step i = %lld: %s", step, hipGetErrorString(e)); return FMCMC_ERR_DEVICE; }
   return FMCMC_OK;
 }
 
@@ -419,14 +456,7 @@ static int build_sweep_args(SweepCtx& cx, fmcmc_state* st, fmcmc_out* out, int r
   if (rf != FMCMC_OK) return rf;
   A.debug = cx.K.mode;   // timing ablations only
   // logistic family: the data-only sums of the linear part and the columns' largest |x| (logit_hs_kernel), once per launch
-  if (m.family == FMCMC_FAM_LOGISTIC) {
-    double* hs = nullptr;
-    const int rh = cx.scratch.grab(&hs, sizeof(double) * (size_t)(2 * MAXK + 2), "logistic sums");
-    if (rh != FMCMC_OK) return rh;
-    hipLaunchKernelGGL(logit_hs_kernel, dim3(1), dim3(NT), 0, cx.stream, m.X, m.y, (long long)m.n, m.p, m.intercept ? 1 : 0, hs);
-    A.lg_hs = hs;
-  }
-  return FMCMC_OK;
+  return (m.family == FMCMC_FAM_LOGISTIC) ? enqueue_logit_sums(m, cx.scratch, cx.stream, &A.lg_hs) : FMCMC_OK;
 }
 
 // ---- step 3, form by form.  Each returns an FMCMC_* code (a refusal with its own message) and leaves a failed launch in cx.e.
@@ -773,34 +803,22 @@ static int run_fun(const fmcmc_kernel* kn, const uint8_t* fx, const double* lb, 
   std::vector<double> h_th, h_f;
   if (host_fun) { h_th.resize(n_th); h_f.resize((size_t)C); }
   auto evaluate = [&](long long step) -> int {
-    int rc;
-    if (host_fun) {
-      if (hipMemcpyAsync(h_th.data(), th1, sizeof(double) * n_th, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-          hipStreamSynchronize(stream) != hipSuccess) {
-        set_err("cannot read the proposals of loop step i = %lld back from the device", step);
-        return FMCMC_ERR_DEVICE;
-      }
-      rc = fun(h_th.data(), (int64_t)C, (int32_t)k, h_f.data(), (void*)stream, user);
-      if (rc == 0 && hipMemcpyAsync(f1, h_f.data(), sizeof(double) * (size_t)C, hipMemcpyHostToDevice, stream) != hipSuccess) {
-        set_err("cannot copy the log-posterior of loop step i = %lld to the device", step);
-        return FMCMC_ERR_DEVICE;
-      }
-    } else {
-      rc = fun(th1, (int64_t)C, (int32_t)k, f1, (void*)stream, user);
+    if (!host_fun) return call_logpost(fun, th1, C, k, f1, stream, user, step);
+    if (hipMemcpyAsync(h_th.data(), th1, sizeof(double) * n_th, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess) {
+      set_err("cannot read the proposals of loop step i = %lld back from the device", step);
+      return FMCMC_ERR_DEVICE;
     }
-    if (rc != 0) {
-      set_err("the log-posterior callback returned %d at loop step i = %lld%s", rc, step, step == 1 ? " (row 1: the initial values)" : "");
-      return FMCMC_ERR_FUN;
+    const int rc = call_logpost(fun, h_th.data(), C, k, h_f.data(), stream, user, step);
+    if (rc == FMCMC_OK && hipMemcpyAsync(f1, h_f.data(), sizeof(double) * (size_t)C, hipMemcpyHostToDevice, stream) != hipSuccess) {
+      set_err("cannot copy the log-posterior of loop step i = %lld to the device", step);
+      return FMCMC_ERR_DEVICE;
     }
-    return FMCMC_OK;
+    return rc;
   };
   auto launch = [&](long long step, int phase) -> int {
     A.step = step; A.phase = phase;
-    void* kargs[] = {(void*)&A};
-    hipError_t e = hipLaunchKernel(kfn, dim3((unsigned)C), dim3((unsigned)nth), kargs, lds, stream);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) { set_err("HIP launch failed at loop step i = %lld: %s", step, hipGetErrorString(e)); return FMCMC_ERR_DEVICE; }
-    return FMCMC_OK;
+    return launch_step(kfn, C, nth, lds, stream, A, step);
   };
   const long long nsteps = run->nsteps;
   rc = evaluate(1);
@@ -845,14 +863,7 @@ struct EvalCall {
     E.n = m->n; E.prior_div = m->prior_div; E.X = m->X; E.y = m->y;
     kfn = fmh::k_logpost_eval();
     if (!kfn) { set_err("no device kernel for the batched evaluation"); return FMCMC_ERR_DEVICE; }
-    if (m->family == FMCMC_FAM_LOGISTIC) {
-      double* hs = nullptr;
-      const int rh = scratch.grab(&hs, sizeof(double) * (size_t)(2 * MAXK + 2), "logistic sums");
-      if (rh != FMCMC_OK) return rh;
-      hipLaunchKernelGGL(logit_hs_kernel, dim3(1), dim3(NT), 0, stream, m->X, m->y, (long long)m->n, m->p, m->intercept ? 1 : 0, hs);
-      E.hs = hs;
-    }
-    return FMCMC_OK;
+    return (m->family == FMCMC_FAM_LOGISTIC) ? enqueue_logit_sums(*m, scratch, stream, &E.hs) : FMCMC_OK;
   }
   hipError_t enqueue(const double* theta, long long C, double* out, hipStream_t stream) {
     E.theta = theta; E.nchains = C; E.out = out;
@@ -868,18 +879,11 @@ static int run_user(const fmcmc_model* m, fmcmc_logpost_fn fun, fmcmc_proposal_f
   const long long C = run->nchains, nsteps = run->nsteps;
   UserArgs A;
   memset(&A, 0, sizeof(A));
-  A.k = k; A.rng_mode = run->rng_mode; A.nchains = C; A.nsteps = nsteps; A.burnin = run->burnin; A.thin = run->thin;
-  const long long S = fmcmc_kept_rows(run->nsteps, run->burnin, run->thin);
-  A.ldS = out->ld_rows > 0 ? out->ld_rows : S;
-  if (A.ldS < S) { set_err("fmcmc_out.ld_rows (%lld) is smaller than the %lld kept rows of this call", (long long)out->ld_rows, S); return FMCMC_ERR_ARG; }
-  A.chain_base = run->chain_base; A.step_base = run->step_base; A.seed = run->seed; A.fed_logu = run->fed_logu;
-  A.theta0 = st->theta0; A.f0 = st->f0;
-  A.samples = out->samples; A.logpost = out->logpost; A.draws = out->draws; A.accept_count = (long long*)out->accept_count;
-  A.accept_bits = (unsigned int*)out->accept_bits; A.status = out->status; A.status_step = (long long*)out->status_step;
-  A.status_theta = out->status_theta;
+  int rc = fill_run_args(A, k, run, st, out);
+  if (rc != FMCMC_OK) return rc;
   int dev = 0;
   (void)hipGetDevice(&dev);
-  int rc = require_gfx950(dev);
+  rc = require_gfx950(dev);
   if (rc != FMCMC_OK) return rc;
   // scratch of the call: two theta1 [C][k] (the proposal callback reads the last proposal while it writes the new one),
   // f(theta1) [C], the caller's log-ratio [C]
@@ -908,20 +912,11 @@ static int run_user(const fmcmc_model* m, fmcmc_logpost_fn fun, fmcmc_proposal_f
       if (e != hipSuccess) { set_err("HIP launch failed at loop step i = %lld: %s", step, hipGetErrorString(e)); return FMCMC_ERR_DEVICE; }
       return FMCMC_OK;
     }
-    const int rf = fun(th, (int64_t)C, (int32_t)k, f1, (void*)stream, user);
-    if (rf != 0) {
-      set_err("the log-posterior callback returned %d at loop step i = %lld%s", rf, step, step == 1 ? " (row 1: the initial values)" : "");
-      return FMCMC_ERR_FUN;
-    }
-    return FMCMC_OK;
+    return call_logpost(fun, th, C, k, f1, stream, user, step);
   };
   auto launch = [&](const double* th, long long step, int phase) -> int {
     A.th1 = th; A.f1 = f1; A.logratio = (phase == UPH_ACCEPT) ? lr : nullptr; A.step = step; A.phase = phase;
-    void* kargs[] = {(void*)&A};
-    hipError_t e = hipLaunchKernel(kfn, dim3((unsigned)C), dim3((unsigned)nth), kargs, 0, stream);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) { set_err("HIP launch failed at loop step i = %lld: %s", step, hipGetErrorString(e)); return FMCMC_ERR_DEVICE; }
-    return FMCMC_OK;
+    return launch_step(kfn, C, nth, 0, stream, A, step);
   };
   // row 1: f0 = f(initial), theta1 = theta0 and f1 = f0, as the reference initialises them
   (void)hipMemcpyAsync(thb[0], st->theta0, sizeof(double) * n_th, hipMemcpyDeviceToDevice, stream);

@@ -19,8 +19,13 @@
 // __syncthreads().
 //
 // Bit contract: the same operations in the same order as the oracle (fmcmc_oracle.c: propose_normal, propose_adapt -- LDL^T for
-// k <= 64, Cholesky beyond --, propose_ram, scan_sq_canon, ram_factor_update_canon, reflect1) and the family kernels.
+// k <= 64, Cholesky beyond --, propose_ram, scan_sq_canon, ram_factor_update_canon, reflect1) and the family kernels.  The
+// kernel_adapt / kernel_ram arithmetic, the variates, the fresh start and hand-on of the square and the accept / store half
+// are the row owner's pieces of mh_rowowner.hpp (mh_sweep_bigk<true> keeps its own lines of the same arithmetic);
+// mh_user_step shares the accept / store half.  Here stay: the cut of a step into phases, the simple kernels with their
+// single-parameter schemes, and the LDL^T factor of k <= 64.
 #pragma once
+#include "mh_rowowner.hpp"
 
 namespace {
 
@@ -80,17 +85,6 @@ __host__ __device__ inline size_t fun_lds_doubles(int k, int kf, int kind, int n
 }
 
 #ifdef FMH_WITH_FUN_KERNEL   /* compiled into k_fun.hip only */
-// variate `a` of loop step i of local chain c; a == kz: the log accept uniform (the canonical stream, or the fed one)
-__device__ __forceinline__ double fun_variate(const FunArgs& A, long long c, long long i, int a) {
-  const unsigned int st = (unsigned int)(A.step_base + i), cg = (unsigned int)(A.chain_base + c);
-  const bool fed = A.rng_mode == FMCMC_RNG_FED;
-  if (a == A.kz) return fed ? A.fed_logu[c * A.nsteps + (i - 1)] : fmh_log_accept_u(A.seed, st, cg);
-  if (fed) return A.fed_z[(c * A.nsteps + (i - 1)) * A.kz + a];
-  if (A.kind == FMCMC_KERNEL_RAM && A.ram_df > 0.0) return fmh_student_t(A.seed, st, cg, (unsigned int)a, A.ram_df);
-  if (A.kind == FMCMC_KERNEL_UNIF || A.kind == FMCMC_KERNEL_UNIF_REFLECTIVE) return fmh_unif(A.seed, st, cg, (unsigned int)a);
-  return fmh_normal(A.seed, st, cg, (unsigned int)a);
-}
-
 template <int NTH>
 __global__ __launch_bounds__(NTH) void mh_fun_step(const FunArgs A) {
   extern __shared__ double smem[];
@@ -125,95 +119,36 @@ __global__ __launch_bounds__(NTH) void mh_fun_step(const FunArgs A) {
     th1[r] = A.th1[c * k + r];
   }
   const bool start = (ph & FPH_START) != 0;
-  // ---- the chain's carried values (uniform: every thread keeps them)
-  int status = start ? FMCMC_CHAIN_OK : A.status[c];
-  double f0 = start ? A.f1[c] : A.f0[c];
-  long long nacc = start ? 0 : A.accept_count[c];
+  const bool unif = A.kind == FMCMC_KERNEL_UNIF || A.kind == FMCMC_KERNEL_UNIF_REFLECTIVE;   // (the kind is not normalised here)
+  RoCarried ch = ro_carried(A, c, start);   // the chain's carried values (uniform: every thread keeps them)
   long long abs_iter = 0;
   int have_mean = 0, nerr = 0;
   double* const Mg = adaptive ? A.Sigma + c * (long long)kf * kf : nullptr;   // the chain's Sigma / S square
+  // its elements: Sigma / S (i >= j), the Cholesky factor's strictly lower part transposed into the upper half, its diagonal
+  auto bar = []() { __syncthreads(); };
+  auto ma = [&](int a, int b) -> double& { return Mg[a * kf + b]; };
+  auto mbl = [&](int a, int b) -> double& { return Mg[b * kf + a]; };
+  auto mbd = [&](int j) -> double& { return fac[j]; };
   if (adaptive && !(start && A.fresh)) {
     abs_iter = A.abs_iter[c];
     nerr = A.nerrors[c];
     if (adapt) have_mean = A.have_mean[c];
   }
-  const long long nwords = (A.nsteps + 31) >> 5;
-  auto store_row = [&](long long ir, double lpv) {   // row ir of ans: kept when ir > burnin and (ir - burnin) mod thin == 0
-    if (ir > A.burnin && (ir - A.burnin) % A.thin == 0) {
-      const long long s = (ir - A.burnin) / A.thin - 1;
-      if (par) {
-        A.samples[(c * k + r) * A.ldS + s] = th0[r];
-        if (A.draws) A.draws[(c * k + r) * A.ldS + s] = th1[r];
-      }
-      if (A.logpost && r == 0) A.logpost[c * A.ldS + s] = lpv;
-    }
-  };
-  auto fail = [&](long long ir) {
-    if (r == 0) { A.status[c] = status; A.status_step[c] = ir; }
-    if (par) A.status_theta[c * k + r] = th1[r];
-  };
   __syncthreads();
 
   // ================= row 1 (R/mcmc.R:728-735) =================
   if (start) {
-    if (adaptive && A.fresh)
-      for (int e = r; e < kf * kf; e += NTH) {
-        const int a = e / kf, b = e - a * kf;
-        if (b <= a) Mg[e] = (a == b) ? 1.0 * A.eps : 0.0;
-      }
-    if (A.accept_bits)
-      for (long long w = r; w < nwords; w += NTH) A.accept_bits[c * nwords + w] = 0u;
-    if (r == 0) { A.status[c] = FMCMC_CHAIN_OK; A.status_step[c] = 0; }
-    store_row(1, f0);
+    if (adaptive && A.fresh) ro_square_fresh(Mg, kf, A.eps, r, NTH);
+    ro_row1(A, c, r, NTH, par, &th0[r], &th1[r], ch.f0);
     if (adapt && row) A.rsum[c * kf + r] = th0[wr];
     __syncthreads();
   }
 
   // ================= kernel_ram: the adaptation with f(un-reflected theta1), then the reflection =================
-  if ((ph & FPH_RAM) && ram && status == FMCMC_CHAIN_OK) {
+  if ((ph & FPH_RAM) && ram && ch.status == FMCMC_CHAIN_OK) {
     if (A.until > (double)abs_iter && abs_iter > A.warmup && (i % A.freq) == 0) {
-      const double f1u = A.f1[c];
-      double a_n = fmh_exp(f1u - f0);
-      if (fmh_isnan(a_n)) a_n = 0.0;
-      else if (a_n > 1.0) a_n = 1.0;
-      double eta = (double)kf * fmh_exp(A.ram_neg_exp * fmh_log((double)i));
-      if (eta > 1.0) eta = 1.0;
-      if (row) s_z[r] = fun_variate(A, c, i, r);   // (the variates U of this step's proposal, drawn again)
-      if (r == 0) s_flag[0] = 0;
-      __syncthreads();
-      // prefix sums of z^2: Hillis-Steele over the index, offsets 1, 2, 4, ... (scan_sq_canon)
-      double* qa = vq;
-      double* qb = vt;
-      if (row) qa[r] = s_z[r] * s_z[r];
-      __syncthreads();
-      for (int s = 1; s < kf; s <<= 1) {
-        if (row) qb[r] = (r >= s) ? qa[r] + qa[r - s] : qa[r];
-        __syncthreads();
-        double* tmp = qa; qa = qb; qb = tmp;
-      }
-      const double cp = (eta * (a_n - A.arate)) / qa[kf - 1];
-      if (cp != 0.0 && fmh_isfinite(cp)) {
-        if (row) {
-          double dl = 0.0, kl = 0.0;
-          const double Pj1 = qa[r], Pj = (r == 0) ? 0.0 : qa[r - 1];
-          if (!ram_coef(cp, Pj, Pj1, s_z[r], dl, kl)) s_flag[0] = 1;
-          vd[r] = dl; vk[r] = kl;
-        }
-        __syncthreads();
-        if (s_flag[0] != 0) {
-          nerr += 1;
-        } else if (row) {   // S'_rj = S_rj d_j + G_rj kappa_j, G formed from the diagonal down (ram_factor_update_canon)
-          double G = 0.0;
-          for (int j = r; j >= 0; j--) {
-            const double sij = Mg[r * kf + j];
-            Mg[r * kf + j] = fmh_fma(G, vk[j], sij * vd[j]);
-            G = fmh_fma(sij, s_z[j], G);
-          }
-        }
-      }
-      if (A.constr && row)   // Sigma <<- constr[which., which.] * Sigma (R/kernel_ram.R:149-150)
-        for (int b = 0; b <= r; b++) Mg[r * kf + b] = A.constr[r * kf + b] * Mg[r * kf + b];
-      __syncthreads();
+      if (row) s_z[r] = ro_variate(A, c, i, r, unif);   // (the variates U of this step's proposal, drawn again)
+      if (ro_ram_adapt(row, r, kf, i, A.f1[c], ch.f0, A.ram_neg_exp, A.arate, A.constr, s_z, vq, vt, vd, vk, &s_flag[0], bar, ma)) nerr += 1;
     }
     abs_iter += 1;
     if (A.ram_bounded) {
@@ -224,31 +159,15 @@ __global__ __launch_bounds__(NTH) void mh_fun_step(const FunArgs A) {
   }
 
   // ================= accept / store of step i (R/mcmc.R:754-778) =================
-  if ((ph & FPH_ACCEPT) && status == FMCMC_CHAIN_OK) {
-    const double f1 = A.f1[c];
-    if (fmh_isnan(f1)) status = FMCMC_CHAIN_NAN_LOGPOST;
-    const double ratio = f1 - f0;
-    if (status == FMCMC_CHAIN_OK && fmh_isnan(ratio)) status = FMCMC_CHAIN_NAN_RATIO;
-    if (status != FMCMC_CHAIN_OK) {
-      fail(i);
-    } else {
-      const double lu = fun_variate(A, c, i, kz);
-      if (lu < ratio) {
-        if (par) th0[r] = th1[r];
-        f0 = f1;
-        nacc += 1;
-        if (A.accept_bits && r == 0) A.accept_bits[c * nwords + ((i - 1) >> 5)] |= (1u << ((i - 1) & 31));
-      }
-      __syncthreads();
-      store_row(i, f1);
-      if (adapt && row) A.rsum[c * kf + r] = A.rsum[c * kf + r] + th0[wr];
-    }
+  if ((ph & FPH_ACCEPT) && ch.status == FMCMC_CHAIN_OK) {
+    ro_accept_store(A, c, r, par, i, A.f1[c] - ch.f0, ch, &th0[r], &th1[r], bar);
+    if (ch.status == FMCMC_CHAIN_OK && adapt && row) A.rsum[c * kf + r] = A.rsum[c * kf + r] + th0[wr];
   }
 
   // ================= proposal of step ip = i + 1 =================
   const long long ip = i + 1;
-  if ((ph & FPH_PROPOSE) && status == FMCMC_CHAIN_OK && ip <= A.nsteps) {
-    if (r < kz) s_z[r] = fun_variate(A, c, ip, r);
+  if ((ph & FPH_PROPOSE) && ch.status == FMCMC_CHAIN_OK && ip <= A.nsteps) {
+    if (r < kz) s_z[r] = ro_variate(A, c, ip, r, unif);
     __syncthreads();
     if (simple) {   // kernel_normal(_reflective), kernel_unif(_reflective) (R/kernel_normal.R:65-72, :146-164; R/kernel_unif.R)
       if (par) th1[r] = th0[r];
@@ -280,26 +199,11 @@ __global__ __launch_bounds__(NTH) void mh_fun_step(const FunArgs A) {
       }
     } else if (adapt) {   // R/kernel_adapt.R:117-180, bw = 0, freq = 1
       if (A.until > (double)abs_iter && abs_iter > A.warmup && ip > 2) {
-        const double t = (double)(abs_iter - 1);
-        double x = 0.0, mp = 0.0, mt = 0.0;
-        if (row) {
-          x = th0[wr];
-          mp = have_mean ? A.mean_prev[c * kf + r] : (A.rsum[c * kf + r] / (double)(ip - 1));
-          mt = (mp * t + x) / (t + 1);
-          vv[r] = x; vmp[r] = mp; vmt[r] = mt;
-        }
-        __syncthreads();
-        if (row) {
-          const double c1 = (t - 1) / t, c2 = 1.0 / t;
-          for (int b = 0; b <= r; b++) {      // (the lower triangle; element (r, b) has the bits of (b, r))
-            const double ik = (b == r) ? 1.0 * A.eps : 0.0;
-            const double inner = t * (mp * vmp[b]) - (t + 1) * (mt * vmt[b]) + x * vv[b] + 1e-5 * ik;
-            Mg[r * kf + b] = c1 * Mg[r * kf + b] + c2 * inner;
-          }
-          A.mean_prev[c * kf + r] = mt;
-        }
+        const double x = row ? th0[wr] : 0.0;
+        const double mp = !row ? 0.0 : have_mean ? A.mean_prev[c * kf + r] : (A.rsum[c * kf + r] / (double)(ip - 1));
+        const double mt = ro_sigma_update(row, r, (double)(abs_iter - 1), A.eps, x, mp, vv, vmp, vmt, bar, ma);
+        if (row) A.mean_prev[c * kf + r] = mt;
         have_mean = 1;
-        __syncthreads();
       }
       abs_iter += 1;
       bool notpd = false;
@@ -330,64 +234,33 @@ __global__ __launch_bounds__(NTH) void mh_fun_step(const FunArgs A) {
           }
         }
       } else {
-        // left-looking Cholesky, thread = row (chol_lower_canon): L_rb (r > b) at [b][r] of the square, the diagonal in fac
-        for (int j = 0; j < kf; j++) {
-          double s = 0.0;
-          if (row && r >= j) {
-            s = Mg[r * kf + j];
-            for (int b = 0; b < j; b++) s = fmh_fma(-Mg[b * kf + r], Mg[b * kf + j], s);
-            if (r == j) vq[0] = s;
-          }
-          __syncthreads();
-          const double d = vq[0];
-          if (!(d > 0.0) || !fmh_isfinite(d)) { notpd = true; break; }   // (uniform)
-          const double ljj = fmh_sqrt(d);
-          if (r == j) fac[j] = ljj;
-          else if (row && r > j) Mg[j * kf + r] = s / ljj;
-          __syncthreads();
-        }
-        if (!notpd) {
-          if (par) th1[r] = th0[r];
-          __syncthreads();
-          if (row) {
-            double s = 0.0;
-            for (int b = 0; b < r; b++) s = fmh_fma(Mg[b * kf + r], s_z[b], s);
-            s = fmh_fma(fac[r], s_z[r], s);
-            th1[wr] = reflect1(th0[wr] + (s_mu[wr] + s), s_lb[wr], s_ub[wr]);
-          }
-        }
+        // the Cholesky factor (chol_lower_canon): L_rb (r > b) at [b][r] of the square, the diagonal in fac
+        notpd = ro_cholesky(row, r, kf, &vq[0], bar, ma, mbl, mbd);
+        if (!notpd) ro_adapt_propose(row, par, r, wr, th0, th1, s_z, s_mu, s_lb, s_ub, bar, mbl, mbd);
       }
-      if (notpd) { status = FMCMC_CHAIN_NOT_PD; fail(ip); }   // (theta1: the previous proposal, as in the oracle)
-    } else {   // kernel_ram, R/kernel_ram.R:123-126: (S U)_r from the diagonal down to column 0
-      if (row) {
-        double s = 0.0;
-        for (int b = r; b >= 0; b--) s = fmh_fma(Mg[r * kf + b], s_z[b], s);
-        th1[wr] = th0[wr] + s;
+      if (notpd) {   // (theta1: the previous proposal, as in the oracle)
+        ch.status = FMCMC_CHAIN_NOT_PD;
+        ro_fail(A, c, r, par, ch.status, ip, &th1[r]);
       }
+    } else {   // kernel_ram, R/kernel_ram.R:123-126
+      if (row) th1[wr] = th0[wr] + ro_ram_propose(r, s_z, ma);
     }
     __syncthreads();
-    if (par && status == FMCMC_CHAIN_OK) A.th1[c * k + r] = th1[r];
+    if (par && ch.status == FMCMC_CHAIN_OK) A.th1[c * k + r] = th1[r];
   }
 
   // ================= the last launch: the Sigma square as the family path hands it on =================
   if ((ph & FPH_FINISH) && adaptive) {
     __syncthreads();
-    for (int e = r; e < kf * kf; e += NTH) {   // kernel_adapt: the symmetric Sigma; kernel_ram: the lower factor, +0 above
-      const int a = e / kf, b = e - a * kf;
-      if (b > a) Mg[e] = adapt ? Mg[b * kf + a] : 0.0;
-    }
+    ro_square_hand_on(Mg, kf, adapt, r, NTH);
   }
 
   // ---- carried values back to HBM
-  if (par) A.theta0[c * k + r] = th0[r];
-  if (r == 0) {
-    A.f0[c] = f0;
-    A.accept_count[c] = nacc;
-    if (adaptive) {
-      A.abs_iter[c] = abs_iter;
-      A.nerrors[c] = nerr;
-      if (adapt) A.have_mean[c] = have_mean;
-    }
+  ro_write_back(A, c, r, par, ch, &th0[r]);
+  if (r == 0 && adaptive) {
+    A.abs_iter[c] = abs_iter;
+    A.nerrors[c] = nerr;
+    if (adapt) A.have_mean[c] = have_mean;
   }
 }
 #endif  // FMH_WITH_FUN_KERNEL

@@ -1,5 +1,6 @@
 // mh_user.hpp -- the device half of a USER-DEFINED transition kernel (fmcmc_mcmc_run_user_dev; R/kernel.R:136-317, kernel_new):
-//   mh_user_step<NTH>     the accept / store half of mh_fun_step (mh_fun.hpp) and nothing else.  The callback path cuts the step
+//   mh_user_step<NTH>     the accept / store half of mh_fun_step (mh_fun.hpp) and nothing else: the carried values, row 1, the
+//                         decision and the write-back ARE that kernel's, the pieces of mh_rowowner.hpp.  The callback path cuts the step
 //                         at the evaluation; a user kernel cuts it once more, at the proposal: theta1 [C][k] comes from the
 //                         caller's proposal callback, f1 [C] from the evaluation, the log-ratio [C] from the caller's logratio
 //                         callback (none: f1 - f0 formed here, the decision of the built-in kernels bit for bit).
@@ -17,6 +18,7 @@
 //                         column; the coefficients are broadcast from LDS.
 // Compiled into k_fun.hip only (FMH_WITH_FUN_KERNEL); mh_engine.hip includes the argument structs.
 #pragma once
+#include "mh_rowowner.hpp"
 
 namespace {
 
@@ -73,55 +75,14 @@ __global__ __launch_bounds__(NTH) void mh_user_step(const UserArgs A) {
   const bool par = r < k, start = A.phase == UPH_START;
   const double th1 = par ? A.th1[c * k + r] : 0.0;
   double th0 = par ? A.theta0[c * k + r] : 0.0;
-  // ---- the chain's carried values (uniform: every thread keeps them)
-  int status = start ? FMCMC_CHAIN_OK : A.status[c];
-  double f0 = start ? A.f1[c] : A.f0[c];
-  long long nacc = start ? 0 : A.accept_count[c];
-  const long long nwords = (A.nsteps + 31) >> 5;
-  auto store_row = [&](long long ir, double lpv) {   // row ir of ans: kept when ir > burnin and (ir - burnin) mod thin == 0
-    if (ir > A.burnin && (ir - A.burnin) % A.thin == 0) {
-      const long long s = (ir - A.burnin) / A.thin - 1;
-      if (par) {
-        A.samples[(c * k + r) * A.ldS + s] = th0;
-        if (A.draws) A.draws[(c * k + r) * A.ldS + s] = th1;
-      }
-      if (A.logpost && r == 0) A.logpost[c * A.ldS + s] = lpv;
-    }
-  };
+  RoCarried ch = ro_carried(A, c, start);   // the chain's carried values (uniform: every thread keeps them)
   __syncthreads();   // (every wave has read the status before thread 0 writes it)
 
-  if (start) {   // row 1 (R/mcmc.R:728-735)
-    if (A.accept_bits)
-      for (long long w = r; w < nwords; w += NTH) A.accept_bits[c * nwords + w] = 0u;
-    if (r == 0) { A.status[c] = FMCMC_CHAIN_OK; A.status_step[c] = 0; }
-    store_row(1, f0);
-  } else if (status == FMCMC_CHAIN_OK) {   // accept / store of step i (R/mcmc.R:754-778)
-    const double f1 = A.f1[c];
-    if (fmh_isnan(f1)) status = FMCMC_CHAIN_NAN_LOGPOST;
-    const double ratio = A.logratio ? A.logratio[c] : f1 - f0;
-    if (status == FMCMC_CHAIN_OK && fmh_isnan(ratio)) status = FMCMC_CHAIN_NAN_RATIO;
-    if (status != FMCMC_CHAIN_OK) {
-      if (r == 0) { A.status[c] = status; A.status_step[c] = i; }
-      if (par) A.status_theta[c * k + r] = th1;
-    } else {
-      const double lu = (A.rng_mode == FMCMC_RNG_FED) ? A.fed_logu[c * A.nsteps + (i - 1)]
-                                                      : fmh_log_accept_u(A.seed, (unsigned int)(A.step_base + i), (unsigned int)(A.chain_base + c));
-      if (lu < ratio) {
-        th0 = th1;
-        f0 = f1;
-        nacc += 1;
-        if (A.accept_bits && r == 0) A.accept_bits[c * nwords + ((i - 1) >> 5)] |= (1u << ((i - 1) & 31));
-      }
-      store_row(i, f1);
-    }
-  }
-
-  // ---- carried values back to HBM
-  if (par) A.theta0[c * k + r] = th0;
-  if (r == 0) {
-    A.f0[c] = f0;
-    A.accept_count[c] = nacc;
-  }
+  if (start)   // row 1 (R/mcmc.R:728-735)
+    ro_row1(A, c, r, NTH, par, &th0, &th1, ch.f0);
+  else if (ch.status == FMCMC_CHAIN_OK)   // accept / store of step i (R/mcmc.R:754-778); theta0 is this thread's own: no barrier
+    ro_accept_store(A, c, r, par, i, A.logratio ? A.logratio[c] : A.f1[c] - ch.f0, ch, &th0, &th1, []() {});
+  ro_write_back(A, c, r, par, ch, &th0);
 }
 
 __global__ __launch_bounds__(NT) void logpost_eval_kernel(const EvalArgs A) {

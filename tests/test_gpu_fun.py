@@ -43,14 +43,21 @@ def _model(k, seed):
     return 1, X, y, np.array([list(beta) + [2.0]])
 
 
-def run_fun_both(E, O, k, kind, nchains=4, nsteps=60, calls=2, burnin=0, thin=1, seed=77, chain_base=0, shards=1, **kw):
-    """`calls` consecutive calls of the callback path against the oracle (and the first against the family path), bitwise"""
-    import torch
-    from fmcmc_amd import _abi as abi
-    from fmcmc_amd.models import batched_fun
+def fun_inputs(k, nchains, seed=77):
+    """the model and the initial values run_fun_both works on"""
     fam, X, y, base = _model(k, 100 + k)
     init = jitter_init(base[0], nchains, seed + k)
     init[:, -1] = np.abs(init[:, -1]) + 0.5
+    return fam, X, y, init
+
+
+def run_fun_both(E, O, k, kind, nchains=4, nsteps=60, calls=2, burnin=0, thin=1, seed=77, chain_base=0, shards=1, precheck=None, **kw):
+    """`calls` consecutive calls of the callback path against the oracle (and the first against the family path), bitwise.
+    precheck(ro): what a test asserts of the oracle's result alone, before the GPU runs."""
+    import torch
+    from fmcmc_amd import _abi as abi
+    from fmcmc_amd.models import batched_fun
+    fam, X, y, init = fun_inputs(k, nchains, seed)
     om = O.Model(fam, X, y)
     ok = O.Kernel(kind, k, **kw)
     spec = lambda: E.KernelSpec(kind, k, ok.mu, ok.scale, ok.lb, ok.ub, ok.fixed, scheme=ok.scheme, freq=ok.freq,
@@ -64,6 +71,8 @@ def run_fun_both(E, O, k, kind, nchains=4, nsteps=60, calls=2, burnin=0, thin=1,
     ost = O.ChainState(init, ok.kf)
     for call in range(calls):
         ro = O.run(om, ok, nsteps=nsteps, burnin=burnin, thin=thin, seed=seed, chain_base=chain_base, state=ost)
+        if precheck is not None:
+            precheck(ro)
         for (a, b), gst in zip(parts, gsts):
             rg = E.sweep(gf, gk, gst, nsteps, burnin=burnin, thin=thin, seed=seed, chain_base=chain_base + a, check=False)
             torch.cuda.synchronize()
@@ -71,6 +80,8 @@ def run_fun_both(E, O, k, kind, nchains=4, nsteps=60, calls=2, burnin=0, thin=1,
             sl = slice(a, b)
             assert np.array_equal(rg.status.cpu().numpy(), ro.status[sl])
             assert np.array_equal(rg.status_step.cpu().numpy(), ro.status_step[sl])
+            bad = ro.status[sl] != 0
+            assert _bits_equal(rg.status_theta.cpu().numpy()[bad], ro.status_theta[sl][bad]), "status_theta"
             assert np.array_equal(rg.accept_bits.cpu().numpy().view(np.uint32), ro.accept_bits[sl]), "accept bitmap"
             assert np.array_equal(rg.accept_count.cpu().numpy(), ro.accept_count[sl])
             good = ro.status[sl] == 0
@@ -146,6 +157,48 @@ def test_bitwise_above_a_wavefront(E, O, name, kw, k):
     if kind == O.K_NORMAL and "scheme" not in kw and k == 130:
         kw["fixed"] = [j == 7 for j in range(k)]
     run_fun_both(E, O, k, kind, nchains=3, nsteps=25, **kw)
+
+
+NOT_PD_CASES = {"eps_negative": dict(eps=-1e-4), "warmup_0": dict(warmup=0)}
+
+
+def not_pd_in_the_oracle(case, ro):
+    """every chain of eps < 0 (the first pivot is negative: step 2) and at least one of warmup = 0 ends NOT_PD: not vacuous"""
+    bad = ro.status == 3
+    assert bad.all() and (ro.status_step == 2).all() if case == "eps_negative" else bad.any()
+
+
+@pytest.mark.parametrize("k", [5, 64, 65])
+@pytest.mark.parametrize("case", list(NOT_PD_CASES))
+def test_not_positive_definite_is_the_oracles_status(E, O, case, k):
+    """FMCMC_CHAIN_NOT_PD from the LDL^T factor ("fun", k = 5 and 64) and from the row owner's Cholesky ("fun-wg", k = 65: the
+    uniform early exit between its barriers); the form (fmcmc_last_kernel), status, status_step and status_theta are
+    run_fun_both's assertions"""
+    run_fun_both(E, O, k, O.K_ADAPT, nchains=3, nsteps=12, calls=1, precheck=lambda ro: not_pd_in_the_oracle(case, ro), **NOT_PD_CASES[case])
+
+
+# the fewest rows beyond a wavefront, k = 65: one free parameter (a scan of zero levels, a 1 x 1 factor) and 64 of them
+EDGE_KERNELS = {"ram": ("K_RAM", 80, dict()), "ram_bounded": ("K_RAM", 80, dict(lb=-2.0, ub=3.0)), "adapt": ("K_ADAPT", 40, dict(warmup=5))}
+EDGE_SEED = 87   # (of the seeds 77 .. 91, one at which the oracle rejects a step in each of the six cases)
+
+
+def edge_case(kind_name, kf):
+    kind, nsteps, kw = EDGE_KERNELS[kind_name]
+    return kind, nsteps, dict(kw, fixed=[j != 3 for j in range(65)] if kf == 1 else [j == 5 for j in range(65)])
+
+
+def edge_in_the_oracle(ro, nsteps):
+    """at least one accepted and one rejected step, every chain alive"""
+    assert (ro.status == 0).all()
+    assert 0 < ro.accept_count.sum() < ro.accept_count.size * (nsteps - 1)
+
+
+@pytest.mark.parametrize("kf", [1, 64])
+@pytest.mark.parametrize("kind_name", list(EDGE_KERNELS))
+def test_fewest_rows_beyond_a_wavefront(E, O, kind_name, kf):
+    kind, nsteps, kw = edge_case(kind_name, kf)
+    kind = getattr(O, kind)
+    run_fun_both(E, O, 65, kind, nchains=3, nsteps=nsteps, calls=1, seed=EDGE_SEED, precheck=lambda ro: edge_in_the_oracle(ro, nsteps), **kw)
 
 
 @pytest.mark.parametrize("kind_name", ["normal", "adapt", "ram_bounded"])

@@ -93,6 +93,88 @@ def test_forced_hbm_form_equals_the_lds_form(E, O, monkeypatch, k):
     assert abi.last_kernel() == "big-k"
 
 
+def test_constr_on_the_lds_form(E, O):
+    """kernel_ram's constr with the packed triangles in LDS (the forced HBM form has it above), with and without bounds."""
+    from fmcmc_amd import _abi as abi
+    k = 70
+    X, y, init = _linreg(k, 5070, n=200)
+    constr = np.ones((k, k))
+    constr[k // 2:, :10] = 0.0
+    for kw in (dict(), dict(lb=-1.5, ub=2.5)):
+        run_both(E, O, O.FAM_LINREG, X, y, O.K_RAM, k, init, nsteps=30, constr=constr, **kw)
+        assert abi.last_kernel() == "big-k"
+
+
+# ---- the edges of the row owner's arithmetic at the fewest rows beyond a wavefront, k = 65; 3 chains, n = 200
+def _form(monkeypatch, form):
+    if form == "big-k-hbm":
+        set_knob(monkeypatch, "bigkhbm", 1)
+
+
+def _status_as_the_oracle(rg, ro):
+    assert np.array_equal(rg.status_step.cpu().numpy(), ro.status_step)
+    bad = ro.status != 0
+    assert np.array_equal(rg.status_theta.cpu().numpy()[bad].view(np.uint64), np.ascontiguousarray(ro.status_theta[bad]).view(np.uint64))
+
+
+NOT_PD_CASES = {"eps_negative": dict(eps=-1e-4), "warmup_0": dict(warmup=0)}
+
+
+def not_pd_inputs(case):
+    X, y, init = _linreg(65, 6500, n=200)
+    return X, y, init, 12, NOT_PD_CASES[case]
+
+
+def not_pd_in_the_oracle(case, ro):
+    """every chain of eps < 0 (the first pivot is negative: step 2) and at least one of warmup = 0 ends NOT_PD: not vacuous"""
+    bad = ro.status == 3
+    assert bad.all() if case == "eps_negative" else bad.any()
+    if case == "eps_negative":
+        assert (ro.status_step == 2).all()
+
+
+@pytest.mark.parametrize("form", ["big-k", "big-k-hbm"])
+@pytest.mark.parametrize("case", list(NOT_PD_CASES))
+def test_not_positive_definite_is_the_oracles_status(E, O, monkeypatch, case, form):
+    """FMCMC_CHAIN_NOT_PD: the uniform early exit from the Cholesky's column loop, between its barriers"""
+    from fmcmc_amd import _abi as abi
+    X, y, init, nsteps, kw = not_pd_inputs(case)
+    _form(monkeypatch, form)
+    rg, ro = run_both(E, O, O.FAM_LINREG, X, y, O.K_ADAPT, 65, init, nsteps=nsteps, precheck=lambda ro: not_pd_in_the_oracle(case, ro), **kw)
+    assert abi.last_kernel() == form
+    _status_as_the_oracle(rg, ro)
+
+
+EDGE_KERNELS = {"ram": ("K_RAM", 80, dict()), "ram_bounded": ("K_RAM", 80, dict(lb=-1.5, ub=2.5)), "adapt": ("K_ADAPT", 40, dict(warmup=5))}
+
+
+def edge_inputs(kind_name, kf):
+    """kf = 1: a scan of zero levels and a 1 x 1 factor (one free coefficient); kf = 64 < k: one fixed parameter"""
+    X, y, init = _linreg(65, 6600 + kf, n=200)
+    kind, nsteps, kw = EDGE_KERNELS[kind_name]
+    fixed = [j != 3 for j in range(65)] if kf == 1 else [j == 5 for j in range(65)]
+    return X, y, init, kind, nsteps, dict(kw, fixed=fixed)
+
+
+def edge_in_the_oracle(ro, nsteps):
+    """at least one accepted and one rejected step, every chain alive"""
+    assert (ro.status == 0).all()
+    assert 0 < ro.accept_count.sum() < ro.accept_count.size * (nsteps - 1)
+
+
+@pytest.mark.parametrize("form", ["big-k", "big-k-hbm"])
+@pytest.mark.parametrize("kf", [1, 64])
+@pytest.mark.parametrize("kind_name", list(EDGE_KERNELS))
+def test_fewest_rows_beyond_a_wavefront(E, O, monkeypatch, kind_name, kf, form):
+    from fmcmc_amd import _abi as abi
+    X, y, init, kind, nsteps, kw = edge_inputs(kind_name, kf)
+    kind = getattr(O, kind)
+    _form(monkeypatch, form)
+    rg, ro = run_both(E, O, O.FAM_LINREG, X, y, kind, 65, init, nsteps=nsteps, precheck=lambda ro: edge_in_the_oracle(ro, nsteps), **kw)
+    assert abi.last_kernel() == form
+    _status_as_the_oracle(rg, ro)
+
+
 def test_logistic_regression_with_200_parameters(E, O):
     """The all-family evaluation (g table, scaled coefficient copies, data-only sums) beside the HBM form."""
     from fmcmc_amd import _abi as abi

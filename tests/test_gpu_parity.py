@@ -64,9 +64,10 @@ class _Blocks:
 
 
 def run_both(E, O, fam, X, y, kind, k, initial, nsteps, burnin=0, thin=1, seed=1215, chain_base=0,
-             calls=1, intercept=True, guard=True, prior_div=0.0, threads=1, **kw):
+             calls=1, intercept=True, guard=True, prior_div=0.0, threads=1, precheck=None, **kw):
     """Runs `calls` consecutive sweeps on GPU and oracle; asserts bit-equality after each.  threads > 1: the oracle runs
-    blocks of chains on that many host threads (full-width configs)."""
+    blocks of chains on that many host threads (full-width configs).  precheck(ro): what a test asserts of the oracle's
+    result alone, before the GPU runs."""
     from fmcmc_amd import _abi as abi
     om = O.Model(fam, X, y, intercept=intercept, guard=guard, prior_div=prior_div)
     ok = O.Kernel(kind, k, **kw)
@@ -86,6 +87,8 @@ def run_both(E, O, fam, X, y, kind, k, initial, nsteps, burnin=0, thin=1, seed=1
         else:
             ro = O.run(om, ok, nsteps=nsteps, burnin=burnin, thin=thin, seed=seed, chain_base=chain_base,
                        state=ost)
+        if precheck is not None:
+            precheck(ro)
         rg = E.sweep(gm, gk, gst, nsteps, burnin=burnin, thin=thin, seed=seed, chain_base=chain_base,
                      check=False)
         import torch
