@@ -31,7 +31,9 @@ EXPORTS = ["fmcmc_abi_version", "fmcmc_last_error", "fmcmc_last_kernel", "fmcmc_
            "fmcmc_heidel_work_len", "fmcmc_heidel_out_len", "fmcmc_heidel_dev", "fmcmc_plan_route",
            "fmcmc_chain_order_work_len", "fmcmc_chain_order_dev", "fmcmc_raftery_work_len", "fmcmc_raftery_out_len",
            "fmcmc_raftery_dev", "fmcmc_hpd_work_len", "fmcmc_hpd_dev", "fmcmc_autocov_out_len", "fmcmc_autocov_dev",
-           "fmcmc_logpost_dev", "fmcmc_validate_user", "fmcmc_mcmc_run_user_dev"]
+           "fmcmc_logpost_dev", "fmcmc_validate_user", "fmcmc_mcmc_run_user_dev",
+           "fmcmc_validate_batch", "fmcmc_mcmc_run_batch_dev", "fmcmc_mcmc_run_batch_host"]
+BATCH_STREAM_DATA = 1          # fmcmc_mcmc_run_batch_*: flags bit, read the datasets from global memory every step
 SUMMARY_MAX_PROBS = 16
 CHAIN_ORDER_MAX_RANKS = 2 * SUMMARY_MAX_PROBS
 RAFTERY_MAX_THINNINGS = 32     # thinnings per fmcmc_raftery_dev call
@@ -137,6 +139,14 @@ def lib():
         L.fmcmc_mcmc_run_user_dev.restype = C.c_int
         L.fmcmc_mcmc_run_user_dev.argtypes = [C.POINTER(Model), LOGPOST_FN, PROPOSAL_FN, LOGRATIO_FN, C.c_void_p, C.c_int32,
                                               C.POINTER(Run), C.POINTER(State), C.POINTER(Out), C.c_void_p]
+        L.fmcmc_validate_batch.restype = C.c_int
+        L.fmcmc_validate_batch.argtypes = [C.POINTER(Model), C.c_int64, C.POINTER(Kernel), C.POINTER(Run)]
+        L.fmcmc_mcmc_run_batch_dev.restype = C.c_int
+        L.fmcmc_mcmc_run_batch_dev.argtypes = [C.POINTER(Model), C.c_int64, C.c_int64, C.c_int64, C.POINTER(Kernel), C.POINTER(Run),
+                                               C.POINTER(State), C.POINTER(Out), C.c_uint32, C.c_void_p]
+        L.fmcmc_mcmc_run_batch_host.restype = C.c_int
+        L.fmcmc_mcmc_run_batch_host.argtypes = [C.POINTER(Model), C.c_int64, C.c_int64, C.c_int64, C.POINTER(Kernel), C.POINTER(Run),
+                                                C.POINTER(State), C.POINTER(Out), C.c_uint32, C.c_int]
         L.fmcmc_gelman_partial_len.restype = C.c_int64
         L.fmcmc_gelman_partial_len.argtypes = [C.c_int32]
         L.fmcmc_gelman_partial_dev.restype = C.c_int

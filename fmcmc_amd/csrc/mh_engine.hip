@@ -1,5 +1,6 @@
 // mh_engine.hip — gfx950 (MI355X) many-chain Metropolis-Hastings engine: the C-ABI (include/fmcmc_amd.h), validation, the
-// launcher (launch_sweep: executes the plan of mh_route.hpp's plan_route, one function per form) and the callback sweeps (run_fun; run_user).
+// launcher (launch_sweep: executes the plan of mh_route.hpp's plan_route, one function per form), the callback sweeps (run_fun; run_user)
+// and the sweep of one model on many datasets (run_batch).
 // Two headers belong to this unit alone: mh_prep.hpp (the data-preparation kernels launch_sweep enqueues) and mh_host.hpp (the
 // staging of the host-pointer entry points).  The sweep kernels are instantiated in the k_*.hip translation units (compiled in
 // parallel, fmcmc_amd/build.py) and reached through the look-ups of mh_kernels.hpp; their source is in the headers:
@@ -40,6 +41,7 @@
 #include "mh_route.hpp"   // (kernel selection: plan_route)
 #include "mh_fun.hpp"     // (the callback path: FunArgs, its LDS size; mh_fun_step is instantiated in k_fun.hip)
 #include "mh_user.hpp"    // (a caller-defined transition kernel: UserArgs, EvalArgs; the kernels are instantiated in k_fun.hip)
+#include "mh_batch.hpp"   // (one model on many datasets: BatchArgs, the LDS rule; mh_sweep_batch is instantiated in k_fun.hip)
 #include "mh_prep.hpp"    // (the data-preparation kernels the launcher enqueues in front of a sweep)
 
 static thread_local const char* g_kernel = "";
@@ -946,7 +948,84 @@ static int run_user(const fmcmc_model* m, fmcmc_logpost_fn fun, fmcmc_proposal_f
 }
 
 
-#include "mh_host.hpp"   // (the staging of the two *_host entry points)
+// ==============================================================================================
+// one model on many datasets: the callback sweep with the family's evaluation fused in, one launch (mh_batch.hpp)
+// ==============================================================================================
+// strides of a batch, checked before any device call (fmcmc_validate_batch has no strides to check)
+static int check_batch_strides(const fmcmc_model* m, int64_t x_stride, int64_t y_stride) {
+  const long long need_x = (m->family == FMCMC_FAM_IID_NORMAL || m->p < 1) ? 0 : (long long)m->p * m->n;
+  if (x_stride < need_x || y_stride < m->n) {
+    set_err("the strides of the batch (x_stride = %lld, y_stride = %lld doubles) are smaller than a dataset (p n = %lld, n = %lld)",
+            (long long)x_stride, (long long)y_stride, need_x, (long long)m->n);
+    return FMCMC_ERR_ARG;
+  }
+  if (!m->y || (need_x > 0 && !m->X)) { set_err("the model's data pointers are null"); return FMCMC_ERR_ARG; }
+  return FMCMC_OK;
+}
+
+// The call: every pointer of m / kn / run / st / out is a DEVICE pointer (fx, lb, ub: host copies of the kernel's)
+static int run_batch(const fmcmc_model* m, long long D, long long x_stride, long long y_stride, const fmcmc_kernel* kn, const uint8_t* fx,
+                     const double* lb, const double* ub, const fmcmc_run* run, fmcmc_state* st, fmcmc_out* out, uint32_t flags,
+                     hipStream_t stream) {
+  const int k = kn->k, kf = count_free(kn, fx);
+  const long long C = run->nchains;
+  const bool adapt = kn->kind == FMCMC_KERNEL_ADAPT, ram = kn->kind == FMCMC_KERNEL_RAM, logit = m->family == FMCMC_FAM_LOGISTIC;
+  if (!st->theta0 || !st->f0) { set_err("a batch needs state->theta0 and f0"); return FMCMC_ERR_ARG; }
+  if ((adapt || ram) && (!st->Sigma || !st->abs_iter || (adapt && (!st->mean_prev || !st->have_mean)))) {
+    set_err("kernel_adapt / kernel_ram need state->Sigma and abs_iter (kernel_adapt: mean_prev and have_mean as well)");
+    return FMCMC_ERR_ARG;
+  }
+  if (is_simple_kind(kn->kind) && kn->scheme == FMCMC_SCHEME_RANDOM && run->rng_mode == FMCMC_RNG_FED && !st->scheme_cols) {
+    set_err("rng_mode = FED with scheme = 'random' needs state->scheme_cols");
+    return FMCMC_ERR_ARG;
+  }
+  BatchArgs B;
+  memset(&B, 0, sizeof(B));
+  B.F.kf = kf; B.F.ram_bounded = ram ? any_bounded(fx, lb, ub, k) : 0;
+  int rc = fill_call_args(B.F, kn, run, st, out, kf);
+  if (rc != FMCMC_OK) return rc;
+  B.family = m->family; B.p = m->p; B.intercept = m->intercept ? 1 : 0; B.guard = m->guard ? 1 : 0;
+  B.n = m->n; B.prior_div = m->prior_div; B.X = m->X; B.y = m->y;
+  B.x_stride = x_stride; B.y_stride = y_stride; B.hs_stride = 2 * MAXK + 2; B.chains_per_model = C / D;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  rc = require_gfx950(dev);
+  if (rc != FMCMC_OK) return rc;
+  // scratch of the call: the logistic sums [D][2 MAXK + 2], nerrors [C] when the caller keeps none, the free-parameter list [kf]
+  const size_t n_hs = logit ? (size_t)D * (size_t)B.hs_stride : 0, n_ne = ((adapt || ram) && !st->nerrors) ? (size_t)C : 0;
+  ScratchList scratch(stream);
+  double* hs = nullptr;
+  rc = scratch.grab(&hs, sizeof(double) * n_hs + sizeof(int) * (n_ne + (size_t)kf), "the batch's scratch");
+  if (rc != FMCMC_OK) return rc;
+  int* ne = (int*)(hs + n_hs);
+  int* which = ne + n_ne;
+  if (n_ne) { B.F.nerrors = ne; (void)hipMemsetAsync(ne, 0, sizeof(int) * n_ne, stream); }
+  B.F.which = which;
+  hipLaunchKernelGGL(fun_which_kernel, dim3(1), dim3(64), 0, stream, kn->fixed, k, which);
+  if (logit) {
+    B.hs = hs;
+    hipLaunchKernelGGL(logit_hs_batch_kernel, dim3((unsigned)D), dim3(NT), 0, stream, m->X, m->y, (long long)m->n, m->p, B.intercept, hs,
+                       x_stride, y_stride, B.hs_stride);
+  }
+  const bool lds_data = !(flags & FMCMC_BATCH_STREAM_DATA) && batch_data_in_lds(m->family, m->n, m->p, kf, kn->kind);
+  const void* kfn = fmh::k_batch(lds_data);
+  if (!kfn) { set_err("no device kernel for the batch sweep"); return FMCMC_ERR_DEVICE; }
+  const size_t lds = sizeof(double) * (batch_step_doubles(k, kf, kn->kind) + (lds_data ? batch_data_doubles(m->family, m->n, m->p) : 0));
+  if (lds > 48 * 1024 && hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    (void)hipGetLastError();
+    set_err("LDS budget exceeded (k=%d, n=%lld, p=%d)", k, (long long)m->n, m->p);
+    return FMCMC_ERR_UNSUPPORTED;
+  }
+  g_kernel = lds_data ? "batch-lds" : "batch-stream";
+  void* kargs[] = {(void*)&B};
+  hipError_t e = hipLaunchKernel(kfn, dim3((unsigned)C), dim3(NT), kargs, lds, stream);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) { set_err("HIP launch of the batch sweep failed: %s", hipGetErrorString(e)); return FMCMC_ERR_DEVICE; }
+  return FMCMC_OK;
+}
+
+
+#include "mh_host.hpp"   // (the staging of the *_host entry points)
 
 extern "C" {
 
@@ -1153,6 +1232,79 @@ int fmcmc_mcmc_run_user_dev(const fmcmc_model* m, fmcmc_logpost_fn fun, fmcmc_pr
     if (kexp != k) { set_err("Incorrect length of -initial-: the model has %d parameters, the kernel %d.", kexp, k); return FMCMC_ERR_ARG; }
   }
   return run_user(m, fun, proposal, logratio, user, k, run, st, out, (hipStream_t)hip_stream);
+}
+
+int fmcmc_validate_batch(const fmcmc_model* m, int64_t nmodels, const fmcmc_kernel* kn, const fmcmc_run* run) {
+  if (!m || !kn || !run) { set_err("null argument"); return FMCMC_ERR_ARG; }
+  const int rr = validate_run(kn, run);
+  if (rr != FMCMC_OK) return rr;
+  if (kn->k > FMCMC_MAX_K_WAVE) {
+    set_err("k = %d parameters: a batch of datasets runs up to FMCMC_MAX_K_WAVE = %d parameters per chain", kn->k, FMCMC_MAX_K_WAVE);
+    return FMCMC_ERR_UNSUPPORTED;
+  }
+  if (kn->kind == FMCMC_KERNEL_NMIRROR || kn->kind == FMCMC_KERNEL_UMIRROR) {
+    set_err("a batch of datasets runs with kernel_normal(_reflective), kernel_unif(_reflective), kernel_adapt(bw = 0, freq = 1) "
+            "and kernel_ram; the mirror kernels are not supported on this path");
+    return FMCMC_ERR_UNSUPPORTED;
+  }
+  if (kn->kind == FMCMC_KERNEL_ADAPT && (kn->bw > 0 || kn->freq > 1)) {
+    set_err("a batch of datasets runs kernel_adapt with bw = 0 and freq = 1 only (got bw=%d, freq=%d): the windowed and the "
+            "strided adaptation are not supported on this path", kn->bw, kn->freq);
+    return FMCMC_ERR_UNSUPPORTED;
+  }
+  if (nmodels < 1) { set_err("`nmodels` must be at least 1 (got %lld).", (long long)nmodels); return FMCMC_ERR_ARG; }
+  if (run->nchains % nmodels != 0) {
+    set_err("`nchains` (%lld) must be a multiple of `nmodels` (%lld): every dataset gets the same number of chains.",
+            (long long)run->nchains, (long long)nmodels);
+    return FMCMC_ERR_ARG;
+  }
+  const int kexp = eval_params(m->family, m->p, m->intercept);
+  if (kexp < 0) { set_err("unknown log-posterior family %d", m->family); return FMCMC_ERR_ARG; }
+  if (kexp != kn->k) {
+    set_err("Incorrect length of -initial-: the model has %d parameters, the kernel %d.", kexp, kn->k);
+    return FMCMC_ERR_ARG;
+  }
+  if (m->n < 1) { set_err("the model needs at least one observation"); return FMCMC_ERR_ARG; }
+  return validate_kernel(kn, run);
+}
+
+int fmcmc_mcmc_run_batch_dev(const fmcmc_model* m, int64_t nmodels, int64_t x_stride, int64_t y_stride, const fmcmc_kernel* kn,
+                             const fmcmc_run* run, fmcmc_state* st, fmcmc_out* out, uint32_t flags, void* hip_stream) {
+  if (!m || !kn || !run || !st || !out) { set_err("null argument"); return FMCMC_ERR_ARG; }
+  int rc = check_batch_strides(m, x_stride, y_stride);
+  if (rc != FMCMC_OK) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  KernelHostView v;
+  rc = kernel_host_view(kn, stream, &v);
+  if (rc != FMCMC_OK) return rc;
+  rc = fmcmc_validate_batch(m, nmodels, &v.kh, run);
+  if (rc != FMCMC_OK) return rc;
+  return run_batch(m, nmodels, x_stride, y_stride, kn, v.fx, v.lb, v.ub, run, st, out, flags, stream);
+}
+
+int fmcmc_mcmc_run_batch_host(const fmcmc_model* m, int64_t nmodels, int64_t x_stride, int64_t y_stride, const fmcmc_kernel* kn,
+                              const fmcmc_run* run, fmcmc_state* st, fmcmc_out* out, uint32_t flags, int device) {
+  if (!m || !kn || !run || !st || !out) { set_err("null argument"); return FMCMC_ERR_ARG; }
+  int rv = check_batch_strides(m, x_stride, y_stride);
+  if (rv != FMCMC_OK) return rv;
+  rv = fmcmc_validate_batch(m, nmodels, kn, run);
+  if (rv != FMCMC_OK) return rv;
+  if (!kn->fixed || !kn->lb || !kn->ub || !kn->mu || !kn->scale) { set_err("kernel arrays mu, scale, lb, ub and fixed are required"); return FMCMC_ERR_ARG; }
+  if (fmcmc_device_count() < 1) { set_err("no HIP device: the engine has no CPU fallback"); return FMCMC_ERR_DEVICE; }
+  HostStage H(kn, run, st, out);
+  if (H.adaptive && (!st->Sigma || !st->abs_iter || !st->mean_prev || !st->have_mean)) {
+    set_err("kernel_adapt / kernel_ram need state->Sigma, abs_iter, mean_prev and have_mean");
+    return FMCMC_ERR_ARG;
+  }
+  if (out->ld_rows != 0 && out->ld_rows != (int64_t)H.S) { set_err("fmcmc_out.ld_rows is honoured by fmcmc_mcmc_run_batch_dev only (host buffers are dense)"); return FMCMC_ERR_ARG; }
+  H.open(device);
+  fmcmc_model dm = *m;
+  const bool has_x = m->family != FMCMC_FAM_IID_NORMAL && m->p > 0;
+  if (has_x) H.up(&dm.X, m->X, sizeof(double) * ((size_t)(nmodels - 1) * (size_t)x_stride + (size_t)m->p * m->n));
+  H.up(&dm.y, m->y, sizeof(double) * ((size_t)(nmodels - 1) * (size_t)y_stride + (size_t)m->n));
+  stage_call(H, kn, run, st, out);
+  if (H.rc == FMCMC_OK) H.rc = run_batch(&dm, nmodels, x_stride, y_stride, &H.dk, kn->fixed, kn->lb, kn->ub, &H.dr, &H.ds, &H.dout, flags, H.stream);
+  return fetch_call(H, kn, run, st, out);
 }
 
 }  // extern "C"

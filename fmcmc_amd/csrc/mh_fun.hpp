@@ -23,7 +23,8 @@
 // kernel_adapt / kernel_ram arithmetic, the variates, the fresh start and hand-on of the square and the accept / store half
 // are the row owner's pieces of mh_rowowner.hpp (mh_sweep_bigk<true> keeps its own lines of the same arithmetic);
 // mh_user_step shares the accept / store half.  Here stay: the cut of a step into phases, the simple kernels with their
-// single-parameter schemes, and the LDL^T factor of k <= 64.
+// single-parameter schemes, and the LDL^T factor of k <= 64 -- the last two in fun_propose, the PROPOSE phase as a device
+// function that mh_sweep_batch (mh_batch.hpp: the same step with a family's evaluation fused in, one launch) calls as well.
 #pragma once
 #include "mh_rowowner.hpp"
 
@@ -85,11 +86,120 @@ __host__ __device__ inline size_t fun_lds_doubles(int k, int kf, int kind, int n
 }
 
 #ifdef FMH_WITH_FUN_KERNEL   /* compiled into k_fun.hip only */
+// the LDS vectors of a step (carved by the caller)
+struct FunLds {
+  double *mu, *scale, *lb, *ub;   // [k] the kernel's parameters
+  double *th0, *th1, *z;          // [k], [k], [k + 1]
+  double *vv, *vmp, *vmt, *vd, *vk, *vq, *vt;   // [kf] each
+  double* fac;                    // kernel_adapt: [kf][kf | 1] the LDL^T factor (LDL) | [kf] the Cholesky diagonal
+};
+
+// The proposal of loop step ip >= 2 of local chain c into L.th1, with kernel_adapt's adaptation in front of it: the PROPOSE
+// phase of mh_fun_step and the proposal of mh_sweep_batch's loop (mh_batch.hpp).  Every thread of the workgroup (thread r =
+// row r) calls it; it ends with a barrier behind theta1.  LDL: kernel_adapt factors Sigma as L D L^T in LDS (k <= 64),
+// else by the row owner's Cholesky in the square's upper half.  Mg: the chain's Sigma / S square.  rsum_r, mean_r: this row's
+// element of kernel_adapt's running row sum and of mean_prev, wherever the caller carries them.  A chain whose Sigma is not
+// positive definite gets its status here (theta1: the previous proposal, as in the oracle).
+template <bool LDL>
+__device__ __forceinline__ void fun_propose(const FunArgs& A, const FunLds& L, double* Mg, long long c, int r, long long ip,
+                                            RoCarried& ch, long long& abs_iter, int& have_mean, const double* rsum_r, double* mean_r) {
+  const int k = A.k, kf = A.kf, kz = A.kz, LD = kf | 1;
+  double *s_mu = L.mu, *s_scale = L.scale, *s_lb = L.lb, *s_ub = L.ub, *th0 = L.th0, *th1 = L.th1, *s_z = L.z;
+  double *vv = L.vv, *vmp = L.vmp, *vmt = L.vmt, *vd = L.vd, *vq = L.vq, *fac = L.fac;
+  const bool row = r < kf, par = r < k;
+  const int wr = row ? A.which[r] : 0;
+  const bool adapt = A.kind == FMCMC_KERNEL_ADAPT, simple = !adapt && A.kind != FMCMC_KERNEL_RAM;
+  const bool unif = A.kind == FMCMC_KERNEL_UNIF || A.kind == FMCMC_KERNEL_UNIF_REFLECTIVE;
+  auto bar = []() { __syncthreads(); };
+  auto ma = [&](int a, int b) -> double& { return Mg[a * kf + b]; };
+  auto mbl = [&](int a, int b) -> double& { return Mg[b * kf + a]; };
+  auto mbd = [&](int j) -> double& { return fac[j]; };
+  if (r < kz) s_z[r] = ro_variate(A, c, ip, r, unif);
+  __syncthreads();
+  if (simple) {   // kernel_normal(_reflective), kernel_unif(_reflective) (R/kernel_normal.R:65-72, :146-164; R/kernel_unif.R)
+    if (par) th1[r] = th0[r];
+    __syncthreads();
+    // plan_update_sequence (R/kernel.R:66-133): every scheme but "joint" updates ONE parameter per step
+    const bool single = A.scheme != FMCMC_SCHEME_JOINT;
+    int col = 0;
+    if (A.scheme == FMCMC_SCHEME_ORDERED) {
+      col = A.which[(int)((ip - 1) % kf)];
+    } else if (A.scheme == FMCMC_SCHEME_EXPLICIT) {
+      col = A.scheme_seq[(int)((ip - 1) % A.scheme_len)];
+    } else if (A.scheme == FMCMC_SCHEME_RANDOM) {
+      if (A.rng_mode == FMCMC_RNG_FED) {
+        col = A.scheme_cols[c * A.nsteps + (ip - 1)];
+      } else {
+        // sample(which(!fixed), nsteps, TRUE)[i]; a single free parameter at position j makes R sample from 1:j
+        const unsigned int npool = (kf == 1) ? (unsigned int)(A.which[0] + 1) : (unsigned int)kf;
+        const unsigned int idx = fmh_scheme_index(A.seed, (unsigned int)ip, (unsigned int)(A.chain_base + c), npool);
+        col = (kf == 1) ? (int)idx : A.which[idx];
+        if (A.scheme_cols && r == 0) A.scheme_cols[c * A.nsteps + (ip - 1)] = col;
+      }
+    }
+    const int nupd = single ? 1 : kf;
+    if (r < nupd) {
+      const int j = single ? col : wr;
+      double t = th0[j] + (s_mu[j] + s_scale[j] * s_z[r]);
+      if (A.kind == FMCMC_KERNEL_NORMAL_REFLECTIVE || A.kind == FMCMC_KERNEL_UNIF_REFLECTIVE) t = reflect1(t, s_lb[j], s_ub[j]);
+      th1[j] = t;
+    }
+  } else if (adapt) {   // R/kernel_adapt.R:117-180, bw = 0, freq = 1
+    if (A.until > (double)abs_iter && abs_iter > A.warmup && ip > 2) {
+      const double x = row ? th0[wr] : 0.0;
+      const double mp = !row ? 0.0 : have_mean ? *mean_r : (*rsum_r / (double)(ip - 1));
+      const double mt = ro_sigma_update(row, r, (double)(abs_iter - 1), A.eps, x, mp, vv, vmp, vmt, bar, ma);
+      if (row) *mean_r = mt;
+      have_mean = 1;
+    }
+    abs_iter += 1;
+    bool notpd = false;
+    if constexpr (LDL) {
+      // root-free factor Sigma = L D L^T, left-looking, thread = row (ldl_lower_canon): L strictly lower in fac, W_ib at [b][i], D in vd
+      for (int j = 0; j < kf; j++) {
+        double s = 0.0;
+        if (row && r >= j) {
+          s = Mg[r * kf + j];
+          for (int b = 0; b < j; b++) s = fmh_fma(-fac[r * LD + b], fac[b * LD + j], s);
+          if (r == j) vq[0] = s;
+        }
+        __syncthreads();
+        const double d = vq[0];
+        if (!(d > 0.0) || !fmh_isfinite(d)) { notpd = true; break; }   // (uniform)
+        if (r == j) { fac[j * LD + j] = 1.0; vd[j] = d; }
+        else if (row && r > j) { fac[r * LD + j] = s / d; fac[j * LD + r] = s; }
+        __syncthreads();
+      }
+      if (!notpd) {
+        if (par) th1[r] = th0[r];
+        if (row) vq[r] = fmh_sqrt(vd[r]) * s_z[r];    // u = sqrt(D) z
+        __syncthreads();
+        if (row) {
+          double s = 0.0;
+          for (int b = 0; b <= r; b++) s = fmh_fma(fac[r * LD + b], vq[b], s);   // (L_rr = 1)
+          th1[wr] = reflect1(th0[wr] + (s_mu[wr] + s), s_lb[wr], s_ub[wr]);
+        }
+      }
+    } else {
+      // the Cholesky factor (chol_lower_canon): L_rb (r > b) at [b][r] of the square, the diagonal in fac
+      notpd = ro_cholesky(row, r, kf, &vq[0], bar, ma, mbl, mbd);
+      if (!notpd) ro_adapt_propose(row, par, r, wr, th0, th1, s_z, s_mu, s_lb, s_ub, bar, mbl, mbd);
+    }
+    if (notpd) {   // (theta1: the previous proposal, as in the oracle)
+      ch.status = FMCMC_CHAIN_NOT_PD;
+      ro_fail(A, c, r, par, ch.status, ip, &th1[r]);
+    }
+  } else {   // kernel_ram, R/kernel_ram.R:123-126
+    if (row) th1[wr] = th0[wr] + ro_ram_propose(r, s_z, ma);
+  }
+  __syncthreads();
+}
+
 template <int NTH>
 __global__ __launch_bounds__(NTH) void mh_fun_step(const FunArgs A) {
   extern __shared__ double smem[];
   const int r = threadIdx.x;
-  const int k = A.k, kf = A.kf, kz = A.kz, ph = A.phase;
+  const int k = A.k, kf = A.kf, ph = A.phase;
   const long long c = blockIdx.x;            // one chain per workgroup (grid = nchains)
   const long long i = A.step;
   double* s_mu = smem;
@@ -108,11 +218,9 @@ __global__ __launch_bounds__(NTH) void mh_fun_step(const FunArgs A) {
   double* vt = vq + kf;                      // [kf] scan buffer B
   double* fac = vt + kf;                     // kernel_adapt: [kf][LD] the LDL^T factor (k <= 64) | [kf] the Cholesky diagonal
   int* s_flag = (int*)(fac + ((A.kind == FMCMC_KERNEL_ADAPT) ? (NTH <= 64 ? kf * (kf | 1) : kf) : 0));
-  const int LD = kf | 1;
   const bool row = r < kf, par = r < k;
   const int wr = row ? A.which[r] : 0;      // the free parameter of matrix row r
   const bool adapt = A.kind == FMCMC_KERNEL_ADAPT, ram = A.kind == FMCMC_KERNEL_RAM, adaptive = adapt || ram;
-  const bool simple = !adaptive;
   if (par) {
     s_mu[r] = A.mu[r]; s_scale[r] = A.scale[r]; s_lb[r] = A.lb[r]; s_ub[r] = A.ub[r];
     th0[r] = A.theta0[c * k + r];
@@ -127,8 +235,6 @@ __global__ __launch_bounds__(NTH) void mh_fun_step(const FunArgs A) {
   // its elements: Sigma / S (i >= j), the Cholesky factor's strictly lower part transposed into the upper half, its diagonal
   auto bar = []() { __syncthreads(); };
   auto ma = [&](int a, int b) -> double& { return Mg[a * kf + b]; };
-  auto mbl = [&](int a, int b) -> double& { return Mg[b * kf + a]; };
-  auto mbd = [&](int j) -> double& { return fac[j]; };
   if (adaptive && !(start && A.fresh)) {
     abs_iter = A.abs_iter[c];
     nerr = A.nerrors[c];
@@ -160,92 +266,16 @@ __global__ __launch_bounds__(NTH) void mh_fun_step(const FunArgs A) {
 
   // ================= accept / store of step i (R/mcmc.R:754-778) =================
   if ((ph & FPH_ACCEPT) && ch.status == FMCMC_CHAIN_OK) {
-    ro_accept_store(A, c, r, par, i, A.f1[c] - ch.f0, ch, &th0[r], &th1[r], bar);
+    ro_accept_store(A, c, r, par, i, A.f1[c], A.f1[c] - ch.f0, ch, &th0[r], &th1[r], bar);
     if (ch.status == FMCMC_CHAIN_OK && adapt && row) A.rsum[c * kf + r] = A.rsum[c * kf + r] + th0[wr];
   }
 
   // ================= proposal of step ip = i + 1 =================
   const long long ip = i + 1;
   if ((ph & FPH_PROPOSE) && ch.status == FMCMC_CHAIN_OK && ip <= A.nsteps) {
-    if (r < kz) s_z[r] = ro_variate(A, c, ip, r, unif);
-    __syncthreads();
-    if (simple) {   // kernel_normal(_reflective), kernel_unif(_reflective) (R/kernel_normal.R:65-72, :146-164; R/kernel_unif.R)
-      if (par) th1[r] = th0[r];
-      __syncthreads();
-      // plan_update_sequence (R/kernel.R:66-133): every scheme but "joint" updates ONE parameter per step
-      const bool single = A.scheme != FMCMC_SCHEME_JOINT;
-      int col = 0;
-      if (A.scheme == FMCMC_SCHEME_ORDERED) {
-        col = A.which[(int)((ip - 1) % kf)];
-      } else if (A.scheme == FMCMC_SCHEME_EXPLICIT) {
-        col = A.scheme_seq[(int)((ip - 1) % A.scheme_len)];
-      } else if (A.scheme == FMCMC_SCHEME_RANDOM) {
-        if (A.rng_mode == FMCMC_RNG_FED) {
-          col = A.scheme_cols[c * A.nsteps + (ip - 1)];
-        } else {
-          // sample(which(!fixed), nsteps, TRUE)[i]; a single free parameter at position j makes R sample from 1:j
-          const unsigned int npool = (kf == 1) ? (unsigned int)(A.which[0] + 1) : (unsigned int)kf;
-          const unsigned int idx = fmh_scheme_index(A.seed, (unsigned int)ip, (unsigned int)(A.chain_base + c), npool);
-          col = (kf == 1) ? (int)idx : A.which[idx];
-          if (A.scheme_cols && r == 0) A.scheme_cols[c * A.nsteps + (ip - 1)] = col;
-        }
-      }
-      const int nupd = single ? 1 : kf;
-      if (r < nupd) {
-        const int j = single ? col : wr;
-        double t = th0[j] + (s_mu[j] + s_scale[j] * s_z[r]);
-        if (A.kind == FMCMC_KERNEL_NORMAL_REFLECTIVE || A.kind == FMCMC_KERNEL_UNIF_REFLECTIVE) t = reflect1(t, s_lb[j], s_ub[j]);
-        th1[j] = t;
-      }
-    } else if (adapt) {   // R/kernel_adapt.R:117-180, bw = 0, freq = 1
-      if (A.until > (double)abs_iter && abs_iter > A.warmup && ip > 2) {
-        const double x = row ? th0[wr] : 0.0;
-        const double mp = !row ? 0.0 : have_mean ? A.mean_prev[c * kf + r] : (A.rsum[c * kf + r] / (double)(ip - 1));
-        const double mt = ro_sigma_update(row, r, (double)(abs_iter - 1), A.eps, x, mp, vv, vmp, vmt, bar, ma);
-        if (row) A.mean_prev[c * kf + r] = mt;
-        have_mean = 1;
-      }
-      abs_iter += 1;
-      bool notpd = false;
-      if constexpr (NTH <= 64) {
-        // root-free factor Sigma = L D L^T, left-looking, thread = row (ldl_lower_canon): L strictly lower in fac, W_ib at [b][i], D in vd
-        for (int j = 0; j < kf; j++) {
-          double s = 0.0;
-          if (row && r >= j) {
-            s = Mg[r * kf + j];
-            for (int b = 0; b < j; b++) s = fmh_fma(-fac[r * LD + b], fac[b * LD + j], s);
-            if (r == j) vq[0] = s;
-          }
-          __syncthreads();
-          const double d = vq[0];
-          if (!(d > 0.0) || !fmh_isfinite(d)) { notpd = true; break; }   // (uniform)
-          if (r == j) { fac[j * LD + j] = 1.0; vd[j] = d; }
-          else if (row && r > j) { fac[r * LD + j] = s / d; fac[j * LD + r] = s; }
-          __syncthreads();
-        }
-        if (!notpd) {
-          if (par) th1[r] = th0[r];
-          if (row) vq[r] = fmh_sqrt(vd[r]) * s_z[r];    // u = sqrt(D) z
-          __syncthreads();
-          if (row) {
-            double s = 0.0;
-            for (int b = 0; b <= r; b++) s = fmh_fma(fac[r * LD + b], vq[b], s);   // (L_rr = 1)
-            th1[wr] = reflect1(th0[wr] + (s_mu[wr] + s), s_lb[wr], s_ub[wr]);
-          }
-        }
-      } else {
-        // the Cholesky factor (chol_lower_canon): L_rb (r > b) at [b][r] of the square, the diagonal in fac
-        notpd = ro_cholesky(row, r, kf, &vq[0], bar, ma, mbl, mbd);
-        if (!notpd) ro_adapt_propose(row, par, r, wr, th0, th1, s_z, s_mu, s_lb, s_ub, bar, mbl, mbd);
-      }
-      if (notpd) {   // (theta1: the previous proposal, as in the oracle)
-        ch.status = FMCMC_CHAIN_NOT_PD;
-        ro_fail(A, c, r, par, ch.status, ip, &th1[r]);
-      }
-    } else {   // kernel_ram, R/kernel_ram.R:123-126
-      if (row) th1[wr] = th0[wr] + ro_ram_propose(r, s_z, ma);
-    }
-    __syncthreads();
+    const FunLds L{s_mu, s_scale, s_lb, s_ub, th0, th1, s_z, vv, vmp, vmt, vd, vk, vq, vt, fac};
+    fun_propose<(NTH <= 64)>(A, L, Mg, c, r, ip, ch, abs_iter, have_mean, adapt ? &A.rsum[c * kf + r] : nullptr,
+                             adapt ? &A.mean_prev[c * kf + r] : nullptr);
     if (par && ch.status == FMCMC_CHAIN_OK) A.th1[c * k + r] = th1[r];
   }
 

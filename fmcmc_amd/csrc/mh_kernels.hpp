@@ -54,4 +54,6 @@ FMH_HIDDEN const void* k_fun(int nth);
 // logpost_eval_kernel, the families' log-posterior at caller-given points (one workgroup of 512 threads per chain)
 FMH_HIDDEN const void* k_user(int nth);
 FMH_HIDDEN const void* k_logpost_eval();
+// k_fun.hip: mh_sweep_batch<LDS_DATA> (mh_batch.hpp), one model on many datasets: the dataset in LDS, or streamed every step
+FMH_HIDDEN const void* k_batch(bool lds_data);
 }  // namespace fmh

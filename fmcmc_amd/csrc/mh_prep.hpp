@@ -55,8 +55,8 @@ __global__ void mfma_build_stream(const double* X, const double* y, long long n,
 // Data-only sums of the canonical logistic form (include/fmh_detmath.h, fmh_logit_g; oracle: logit_hs): hs[0] = sum_i w_i when
 // the model has an intercept, hs[ic + j] = sum_i w_i x_ij, w_i = +1/2 (y_i != 0) or -1/2 -- every product exact, the sums over
 // the 512 canonical lanes in index order and their tree -- and behind them, for the range check of the fast loops, the largest
-// |x| of every column (a NaN stays).  One workgroup, once per launch: n (p + 1) additions.
-__global__ __launch_bounds__(NT) void logit_hs_kernel(const double* X, const double* y, long long n, int p, int ic, double* hs) {
+// |x| of every column (a NaN stays).  One workgroup per dataset, once per launch: n (p + 1) additions.
+__device__ __forceinline__ void logit_hs_wg(const double* X, const double* y, long long n, int p, int ic, double* hs) {
   __shared__ double s_w[NW], s_m[NW];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int col = -ic; col < p; col++) {
@@ -84,6 +84,15 @@ __global__ __launch_bounds__(NT) void logit_hs_kernel(const double* X, const dou
     }
     __syncthreads();
   }
+}
+__global__ __launch_bounds__(NT) void logit_hs_kernel(const double* X, const double* y, long long n, int p, int ic, double* hs) {
+  logit_hs_wg(X, y, n, p, ic, hs);
+}
+// the same sums of every dataset of a batch (mh_batch.hpp): workgroup d serves X + d x_stride, y + d y_stride -> hs + d hs_stride
+__global__ __launch_bounds__(NT) void logit_hs_batch_kernel(const double* X, const double* y, long long n, int p, int ic, double* hs,
+                                                            long long x_stride, long long y_stride, long long hs_stride) {
+  const long long d = blockIdx.x;
+  logit_hs_wg(X + d * x_stride, y + d * y_stride, n, p, ic, hs + d * hs_stride);
 }
 // per-workgroup slices for the observation-sharded logistic evaluation (mh_common.hpp, logit_shard): workgroup b owns the
 // canonical lanes 2 b, 2 b + 1; xs[((b nslots + slot) 2 + q) p + j] = x_ij of observation i = 512 slot + 2 b + q (0 beyond n)

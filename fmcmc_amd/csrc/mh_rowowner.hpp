@@ -1,6 +1,6 @@
 // mh_rowowner.hpp -- the arithmetic of a ROW OWNER: a kernel that gives a chain one workgroup and makes thread r row r of the
-// chain's matrices.  Callers: mh_fun_step<NTH> (mh_fun.hpp: every piece) and mh_user_step<NTH> (mh_user.hpp: the accept / store
-// half).  mh_sweep_bigk<HBM> (mh_bigk.hpp) still carries its own lines of the same arithmetic: its latency-bound loops change
+// chain's matrices.  Callers: mh_fun_step<NTH> (mh_fun.hpp: every piece), mh_sweep_batch (mh_batch.hpp: every piece, the step
+// loop in one launch) and mh_user_step<NTH> (mh_user.hpp: the accept / store half).  mh_sweep_bigk<HBM> (mh_bigk.hpp) still carries its own lines of the same arithmetic: its latency-bound loops change
 // their time by 1-6 % with any edit around them (profiles/bench_rowowner_placement.json), so it joins only with a shape measured
 // neutral.  Every operation and its order is pinned to the oracle (fmcmc_oracle.c: propose_adapt, chol_lower_canon,
 // scan_sq_canon, ram_factor_update_canon, propose_ram, reflect1; the accept rule of R/mcmc.R:754-778).
@@ -220,12 +220,12 @@ __device__ __forceinline__ void ro_row1(const Args& A, long long c, int r, int n
   if (r == 0) { A.status[c] = FMCMC_CHAIN_OK; A.status_step[c] = 0; }
   ro_store_row(A, c, r, par, 1, th0, th1, f0);
 }
-// step i (R/mcmc.R:754-778): the NaN checks, log u < ratio, theta0 / f0 / the count / the bit, the kept row.  bar(): between
-// the new theta0 and its readers, for a caller that keeps theta0 where other threads read it.
+// step i (R/mcmc.R:754-778): the NaN checks, log u < ratio, theta0 / f0 / the count / the bit, the kept row.  f1: f(theta1), from
+// wherever the caller keeps it (uniform).  bar(): between the new theta0 and its readers, for a caller that keeps theta0 where
+// other threads read it.
 template <class Args, class Bar>
-__device__ __forceinline__ void ro_accept_store(const Args& A, long long c, int r, bool par, long long i, double ratio, RoCarried& ch,
-                                                double* th0, const double* th1, Bar bar) {
-  const double f1 = A.f1[c];
+__device__ __forceinline__ void ro_accept_store(const Args& A, long long c, int r, bool par, long long i, double f1, double ratio,
+                                                RoCarried& ch, double* th0, const double* th1, Bar bar) {
   if (fmh_isnan(f1)) ch.status = FMCMC_CHAIN_NAN_LOGPOST;
   else if (fmh_isnan(ratio)) ch.status = FMCMC_CHAIN_NAN_RATIO;
   if (ch.status != FMCMC_CHAIN_OK) {

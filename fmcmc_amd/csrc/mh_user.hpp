@@ -15,7 +15,8 @@
 //                         thread = canonical lane: lane l accumulates the observations i = l, l + 512, .. in index order, the
 //                         lanes combine by the xor butterfly (wave_xor_sum, then the eight waves' values pairwise), thread 0
 //                         evaluates the closed form.  X column-major [p][n]: a wavefront reads 64 consecutive doubles of a
-//                         column; the coefficients are broadcast from LDS.
+//                         column; the coefficients are broadcast from LDS.  Its body is logpost_canon_wg, a device function
+//                         that mh_sweep_batch (mh_batch.hpp) calls as well, with the data wherever that kernel keeps them.
 // Compiled into k_fun.hip only (FMH_WITH_FUN_KERNEL); mh_engine.hip includes the argument structs.
 #pragma once
 #include "mh_rowowner.hpp"
@@ -81,19 +82,23 @@ __global__ __launch_bounds__(NTH) void mh_user_step(const UserArgs A) {
   if (start)   // row 1 (R/mcmc.R:728-735)
     ro_row1(A, c, r, NTH, par, &th0, &th1, ch.f0);
   else if (ch.status == FMCMC_CHAIN_OK)   // accept / store of step i (R/mcmc.R:754-778); theta0 is this thread's own: no barrier
-    ro_accept_store(A, c, r, par, i, A.logratio ? A.logratio[c] : A.f1[c] - ch.f0, ch, &th0, &th1, []() {});
+    ro_accept_store(A, c, r, par, i, A.f1[c], A.logratio ? A.logratio[c] : A.f1[c] - ch.f0, ch, &th0, &th1, []() {});
   ro_write_back(A, c, r, par, ch, &th0);
 }
 
-__global__ __launch_bounds__(NT) void logpost_eval_kernel(const EvalArgs A) {
-  __shared__ double s_th[MAXK], s_w[NW];
+// The canonical log-posterior of ONE parameter vector by the NT threads of a workgroup (the oracle's logpost_canon): the body of
+// logpost_eval_kernel and of mh_sweep_batch's evaluation (mh_batch.hpp).  th: the k parameters (global memory or LDS); xat(j, i)
+// / yat(i): element i of column j of X / of y, from wherever the caller keeps the data; s_th [ic + p], s_w [NW]: LDS scratch.
+// Every thread calls it (two barriers; the caller's th is visible to the workgroup before); thread 0 returns f, the others 0.
+// The caller puts a barrier between thread 0's return and the next call.
+template <class FX, class FY>
+__device__ __forceinline__ double logpost_canon_wg(int family, int p, int intercept, int guard, long long n, double prior_div,
+                                                   const double* hs, const double* th, FX xat, FY yat, double* s_th, double* s_w) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long long c = blockIdx.x, n = A.n;   // one chain per workgroup (grid = nchains)
-  const bool logit = A.family == FMCMC_FAM_LOGISTIC;
-  const int pp = (A.family == FMCMC_FAM_IID_NORMAL) ? 0 : A.p;
-  const int ic = (A.family == FMCMC_FAM_IID_NORMAL) ? 1 : A.intercept;
-  const int k = eval_params(A.family, A.p, A.intercept);
-  const double* th = A.theta + c * k;
+  const bool logit = family == FMCMC_FAM_LOGISTIC;
+  const int pp = (family == FMCMC_FAM_IID_NORMAL) ? 0 : p;
+  const int ic = (family == FMCMC_FAM_IID_NORMAL) ? 1 : intercept;
+  const int k = eval_params(family, p, intercept);
   // the coefficients the observation loop reads: the logistic ones scaled by 64 (exact), so that the table's reduced argument
   // falls out of eta (include/fmh_detmath.h, fmh_logit_g_scaled)
   for (int j = tid; j < ic + pp; j += NT) s_th[j] = logit ? th[j] * FMH_LG_SCALE : th[j];
@@ -101,28 +106,28 @@ __global__ __launch_bounds__(NT) void logpost_eval_kernel(const EvalArgs A) {
   double acc = 0.0;
   for (long long i = tid; i < n; i += NT) {
     double m = ic ? s_th[0] : 0.0;
-    for (int j = 0; j < pp; j++) m = fmh_fma(A.X[(long long)j * n + i], s_th[ic + j], m);
+    for (int j = 0; j < pp; j++) m = fmh_fma(xat(j, i), s_th[ic + j], m);
     if (logit) {
       acc = acc + fmh_logit_g_scaled(fmh_abs(m));
     } else {
-      const double r = A.y[i] - m;
+      const double r = yat(i) - m;
       acc = fmh_fma(r, r, acc);
     }
   }
   const double v = wave_xor_sum(acc);
   if (lane == 0) s_w[wave] = v;
   __syncthreads();
-  if (tid != 0) return;
+  if (tid != 0) return 0.0;
   const double tot = ((s_w[0] + s_w[1]) + (s_w[2] + s_w[3])) + ((s_w[4] + s_w[5]) + (s_w[6] + s_w[7]));
   double f;
   if (logit) {   // logl = sum_j b_j hs_j - sum_i g(|eta_i|) - sum_j b_j^2 / prior_div
     double lin = 0.0;
-    for (int j = 0; j < k; j++) lin = fmh_fma(th[j], A.hs[j], lin);
+    for (int j = 0; j < k; j++) lin = fmh_fma(th[j], hs[j], lin);
     f = lin - tot;
-    if (A.prior_div != 0.0) {
+    if (prior_div != 0.0) {
       double ss = 0.0;
       for (int j = 0; j < k; j++) ss = fmh_fma(th[j], th[j], ss);
-      f = f - ss / A.prior_div;
+      f = f - ss / prior_div;
     }
   } else {
     const double sigma = th[ic + pp];
@@ -136,8 +141,18 @@ __global__ __launch_bounds__(NT) void logpost_eval_kernel(const EvalArgs A) {
       f = -((double)n * t1) - q;
     }
   }
-  if (A.guard && !fmh_isfinite(f)) f = -fmh_inf();
-  A.out[c] = f;
+  if (guard && !fmh_isfinite(f)) f = -fmh_inf();
+  return f;
+}
+
+__global__ __launch_bounds__(NT) void logpost_eval_kernel(const EvalArgs A) {
+  __shared__ double s_th[MAXK], s_w[NW];
+  const long long c = blockIdx.x, n = A.n;   // one chain per workgroup (grid = nchains)
+  const int k = eval_params(A.family, A.p, A.intercept);
+  const double f = logpost_canon_wg(A.family, A.p, A.intercept, A.guard, n, A.prior_div, A.hs, A.theta + c * k,
+                                    [&](int j, long long i) { return A.X[(long long)j * n + i]; }, [&](long long i) { return A.y[i]; },
+                                    s_th, s_w);
+  if (threadIdx.x == 0) A.out[c] = f;
 }
 #endif  // FMH_WITH_FUN_KERNEL
 

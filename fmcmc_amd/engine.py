@@ -91,6 +91,40 @@ class DeviceModel:
         return out
 
 
+class DeviceModelBatch:
+    """D datasets of one family and one shape, resident in HBM as X [D][p][n] and y [D][n] (fmcmc_mcmc_run_batch_dev):
+    Xs [D, n, p] (or [D, n], or None when p = 0), ys [D, n]."""
+
+    def __init__(self, family, Xs, ys, intercept=True, guard=True, prior_div=0.0, device=None):
+        self.device = _dev(device)
+        ys = np.asarray(ys, dtype=np.float64)
+        if ys.ndim != 2 or ys.shape[0] < 1:
+            raise ValueError("ys must be [D, n] with D >= 1; got shape %s" % (ys.shape,))
+        D, n = ys.shape
+        if Xs is None:
+            Xc, p = None, 0
+        else:
+            Xs = np.asarray(Xs, dtype=np.float64)
+            if Xs.ndim == 2:
+                Xs = Xs[:, :, None]
+            if Xs.ndim != 3 or Xs.shape[0] != D or Xs.shape[1] != n:
+                raise ValueError("Xs must be [D, n, p] = [%d, %d, p]; got shape %s" % (D, n, Xs.shape))
+            p = Xs.shape[2]
+            Xc = _t(Xs.transpose(0, 2, 1), torch.float64, self.device) if p else None   # [D][p][n]
+        self.family, self.Xc, self.y, self.n, self.p, self.nmodels = family, Xc, _t(ys, torch.float64, self.device), int(n), int(p), int(D)
+        self.intercept, self.guard, self.prior_div = int(bool(intercept)), int(bool(guard)), float(prior_div)
+
+    k = DeviceModel.k
+
+    def c(self):
+        """fmcmc_model of dataset 0 (the shape of all of them)"""
+        return abi.Model(self.family, self.p, self.n, self.Xc.data_ptr() if self.Xc is not None else None,
+                         self.y.data_ptr(), self.intercept, self.guard, self.prior_div)
+
+    x_stride = property(lambda self: self.p * self.n)
+    y_stride = property(lambda self: self.n)
+
+
 class DeviceFun:
     """A batched user-defined log-posterior (models.BatchedFun) bound to a device: what sweep() hands to
     fmcmc_mcmc_run_fun_dev instead of a family's fmcmc_model."""
@@ -301,6 +335,35 @@ def sweep(model, kernel, state, nsteps, burnin=0, thin=1, seed=0, chain_base=0,
                                       C.c_void_p(stream.cuda_stream))
     return _finish_call(out, state, rc, "fmcmc_mcmc_run_fun_dev" if isinstance(model, DeviceFun) else "fmcmc_mcmc_run_dev",
                         nsteps, burnin, thin, chain_base, check)
+
+
+def sweep_batch(batch, kernel, state, nsteps, burnin=0, thin=1, seed=0, chain_base=0,
+                want_logpost=True, want_draws=True, want_bits=True, fed_logu=None, fed_z=None,
+                stream=None, check=True, into=None, row0=0, stream_data=False):
+    """sweep() for one model on many datasets (fmcmc_mcmc_run_batch_dev): batch is a DeviceModelBatch of D datasets, state
+    holds D x chains_per_model chains, dataset by dataset -- local chain c samples dataset c // chains_per_model with the
+    stream of global chain chain_base + c.  One launch runs every step of every chain; the keywords and the result are
+    sweep()'s.  stream_data = True reads the datasets from global memory every step instead of holding each in LDS
+    (FMCMC_BATCH_STREAM_DATA; the same bits)."""
+    L = abi.lib()
+    dev = state.device
+    out, crun, cout = _call_buffers(state, nsteps, burnin, thin, seed, chain_base, want_logpost, want_draws, want_bits,
+                                    fed_logu, fed_z, into, row0)
+    Cn, k = state.theta0.shape
+    if k != batch.k:
+        raise ValueError("Incorrect length of -initial-: the model has %d parameters, got %d." % (batch.k, k))
+    if kernel.kind in abi.SIMPLE_KERNELS and kernel.scheme == abi.SCHEME_RANDOM and state.scheme_cols is None:
+        if crun.rng_mode == abi.RNG_FED:
+            raise ValueError("rng_mode = FED with scheme = 'random' needs state.scheme_cols (the plan R drew)")
+        state.scheme_cols = torch.zeros((Cn, nsteps), dtype=torch.int32, device=dev)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev)
+    cm, ck, cs = batch.c(), kernel.c(), state.c(nsteps)
+    with torch.cuda.device(dev):
+        rc = L.fmcmc_mcmc_run_batch_dev(C.byref(cm), batch.nmodels, batch.x_stride, batch.y_stride, C.byref(ck), C.byref(crun),
+                                        C.byref(cs), C.byref(cout), abi.BATCH_STREAM_DATA if stream_data else 0,
+                                        C.c_void_p(stream.cuda_stream))
+    return _finish_call(out, state, rc, "fmcmc_mcmc_run_batch_dev", nsteps, burnin, thin, chain_base, check)
 
 
 def _call_buffers(state, nsteps, burnin, thin, seed, chain_base, want_logpost, want_draws, want_bits, fed_logu, fed_z, into, row0):

@@ -525,3 +525,123 @@ def MCMC(initial, fun, nsteps, *, seed=None, nchains=1, burnin=0, thin=1, kernel
                                         keep_logpost=keep_logpost, keep_draws=keep_draws, fed=fed)
     MCMC_OUTPUT.elapsed = time.time() - t0
     return ans
+
+
+# ------------------------------------------------------------------------------ one model on many datasets
+class McmcBatch:
+    """The result of MCMC_batch(): D datasets x nchains chains, resident in HBM.  len(ans) == D; ans[d] is the DeviceChains
+    of dataset d's chains (slices of the call's buffers, no copies: gelman_diag(ans[d]), summary(ans[d]), ... work per
+    dataset); ans.chains holds all D x nchains chains, dataset by dataset, for the per-chain diagnostics in one launch;
+    ans.to_host() is a list of D McmcList."""
+
+    def __init__(self, chains, nmodels, nchains):
+        self.chains, self.nmodels, self.nchains = chains, int(nmodels), int(nchains)
+
+    def __len__(self):
+        return self.nmodels
+
+    def __getitem__(self, d):
+        if not -self.nmodels <= d < self.nmodels:
+            raise IndexError("dataset index out of range")
+        d %= self.nmodels
+        a, ch = d * self.nchains, self.chains
+        sl = slice(a, a + self.nchains)
+        cut = lambda t: None if t is None else t[sl]
+        dc = DeviceChains(cut(ch._samples), cut(ch._logpost), cut(ch._draws), ch.iters, ch.thin, ch.names, ch.chain_base + a,
+                          self.nchains, nrows=ch.nrows)
+        dc.accept_count = ch.accept_count[sl]
+        return dc
+
+    def __iter__(self):
+        return (self[d] for d in range(self.nmodels))
+
+    def last_rows(self):
+        """[D x nchains][k]: the last kept row of every chain (a device tensor)"""
+        return self.chains._samples[:, :, self.chains.nrows - 1]
+
+    def to_host(self):
+        out = []
+        for d in range(self.nmodels):
+            h = self[d].to_host()
+            out.append(h if isinstance(h, McmcList) else McmcList([h]))
+        return out
+
+
+def batch_initial(initial, nmodels, nchains):
+    """`initial` of MCMC_batch() as the [D x nchains][k] matrix of the call (dataset by dataset) and the parameter names:
+    [k] (every chain of every dataset), [nchains][k] (recycled over the datasets), [D][nchains][k], or a previous McmcBatch
+    (each chain's last row; a device tensor then)."""
+    if isinstance(initial, McmcBatch):
+        if initial.nmodels != nmodels or initial.nchains != nchains:
+            raise ValueError("The previous result passed by `initial` has %d datasets x %d chains; this call has %d x %d."
+                             % (initial.nmodels, initial.nchains, nmodels, nchains))
+        if initial.chains.nrows < 1:
+            raise ValueError("The previous result passed by `initial` has no kept row to continue from.")
+        return initial.last_rows(), initial.chains.names
+    names = None
+    if isinstance(initial, dict):
+        names, initial = list(initial.keys()), list(initial.values())
+    a = np.asarray(initial, dtype=np.float64)
+    if a.ndim <= 1:
+        a = np.atleast_1d(a)
+        if a.size == 0:
+            raise ValueError("The `initial` vector is of length zero.")
+        a = np.tile(a, (nmodels * nchains, 1))
+    elif a.ndim == 2:
+        if a.shape[0] != nchains:
+            raise ValueError("The number of rows of `initial` (%d) must coincide with the number of chains per dataset (%d)."
+                             % (a.shape[0], nchains))
+        a = np.tile(a, (nmodels, 1))
+    elif a.ndim == 3:
+        if a.shape[0] != nmodels or a.shape[1] != nchains:
+            raise ValueError("A three-way `initial` must be [datasets][chains][parameters] = [%d][%d][k]; got %s."
+                             % (nmodels, nchains, list(a.shape)))
+        a = a.reshape(nmodels * nchains, a.shape[2])
+    else:
+        raise ValueError("`initial` must be a vector, a [nchains][k] matrix, a [D][nchains][k] array or a previous McmcBatch.")
+    if names is None:
+        names = ["par%d" % (j + 1) for j in range(a.shape[1])]
+    return np.ascontiguousarray(a), names
+
+
+def MCMC_batch(initial, batch, nsteps, nchains=1, burnin=0, thin=1, kernel=None, seed=None, device=None, keep_logpost=True,
+               keep_draws=True, conv_checker=None):
+    """MCMC() of one model on every dataset of `batch` (models.model_batch) in ONE launch: nchains chains per dataset, the
+    chains of dataset d are the global chains d nchains .. (d + 1) nchains - 1 and every one of them is bit for bit the chain
+    MCMC(fun = batch[d]) runs under that id.  initial: see batch_initial; a previous McmcBatch continues every chain from its
+    last row with the kernel object's carried state.  Kernels: kernel_normal(_reflective), kernel_unif(_reflective) (every
+    scheme), kernel_adapt(bw = 0, freq = 1), kernel_ram, up to 64 parameters.  Returns an McmcBatch."""
+    from .models import ModelBatch
+    if conv_checker is not None:
+        raise ValueError("MCMC_batch runs without a -conv_checker-: the datasets would stop at different times. Check "
+                         "gelman_diag(ans[d]) per dataset and continue with initial = ans.")
+    if not isinstance(batch, ModelBatch):
+        raise TypeError("-batch- must be a model_batch(...) of the engine's closed-form families.")
+    if kernel is None:
+        kernel = kernel_normal()
+    if isinstance(kernel, fmcmc_user_kernel):
+        raise ValueError("MCMC_batch runs the built-in kernels: a kernel_new() kernel calls back to the host every step.")
+    if not isinstance(kernel, fmcmc_kernel):
+        raise TypeError("-kernel- must be an fmcmc_kernel (kernel_normal, kernel_normal_reflective, kernel_adapt, kernel_ram).")
+    if _dist()[2] > 1:
+        raise ValueError("MCMC_batch runs on one rank: shard the datasets over the ranks and call it once per rank.")
+    D = batch.nmodels
+    _validate_common(nsteps, nchains, burnin, thin, False)
+    init, names = batch_initial(initial, D, nchains)
+    if init.shape[1] != batch.k:
+        raise ValueError("Incorrect length of -initial-: the model has %d parameters, got %d." % (batch.k, init.shape[1]))
+    if not isinstance(initial, (dict, McmcBatch)) and batch.names and len(batch.names) == len(names):
+        names = list(batch.names)
+    if seed is None:
+        _seed_counter[0] = (_seed_counter[0] * 6364136223846793005 + 1442695040888963407) & 0xFFFFFFFFFFFFFFFF
+        seed = _seed_counter[0] & 0x7FFFFFFFFFFFFFFF
+    gm = batch.device_model(device)
+    kernel._init(init.shape[1])
+    if kernel._spec is None or kernel._spec.device != gm.device:
+        kernel._spec = kernel.spec(gm.device)
+    st = kernel.state_for(init, gm.device)
+    out = engine.sweep_batch(gm, kernel._spec, st, nsteps, burnin=burnin, thin=thin, seed=seed, want_logpost=keep_logpost,
+                             want_draws=keep_draws, want_bits=False)
+    dc = DeviceChains(out.samples, out.logpost, out.draws, out.iters, thin, names, 0, D * nchains)
+    dc.accept_count = out.accept_count
+    return McmcBatch(dc, D, nchains)

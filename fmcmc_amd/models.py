@@ -133,3 +133,54 @@ def batched_fun(fn, k, names=None):
     """A user-defined log-posterior for MCMC(): fn(theta [C_local, k] float64 tensor on the device) -> [C_local] float64
     tensor on the same device.  names: optional parameter names (as the names of a named `initial`)."""
     return BatchedFun(fn, k, names)
+
+
+class ModelBatch:
+    """One closed-form family fitted to D datasets of one shape (model_batch): what MCMC_batch() samples in one launch.
+    batch[d] is dataset d's LogPosterior; the data go to HBM once per device, as X [D][p][n] and y [D][n]."""
+
+    def __init__(self, models):
+        self.models = models
+        m0 = models[0]
+        self.family, self.p, self.n = m0.family, m0.p, int(m0.y.shape[0])
+        self.intercept, self.guard, self.prior_div, self.names = m0.intercept, m0.guard, m0.prior_div, m0.names
+        self._dev = {}
+
+    nmodels = property(lambda self: len(self.models))
+    k = property(lambda self: self.models[0].k)
+
+    def __len__(self):
+        return len(self.models)
+
+    def __getitem__(self, d):
+        return self.models[d]
+
+    def device_model(self, device):
+        from .engine import DeviceModelBatch
+        key = str(device)
+        if key not in self._dev:
+            Xs = np.stack([m.X for m in self.models]) if self.p else None
+            self._dev[key] = DeviceModelBatch(self.family, Xs, np.stack([m.y for m in self.models]), self.intercept,
+                                              self.guard, self.prior_div, device=device)
+        return self._dev[key]
+
+
+def model_batch(models):
+    """A batch of datasets for MCMC_batch(): `models` is a sequence of LogPosterior (gaussian_linreg / logistic / iid_normal
+    objects) of one family with equal p, n, intercept, guard and prior_div."""
+    models = list(models)
+    if not models:
+        raise ValueError("model_batch: -models- is empty.")
+    for d, m in enumerate(models):
+        if not isinstance(m, LogPosterior):
+            raise TypeError("model_batch: models[%d] is a %s, not one of the engine's closed-form families (gaussian_linreg, "
+                            "logistic, iid_normal)." % (d, type(m).__name__))
+    m0 = models[0]
+    shape = lambda m: (("family", m.family), ("p", m.p), ("n", int(m.y.shape[0])), ("intercept", m.intercept),
+                       ("guard", m.guard), ("prior_div", m.prior_div))
+    for d, m in enumerate(models[1:], 1):
+        for (name, a), (_, b) in zip(shape(m0), shape(m)):
+            if a != b:
+                raise ValueError("model_batch: every dataset must have the same -%s-: models[0] has %r, models[%d] has %r."
+                                 % (name, a, d, b))
+    return ModelBatch(models)

@@ -316,6 +316,31 @@ int fmcmc_mcmc_run_user_dev(const fmcmc_model* model /* or NULL */, fmcmc_logpos
                             fmcmc_proposal_fn proposal, fmcmc_logratio_fn logratio /* NULL: f1 - f0 */, void* user,
                             int32_t k, const fmcmc_run* run, fmcmc_state* state, fmcmc_out* out, void* hip_stream);
 
+/* ---- one model fitted to many datasets in one call (a simulation study, a bootstrap, one regression per subject) ------------
+ * `model` gives the family and the shape every dataset shares (p, n, intercept, guard, prior_div) and the X / y of dataset 0;
+ * dataset d lies x_stride / y_stride doubles behind it (x_stride >= p n, y_stride >= n; X is [p][n] per dataset).  run->nchains
+ * is the total, nmodels x chains_per_model: local chain c samples dataset c / chains_per_model with the stream of global chain
+ * run->chain_base + c, so a caller may shard by whole datasets (X / y of its first one, chain_base advanced).  Everything else
+ * -- kernel, run, state, out with their layouts, ld_rows, FED mode, step_base, the carried kernel state, chain statuses -- is
+ * fmcmc_mcmc_run_dev's, and every output is bit for bit what that entry gives dataset d's chains on their own.
+ * One launch runs every step of every chain (one workgroup per chain; fmcmc_last_kernel(): "batch-lds" -- each workgroup holds
+ * its dataset in LDS -- or "batch-stream" -- it reads it from global memory every step; the library picks by size,
+ * FMCMC_BATCH_STREAM_DATA in `flags` forces the second).  Kernels: those of fmcmc_validate_fun (kernel_normal(_reflective) /
+ * kernel_unif(_reflective) with every scheme, kernel_adapt(bw = 0, freq = 1), kernel_ram with every option) up to
+ * FMCMC_MAX_K_WAVE parameters; refused with FMCMC_ERR_UNSUPPORTED / FMCMC_ERR_ARG: k > FMCMC_MAX_K_WAVE, the mirror kernels,
+ * the windowed / strided kernel_adapt, nmodels < 1, nchains not a multiple of nmodels, strides smaller than a dataset.
+ * fmcmc_validate_batch needs no device and applies fmcmc_validate's model and run checks with their messages (strides are
+ * checked by the run entries, before any device call). */
+enum { FMCMC_BATCH_STREAM_DATA = 1 };
+int fmcmc_validate_batch(const fmcmc_model* model, int64_t nmodels, const fmcmc_kernel* kernel, const fmcmc_run* run);
+int fmcmc_mcmc_run_batch_dev(const fmcmc_model* model /* shape; X, y: dataset 0 */, int64_t nmodels,
+                             int64_t x_stride, int64_t y_stride /* doubles between datasets */,
+                             const fmcmc_kernel* kernel, const fmcmc_run* run, fmcmc_state* state, fmcmc_out* out,
+                             uint32_t flags, void* hip_stream);
+int fmcmc_mcmc_run_batch_host(const fmcmc_model* model, int64_t nmodels, int64_t x_stride, int64_t y_stride,
+                              const fmcmc_kernel* kernel, const fmcmc_run* run, fmcmc_state* state, fmcmc_out* out,
+                              uint32_t flags, int device);   /* every pointer a host pointer */
+
 /* Gelman-Rubin partial sums over local chains (R/convergence.R:191-246 -> coda::gelman.diag).
  * Window = kept rows [row0, row0+N) of each chain. partial has fmcmc_gelman_partial_len(p)
  * doubles: {m, sum xbar[p], sum xbar xbar^T[p*p], sum S_c[p*p], sum s2[p], sum s2^2[p],
