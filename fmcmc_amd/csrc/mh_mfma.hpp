@@ -1,6 +1,7 @@
 // mh_mfma.hpp -- mh_sweep_mfma<KIND, NG, NS, DBG>: the headline kernel, bit-exact fp64 MFMA evaluation.
 #pragma once
 #include "mh_owner.hpp"
+#include "mh_sigtree.hpp"
 
 namespace {
 
@@ -56,6 +57,12 @@ constexpr int MF_TCS = 8 * PIPE_TRS + 2;   // (the replicated kernel's tile, mh_
 template <int KIND, int NG, int NS, bool DBG, bool BIG = false, bool EXT = false>
 __global__ __launch_bounds__(NT) void mh_sweep_mfma(const SweepArgs A) {
   constexpr int CW = 4;
+  // TREE: the sigma-only half of the closed form comes from the look-ahead tree (mh_sigtree.hpp).  On for the one-group resident
+  // normal / uniform instantiations, the headline's family, where no row of the resource table gets worse (profiles/r06_resources.md)
+  // and the headline is measured (-1.56 %).  With the tree the reflective, two-group, BIG and streamed instantiations gain 2 - 6
+  // VGPR spills at the register limit or lose an occupancy step at a few small NS, and nobody has timed them: they keep the
+  // per-step block, and their device code is the parent's.
+  constexpr bool TREE = KIND == FMCMC_KERNEL_NORMAL && NG == 1 && !BIG && !EXT;
 #ifndef MFO_MB
 #define MFO_MB 12
 #endif
@@ -71,6 +78,7 @@ __global__ __launch_bounds__(NT) void mh_sweep_mfma(const SweepArgs A) {
   double* s_th1 = smem;                            // [CW][PIPE_KMAX]
   double* s_par = s_th1 + CW * PIPE_KMAX;          // [4][PIPE_KMAX]
   double* s_fold = s_par + 4 * PIPE_KMAX;          // [CW][NW] per-wave sums of every chain (canonical levels 1..32 done)
+  double* s_tree = s_fold + CW * NW;               // [CW][ST_TAB] the owners' look-ahead tables (mh_sigtree.hpp)
   const long long cg0 = (long long)blockIdx.x * CW;
   const int ncw = (int)((A.nchains - cg0 < CW) ? (A.nchains - cg0) : CW);
   const int nsteps = (int)A.nsteps, burnin = (int)A.burnin, thin = (int)A.thin;
@@ -124,8 +132,11 @@ __global__ __launch_bounds__(NT) void mh_sweep_mfma(const SweepArgs A) {
   const bool plane = owner && (lane < k);
   const int jl = (lane < k) ? lane : 0;
   const bool fixed_l = A.fixed[jl] != 0;
+  // (lanes ST_ZLANE .. ST_ZLANE + ST_LOOK - 1 of an owner: sigma's variate of the rows ahead, for the look-ahead tree)
+  const int look = lane - ST_ZLANE;
+  const bool zl = TREE && look >= 0 && look < ST_LOOK;
   int zidx = 0;
-  for (int j = 0; j < jl; j++) zidx += A.fixed[j] ? 0 : 1;
+  for (int j = 0; j < (zl ? k - 1 : jl); j++) zidx += A.fixed[j] ? 0 : 1;
   if (zidx > kz - 1) zidx = kz > 0 ? kz - 1 : 0;   // lanes without a variate of their own read a valid neighbour (value unused)
   double th0 = plane ? A.theta0[(long long)cl * k + lane] : 0.0;
   double th1 = th0;
@@ -148,11 +159,14 @@ __global__ __launch_bounds__(NT) void mh_sweep_mfma(const SweepArgs A) {
   unsigned int srow8 = 0;
   // (wave-uniform 64-bit base + a 32-bit offset per lane and row: nsteps kz 8 < 2^32 is the dispatcher's condition)
   const char* const z_base = reinterpret_cast<const char*>(A.fed_z) + (BIG ? ((long long)cl * nsteps) * kz * 8 : 0ll);   // wave-uniform
-  const unsigned int z_lane = (unsigned int)(((BIG ? 0ll : (long long)cl * nsteps) * kz + zidx) * 8);
+  const unsigned int z_lane = (unsigned int)((((BIG ? 0ll : (long long)cl * nsteps) + (zl ? look : 0)) * kz + zidx) * 8);
+  // the last variate of the chain's block: the rows ahead of the last steps stop here (nobody looks their nodes up)
+  const unsigned int z_end = (unsigned int)((((BIG ? 0ll : (long long)cl * nsteps) + nsteps) * kz - 1) * 8);
   const double* const lu_row = A.fed_logu + (long long)cl * nsteps;
   const double dn = uniform_d((double)A.n);
   auto ld_z = [&](int row) -> double {
-    return *reinterpret_cast<const double*>(z_base + (z_lane + (unsigned int)row * (unsigned int)(kz * 8)));
+    const unsigned int off = z_lane + (unsigned int)row * (unsigned int)(kz * 8);
+    return *reinterpret_cast<const double*>(z_base + ((!TREE || off < z_end) ? off : z_end));
   };
   // every lane of an owner wavefront keeps one variate and the log-uniform of the next step in flight (unconditional,
   // clamped addresses: a conditional load costs a register copy behind the load, i.e. an exposed wait)
@@ -174,6 +188,20 @@ __global__ __launch_bounds__(NT) void mh_sweep_mfma(const SweepArgs A) {
   bool st_acc = false;
   double st_th0 = 0.0, st_th1 = 0.0, st_f1 = 0.0;
   unsigned long long te = 0, tb1 = 0, to = 0, tb2 = 0, tf = 0, tc = 0, td = 0;
+  int node = ST_NODES;                       // of the look-ahead tree: every launch starts with a pass
+  // the node's values, looked up behind the releasing barrier as soon as the decision is known (the LDS round trip hides under the
+  // first MFMAs instead of standing in front of the barrier), or right behind a pass
+  double nt1_fast = 0.0, ss_fast = 1.0, rs_fast = 1.0;
+  int st_fl = 0;
+  auto look_up = [&]() {
+    typedef double st_d2 __attribute__((ext_vector_type(2)));
+    const st_d2* e = reinterpret_cast<const st_d2*>(s_tree + myc * ST_TAB + node * ST_ENTRY);
+    const st_d2 e0 = e[0], e1 = e[1];
+    nt1_fast = uniform_d(e0[0]);
+    ss_fast = uniform_d(e0[1]);
+    rs_fast = uniform_d(e1[0]);
+    st_fl = __builtin_amdgcn_readfirstlane((int)__double_as_longlong(e1[1]));
+  };
   for (int v = 1; v <= nsteps; v++) {
     unsigned long long t_0 = dbg ? clk() : 0;
     // ================= evaluation of version v of all 4 chains =================
@@ -287,26 +315,42 @@ __global__ __launch_bounds__(NT) void mh_sweep_mfma(const SweepArgs A) {
     // (Measured: moving log(sigma) of the owners in front of, or right behind, their MFMAs makes the step SLOWER:
     //  fp64 VALU work issued while the SIMD partner runs MFMAs slows those -- one fp64 datapath -- whereas in
     //  the owner phase below that datapath is idle.)
-    // sigma-only part of the closed form: the owner waves are the first of their SIMD to finish their MFMAs (the older
-    // wave wins the arbitration) and would wait ~1200 ticks at the barrier; its ~65 fp64 instructions run there, in the
-    // shadow of the partner wave's MFMAs, instead of in the exposed owner phase.  The results are wave-uniform (SGPRs).
-    double sigma = 0.0, nt1_fast = 0.0, ss_fast = 1.0, rs_fast = 1.0;
+    // sigma-only part of the closed form.  Until round 5 every step ran its ~100 instructions here, behind the owners' MFMAs,
+    // for ONE double per wave; now one pass in six steps prepares the 63 sigmas the next six proposals can carry, one per lane
+    // (mh_sigtree.hpp), and a step looks up the node its decisions led to (look_up, behind the releasing barrier).  A pass runs
+    // on the first step of a launch, after the sixth look-up and after every pass through the rare branch (node >= ST_NODES);
+    // node 0 is the sigma of the actual th1.  The pass stays HERE: its fp64 chain in front of the MFMAs would slow the partner's
+    // (above).  The look-up does not: in front of this barrier its LDS round trip was exposed (profiles/r06_sigma_tree.md: 0.6 %
+    // gained with it here, 1.6 % with it behind the releasing barrier).
+    double sigma = 0.0;
     bool sg_fast = false, ok_fast = false;
-    if (owner) {
-      sigma = readlane_d(th1, k - 1);
-      const unsigned sg_hi = (unsigned)(fmh_d2u(sigma) >> 32);
-      sg_fast = (sg_hi - 0x00100000u) < 0x7fe00000u;                     // positive, finite, normal
-      const double sg = sg_fast ? sigma : 1.0;
+    if constexpr (TREE) {
+      if (owner && node >= ST_NODES) {
+        sigtree_build<KIND>((st_lds_d*)(s_tree + myc * ST_TAB), (const st_lds_d*)s_par, th0, th1, z_nx, k, (int)((__ballot(fixed_l) >> (k - 1)) & 1ull), dn);
+        node = 0;
+        look_up();
+      }
+      sg_fast = (st_fl & 1) != 0;
+      ok_fast = (st_fl & 2) != 0;
+    } else {
+      // the per-step form: ~65 fp64 instructions in the shadow of the partner wave's MFMAs; the results are wave-uniform (SGPRs)
+      nt1_fast = 0.0; ss_fast = 1.0; rs_fast = 1.0;
+      if (owner) {
+        sigma = readlane_d(th1, k - 1);
+        const unsigned sg_hi = (unsigned)(fmh_d2u(sigma) >> 32);
+        sg_fast = (sg_hi - 0x00100000u) < 0x7fe00000u;                     // positive, finite, normal
+        const double sg = sg_fast ? sigma : 1.0;
 #ifdef MFO_NOLOG   /* timing ablation (tools/exp_mfmar.hip): what the logarithm in the owners' MFMA slack costs */
-      const double t1_fast = sg + FMH_K(FMH_LN_SQRT_2PI);
+        const double t1_fast = sg + FMH_K(FMH_LN_SQRT_2PI);
 #else
-      const double t1_fast = fmh_log_pn(sg) + FMH_K(FMH_LN_SQRT_2PI);   // same bits as fmh_log(sigma) on this range
+        const double t1_fast = fmh_log_pn(sg) + FMH_K(FMH_LN_SQRT_2PI);   // same bits as fmh_log(sigma) on this range
 #endif
-      nt1_fast = uniform_d(dn * t1_fast);
-      ss_fast = uniform_d(sg * sg);
-      // denominator half of (0.5 tot) / sigma^2 (mh_common.hpp: div_recip / div_finish), in the same slack
-      ok_fast = sg_fast && mfr_div_safe(ss_fast);
-      rs_fast = uniform_d(div_recip(ok_fast ? ss_fast : 1.0));
+        nt1_fast = uniform_d(dn * t1_fast);
+        ss_fast = uniform_d(sg * sg);
+        // denominator half of (0.5 tot) / sigma^2 (mh_common.hpp: div_recip / div_finish), in the same slack
+        ok_fast = sg_fast && mfr_div_safe(ss_fast);
+        rs_fast = uniform_d(div_recip(ok_fast ? ss_fast : 1.0));
+      }
     }
     unsigned long long t_1 = dbg ? clk() : 0;
     lds_barrier();
@@ -353,12 +397,13 @@ __global__ __launch_bounds__(NT) void mh_sweep_mfma(const SweepArgs A) {
         th0_row = th0;
         propose(false);
       } else {
+        if constexpr (TREE) node = ST_STALE;    // the next step starts from a fresh pass
         keep_row = false;
         if (sg_fast) {
           f1 = -nt1_fast - h / ss_fast;
           if (A.guard && !fmh_isfinite(f1)) f1 = -fmh_inf();
         } else {
-          f1 = linreg_logpost(tot, sigma, dn, A.guard);
+          f1 = linreg_logpost(tot, TREE ? readlane_d(th1_eval, k - 1) : sigma, dn, A.guard);
         }
         if (v == 1) {
           f0 = f1;
@@ -398,6 +443,10 @@ __global__ __launch_bounds__(NT) void mh_sweep_mfma(const SweepArgs A) {
       lu_nx = lu_row[v < nsteps ? v : nsteps - 1];
       if (kz > 0) z_nx = ld_z(v + 1 < nsteps ? v + 1 : nsteps - 1);
       nacc += st_acc ? 1 : 0;
+      if constexpr (TREE) {
+        node = st_child(node, __builtin_amdgcn_readfirstlane(st_acc ? 1 : 0));
+        if (node < ST_NODES) look_up();
+      }
       bitword |= (st_acc ? 1u : 0u) << ((v - 1) & 31);
       if (st_keep && v > burnin) {
         thin_ctr += 1;
@@ -428,6 +477,6 @@ __global__ __launch_bounds__(NT) void mh_sweep_mfma(const SweepArgs A) {
   }
 }
 
-size_t mfma_lds_bytes() { return sizeof(double) * ((size_t)8 * PIPE_KMAX + 4 * NW); }
+size_t mfma_lds_bytes() { return sizeof(double) * ((size_t)8 * PIPE_KMAX + 4 * NW + 4 * ST_TAB); }
 
 }  // namespace
