@@ -59,10 +59,14 @@ __global__ __launch_bounds__(NT) void mh_sweep_mfma(const SweepArgs A) {
   constexpr int CW = 4;
   // TREE: the sigma-only half of the closed form comes from the look-ahead tree (mh_sigtree.hpp).  On for the one-group resident
   // normal / uniform instantiations, the headline's family, where no row of the resource table gets worse (profiles/r06_resources.md)
-  // and the headline is measured (-1.56 %).  With the tree the reflective, two-group, BIG and streamed instantiations gain 2 - 6
-  // VGPR spills at the register limit or lose an occupancy step at a few small NS, and nobody has timed them: they keep the
+  // and the headline is measured (-1.56 %, and -1.58 % more with the shorter pass of round 7).  Round 7 also switches it on for their
+  // BIG twins from nine slots up: a call of 1.2e5 steps runs on <1, 1, 20, BIG>, and with the per-step block it fell 2.8 - 3.0 %
+  // behind a 1e4-step call per step, the edge of what tests/test_gpu_perf_guard.py allows; with the tree 1.9 - 2.2 % (2.056 -> 2.029 us
+  // per step, profiles/r07_owner_window.md), although that instantiation goes from 8 to 12 spilled VGPRs.  Below nine slots the
+  // BIG forms with the tree lose an occupancy step at NS = 4 and 8; the reflective, two-group and streamed instantiations gain 2 - 6
+  // VGPR spills at the register limit or lose an occupancy step at a few small NS, and nobody has timed those: they keep the
   // per-step block, and their device code is the parent's.
-  constexpr bool TREE = KIND == FMCMC_KERNEL_NORMAL && NG == 1 && !BIG && !EXT;
+  constexpr bool TREE = KIND == FMCMC_KERNEL_NORMAL && NG == 1 && !EXT && (!BIG || NS >= 9);
 #ifndef MFO_MB
 #define MFO_MB 12
 #endif

@@ -46,19 +46,25 @@ __device__ __noinline__ void sigtree_build(st_lds_d* tab, const st_lds_d* par, d
   const double mu = par[0 * PIPE_KMAX + k - 1], sc = par[1 * PIPE_KMAX + k - 1];
   const double lb = par[2 * PIPE_KMAX + k - 1], ub = par[3 * PIPE_KMAX + k - 1];
   double a = readlane_d(th0, k - 1), b = readlane_d(th1, k - 1);
-#pragma unroll 1
-  for (int j = 0; j < ST_LOOK; j++) {              // decision j + 1 of the lane's path, then the owner's propose()
-    const bool on = j < d;
-    const double dz = mu + sc * readlane_d(z, ST_ZLANE + j);
-    const bool acc = ((path >> (on ? d - 1 - j : 0)) & 1) != 0;
-    const double a1 = acc ? b : a;
-    double t = a1 + dz;
-    if (KIND == FMCMC_KERNEL_NORMAL_REFLECTIVE) {
-      if (on && !fixed) t = reflect1(t, lb, ub);
+  // The replay is the pass's only loop and ran 24 instructions a level (round 7: the pass costs an owner ~1700 cycles, 6 % of the
+  // step, profiles/r07_owner_window.md); now ten.  The increments of all levels come from ONE multiply and add, in the lanes that
+  // hold the variates (the same doubles as mu + sc * z computed level by level).  The decisions of a lane sit left-aligned in
+  // `take`: bit 31 - j is set where level j belongs to the lane's path AND accepts, so levels behind the lane's depth take nothing.
+  // A fixed sigma skips the replay: its proposal is its state on every path (th1 == th0 in that lane, whatever the decisions).
+  const double dzl = mu + sc * z;
+  const unsigned take = ((unsigned)path << (31 - d)) << 1;
+  if (!fixed) {
+#pragma unroll
+    for (int j = 0; j < ST_LOOK; j++) {            // decision j + 1 of the lane's path, then the owner's propose()
+      const bool on = j < d;
+      const double a1 = (take & (0x80000000u >> j)) ? b : a;
+      double t = a1 + readlane_d(dzl, ST_ZLANE + j);
+      if (KIND == FMCMC_KERNEL_NORMAL_REFLECTIVE) {
+        if (on) t = reflect1(t, lb, ub);
+      }
+      a = a1;
+      b = on ? t : b;
     }
-    t = fixed ? a1 : t;
-    a = on ? a1 : a;
-    b = on ? t : b;
   }
   const unsigned sg_hi = (unsigned)(fmh_d2u(b) >> 32);
   const bool sg_fast = (sg_hi - 0x00100000u) < 0x7fe00000u;                     // positive, finite, normal
