@@ -32,7 +32,8 @@ EXPORTS = ["fmcmc_abi_version", "fmcmc_last_error", "fmcmc_last_kernel", "fmcmc_
            "fmcmc_chain_order_work_len", "fmcmc_chain_order_dev", "fmcmc_raftery_work_len", "fmcmc_raftery_out_len",
            "fmcmc_raftery_dev", "fmcmc_hpd_work_len", "fmcmc_hpd_dev", "fmcmc_autocov_out_len", "fmcmc_autocov_dev",
            "fmcmc_logpost_dev", "fmcmc_validate_user", "fmcmc_mcmc_run_user_dev",
-           "fmcmc_validate_batch", "fmcmc_mcmc_run_batch_dev", "fmcmc_mcmc_run_batch_host"]
+           "fmcmc_validate_batch", "fmcmc_mcmc_run_batch_dev", "fmcmc_mcmc_run_batch_host",
+           "fmcmc_mcmc_run_batch_sel_dev", "fmcmc_gelman_groups_work_len", "fmcmc_gelman_groups_dev"]
 BATCH_STREAM_DATA = 1          # fmcmc_mcmc_run_batch_*: flags bit, read the datasets from global memory every step
 SUMMARY_MAX_PROBS = 16
 CHAIN_ORDER_MAX_RANKS = 2 * SUMMARY_MAX_PROBS
@@ -144,6 +145,9 @@ def lib():
         L.fmcmc_mcmc_run_batch_dev.restype = C.c_int
         L.fmcmc_mcmc_run_batch_dev.argtypes = [C.POINTER(Model), C.c_int64, C.c_int64, C.c_int64, C.POINTER(Kernel), C.POINTER(Run),
                                                C.POINTER(State), C.POINTER(Out), C.c_uint32, C.c_void_p]
+        L.fmcmc_mcmc_run_batch_sel_dev.restype = C.c_int
+        L.fmcmc_mcmc_run_batch_sel_dev.argtypes = [C.POINTER(Model), C.c_int64, C.c_int64, C.c_int64, C.POINTER(Kernel), C.POINTER(Run),
+                                                   C.POINTER(State), C.POINTER(Out), C.c_void_p, C.c_uint32, C.c_void_p]
         L.fmcmc_mcmc_run_batch_host.restype = C.c_int
         L.fmcmc_mcmc_run_batch_host.argtypes = [C.POINTER(Model), C.c_int64, C.c_int64, C.c_int64, C.POINTER(Kernel), C.POINTER(Run),
                                                 C.POINTER(State), C.POINTER(Out), C.c_uint32, C.c_int]
@@ -155,6 +159,11 @@ def lib():
         L.fmcmc_gelman_partial_dev.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64,
                                                C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p]
+        L.fmcmc_gelman_groups_work_len.restype = C.c_int64
+        L.fmcmc_gelman_groups_work_len.argtypes = [C.c_int64, C.c_int64, C.c_int32]
+        L.fmcmc_gelman_groups_dev.restype = C.c_int
+        L.fmcmc_gelman_groups_dev.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                              C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.fmcmc_gelman_finish.restype = C.c_int
         L.fmcmc_gelman_finish.argtypes = [_dp, C.c_int32, C.c_int64, _dp, _dp]
         L.fmcmc_summary_work_len.restype = C.c_int64

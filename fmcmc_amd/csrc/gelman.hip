@@ -217,6 +217,70 @@ __global__ __launch_bounds__(GT) void gelman_sum_kernel(const double* __restrict
   if (g == 0 && e < len) partial[e] = ((s_g[0][el] + s_g[1][el]) + s_g[2][el]) + s_g[3][el];
 }
 
+// gelman_sum_kernel per GROUP of Cm consecutive chains (fmcmc_gelman_groups_dev: one model on many datasets, a group = the chains
+// of one dataset): row grp of `partials` is, bit for bit, what gelman_sum_kernel leaves for the Cm chains of the group alone,
+// centred on the window's first row of the group's first chain.  `work` holds the PLAIN window means (gelman_cov_mfma with
+// center == NULL: xbar - 0.0 is xbar), so the one subtraction that kernel would have made is made here, where the group is known:
+// xb = work - centre, with the centre read from the samples.  One block per (group, 64 elements of the row), four threads per
+// element; thread g walks the chains g, g + 4, ... of the group, the four sums are joined as ((g0 + g1) + g2) + g3.
+// A row has two more doubles than a partial: the sum and the sum of squares of every entry of the group's window, from the
+// chains' means and variances (rm_invariant, R/convergence.R:171-173; convergence_gelman.check_device forms them with torch
+// reductions), summed chain by chain and column by column within a chain: N sum xbar and sum ((N - 1) s2 + N xbar^2), xbar =
+// xb + centre.  A group whose `active` entry is 0 leaves its row as it was; the test is uniform per block and comes first.
+__global__ __launch_bounds__(GT) void gelman_group_sum_kernel(const double* __restrict__ work, const double* __restrict__ samples,
+                                                              long long S, int k, long long row0, long long N,
+                                                              const int* __restrict__ cols, long long Cm, int p, int nslices,
+                                                              const int* __restrict__ active, double* __restrict__ partials) {
+  __shared__ double s_g[4][64];
+  const long long grp = blockIdx.x / nslices;
+  if (active && active[grp] == 0) return;
+  const int el = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const int stride = p + p * p;
+  const int len = 1 + 5 * p + 2 * p * p;
+  const int e = (int)(blockIdx.x % nslices) * 64 + el;
+  const double* w = work + grp * Cm * stride;                            // the group's chains
+  const double* ctr = samples + grp * Cm * (long long)k * S + row0;       // centre of column a: ctr[cols[a] * S]
+  const double dn = (double)N;
+  double s = 0.0;
+  if (e < len) {
+    if (e == 0) {
+      s = (g == 0) ? (double)Cm : 0.0;
+    } else if (e < 1 + p) {  // sum xbar
+      const int a = e - 1;
+      const double ca = ctr[(long long)cols[a] * S];
+      for (long long c = g; c < Cm; c += 4) s += w[c * stride + a] - ca;
+    } else if (e < 1 + p + p * p) {  // sum xbar xbar^T
+      const int ab = e - 1 - p, a = ab / p, b = ab % p;
+      const double ca = ctr[(long long)cols[a] * S], cb = ctr[(long long)cols[b] * S];
+      for (long long c = g; c < Cm; c += 4) s = __builtin_fma(w[c * stride + a] - ca, w[c * stride + b] - cb, s);
+    } else if (e < 1 + p + 2 * p * p) {  // sum S_c
+      const int ab = e - 1 - p - p * p;
+      for (long long c = g; c < Cm; c += 4) s += w[c * stride + p + ab];
+    } else {
+      const int r = e - 1 - p - 2 * p * p, which = r / p, a = r % p;
+      const double ca = ctr[(long long)cols[a] * S];
+      for (long long c = g; c < Cm; c += 4) {
+        double s2 = w[c * stride + p + a * p + a], xb = w[c * stride + a] - ca;
+        double v = (which == 0) ? s2 : (which == 1) ? s2 * s2 : (which == 2) ? s2 * xb : s2 * xb * xb;
+        s += v;
+      }
+    }
+  } else if (e < len + 2) {  // every entry of the window: the sum (len), the sum of squares (len + 1)
+    for (long long c = g; c < Cm; c += 4)
+      for (int a = 0; a < p; a++) {
+        const double ca = ctr[(long long)cols[a] * S];
+        const double x = (w[c * stride + a] - ca) + ca, s2 = w[c * stride + p + a * p + a];
+        s += (e == len) ? x : (dn - 1.0) * s2 + dn * x * x;
+      }
+  }
+  s_g[g][el] = s;
+  __syncthreads();
+  if (g == 0 && e < len + 2) {
+    const double v = ((s_g[0][el] + s_g[1][el]) + s_g[2][el]) + s_g[3][el];
+    partials[grp * (len + 2) + e] = (e == len) ? dn * v : v;
+  }
+}
+
 // Largest eigenvalue of a symmetric matrix (row-major, destroyed): Householder reduction to tridiagonal form, then the QL
 // iteration with implicit shifts on the diagonal / sub-diagonal pair (eigenvalues only, nothing accumulated): O(p^3) once and
 // O(p^2) per eigenvalue.  (The cyclic Jacobi sweeps this replaces ran until the off-diagonal norm was below 1e-300:
@@ -344,6 +408,48 @@ int fmcmc_gelman_partial_dev(const double* samples, int64_t nchains, int32_t k, 
   const int plen = 1 + 5 * (int)p + 2 * (int)p * (int)p;
   hipLaunchKernelGGL(gelman_sum_kernel, dim3((unsigned)((plen + 63) / 64)), dim3(GT), 0, st, work, (long long)nchains, (int)p, partial);
   return hipGetLastError() == hipSuccess ? FMCMC_OK : FMCMC_ERR_DEVICE;
+}
+
+int64_t fmcmc_gelman_groups_work_len(int64_t ngroups, int64_t chains_per_group, int32_t p) {
+  return fmcmc_gelman_work_len(ngroups * chains_per_group, p);
+}
+
+// The reduction of fmcmc_gelman_partial_dev for ngroups groups of chains_per_group consecutive chains in two launches: the
+// window means and covariances of ALL chains (gelman_cov_mfma, uncentred), then gelman_group_sum_kernel.  p <= FMCMC_MAX_K_WAVE.
+int fmcmc_gelman_groups_dev(const double* samples, int64_t ngroups, int64_t chains_per_group, int32_t k, int64_t S, int64_t row0,
+                            int64_t N, const int32_t* cols, int32_t p, const int32_t* active, double* work, double* partials,
+                            void* hip_stream) {
+  const char* who = "fmcmc_gelman_groups_dev";
+  if (!samples || !cols || !work || !partials) return fail(FMCMC_ERR_ARG, "%s: null argument", who);
+  if (ngroups < 1 || chains_per_group < 1 || k < 1 || p < 1)
+    return fail(FMCMC_ERR_ARG, "%s: ngroups = %lld, chains_per_group = %lld, k = %d, p = %d: each must be at least 1", who,
+                (long long)ngroups, (long long)chains_per_group, (int)k, (int)p);
+  if (N < 2 || row0 < 0 || row0 + N > S)
+    return fail(FMCMC_ERR_ARG, "%s: the window [%lld, %lld) needs at least two of the %lld rows of a chain", who, (long long)row0,
+                (long long)(row0 + N), (long long)S);
+  if (p > FMCMC_MAX_K_WAVE)
+    return fail(FMCMC_ERR_UNSUPPORTED, "%s: p = %d columns; the grouped reduction takes up to FMCMC_MAX_K_WAVE = %d", who, (int)p,
+                FMCMC_MAX_K_WAVE);
+  const int plen = 1 + 5 * (int)p + 2 * (int)p * (int)p;
+  const int nslices = (plen + 2 + 63) / 64;
+  if (chains_per_group > 0x7fffffffLL / ngroups || ngroups > 0x7fffffffLL / nslices)
+    return fail(FMCMC_ERR_UNSUPPORTED, "%s: %lld groups x %lld chains exceed one launch", who, (long long)ngroups,
+                (long long)chains_per_group);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const long long nchains = ngroups * chains_per_group;
+#define GELMAN_LAUNCH(NA)                                                                                                  \
+  hipLaunchKernelGGL((gelman_cov_mfma<NA, true>), dim3((unsigned)nchains), dim3(GT), 0, st, samples, (long long)S, (int)k,  \
+                     (long long)row0, (long long)N, cols, (int)p, 1, (const double*)nullptr, work)
+  switch ((p + 15) / 16) {
+    case 1: GELMAN_LAUNCH(1); break;
+    case 2: GELMAN_LAUNCH(2); break;
+    case 3: GELMAN_LAUNCH(3); break;
+    default: GELMAN_LAUNCH(4); break;
+  }
+#undef GELMAN_LAUNCH
+  hipLaunchKernelGGL(gelman_group_sum_kernel, dim3((unsigned)(ngroups * nslices)), dim3(GT), 0, st, work, samples, (long long)S,
+                     (int)k, (long long)row0, (long long)N, cols, (long long)chains_per_group, (int)p, nslices, active, partials);
+  return hipGetLastError() == hipSuccess ? FMCMC_OK : fail(FMCMC_ERR_DEVICE, "%s: the launch failed", who);
 }
 
 // Host finish. partial is the (all-reduced) vector; xbar sums are relative to `center`.

@@ -1,4 +1,4 @@
-// mh_batch.hpp -- mh_sweep_batch<LDS_DATA>: ONE model fitted to MANY datasets in one launch (fmcmc_mcmc_run_batch_*; Python:
+// mh_batch.hpp -- mh_sweep_batch<LDS_DATA, MASKED>: ONE model fitted to MANY datasets in one launch (fmcmc_mcmc_run_batch_*; Python:
 // MCMC_batch).  The callback path (mh_fun.hpp) cuts a step at the evaluation and returns to the host; here the evaluation is a
 // family's closed form, so the whole loop i = 2 .. nsteps runs inside one kernel:
 //   row 1      f0 = f(initial), kernel state initialised, row stored                                    (mh_fun_step: START)
@@ -16,7 +16,8 @@
 // theta0, theta1, the variates, kernel_adapt's LDL^T factor, running row sum and mean_prev live in LDS for the whole call, f0,
 // the accept count, abs_iter, nerrors, have_mean in registers (uniform); Sigma / S is worked in place in the chain's Sigma
 // square in HBM (the owner pieces' barriers are __syncthreads).  A chain whose status turns non-zero leaves its loop: uniform,
-// one workgroup serves one chain, so every barrier sits in uniform control flow.
+// one workgroup serves one chain, so every barrier sits in uniform control flow.  BatchArgs.active switches whole datasets off
+// (MCMC_batch(stop_each = ...): the datasets that have converged): their workgroups return at once.
 //
 // Where the data sit (the same bits): LDS_DATA = true ("batch-lds") copies the dataset into LDS once, column-major as in HBM --
 // lane l reads address l of a column, consecutive doubles, no bank conflict --; false ("batch-stream") reads it from global
@@ -38,6 +39,7 @@ struct BatchArgs {
   const double* hs;          // logistic: [D][hs_stride] the data-only sums of every dataset
   long long x_stride, y_stride, hs_stride;
   long long chains_per_model;
+  const int* active;         // [nmodels] or NULL: the chains of a dataset whose entry is 0 do not run (fmcmc_mcmc_run_batch_sel_dev)
 };
 
 // LDS doubles of the dataset copy: logistic reads X only (y is in hs), the Gaussian families X and y
@@ -61,7 +63,10 @@ inline bool batch_data_in_lds(int family, long long n, int p, int kf, int kind) 
 // (four waves per SIMD = two workgroups per CU: the loop waits on its barriers and on the owners' serial chains, a second
 // workgroup fills the gaps -- 128 VGPRs with 312 B of scratch per lane against 221 VGPRs and one workgroup per CU: 9.7 against
 // 14.5 us per step at tools/bench_batch.py's shape)
-template <bool LDS_DATA>
+// MASKED = false (active == NULL) is the kernel without a word of the mask: the early exit below, small as it is, moves the
+// register allocation of a kernel that spills 266 SGPRs, and the step loop then reloads more of them -- 9.60 against 9.51 us
+// per step at that shape with the test compiled in and a NULL mask.
+template <bool LDS_DATA, bool MASKED>
 __global__ __launch_bounds__(NT, 4) void mh_sweep_batch(const BatchArgs B) {
   extern __shared__ double smem[];
   __shared__ double s_th[FMCMC_MAX_K_WAVE], s_w[NW], s_f[2];
@@ -70,6 +75,11 @@ __global__ __launch_bounds__(NT, 4) void mh_sweep_batch(const BatchArgs B) {
   const int k = A.k, kf = A.kf;
   const long long c = blockIdx.x;            // one chain per workgroup (grid = nchains)
   const long long d = c / B.chains_per_model, n = B.n;
+  // a dataset that is switched off: its chains' state, rows and outputs stay as they are.  One workgroup serves one chain, so
+  // the test is uniform, and it comes before the first LDS access and the first barrier.
+  if constexpr (MASKED) {
+    if (B.active[d] == 0) return;
+  }
   double* s_mu = smem;
   double* s_scale = s_mu + k;
   double* s_lb = s_scale + k;

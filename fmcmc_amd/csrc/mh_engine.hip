@@ -963,10 +963,11 @@ static int check_batch_strides(const fmcmc_model* m, int64_t x_stride, int64_t y
   return FMCMC_OK;
 }
 
-// The call: every pointer of m / kn / run / st / out is a DEVICE pointer (fx, lb, ub: host copies of the kernel's)
+// The call: every pointer of m / kn / run / st / out is a DEVICE pointer (fx, lb, ub: host copies of the kernel's); active: the
+// device mask [D] of the datasets that run, or NULL for all of them
 static int run_batch(const fmcmc_model* m, long long D, long long x_stride, long long y_stride, const fmcmc_kernel* kn, const uint8_t* fx,
-                     const double* lb, const double* ub, const fmcmc_run* run, fmcmc_state* st, fmcmc_out* out, uint32_t flags,
-                     hipStream_t stream) {
+                     const double* lb, const double* ub, const fmcmc_run* run, fmcmc_state* st, fmcmc_out* out, const int32_t* active,
+                     uint32_t flags, hipStream_t stream) {
   const int k = kn->k, kf = count_free(kn, fx);
   const long long C = run->nchains;
   const bool adapt = kn->kind == FMCMC_KERNEL_ADAPT, ram = kn->kind == FMCMC_KERNEL_RAM, logit = m->family == FMCMC_FAM_LOGISTIC;
@@ -987,6 +988,7 @@ static int run_batch(const fmcmc_model* m, long long D, long long x_stride, long
   B.family = m->family; B.p = m->p; B.intercept = m->intercept ? 1 : 0; B.guard = m->guard ? 1 : 0;
   B.n = m->n; B.prior_div = m->prior_div; B.X = m->X; B.y = m->y;
   B.x_stride = x_stride; B.y_stride = y_stride; B.hs_stride = 2 * MAXK + 2; B.chains_per_model = C / D;
+  B.active = active;
   int dev = 0;
   (void)hipGetDevice(&dev);
   rc = require_gfx950(dev);
@@ -1008,7 +1010,7 @@ static int run_batch(const fmcmc_model* m, long long D, long long x_stride, long
                        x_stride, y_stride, B.hs_stride);
   }
   const bool lds_data = !(flags & FMCMC_BATCH_STREAM_DATA) && batch_data_in_lds(m->family, m->n, m->p, kf, kn->kind);
-  const void* kfn = fmh::k_batch(lds_data);
+  const void* kfn = fmh::k_batch(lds_data, active != nullptr);
   if (!kfn) { set_err("no device kernel for the batch sweep"); return FMCMC_ERR_DEVICE; }
   const size_t lds = sizeof(double) * (batch_step_doubles(k, kf, kn->kind) + (lds_data ? batch_data_doubles(m->family, m->n, m->p) : 0));
   if (lds > 48 * 1024 && hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
@@ -1270,6 +1272,12 @@ int fmcmc_validate_batch(const fmcmc_model* m, int64_t nmodels, const fmcmc_kern
 
 int fmcmc_mcmc_run_batch_dev(const fmcmc_model* m, int64_t nmodels, int64_t x_stride, int64_t y_stride, const fmcmc_kernel* kn,
                              const fmcmc_run* run, fmcmc_state* st, fmcmc_out* out, uint32_t flags, void* hip_stream) {
+  return fmcmc_mcmc_run_batch_sel_dev(m, nmodels, x_stride, y_stride, kn, run, st, out, nullptr, flags, hip_stream);
+}
+
+int fmcmc_mcmc_run_batch_sel_dev(const fmcmc_model* m, int64_t nmodels, int64_t x_stride, int64_t y_stride, const fmcmc_kernel* kn,
+                                 const fmcmc_run* run, fmcmc_state* st, fmcmc_out* out, const int32_t* active, uint32_t flags,
+                                 void* hip_stream) {
   if (!m || !kn || !run || !st || !out) { set_err("null argument"); return FMCMC_ERR_ARG; }
   int rc = check_batch_strides(m, x_stride, y_stride);
   if (rc != FMCMC_OK) return rc;
@@ -1279,7 +1287,7 @@ int fmcmc_mcmc_run_batch_dev(const fmcmc_model* m, int64_t nmodels, int64_t x_st
   if (rc != FMCMC_OK) return rc;
   rc = fmcmc_validate_batch(m, nmodels, &v.kh, run);
   if (rc != FMCMC_OK) return rc;
-  return run_batch(m, nmodels, x_stride, y_stride, kn, v.fx, v.lb, v.ub, run, st, out, flags, stream);
+  return run_batch(m, nmodels, x_stride, y_stride, kn, v.fx, v.lb, v.ub, run, st, out, active, flags, stream);
 }
 
 int fmcmc_mcmc_run_batch_host(const fmcmc_model* m, int64_t nmodels, int64_t x_stride, int64_t y_stride, const fmcmc_kernel* kn,
@@ -1303,7 +1311,7 @@ int fmcmc_mcmc_run_batch_host(const fmcmc_model* m, int64_t nmodels, int64_t x_s
   if (has_x) H.up(&dm.X, m->X, sizeof(double) * ((size_t)(nmodels - 1) * (size_t)x_stride + (size_t)m->p * m->n));
   H.up(&dm.y, m->y, sizeof(double) * ((size_t)(nmodels - 1) * (size_t)y_stride + (size_t)m->n));
   stage_call(H, kn, run, st, out);
-  if (H.rc == FMCMC_OK) H.rc = run_batch(&dm, nmodels, x_stride, y_stride, &H.dk, kn->fixed, kn->lb, kn->ub, &H.dr, &H.ds, &H.dout, flags, H.stream);
+  if (H.rc == FMCMC_OK) H.rc = run_batch(&dm, nmodels, x_stride, y_stride, &H.dk, kn->fixed, kn->lb, kn->ub, &H.dr, &H.ds, &H.dout, nullptr, flags, H.stream);
   return fetch_call(H, kn, run, st, out);
 }
 

@@ -54,6 +54,7 @@ FMH_HIDDEN const void* k_fun(int nth);
 // logpost_eval_kernel, the families' log-posterior at caller-given points (one workgroup of 512 threads per chain)
 FMH_HIDDEN const void* k_user(int nth);
 FMH_HIDDEN const void* k_logpost_eval();
-// k_fun.hip: mh_sweep_batch<LDS_DATA> (mh_batch.hpp), one model on many datasets: the dataset in LDS, or streamed every step
-FMH_HIDDEN const void* k_batch(bool lds_data);
+// k_fun.hip: mh_sweep_batch<LDS_DATA, MASKED> (mh_batch.hpp), one model on many datasets: the dataset in LDS, or streamed every
+// step; with or without the dataset mask of fmcmc_mcmc_run_batch_sel_dev
+FMH_HIDDEN const void* k_batch(bool lds_data, bool masked);
 }  // namespace fmh

@@ -339,14 +339,20 @@ def sweep(model, kernel, state, nsteps, burnin=0, thin=1, seed=0, chain_base=0,
 
 def sweep_batch(batch, kernel, state, nsteps, burnin=0, thin=1, seed=0, chain_base=0,
                 want_logpost=True, want_draws=True, want_bits=True, fed_logu=None, fed_z=None,
-                stream=None, check=True, into=None, row0=0, stream_data=False):
-    """sweep() for one model on many datasets (fmcmc_mcmc_run_batch_dev): batch is a DeviceModelBatch of D datasets, state
+                stream=None, check=True, into=None, row0=0, stream_data=False, active=None):
+    """sweep() for one model on many datasets (fmcmc_mcmc_run_batch_sel_dev): batch is a DeviceModelBatch of D datasets, state
     holds D x chains_per_model chains, dataset by dataset -- local chain c samples dataset c // chains_per_model with the
     stream of global chain chain_base + c.  One launch runs every step of every chain; the keywords and the result are
     sweep()'s.  stream_data = True reads the datasets from global memory every step instead of holding each in LDS
-    (FMCMC_BATCH_STREAM_DATA; the same bits)."""
+    (FMCMC_BATCH_STREAM_DATA; the same bits).  active: None, or an int32 device tensor [D] -- the chains of a dataset whose
+    entry is 0 do not run: their state, their rows of `into` and their entries of every output stay as they were (the
+    outputs this call allocates: zeros, NaN samples)."""
     L = abi.lib()
     dev = state.device
+    if active is not None and (not torch.is_tensor(active) or active.dtype != torch.int32 or tuple(active.shape) != (batch.nmodels,)
+                               or not active.is_contiguous() or not _on(active, dev)):
+        raise ValueError("sweep_batch(active=...): a contiguous int32 tensor of shape [%d] on %s is needed; got %s" % (
+            batch.nmodels, dev, _describe(active)))
     out, crun, cout = _call_buffers(state, nsteps, burnin, thin, seed, chain_base, want_logpost, want_draws, want_bits,
                                     fed_logu, fed_z, into, row0)
     Cn, k = state.theta0.shape
@@ -360,10 +366,10 @@ def sweep_batch(batch, kernel, state, nsteps, burnin=0, thin=1, seed=0, chain_ba
         stream = torch.cuda.current_stream(dev)
     cm, ck, cs = batch.c(), kernel.c(), state.c(nsteps)
     with torch.cuda.device(dev):
-        rc = L.fmcmc_mcmc_run_batch_dev(C.byref(cm), batch.nmodels, batch.x_stride, batch.y_stride, C.byref(ck), C.byref(crun),
-                                        C.byref(cs), C.byref(cout), abi.BATCH_STREAM_DATA if stream_data else 0,
-                                        C.c_void_p(stream.cuda_stream))
-    return _finish_call(out, state, rc, "fmcmc_mcmc_run_batch_dev", nsteps, burnin, thin, chain_base, check)
+        rc = L.fmcmc_mcmc_run_batch_sel_dev(C.byref(cm), batch.nmodels, batch.x_stride, batch.y_stride, C.byref(ck), C.byref(crun),
+                                            C.byref(cs), C.byref(cout), active.data_ptr() if active is not None else None,
+                                            abi.BATCH_STREAM_DATA if stream_data else 0, C.c_void_p(stream.cuda_stream))
+    return _finish_call(out, state, rc, "fmcmc_mcmc_run_batch_sel_dev", nsteps, burnin, thin, chain_base, check)
 
 
 def _call_buffers(state, nsteps, burnin, thin, seed, chain_base, want_logpost, want_draws, want_bits, fed_logu, fed_z, into, row0):

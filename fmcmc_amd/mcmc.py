@@ -402,6 +402,21 @@ def _store_output(dc, kernel):
     MCMC_OUTPUT.kernel = kernel
 
 
+def bulk_plan(nsteps, burnin, freq):
+    """The steps of the bulks of an auto-stop call (R/mcmc.R:868-884): nsteps - burnin in bulks of `freq` and a remainder bulk,
+    one bulk of nsteps when two bulks of `freq` do not fit, `burnin` added to the first."""
+    if freq * 2 > nsteps:
+        freq = 0
+    if freq > 0:
+        bulks = [freq] * ((nsteps - burnin) // freq)
+        if (nsteps - burnin) % freq:
+            bulks.append((nsteps - burnin) - sum(bulks))
+    else:
+        bulks = [nsteps]
+    bulks[0] += burnin
+    return bulks
+
+
 def MCMC_with_conv_checker(initial, fun, nsteps, nchains, burnin, thin, kernel, multicore, conv_checker, cl=None,
                            progress=False, chain_id=1, seed=0, device=None, _return_device=False, verbose=True,
                            keep_logpost=True, keep_draws=True, fed=None):
@@ -413,15 +428,7 @@ def MCMC_with_conv_checker(initial, fun, nsteps, nchains, burnin, thin, kernel, 
     if freq is None:
         freq = nsteps // 2
         warnings.warn("The -conv_checker- function has no freq attribute. Default value set to be %d" % freq)
-    if freq * 2 > nsteps:
-        freq = 0
-    if freq > 0:
-        bulks = [freq] * ((nsteps - burnin) // freq)
-        if (nsteps - burnin) % freq:
-            bulks.append((nsteps - burnin) - sum(bulks))
-    else:
-        bulks = [nsteps]
-    bulks[0] += burnin
+    bulks = bulk_plan(nsteps, burnin, freq)
     if kernel is None:
         kernel = kernel_normal()
     if not isinstance(fun, (LogPosterior, BatchedFun)):
@@ -532,10 +539,41 @@ class McmcBatch:
     """The result of MCMC_batch(): D datasets x nchains chains, resident in HBM.  len(ans) == D; ans[d] is the DeviceChains
     of dataset d's chains (slices of the call's buffers, no copies: gelman_diag(ans[d]), summary(ans[d]), ... work per
     dataset); ans.chains holds all D x nchains chains, dataset by dataset, for the per-chain diagnostics in one launch;
-    ans.to_host() is a list of D McmcList."""
+    ans.to_host() is a list of D McmcList; ans.gelman_diag() is gelman_diag(ans[d]) of every dataset from one reduction.
 
-    def __init__(self, chains, nmodels, nchains):
-        self.chains, self.nmodels, self.nchains = chains, int(nmodels), int(nchains)
+    After MCMC_batch(stop_each = ...) the datasets stopped at different bulks and the result is ragged:
+      converged [D] bool      did the dataset pass the test
+      steps [D]               the steps it ran
+      nrows [D]               the rows it kept; its rows beyond them are NaN
+      rhat_history            a list of (steps so far, values [D]): the statistic of every check, NaN where a dataset was
+                              not tested (frozen before, or a check that could not be computed)
+    ans[d], last_rows() and to_host() use each dataset's own rows and iteration labels; ans.chains covers the rows EVERY
+    dataset has (min(nrows)), so the per-chain diagnostics stay finite on it; ans.history holds all rows.  Without
+    stop_each: converged is None, steps and nrows are the call's for every dataset, rhat_history is empty."""
+
+    def __init__(self, chains, nmodels, nchains, nrows=None, steps=None, converged=None, rhat_history=None):
+        self.nmodels, self.nchains = int(nmodels), int(nchains)
+        self.history = chains                # every row of the call
+        self.nrows = np.full(self.nmodels, chains.nrows, dtype=np.int64) if nrows is None else np.asarray(nrows, dtype=np.int64)
+        if self.nrows.shape != (self.nmodels,) or (self.nrows < 0).any() or (self.nrows.size and self.nrows.max() > chains.nrows):
+            raise ValueError("`nrows` must give every dataset's rows, at most the %d of the buffers" % chains.nrows)
+        self.steps = None if steps is None else np.asarray(steps, dtype=np.int64)
+        self.converged = None if converged is None else np.asarray(converged, dtype=bool)
+        self.rhat_history = list(rhat_history or [])
+        common = int(self.nrows.min()) if self.nrows.size else chains.nrows
+        if common == chains.nrows:
+            self.chains = chains
+        else:                                # the rows every dataset has
+            self.chains = DeviceChains(chains._samples, chains._logpost, chains._draws, chains.iters[:common], chains.thin,
+                                       chains.names, chains.chain_base, chains.nchains_total, nrows=common)
+            if hasattr(chains, "accept_count"):
+                self.chains.accept_count = chains.accept_count
+
+    @property
+    def ragged(self):
+        """did the datasets stop after different numbers of steps (or keep different numbers of rows)"""
+        differ = lambda v: v is not None and v.size > 0 and bool((v != v[0]).any())
+        return differ(self.nrows) or differ(self.steps)
 
     def __len__(self):
         return self.nmodels
@@ -544,20 +582,26 @@ class McmcBatch:
         if not -self.nmodels <= d < self.nmodels:
             raise IndexError("dataset index out of range")
         d %= self.nmodels
-        a, ch = d * self.nchains, self.chains
+        a, ch, nr = d * self.nchains, self.history, int(self.nrows[d])
         sl = slice(a, a + self.nchains)
         cut = lambda t: None if t is None else t[sl]
-        dc = DeviceChains(cut(ch._samples), cut(ch._logpost), cut(ch._draws), ch.iters, ch.thin, ch.names, ch.chain_base + a,
-                          self.nchains, nrows=ch.nrows)
-        dc.accept_count = ch.accept_count[sl]
+        dc = DeviceChains(cut(ch._samples), cut(ch._logpost), cut(ch._draws), ch.iters[:nr], ch.thin, ch.names, ch.chain_base + a,
+                          self.nchains, nrows=nr)
+        if hasattr(ch, "accept_count"):
+            dc.accept_count = ch.accept_count[sl]
         return dc
 
     def __iter__(self):
         return (self[d] for d in range(self.nmodels))
 
     def last_rows(self):
-        """[D x nchains][k]: the last kept row of every chain (a device tensor)"""
-        return self.chains._samples[:, :, self.chains.nrows - 1]
+        """[D x nchains][k]: the last kept row of every chain (a device tensor), each dataset's own"""
+        smp = self.history._samples
+        if not self.ragged:
+            return smp[:, :, int(self.nrows[0]) - 1]
+        import torch
+        last = torch.as_tensor(np.repeat(self.nrows - 1, self.nchains)).to(smp.device)
+        return smp[torch.arange(smp.shape[0], device=smp.device), :, last]
 
     def to_host(self):
         out = []
@@ -565,6 +609,12 @@ class McmcBatch:
             h = self[d].to_host()
             out.append(h if isinstance(h, McmcList) else McmcList([h]))
         return out
+
+    def gelman_diag(self, confidence=0.95, autoburnin=True, multivariate=True, cols=None):
+        """gelman_diag(ans[d]) of every dataset (a list of GelmanDiag with the stacked psrf [D][p][2] and mpsrf [D]) from one
+        grouped reduction on the device; on a ragged result every dataset is tested on its own rows."""
+        from .summary import gelman_diag_batch
+        return gelman_diag_batch(self, confidence, autoburnin, multivariate, cols)
 
 
 def batch_initial(initial, nmodels, nchains):
@@ -575,7 +625,12 @@ def batch_initial(initial, nmodels, nchains):
         if initial.nmodels != nmodels or initial.nchains != nchains:
             raise ValueError("The previous result passed by `initial` has %d datasets x %d chains; this call has %d x %d."
                              % (initial.nmodels, initial.nchains, nmodels, nchains))
-        if initial.chains.nrows < 1:
+        if initial.ragged:
+            raise ValueError("The previous result passed by `initial` is ragged: its datasets stopped after different numbers "
+                             "of steps (stop_each), so their chains stand at different places of their variate streams, and "
+                             "a call has one step base (fmcmc_run.step_base) for all of its chains. Continue the datasets "
+                             "that are left with a call of their own.")
+        if initial.nrows.min() < 1:
             raise ValueError("The previous result passed by `initial` has no kept row to continue from.")
         return initial.last_rows(), initial.chains.names
     names = None
@@ -605,16 +660,31 @@ def batch_initial(initial, nmodels, nchains):
 
 
 def MCMC_batch(initial, batch, nsteps, nchains=1, burnin=0, thin=1, kernel=None, seed=None, device=None, keep_logpost=True,
-               keep_draws=True, conv_checker=None):
+               keep_draws=True, conv_checker=None, stop_each=None, verbose=False):
     """MCMC() of one model on every dataset of `batch` (models.model_batch) in ONE launch: nchains chains per dataset, the
     chains of dataset d are the global chains d nchains .. (d + 1) nchains - 1 and every one of them is bit for bit the chain
     MCMC(fun = batch[d]) runs under that id.  initial: see batch_initial; a previous McmcBatch continues every chain from its
     last row with the kernel object's carried state.  Kernels: kernel_normal(_reflective), kernel_unif(_reflective) (every
-    scheme), kernel_adapt(bw = 0, freq = 1), kernel_ram, up to 64 parameters.  Returns an McmcBatch."""
+    scheme), kernel_adapt(bw = 0, freq = 1), kernel_ram, up to 64 parameters.  Returns an McmcBatch.
+
+    stop_each = convergence_gelman(freq, threshold, check_invariant): every dataset stops on its own.  The call runs in the
+    bulks of MCMC(conv_checker = ...) (bulk_plan); after each bulk ONE grouped reduction tests the datasets that still run
+    (summary.enqueue_gelman_groups), the host finishes them, and a dataset whose statistic (mpsrf; psrf at one free parameter)
+    is below the threshold is frozen: the next bulks skip its chains (engine.sweep_batch(active = ...)), whose state and rows
+    stay as they are.  Every dataset's rows, statistics and stop bulk are those of MCMC(fun = batch[d], conv_checker = ...)
+    run with its chains' global ids.  The checker object is only read (freq, threshold, check_invariant)."""
     from .models import ModelBatch
     if conv_checker is not None:
-        raise ValueError("MCMC_batch runs without a -conv_checker-: the datasets would stop at different times. Check "
-                         "gelman_diag(ans[d]) per dataset and continue with initial = ans.")
+        raise ValueError("MCMC_batch runs without a -conv_checker-: the datasets would stop at different times. Pass "
+                         "stop_each = convergence_gelman(...) to stop every dataset on its own, or check gelman_diag(ans) "
+                         "and continue with initial = ans.")
+    if stop_each is not None:
+        from .convergence import convergence_gelman
+        if not isinstance(stop_each, convergence_gelman):
+            raise TypeError("-stop_each- must be a convergence_gelman(freq, threshold, check_invariant): the single-chain "
+                            "checkers have no batched form.")
+        if nchains < 2:
+            raise ValueError("Convergence test with the Gelman is only available when `nchains` > 1L.")
     if not isinstance(batch, ModelBatch):
         raise TypeError("-batch- must be a model_batch(...) of the engine's closed-form families.")
     if kernel is None:
@@ -640,8 +710,70 @@ def MCMC_batch(initial, batch, nsteps, nchains=1, burnin=0, thin=1, kernel=None,
     if kernel._spec is None or kernel._spec.device != gm.device:
         kernel._spec = kernel.spec(gm.device)
     st = kernel.state_for(init, gm.device)
+    if stop_each is not None:
+        return _batch_stop_each(gm, kernel, st, D, nchains, nsteps, burnin, thin, seed, names, keep_logpost, keep_draws,
+                                stop_each, verbose)
     out = engine.sweep_batch(gm, kernel._spec, st, nsteps, burnin=burnin, thin=thin, seed=seed, want_logpost=keep_logpost,
                              want_draws=keep_draws, want_bits=False)
     dc = DeviceChains(out.samples, out.logpost, out.draws, out.iters, thin, names, 0, D * nchains)
     dc.accept_count = out.accept_count
-    return McmcBatch(dc, D, nchains)
+    return McmcBatch(dc, D, nchains, steps=np.full(D, nsteps, dtype=np.int64))
+
+
+def _batch_stop_each(gm, kernel, st, D, nchains, nsteps, burnin, thin, seed, names, keep_logpost, keep_draws, checker, verbose):
+    """The auto-stop loop of MCMC_batch(stop_each = ...): MCMC_with_conv_checker's loop with a verdict per dataset."""
+    import torch
+    from .convergence import _window, convergence_gelman
+    from .summary import enqueue_gelman_groups
+    dev, Cn, k = gm.device, D * nchains, int(st.theta0.shape[1])
+    bulks = bulk_plan(nsteps, burnin, checker.freq)
+    capacity = sum(engine.kept_rows(nb, burnin if bi == 0 else 0, thin) for bi, nb in enumerate(bulks))
+    # the history of all bulks, allocated once and NaN everywhere: the rows a frozen dataset never writes stay NaN
+    nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64, device=dev)
+    hist = DeviceChains(nan(Cn, k, capacity), nan(Cn, capacity) if keep_logpost else None,
+                        nan(Cn, k, capacity) if keep_draws else None, np.zeros(0, dtype=np.int64), thin, names, 0, Cn, nrows=0)
+    hist.accept_count = torch.zeros(Cn, dtype=torch.int64, device=dev)
+    own = convergence_gelman(checker.freq, checker.threshold, checker.check_invariant)   # (the caller's object is only read)
+    free = np.nonzero(~kernel.fixed)[0]
+    p = int(free.size)
+    active = np.ones(D, dtype=bool)
+    nrows, steps, converged = np.zeros(D, dtype=np.int64), np.zeros(D, dtype=np.int64), np.zeros(D, dtype=bool)
+    rhat = []
+    for bi, nb in enumerate(bulks):
+        mask = None if active.all() else torch.as_tensor(active.astype(np.int32)).to(dev)
+        if bi > 0:
+            burnin = 0
+            if hist.nrows > 0:
+                # the last KEPT row of every chain that goes on (MCMC_with_conv_checker); a frozen chain keeps its theta0
+                last = hist._samples[:, :, hist.nrows - 1]
+                if mask is None:
+                    st.theta0.copy_(last)
+                else:
+                    st.theta0.copy_(torch.where(mask.repeat_interleave(nchains)[:, None] != 0, last, st.theta0))
+        _validate_common(nb, nchains, burnin, thin, False)
+        out = engine.sweep_batch(gm, kernel._spec, st, nb, burnin=burnin, thin=thin, seed=seed, want_bits=False,
+                                 into=(hist._samples, hist._logpost, hist._draws), row0=hist.nrows, active=mask)
+        hist.extend(out.iters)
+        hist.accept_count = out.accept_count if mask is None else torch.where(mask.repeat_interleave(nchains) != 0,
+                                                                              out.accept_count, hist.accept_count)
+        nrows[active], steps[active] = hist.nrows, steps[active] + nb
+        total = int(sum(bulks[:bi + 1]))
+        vals = np.full(D, np.nan)
+        row0, N = _window(hist.iters)
+        if N >= 2:
+            partials, _work, _cols = enqueue_gelman_groups(hist, D, nchains, row0, N, free, mask)
+            ph = partials.cpu().numpy()
+            plen = ph.shape[1] - 2
+            for d in np.nonzero(active)[0]:
+                own.last = None
+                if own._finish(ph[d], p, N, int(hist.iters[-1]), plen, nchains):
+                    converged[d] = True
+                if own.last is not None:
+                    vals[d] = own.last
+        rhat.append((total, vals))
+        active &= ~converged
+        if verbose:
+            print("%d steps: %d of %d datasets have converged." % (total, int(converged.sum()), D))
+        if not active.any():
+            break
+    return McmcBatch(hist, D, nchains, nrows=nrows, steps=steps, converged=converged, rhat_history=rhat)

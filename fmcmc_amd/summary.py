@@ -772,14 +772,95 @@ def enqueue_gelman(dc, row0, N, cols):
     return partial, work, o.cols
 
 
+def enqueue_gelman_groups(dc, ngroups, chains_per_group, row0, N, cols, active=None):
+    """The one call site of fmcmc_gelman_groups_dev (current torch stream): the window [row0, row0 + N) of the rows of `dc`,
+    whose chains are ngroups groups of chains_per_group consecutive chains (McmcBatch: a group = a dataset), reduced group by
+    group, each centred on the window's first row of its first chain.  active: None or an int32 device tensor [ngroups]; the
+    rows of the groups whose entry is 0 keep their NaN prefill.  Returns the device tensors (partials
+    [ngroups][fmcmc_gelman_partial_len(p) + 2], work) and the columns; nothing is synchronised."""
+    import torch
+    o = _open(dc, cols, "compare")
+    ngroups, cpg = int(ngroups), int(chains_per_group)
+    if ngroups < 1 or cpg < 1 or ngroups * cpg != o.Cn:
+        raise ValueError("%d groups of %d chains are not the %d chains of the result" % (ngroups, cpg, o.Cn))
+    if row0 < 0 or N < 2 or row0 + N > dc.nrows:
+        raise ValueError("the window [%d, %d) needs at least two of the %d kept rows" % (row0, row0 + N, dc.nrows))
+    if o.p > abi.MAX_K_WAVE:
+        raise NotImplementedError("the grouped Gelman-Rubin reduction takes at most %d columns per call" % abi.MAX_K_WAVE)
+    if active is not None and (not torch.is_tensor(active) or active.dtype != torch.int32 or tuple(active.shape) != (ngroups,)
+                               or not active.is_contiguous() or active.device != o.dev):
+        raise ValueError("`active` must be a contiguous int32 tensor of shape [%d] on %s" % (ngroups, o.dev))
+    plen = int(o.L.fmcmc_gelman_partial_len(o.p))
+    partials = torch.full((ngroups, plen + 2), float("nan"), dtype=torch.float64, device=o.dev)
+    work = _doubles(o, o.L.fmcmc_gelman_groups_work_len(ngroups, cpg, o.p))
+    with torch.cuda.device(o.dev):
+        rc = o.L.fmcmc_gelman_groups_dev(o.smp.data_ptr(), ngroups, cpg, o.k, o.cap, int(row0), int(N), o.cols_d.data_ptr(), o.p,
+                                         active.data_ptr() if active is not None else None, work.data_ptr(),
+                                         partials.data_ptr(), _stream(o.dev))
+    if rc != abi.OK:
+        raise (NotImplementedError if rc == abi.ERR_UNSUPPORTED else ValueError if rc == abi.ERR_ARG else RuntimeError)(
+            abi.last_error())
+    return partials, work, o.cols
+
+
+class GelmanDiagBatch(list):
+    """gelman_diag() of an McmcBatch: a list of D GelmanDiag, one per dataset (what gelman_diag(ans[d]) returns), with the
+    stacked arrays psrf [D][p][2] ("Point est.", "Upper C.I.") and mpsrf [D] (NaN where a GelmanDiag has None)."""
+
+    def __init__(self, diags):
+        super().__init__(diags)
+        self.psrf = np.stack([g.psrf for g in self]) if len(self) else np.zeros((0, 0, 2))
+        self.mpsrf = np.array([np.nan if g.mpsrf is None else g.mpsrf for g in self], dtype=np.float64)
+
+    def __repr__(self):
+        return "<GelmanDiagBatch ndatasets=%d nvar=%d>" % (len(self), self.psrf.shape[1])
+
+
+def gelman_diag_batch(ans, confidence=0.95, autoburnin=True, multivariate=True, cols=None):
+    """gelman_diag(ans[d]) for every dataset d of an McmcBatch from ONE grouped reduction (fmcmc_gelman_groups_dev) and one copy
+    back: the same partial vectors bit for bit, the same host finish.  After MCMC_batch(stop_each = ...) the datasets hold
+    different numbers of rows; each is tested on its own rows (its own autoburnin window), with one reduction per distinct
+    row count -- at most one per bulk of that call."""
+    import torch
+    from .convergence import _window
+    _single_process()
+    if ans.nchains < 2:
+        raise ValueError(_GELMAN_FEW_CHAINS)
+    full = ans.history
+    D = ans.nmodels
+    counts = ans.nrows
+    diags = [None] * D
+    for nr in sorted(set(int(v) for v in counts)):
+        sel = np.nonzero(counts == nr)[0]
+        iters = full.iters[:nr]
+        row0, N = _window(iters) if autoburnin else (0, nr)
+        if N < 2:
+            raise ValueError("the window [%d, %d) needs at least two of the %d kept rows" % (row0, row0 + N, nr))
+        active = None
+        if sel.size != D:
+            mask = np.zeros(D, dtype=np.int32)
+            mask[sel] = 1
+            active = torch.as_tensor(mask).to(full._samples.device)
+        partials, _work, cs = enqueue_gelman_groups(full, D, ans.nchains, row0, N, cols, active)
+        ph = partials.cpu().numpy()
+        p = int(cs.size)
+        for d in sel:
+            diags[d] = gelman_diag_finish(ph[d, :-2], p, N, confidence, multivariate, _names(full, cs), int(iters[row0]),
+                                          int(iters[-1]))
+    return GelmanDiagBatch(diags)
+
+
 def gelman_diag(x, confidence=0.95, autoburnin=True, multivariate=True, cols=None):
-    """coda::gelman.diag of a result: x a DeviceChains (read in place), an Mcmc or a McmcList (uploaded first).  With
+    """coda::gelman.diag of a result: x a DeviceChains (read in place), an Mcmc or a McmcList (uploaded first); an McmcBatch
+    gives a GelmanDiagBatch, one GelmanDiag per dataset from one grouped reduction (gelman_diag_batch).  With
     `autoburnin` the factors are those of the second half of the rows (coda's window, the one convergence_gelman tests).
     The device reduces every chain's window to its mean and covariance and sums them (fmcmc_gelman_partial_dev, any
     p <= 256); gelman_diag_finish does the rest on that vector.  coda's `transform = TRUE` (log / logit of bounded
     variables before the test) is not offered: transform the columns before the call."""
     from .convergence import _window
-    from .mcmc import Mcmc, McmcList
+    from .mcmc import Mcmc, McmcBatch, McmcList
+    if isinstance(x, McmcBatch):
+        return gelman_diag_batch(x, confidence, autoburnin, multivariate, cols)
     _single_process()
     if isinstance(x, Mcmc) or (isinstance(x, McmcList) and len(x) < 2):       # (before anything is uploaded)
         raise ValueError(_GELMAN_FEW_CHAINS)

@@ -337,6 +337,16 @@ int fmcmc_mcmc_run_batch_dev(const fmcmc_model* model /* shape; X, y: dataset 0 
                              int64_t x_stride, int64_t y_stride /* doubles between datasets */,
                              const fmcmc_kernel* kernel, const fmcmc_run* run, fmcmc_state* state, fmcmc_out* out,
                              uint32_t flags, void* hip_stream);
+/* fmcmc_mcmc_run_batch_dev with a dataset mask: active[nmodels] (device int32, NULL = every dataset).  The chains of a dataset
+ * whose entry is 0 do not run: their theta0, f0, Sigma, abs_iter, mean_prev, have_mean, nerrors, their output rows, status,
+ * status_step, status_theta, accept count and bitmap are left exactly as they were; every other chain's outputs are bit for
+ * bit those of fmcmc_mcmc_run_batch_dev (which is this entry with NULL).  fmcmc_run.step_base is one number: chains that sat
+ * out a call are behind the others in their variate streams, so a later call runs them with the others only when the caller
+ * accepts that (MCMC_batch(stop_each = ...) never runs them again).  No host-pointer variant: a stop loop over host pointers
+ * would stage the data again for every call. */
+int fmcmc_mcmc_run_batch_sel_dev(const fmcmc_model* model, int64_t nmodels, int64_t x_stride, int64_t y_stride,
+                                 const fmcmc_kernel* kernel, const fmcmc_run* run, fmcmc_state* state, fmcmc_out* out,
+                                 const int32_t* active, uint32_t flags, void* hip_stream);
 int fmcmc_mcmc_run_batch_host(const fmcmc_model* model, int64_t nmodels, int64_t x_stride, int64_t y_stride,
                               const fmcmc_kernel* kernel, const fmcmc_run* run, fmcmc_state* state, fmcmc_out* out,
                               uint32_t flags, int device);   /* every pointer a host pointer */
@@ -356,6 +366,19 @@ int fmcmc_gelman_partial_dev(const double* samples, int64_t nchains, int32_t k, 
                              int64_t row0, int64_t N, const int32_t* cols, int32_t p,
                              const double* center, double* work, double* partial,
                              void* hip_stream);
+/* The same reduction for ngroups groups of chains_per_group consecutive chains (group g = chains g chains_per_group ..; one
+ * model on many datasets: a group = the chains of a dataset) in two launches on the caller's stream.  partials is
+ * [ngroups][fmcmc_gelman_partial_len(p) + 2] (device): the head of row g is bit for bit the partial that
+ * fmcmc_gelman_partial_dev gives for the chains of group g alone with center = the window's first row (row0) of the group's
+ * first chain at the columns cols; the two doubles behind it are the sum and the sum of squares of every entry of the group's
+ * window, formed from the chains' means and variances in a fixed order (rm_invariant's test, R/convergence.R:171-173).
+ * active[ngroups] (device int32, NULL = all): the row of a group whose entry is 0 is not written.  work:
+ * fmcmc_gelman_groups_work_len doubles, left as work[c] = {xbar[p] (NOT centred), S_c[p][p]} per chain.
+ * 1 <= p <= FMCMC_MAX_K_WAVE (FMCMC_ERR_UNSUPPORTED beyond); the finish is fmcmc_gelman_finish per row, on the host. */
+int64_t fmcmc_gelman_groups_work_len(int64_t ngroups, int64_t chains_per_group, int32_t p);
+int fmcmc_gelman_groups_dev(const double* samples, int64_t ngroups, int64_t chains_per_group, int32_t k, int64_t S,
+                            int64_t row0, int64_t N, const int32_t* cols, int32_t p, const int32_t* active,
+                            double* work, double* partials, void* hip_stream);
 /* Host finish on the (all-reduced) partial: psrf[p] point estimates, *mpsrf (NaN if p == 1).
  * Returns FMCMC_ERR_CHAIN when W is not positive definite (gelman.diag would fail); psrf[p] is complete then too. */
 int fmcmc_gelman_finish(const double* partial, int32_t p, int64_t N, double* psrf,
