@@ -33,7 +33,8 @@ EXPORTS = ["fmcmc_abi_version", "fmcmc_last_error", "fmcmc_last_kernel", "fmcmc_
            "fmcmc_raftery_dev", "fmcmc_hpd_work_len", "fmcmc_hpd_dev", "fmcmc_autocov_out_len", "fmcmc_autocov_dev",
            "fmcmc_logpost_dev", "fmcmc_validate_user", "fmcmc_mcmc_run_user_dev",
            "fmcmc_validate_batch", "fmcmc_mcmc_run_batch_dev", "fmcmc_mcmc_run_batch_host",
-           "fmcmc_mcmc_run_batch_sel_dev", "fmcmc_gelman_groups_work_len", "fmcmc_gelman_groups_dev"]
+           "fmcmc_mcmc_run_batch_sel_dev", "fmcmc_gelman_groups_work_len", "fmcmc_gelman_groups_dev",
+           "fmcmc_summary_groups_work_len", "fmcmc_summary_groups_dev"]
 BATCH_STREAM_DATA = 1          # fmcmc_mcmc_run_batch_*: flags bit, read the datasets from global memory every step
 SUMMARY_MAX_PROBS = 16
 CHAIN_ORDER_MAX_RANKS = 2 * SUMMARY_MAX_PROBS
@@ -173,6 +174,12 @@ def lib():
         L.fmcmc_summary_dev.restype = C.c_int
         L.fmcmc_summary_dev.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                         C.c_int32, _dp, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fmcmc_summary_groups_work_len.restype = C.c_int64
+        L.fmcmc_summary_groups_work_len.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int32]
+        L.fmcmc_summary_groups_dev.restype = C.c_int
+        L.fmcmc_summary_groups_dev.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                               C.c_void_p, C.c_int32, C.c_void_p, _dp, C.c_int32, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]
         for nm in ("fmcmc_heidel_work_len", "fmcmc_heidel_out_len"):
             getattr(L, nm).restype = C.c_int64
             getattr(L, nm).argtypes = [C.c_int64, C.c_int32, C.c_int64]

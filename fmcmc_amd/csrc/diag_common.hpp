@@ -1,6 +1,8 @@
 // diag_common.hpp — what the device diagnostics share (summary.hip, raftery.hip, gelman.hip): the error text, the pair load, the
-// order-preserving keys of the radix selects, the window checks of the windowed entries and the walk over one series.  Kernels,
-// reductions and the two selects themselves stay in their units.  Everything here is local to the unit that includes it.
+// order-preserving keys of the radix selects, the window checks of the windowed entries, the walk over one series and the
+// one-workgroup radix select over the segments of a column (raftery.hip: one series; summary.hip: the chains of a group).  Kernels,
+// reductions and the multi-workgroup select of fmcmc_summary_dev stay in their units.  Everything here is local to the unit that
+// includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -115,6 +117,125 @@ inline int allow_lds(const char* who, Kernel kernel, size_t lds) {   // dynamic 
       hipSuccess)
     return fail(FMCMC_ERR_DEVICE, "%s: %zu bytes of LDS refused", who, lds);
   return FMCMC_OK;
+}
+
+// --------------------------------------------------------------------------------------- the one-workgroup radix select
+// Exact order statistics of the values of `nseg` segments of N rows each (segment c starts at x + c seg_stride; one series is
+// one segment) by a workgroup of SEL_T threads: most-significant-digit radix select on the keys, 8 passes of 8 bits, the
+// histograms in LDS.  Targets with the same prefix share one histogram (that of their "leader"), SEL_HG leaders are counted per
+// walk over the values; while all nseg N keys fit in LDS (<= LDS_ROWS) they are staged there once, segment c at s_k + c N, else
+// every walk re-reads the segments through walk_pairs.  Every count is an integer: neither the arrival order of the LDS
+// atomics nor the launch changes a result.
+constexpr int SEL_T = 512;          // threads of the workgroup
+constexpr int SEL_RANKS = 32;       // targets per call: 2 x SUMMARY_MAX_PROBS
+constexpr int SEL_HG = 4;           // histograms (leaders) per walk over the values
+constexpr int SEL_LU = 4;           // pairs in flight per thread
+
+struct OrderRanks { unsigned int r[SEL_RANKS]; };   // 0-based, each < nseg N < 2^32
+
+struct SelectLds {
+  unsigned int hist[SEL_HG][256];                   // counts of a walk, then their exclusive prefix sums
+  unsigned long long prefix[SEL_RANKS];             // per target: the key bits fixed so far
+  unsigned int rank[SEL_RANKS];                     // per target: its rank among the values that share its prefix
+  int slot[SEL_RANKS];                              // per target: the position of its leader in `list`
+  int list[SEL_RANKS];                              // the leaders of this pass
+  int nlead;
+  unsigned int nf;                                  // non-finite values of all segments
+};
+
+// Reads every segment once: counts the non-finite values of all of them into L.nf and, when `staged`, leaves key_of(row i of
+// segment c) in s_k[c N + i].
+__device__ __forceinline__ void stage_series(const double* __restrict__ x, long long N, long long nseg, long long seg_stride,
+                                             bool staged, unsigned long long* s_k, SelectLds& L) {
+  if (threadIdx.x == 0) L.nf = 0u;
+  __syncthreads();
+  unsigned int nf = 0u;
+  for (long long c = 0; c < nseg; c++) {
+    unsigned long long* kc = s_k + c * N;
+    walk_pairs<SEL_T, SEL_LU>(x + c * seg_stride, N, [&](long long i, double a, double b, bool has_b) {
+      nf += fmh_isfinite(a) ? 0u : 1u;
+      if (staged) kc[i] = key_of(a);
+      if (has_b) {
+        nf += fmh_isfinite(b) ? 0u : 1u;
+        if (staged) kc[i + 1] = key_of(b);
+      }
+    });
+  }
+  if (nf) atomicAdd(&L.nf, nf);
+  __syncthreads();
+}
+
+// Radix select of the nt targets whose ranks (among the nseg N values) are in L.rank (L.prefix zeroed): on return L.prefix[t] is
+// the key of the order statistic of target t.  Every thread of the workgroup calls it; it starts and ends with a barrier.
+__device__ __forceinline__ void select_series(const double* __restrict__ x, long long N, long long nseg, long long seg_stride,
+                                              bool staged, const unsigned long long* s_k, int nt, SelectLds& L) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int pass = 0; pass < 8; pass++) {
+    __syncthreads();
+    if (tid == 0) {                                  // leaders: the first target of every distinct prefix
+      int n = 0;
+      for (int t = 0; t < nt; t++) {
+        int l = t;
+        for (int u = 0; u < t; u++)
+          if (L.prefix[u] == L.prefix[t]) { l = u; break; }
+        if (l == t) { L.slot[t] = n; L.list[n] = t; n++; }
+        else L.slot[t] = L.slot[l];
+      }
+      L.nlead = n;
+    }
+    __syncthreads();
+    const int nlead = L.nlead;
+    for (int g0 = 0; g0 < nlead; g0 += SEL_HG) {
+      const int ng = nlead - g0 < SEL_HG ? nlead - g0 : SEL_HG;
+      unsigned long long pg[SEL_HG];
+#pragma unroll
+      for (int g = 0; g < SEL_HG; g++) pg[g] = L.prefix[L.list[g0 + (g < ng ? g : 0)]];
+      for (int e = tid; e < SEL_HG * 256; e += SEL_T) (&L.hist[0][0])[e] = 0u;
+      __syncthreads();
+      auto count = [&](unsigned long long kx) {
+        const unsigned long long high = radix_high(kx, pass);
+        const unsigned int digit = radix_digit(kx, pass);
+#pragma unroll
+        for (int g = 0; g < SEL_HG; g++)
+          if (g < ng && high == pg[g]) atomicAdd(&L.hist[g][digit], 1u);
+      };
+      if (staged) {
+        for (int i = tid; i < (int)(nseg * N); i += SEL_T) count(s_k[i]);
+      } else {
+        for (long long c = 0; c < nseg; c++)
+          walk_pairs<SEL_T, SEL_LU>(x + c * seg_stride, N,
+                                    [&](long long, double a, double b, bool has_b) { count(key_of(a)); if (has_b) count(key_of(b)); });
+      }
+      __syncthreads();
+      if (wave < ng) {                               // one wavefront per histogram: exclusive prefix sums, four bins a lane
+        unsigned int* h = &L.hist[wave][4 * lane];
+        const unsigned int c0 = h[0], c1 = h[1], c2 = h[2], c3 = h[3];
+        const unsigned int mine = c0 + c1 + c2 + c3;
+        unsigned int incl = mine;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const unsigned int up = __shfl_up(incl, o, 64);
+          if (lane >= o) incl += up;
+        }
+        const unsigned int excl = incl - mine;
+        h[0] = excl; h[1] = excl + c0; h[2] = excl + c0 + c1; h[3] = excl + c0 + c1 + c2;
+      }
+      __syncthreads();
+      if (tid < nt && L.slot[tid] >= g0 && L.slot[tid] < g0 + ng) {
+        // the bin that holds the rank: the largest b whose exclusive sum is <= rank (the rank is below the total, so that
+        // bin is not empty).  Only targets of this group change, and no later group of the pass reads their prefixes.
+        const unsigned int* cum = L.hist[L.slot[tid] - g0];
+        const unsigned int r = L.rank[tid];
+        int b = 0;
+#pragma unroll
+        for (int step = 128; step >= 1; step >>= 1)
+          if (cum[b + step] <= r) b += step;
+        L.prefix[tid] = (L.prefix[tid] << 8) | (unsigned long long)b;
+        L.rank[tid] = r - cum[b];
+      }
+      __syncthreads();
+    }
+  }
 }
 
 }  // namespace

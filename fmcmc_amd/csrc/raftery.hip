@@ -4,9 +4,9 @@
 // One chain's column is N contiguous doubles (samples + (c k + col) S + row0), as in summary.hip.  One workgroup per series:
 //   1. stage        the series is read once with 8-byte-aligned pair loads, its non-finite values are counted, and while it fits
 //                   (N <= LDS_ROWS, the tile of summary_series_kernel) its order-preserving keys are kept in LDS;
-//   2. select       exact order statistics at up to 32 ranks by a most-significant-digit radix select on the keys: 8 passes of
-//                   8 bits, the histograms in LDS.  Targets with the same prefix share one histogram (that of their "leader"),
-//                   HG leaders are counted per walk over the series; a series too long for LDS is re-read every walk;
+//   2. select       exact order statistics at up to 32 ranks by the one-workgroup radix select of diag_common.hpp
+//                   (stage_series / select_series, here over one segment: the series); a series too long for LDS is re-read
+//                   every walk;
 //   3. raftery      u = type-7 quantile from the two order statistics (two rounded products, one rounded sum), the indicator
 //                   Z_t = (x_t <= u) bit-packed into `work` by wave ballots, then per thinning j (one wavefront each) the
 //                   2x2x2 table of the consecutive triples of Z at rows 0, j, 2j, ... and its last pair.
@@ -19,117 +19,15 @@
 
 namespace {
 
-constexpr int OT = 512;             // threads of a series workgroup
+constexpr int OT = SEL_T;           // threads of a series workgroup: that of the select (diag_common.hpp)
 constexpr int OW = OT / 64;
-constexpr int MAXRANKS = 32;        // targets per call: 2 x SUMMARY_MAX_PROBS
-constexpr int HG = 4;               // histograms (leaders) per walk over the series
+constexpr int MAXRANKS = SEL_RANKS; // targets per call
 constexpr int MAXNJ = 32;           // thinnings per launch
-constexpr int LU = 4;               // pairs in flight per thread
+constexpr int LU = SEL_LU;          // pairs in flight per thread
 constexpr int HEAD = 4;             // doubles per series at the head of the raftery output: u, x_(lo), x_(hi), non-finite count
 constexpr int CNT = 10;             // integers per (series, thinning): T[a][b][c] at 4 a + 2 b + c, then Z_{m-2}, Z_{m-1}
 constexpr int HPD_MAX_TAIL = 8192;  // rows of each tail of chain_hpd_kernel held in LDS (two tails of 64 KB)
 constexpr int HPD_OUT = 4;          // doubles per series of the hpd output: lower, upper, i*, non-finite count
-
-struct OrderRanks { unsigned int r[MAXRANKS]; };    // 0-based, each < N < 2^32
-
-struct SelectLds {
-  unsigned int hist[HG][256];                       // counts of a walk, then their exclusive prefix sums
-  unsigned long long prefix[MAXRANKS];              // per target: the key bits fixed so far
-  unsigned int rank[MAXRANKS];                      // per target: its rank among the values that share its prefix
-  int slot[MAXRANKS];                               // per target: the position of its leader in `list`
-  int list[MAXRANKS];                               // the leaders of this pass
-  int nlead;
-  unsigned int nf;                                  // non-finite values of the series
-};
-
-// Reads the series once: counts its non-finite values into L.nf and, when `staged`, leaves key_of(x[i]) in s_k[i].
-__device__ __forceinline__ void stage_series(const double* __restrict__ x, long long N, bool staged, unsigned long long* s_k,
-                                             SelectLds& L) {
-  if (threadIdx.x == 0) L.nf = 0u;
-  __syncthreads();
-  unsigned int nf = 0u;
-  walk_pairs<OT, LU>(x, N, [&](long long i, double a, double b, bool has_b) {
-    nf += fmh_isfinite(a) ? 0u : 1u;
-    if (staged) s_k[i] = key_of(a);
-    if (has_b) {
-      nf += fmh_isfinite(b) ? 0u : 1u;
-      if (staged) s_k[i + 1] = key_of(b);
-    }
-  });
-  if (nf) atomicAdd(&L.nf, nf);
-  __syncthreads();
-}
-
-// Radix select of the nt targets whose ranks are in L.rank (L.prefix zeroed): on return L.prefix[t] is the key of the order
-// statistic of target t.  Every thread of the workgroup calls it; it starts and ends with a barrier.
-__device__ __forceinline__ void select_series(const double* __restrict__ x, long long N, bool staged,
-                                              const unsigned long long* s_k, int nt, SelectLds& L) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int pass = 0; pass < 8; pass++) {
-    __syncthreads();
-    if (tid == 0) {                                  // leaders: the first target of every distinct prefix
-      int n = 0;
-      for (int t = 0; t < nt; t++) {
-        int l = t;
-        for (int u = 0; u < t; u++)
-          if (L.prefix[u] == L.prefix[t]) { l = u; break; }
-        if (l == t) { L.slot[t] = n; L.list[n] = t; n++; }
-        else L.slot[t] = L.slot[l];
-      }
-      L.nlead = n;
-    }
-    __syncthreads();
-    const int nlead = L.nlead;
-    for (int g0 = 0; g0 < nlead; g0 += HG) {
-      const int ng = nlead - g0 < HG ? nlead - g0 : HG;
-      unsigned long long pg[HG];
-#pragma unroll
-      for (int g = 0; g < HG; g++) pg[g] = L.prefix[L.list[g0 + (g < ng ? g : 0)]];
-      for (int e = tid; e < HG * 256; e += OT) (&L.hist[0][0])[e] = 0u;
-      __syncthreads();
-      auto count = [&](unsigned long long kx) {
-        const unsigned long long high = radix_high(kx, pass);
-        const unsigned int digit = radix_digit(kx, pass);
-#pragma unroll
-        for (int g = 0; g < HG; g++)
-          if (g < ng && high == pg[g]) atomicAdd(&L.hist[g][digit], 1u);
-      };
-      if (staged) {
-        for (int i = tid; i < (int)N; i += OT) count(s_k[i]);
-      } else {
-        walk_pairs<OT, LU>(x, N, [&](long long, double a, double b, bool has_b) { count(key_of(a)); if (has_b) count(key_of(b)); });
-      }
-      __syncthreads();
-      if (wave < ng) {                               // one wavefront per histogram: exclusive prefix sums, four bins a lane
-        unsigned int* h = &L.hist[wave][4 * lane];
-        const unsigned int c0 = h[0], c1 = h[1], c2 = h[2], c3 = h[3];
-        const unsigned int mine = c0 + c1 + c2 + c3;
-        unsigned int incl = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const unsigned int up = __shfl_up(incl, o, 64);
-          if (lane >= o) incl += up;
-        }
-        const unsigned int excl = incl - mine;
-        h[0] = excl; h[1] = excl + c0; h[2] = excl + c0 + c1; h[3] = excl + c0 + c1 + c2;
-      }
-      __syncthreads();
-      if (tid < nt && L.slot[tid] >= g0 && L.slot[tid] < g0 + ng) {
-        // the bin that holds the rank: the largest b whose exclusive sum is <= rank (the rank is below the total, so that
-        // bin is not empty).  Only targets of this group change, and no later group of the pass reads their prefixes.
-        const unsigned int* cum = L.hist[L.slot[tid] - g0];
-        const unsigned int r = L.rank[tid];
-        int b = 0;
-#pragma unroll
-        for (int step = 128; step >= 1; step >>= 1)
-          if (cum[b + step] <= r) b += step;
-        L.prefix[tid] = (L.prefix[tid] << 8) | (unsigned long long)b;
-        L.rank[tid] = r - cum[b];
-      }
-      __syncthreads();
-    }
-  }
-}
 
 __global__ __launch_bounds__(OT) void chain_order_kernel(const double* __restrict__ samples, long long S, int k, long long row0,
                                                          long long N, const int* __restrict__ cols, int p, int nt,
@@ -141,9 +39,9 @@ __global__ __launch_bounds__(OT) void chain_order_kernel(const double* __restric
   const long long series = blockIdx.x, c = series / p;
   const int j = (int)(series % p);
   const double* __restrict__ x = samples + (c * (long long)k + cols[j]) * S + row0;
-  stage_series(x, N, staged != 0, s_k, L);
+  stage_series(x, N, 1, 0, staged != 0, s_k, L);
   if (tid < nt) { L.prefix[tid] = 0ull; L.rank[tid] = ranks.r[tid]; }
-  select_series(x, N, staged != 0, s_k, nt, L);
+  select_series(x, N, 1, 0, staged != 0, s_k, nt, L);
   if (tid < nt) out[series * nt + tid] = value_of(L.prefix[tid]);
   if (tid == 0) nf_out[series] = (double)L.nf;
 }
@@ -163,9 +61,9 @@ __global__ __launch_bounds__(OT) void raftery_kernel(const double* __restrict__ 
   const long long series = blockIdx.x, c = series / p;
   const int col = (int)(series % p);
   const double* __restrict__ x = samples + (c * (long long)k + cols[col]) * S + row0;
-  stage_series(x, N, staged != 0, s_k, L);
+  stage_series(x, N, 1, 0, staged != 0, s_k, L);
   if (tid < 2) { L.prefix[tid] = 0ull; L.rank[tid] = tid ? rank_hi : rank_lo; }
-  select_series(x, N, staged != 0, s_k, 2, L);
+  select_series(x, N, 1, 0, staged != 0, s_k, 2, L);
   // the threshold: summary.type7_quantiles, operation for operation (two rounded products, one rounded sum)
   const double xlo = value_of(L.prefix[0]), xhi = value_of(L.prefix[1]);
   const double u = (interpolate && xhi != xlo) ? __dadd_rn(__dmul_rn(1.0 - h, xlo), __dmul_rn(h, xhi)) : xlo;
@@ -239,9 +137,9 @@ __global__ __launch_bounds__(OT) void chain_hpd_kernel(const double* __restrict_
   const unsigned int T = (unsigned int)N - gap;      // 1 <= T <= P <= HPD_MAX_TAIL
   unsigned long long* lo = s_k;
   unsigned long long* hi = s_k + P;
-  stage_series(x, N, false, s_k, L);
+  stage_series(x, N, 1, 0, false, s_k, L);
   if (tid < 2) { L.prefix[tid] = 0ull; L.rank[tid] = tid ? gap : T - 1u; s_n[tid] = 0u; }
-  select_series(x, N, false, s_k, 2, L);
+  select_series(x, N, 1, 0, false, s_k, 2, L);
   const unsigned long long klo = L.prefix[0], khi = L.prefix[1];
   walk_pairs<OT, LU>(x, N, [&](long long, double a, double b, bool has_b) {
     auto put = [&](unsigned long long kx) {

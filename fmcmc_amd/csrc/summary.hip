@@ -12,6 +12,11 @@
 //                              per (series, candidate) scans the centred tail and sums the squares of its Brownian bridge.
 //   6. summary_lag_kernel      coda::autocorr: autocovariances at up to 32 freely chosen row lags (stage 1 stops at lag M), one
 //                              workgroup per series: the mean as in stage 1, then one walk per eight lags that reads x_{t+h} from global memory.
+//   7. groups                  fmcmc_summary_groups_dev: the summary of every group of consecutive chains on its own (one model on
+//                              many datasets).  Stages 1-2 once over all chains (summary_*_masked_kernel under a group mask: the
+//                              same device bodies), summary_group_pool_kernel = stage 3's body per (group, column), and
+//                              summary_group_select_kernel: the pooled order statistics of a (group, column) by ONE workgroup
+//                              (the one-workgroup radix select of diag_common.hpp over the group's chains).
 // Every sum has a fixed shape, so the results do not depend on the launch.  Nothing here writes `samples`.
 #include "diag_common.hpp"
 
@@ -53,9 +58,9 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
 // taken from there.  A longer series takes the mean from global memory and then walks tiles of tile_rows rows with an M-row
 // halo.  Thread t owns the rows t, t + ST, ... of a tile (conflict-free 8-byte LDS reads for every lag) and keeps one
 // accumulator per lag; the accumulators are joined over the lanes in a fixed pattern and then in wave order.
-__global__ __launch_bounds__(ST) void summary_series_kernel(const double* __restrict__ samples, long long S, int k, long long row0,
-                                                            long long N, const int* __restrict__ cols, int p, int M,
-                                                            int tile_rows, double* __restrict__ acov) {
+__device__ __forceinline__ void series_body(const double* __restrict__ samples, long long S, int k, long long row0, long long N,
+                                            const int* __restrict__ cols, int p, int M, int tile_rows,
+                                            double* __restrict__ acov) {
   extern __shared__ double smem[];
   double* s_x = smem;                          // [tile_rows + PAD]
   double* s_red = smem + tile_rows + PAD;      // [SW * RED]
@@ -178,16 +183,34 @@ __global__ __launch_bounds__(ST) void summary_series_kernel(const double* __rest
   }
 }
 
+__global__ __launch_bounds__(ST) void summary_series_kernel(const double* __restrict__ samples, long long S, int k, long long row0,
+                                                            long long N, const int* __restrict__ cols, int p, int M,
+                                                            int tile_rows, double* __restrict__ acov) {
+  series_body(samples, S, k, row0, N, cols, p, M, tile_rows, acov);
+}
+
+// The same series under the mask of fmcmc_summary_groups_dev: the chains are groups of `cpg` consecutive chains, and the series
+// of a group whose `active` entry is 0 return before they touch anything (the test is uniform per workgroup).
+__global__ __launch_bounds__(ST) void summary_series_masked_kernel(const double* __restrict__ samples, long long S, int k,
+                                                                   long long row0, long long N, const int* __restrict__ cols, int p,
+                                                                   int M, int tile_rows, long long cpg,
+                                                                   const int* __restrict__ active, double* __restrict__ acov) {
+  if (active[((long long)blockIdx.x / p) / cpg] == 0) return;
+  series_body(samples, S, k, row0, N, cols, p, M, tile_rows, acov);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- stage 2
 // stats::ar.yw (Levinson-Durbin, AIC, first minimum) and coda::spectrum0.ar for one series per wavefront.  Lane j holds the
 // coefficient of lag j + 1 and r_{j+1}; step m needs coefficient m - i next to coefficient i and r_{m-i} next to it: both are
 // the same lane reversal over the first m - 1 lanes.
-__global__ __launch_bounds__(256) void summary_ar_kernel(const double* __restrict__ acov, long long nseries, long long N, int M,
-                                                         double* __restrict__ stats) {
+template <bool MASKED>
+__device__ __forceinline__ void ar_body(const double* __restrict__ acov, long long nseries, long long N, int M, int p, long long cpg,
+                                        const int* __restrict__ active, double* __restrict__ stats) {
   const int lane = threadIdx.x & 63;
   long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const bool live = w < nseries;
   if (!live) w = nseries - 1;
+  if (MASKED && active[(w / p) / cpg] == 0) return;    // (uniform per wavefront, and nothing below crosses wavefronts)
   const double* a = acov + w * ACS;
   const double dn = (double)N;
   const double r0 = a[0];
@@ -222,13 +245,24 @@ __global__ __launch_bounds__(256) void summary_ar_kernel(const double* __restric
   }
 }
 
+__global__ __launch_bounds__(256) void summary_ar_kernel(const double* __restrict__ acov, long long nseries, long long N, int M,
+                                                         double* __restrict__ stats) {
+  ar_body<false>(acov, nseries, N, M, 1, 1, nullptr, stats);
+}
+
+__global__ __launch_bounds__(256) void summary_ar_masked_kernel(const double* __restrict__ acov, long long nseries, long long N,
+                                                                int M, int p, long long cpg, const int* __restrict__ active,
+                                                                double* __restrict__ stats) {
+  ar_body<true>(acov, nseries, N, M, p, cpg, active, stats);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- stage 3
 // Per column: pooled mean and centred sum of squares from the chains' {N, mean, M2} (all chains have N rows), sum of spec0,
 // sum of the effective-size terms, non-finite count.  Thread g takes the chains g, g + 256, ... in chain order.
-__global__ __launch_bounds__(256) void summary_pool_kernel(const double* __restrict__ stats, const double* __restrict__ acov,
-                                                           long long C, int p, long long N, double* __restrict__ pooled) {
+__device__ __forceinline__ void pool_body(const double* __restrict__ stats, const double* __restrict__ acov, long long C, int p,
+                                          long long N, int j, double* __restrict__ pooled) {
   __shared__ double s_red[4];
-  const int j = blockIdx.x, tid = threadIdx.x;
+  const int tid = threadIdx.x;
   const double dn = (double)N, dc = (double)C;
   double s = 0.0;
   for (long long c = tid; c < C; c += 256) s += stats[(c * p + j) * 4];
@@ -254,6 +288,22 @@ __global__ __launch_bounds__(256) void summary_pool_kernel(const double* __restr
     o[3] = sess;
     o[4] = snf;
   }
+}
+
+__global__ __launch_bounds__(256) void summary_pool_kernel(const double* __restrict__ stats, const double* __restrict__ acov,
+                                                           long long C, int p, long long N, double* __restrict__ pooled) {
+  pool_body(stats, acov, C, p, N, blockIdx.x, pooled);
+}
+
+// The pool of every group of `cpg` consecutive chains on its own (fmcmc_summary_groups_dev): workgroup g p + j pools column j over
+// the chains of group g into row g of `pooled` (rows of `plen` doubles), with C = cpg in every divisor -- pool_body on the
+// group's slice of `stats` and `acov`, so the same sums in the same order as summary_pool_kernel on those chains alone.
+__global__ __launch_bounds__(256) void summary_group_pool_kernel(const double* __restrict__ stats, const double* __restrict__ acov,
+                                                                 long long cpg, int p, long long N, const int* __restrict__ active,
+                                                                 long long plen, double* __restrict__ pooled) {
+  const long long g = blockIdx.x / p;
+  if (active && active[g] == 0) return;
+  pool_body(stats + g * cpg * p * 4, acov + g * cpg * p * ACS, cpg, p, N, (int)(blockIdx.x % p), pooled + g * plen);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- stage 4
@@ -383,6 +433,30 @@ __global__ __launch_bounds__(64) void select_scan_kernel(unsigned long long* __r
     st[3 * t + 2] = (unsigned long long)lead;
     if (pass == 7) out[(long long)j * nt + t] = value_of(prefix);
   }
+}
+
+// Grouped select (fmcmc_summary_groups_dev): the order statistics of the cpg N pooled values of (group g, column j) by ONE
+// workgroup, g p + j -- the one-workgroup radix select of diag_common.hpp over the cpg segments of N rows that are the group's
+// chains (stride k S).  All eight passes, their histograms and scans stay in LDS: no global atomics, no launches per pass.  The
+// targets are those of select_init_kernel, (prob q, lo | hi) at 2 q + (hi); every group has cpg N values, so the ranks are the
+// same for all of them and travel as a kernel argument.  The keys are exact, so the values are those of the select above.
+__global__ __launch_bounds__(SEL_T) void summary_group_select_kernel(const double* __restrict__ samples, long long S, int k,
+                                                                     long long row0, long long N, long long cpg,
+                                                                     const int* __restrict__ cols, int p, int nt, OrderRanks ranks,
+                                                                     int staged, const int* __restrict__ active, long long plen,
+                                                                     double* __restrict__ pooled) {
+  extern __shared__ unsigned long long s_k[];        // [cpg N] when staged
+  __shared__ SelectLds L;
+  const int tid = threadIdx.x;
+  const long long g = blockIdx.x / p;
+  const int j = (int)(blockIdx.x % p);
+  if (active && active[g] == 0) return;
+  const double* __restrict__ x = samples + (g * cpg * (long long)k + cols[j]) * S + row0;
+  const long long stride = (long long)k * S;
+  stage_series(x, N, cpg, stride, staged != 0, s_k, L);
+  if (tid < nt) { L.prefix[tid] = 0ull; L.rank[tid] = ranks.r[tid]; }
+  select_series(x, N, cpg, stride, staged != 0, s_k, nt, L);
+  if (tid < nt) pooled[g * plen + (long long)p * 5 + (long long)j * nt + tid] = value_of(L.prefix[tid]);
 }
 
 // ------------------------------------------------------------------------------------------------------- Heidelberger-Welch
@@ -520,17 +594,26 @@ __global__ __launch_bounds__(ST) void summary_lag_kernel(const double* __restric
   }
 }
 
-// Stages 1 and 2 for the window [row0, row0 + N) of every series: acov [series][ACS], stats [series][4].
+// Stages 1 and 2 for the window [row0, row0 + N) of every series: acov [series][ACS], stats [series][4].  With `active` (one
+// entry per group of `cpg` consecutive chains) the masked kernels run, which leave the series of inactive groups alone.
 int launch_series_stats(const char* who, hipStream_t st, const double* samples, long long S, int k, long long row0, long long N,
-                        const int* cols, int p, long long series, double* acov, double* stats) {
+                        const int* cols, int p, long long series, double* acov, double* stats, long long cpg = 1,
+                        const int* active = nullptr) {
   const int M = (int)ar_order_max(N);
   const int tile_rows = (int)(N < LDS_ROWS ? N : LDS_ROWS);
   const size_t lds = (size_t)(tile_rows + PAD + SW * RED) * sizeof(double);
-  const int rc = allow_lds(who, summary_series_kernel, lds);
+  const int rc = active ? allow_lds(who, summary_series_masked_kernel, lds) : allow_lds(who, summary_series_kernel, lds);
   if (rc != FMCMC_OK) return rc;
-  hipLaunchKernelGGL(summary_series_kernel, dim3((unsigned)series), dim3(ST), lds, st, samples, S, k, row0, N, cols, p, M,
-                     tile_rows, acov);
-  hipLaunchKernelGGL(summary_ar_kernel, dim3((unsigned)((series + 3) / 4)), dim3(256), 0, st, acov, series, N, M, stats);
+  const dim3 ar_grid((unsigned)((series + 3) / 4));
+  if (active) {
+    hipLaunchKernelGGL(summary_series_masked_kernel, dim3((unsigned)series), dim3(ST), lds, st, samples, S, k, row0, N, cols, p, M,
+                       tile_rows, cpg, active, acov);
+    hipLaunchKernelGGL(summary_ar_masked_kernel, ar_grid, dim3(256), 0, st, acov, series, N, M, p, cpg, active, stats);
+  } else {
+    hipLaunchKernelGGL(summary_series_kernel, dim3((unsigned)series), dim3(ST), lds, st, samples, S, k, row0, N, cols, p, M,
+                       tile_rows, acov);
+    hipLaunchKernelGGL(summary_ar_kernel, ar_grid, dim3(256), 0, st, acov, series, N, M, stats);
+  }
   return FMCMC_OK;
 }
 
@@ -589,6 +672,63 @@ int fmcmc_summary_dev(const double* samples, int64_t nchains, int32_t k, int64_t
       hipLaunchKernelGGL(select_scan_kernel, dim3((unsigned)p), dim3(64), 0, st, state, hist, (int)nprobs, pass,
                          pooled + (long long)p * 5);
     }
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(FMCMC_ERR_DEVICE, "%s: launch failed (%s)", who, hipGetErrorString(e));
+  return FMCMC_OK;
+}
+
+int64_t fmcmc_summary_groups_work_len(int64_t ngroups, int64_t chains_per_group, int32_t p, int32_t nprobs) {
+  if (ngroups < 1 || chains_per_group < 1 || p < 1 || nprobs < 0 || nprobs > MAXPROBS) return 0;
+  if (chains_per_group > 0x7fffffffLL / ngroups || ngroups * chains_per_group > 0x7fffffffLL / p) return 0;
+  return ngroups * chains_per_group * (int64_t)p * (ACS + 4);      // (the select keeps its state in LDS)
+}
+
+// fmcmc_summary_dev for ngroups groups of chains_per_group consecutive chains, each on its own: stages 1-2 over all chains (under
+// `active` their masked forms), one pool workgroup and one select workgroup per (group, column).
+int fmcmc_summary_groups_dev(const double* samples, int64_t ngroups, int64_t chains_per_group, int32_t k, int64_t S, int64_t row0,
+                             int64_t N, const int32_t* cols, int32_t p, const int32_t* active, const double* probs, int32_t nprobs,
+                             double* work, double* chain_stats, double* pooled, void* hip_stream) {
+  const char* who = "fmcmc_summary_groups_dev";
+  if (!samples || !cols || !work || !pooled) return fail(FMCMC_ERR_ARG, "%s: null argument", who);
+  if (ngroups < 1 || chains_per_group < 1)
+    return fail(FMCMC_ERR_ARG, "%s: ngroups = %lld, chains_per_group = %lld: each must be at least 1", who, (long long)ngroups,
+                (long long)chains_per_group);
+  if (chains_per_group > 0x7fffffffLL / ngroups)
+    return fail(FMCMC_ERR_UNSUPPORTED, "%s: %lld groups x %lld chains exceed one launch", who, (long long)ngroups,
+                (long long)chains_per_group);
+  const long long nchains = ngroups * chains_per_group;
+  int rc = check_window(who, samples, cols, work, pooled, nchains, k, S, row0, N, p);
+  if (rc != FMCMC_OK) return rc;
+  if (nprobs < 0 || nprobs > MAXPROBS) return fail(FMCMC_ERR_ARG, "%s: nprobs = %d outside [0, %d]", who, (int)nprobs, MAXPROBS);
+  if (nprobs > 0 && !probs) return fail(FMCMC_ERR_ARG, "%s: null argument", who);
+  for (int q = 0; q < nprobs; q++)
+    if (!(probs[q] >= 0.0 && probs[q] <= 1.0)) return fail(FMCMC_ERR_ARG, "%s: probs[%d] = %g is outside [0, 1]", who, q, probs[q]);
+  if (chains_per_group > 0xffffffffLL / N)          // (N < 3162278 here: the product below cannot overflow)
+    return fail(FMCMC_ERR_UNSUPPORTED, "%s: %lld chains x %lld rows in a group; the select of a group ranks fewer than 2^32 values",
+                who, (long long)chains_per_group, (long long)N);
+
+  hipStream_t st = (hipStream_t)hip_stream;
+  const long long series = nchains * (long long)p, cpg = chains_per_group;
+  const long long plen = fmcmc_summary_pooled_len(p, nprobs);
+  double* acov = work;
+  double* stats = chain_stats ? chain_stats : work + series * ACS;
+  rc = launch_series_stats(who, st, samples, S, k, row0, N, cols, p, series, acov, stats, cpg, active);
+  if (rc != FMCMC_OK) return rc;
+  hipLaunchKernelGGL(summary_group_pool_kernel, dim3((unsigned)(ngroups * p)), dim3(256), 0, st, stats, acov, cpg, (int)p,
+                     (long long)N, active, plen, pooled);
+  if (nprobs > 0) {
+    OrderRanks ranks;                            // among the pooled values of a group's column
+    for (int q = 0; q < MAXPROBS; q++) {
+      const Type7 r = type7_ranks(cpg * (long long)N, q < nprobs ? probs[q] : 0.0);
+      ranks.r[2 * q] = (unsigned int)r.lo; ranks.r[2 * q + 1] = (unsigned int)r.hi;
+    }
+    const int staged = cpg * (long long)N <= LDS_ROWS;
+    const size_t lds = staged ? (size_t)(cpg * N) * sizeof(unsigned long long) : 0;
+    rc = allow_lds(who, summary_group_select_kernel, lds);
+    if (rc != FMCMC_OK) return rc;
+    hipLaunchKernelGGL(summary_group_select_kernel, dim3((unsigned)(ngroups * p)), dim3(SEL_T), lds, st, samples, (long long)S,
+                       (int)k, (long long)row0, (long long)N, cpg, cols, (int)p, 2 * (int)nprobs, ranks, staged, active, plen, pooled);
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(FMCMC_ERR_DEVICE, "%s: launch failed (%s)", who, hipGetErrorString(e));

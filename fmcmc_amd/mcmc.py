@@ -616,6 +616,18 @@ class McmcBatch:
         from .summary import gelman_diag_batch
         return gelman_diag_batch(self, confidence, autoburnin, multivariate, cols)
 
+    def summary(self, quantiles=(0.025, 0.25, 0.5, 0.75, 0.975), cols=None):
+        """summary(ans[d]) of every dataset (a list of McmcSummary with the stacked statistics [D][p][4], quantiles [D][p][nprobs],
+        ess [D][p] and per_chain arrays) from one grouped call on the device; on a ragged result every dataset is summarised on
+        its own rows."""
+        from .summary import summary_batch
+        return summary_batch(self, quantiles, cols)
+
+    def effective_size(self, cols=None):
+        """effective_size(ans[d]) of every dataset, [D][p], from one grouped call on the device."""
+        from .summary import effective_size_batch
+        return effective_size_batch(self, cols)
+
 
 def batch_initial(initial, nmodels, nchains):
     """`initial` of MCMC_batch() as the [D x nchains][k] matrix of the call (dataset by dataset) and the parameter names:

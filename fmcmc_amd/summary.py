@@ -232,7 +232,11 @@ def _per_chain(cs, N):
 
 
 def summary(x, quantiles=DEFAULT_QUANTILES, cols=None):
-    """coda::summary of a result: x a DeviceChains (read in place), an Mcmc or a McmcList (uploaded first)."""
+    """coda::summary of a result: x a DeviceChains (read in place), an Mcmc or a McmcList (uploaded first); an McmcBatch gives
+    an McmcSummaryBatch, one McmcSummary per dataset from one grouped call (summary_batch)."""
+    from .mcmc import McmcBatch
+    if isinstance(x, McmcBatch):
+        return summary_batch(x, quantiles, cols)
     dc = _as_device_chains(x)
     probs = tuple(float(q) for q in np.atleast_1d(np.asarray(quantiles, dtype=np.float64)))
     if len(probs) > abi.SUMMARY_MAX_PROBS:
@@ -245,7 +249,11 @@ def summary(x, quantiles=DEFAULT_QUANTILES, cols=None):
 
 
 def effective_size(x, cols=None):
-    """coda::effectiveSize: per column, the sum over the chains of N var / spec0 (0 where spec0 is 0)."""
+    """coda::effectiveSize: per column, the sum over the chains of N var / spec0 (0 where spec0 is 0); [D][p] for an McmcBatch,
+    row d what effective_size(ans[d]) gives, from one grouped call."""
+    from .mcmc import McmcBatch
+    if isinstance(x, McmcBatch):
+        return effective_size_batch(x, cols)
     dc = _as_device_chains(x)
     ps, _, _ = window_stats(dc, 0, int(dc.nrows), cols, (), want_chains=False)
     return ps[:, 3].copy()
@@ -871,6 +879,153 @@ def gelman_diag(x, confidence=0.95, autoburnin=True, multivariate=True, cols=Non
     partial, _work, cols = enqueue_gelman(dc, row0, N, cols)
     return gelman_diag_finish(partial.cpu().numpy(), int(cols.size), N, confidence, multivariate, _names(dc, cols),
                               int(dc.iters[row0]), int(dc.iters[-1]))
+
+
+# ------------------------------------------------------------------------------------------------ summary of an McmcBatch
+def enqueue_summary_groups(dc, ngroups, chains_per_group, row0, N, cols, probs, active=None, want_chains=True):
+    """The one call site of fmcmc_summary_groups_dev (current torch stream): the window [row0, row0 + N) of the rows of `dc`,
+    whose chains are ngroups groups of chains_per_group consecutive chains (McmcBatch: a group = a dataset), summarised group by
+    group.  active: None or an int32 device tensor [ngroups]; the rows of the groups whose entry is 0 keep their NaN prefill.
+    Returns the device tensors (pooled [ngroups][fmcmc_summary_pooled_len(p, nprobs)], chain_stats [ngroups chains_per_group][p][4]
+    or None, work) and the columns; nothing is synchronised."""
+    import torch
+    o = _open(dc, cols, "summarise")
+    ngroups, cpg = int(ngroups), int(chains_per_group)
+    if ngroups < 1 or cpg < 1 or ngroups * cpg != o.Cn:
+        raise ValueError("%d groups of %d chains are not the %d chains of the result" % (ngroups, cpg, o.Cn))
+    if row0 < 0 or row0 + N > dc.nrows:
+        raise ValueError("the window [%d, %d) is outside the %d kept rows" % (row0, row0 + N, dc.nrows))
+    if active is not None and (not torch.is_tensor(active) or active.dtype != torch.int32 or tuple(active.shape) != (ngroups,)
+                               or not active.is_contiguous() or active.device != o.dev):
+        raise ValueError("`active` must be a contiguous int32 tensor of shape [%d] on %s" % (ngroups, o.dev))
+    probs_h = np.ascontiguousarray(probs, dtype=np.float64)
+    nprobs = int(probs_h.size)
+    nan = float("nan")
+    plen = max(int(o.L.fmcmc_summary_pooled_len(o.p, nprobs)), 1)
+    pooled = torch.full((ngroups, plen), nan, dtype=torch.float64, device=o.dev)
+    chain_stats = torch.full((o.Cn, o.p, 4), nan, dtype=torch.float64, device=o.dev) if want_chains else None
+    work = _doubles(o, o.L.fmcmc_summary_groups_work_len(ngroups, cpg, o.p, nprobs))
+    with torch.cuda.device(o.dev):
+        rc = o.L.fmcmc_summary_groups_dev(o.smp.data_ptr(), ngroups, cpg, o.k, o.cap, int(row0), int(N), o.cols_d.data_ptr(), o.p,
+                                          active.data_ptr() if active is not None else None,
+                                          probs_h.ctypes.data_as(C.POINTER(C.c_double)), nprobs, work.data_ptr(),
+                                          chain_stats.data_ptr() if want_chains else None, pooled.data_ptr(), _stream(o.dev))
+    if rc != abi.OK:
+        raise (NotImplementedError if rc == abi.ERR_UNSUPPORTED else ValueError if rc == abi.ERR_ARG else RuntimeError)(
+            abi.last_error())
+    return pooled, chain_stats, work, o.cols
+
+
+class McmcSummaryBatch(list):
+    """summary() of an McmcBatch: a list of D McmcSummary, one per dataset (what summary(ans[d]) returns), with the stacked arrays
+    a simulation study reads: statistics [D][p][4], quantiles [D][p][nprobs], ess [D][p], and per_chain (mean, sd, tsse, ess,
+    spec0, order; each [D nchains][p], dataset by dataset)."""
+
+    def __init__(self, summaries):
+        super().__init__(summaries)
+        stack = lambda get, tail: np.stack([get(s) for s in self]) if len(self) else np.zeros((0,) + tail)
+        self.statistics = stack(lambda s: s.statistics, (0, 4))
+        self.quantiles = stack(lambda s: s.quantiles, (0, 0))
+        self.ess = stack(lambda s: s.ess, (0,))
+        fields = ("mean", "sd", "tsse", "ess", "spec0", "order")
+        self.per_chain = SimpleNamespace(**{f: np.concatenate([getattr(s.per_chain, f) for s in self]) for f in fields}) \
+            if len(self) else None
+
+    def __repr__(self):
+        return "<McmcSummaryBatch ndatasets=%d nvar=%d>" % (len(self), self.statistics.shape[1])
+
+
+def _pooled_parts(pooled_row, p, nprobs):
+    """One row of the grouped call's `pooled` -> (pooled_stats [p][5], order_stats [p][nprobs][2])."""
+    return pooled_row[:5 * p].reshape(p, 5), pooled_row[5 * p:5 * p + 2 * p * nprobs].reshape(p, nprobs, 2)
+
+
+def summary_batch_finish(pooled, chain_stats, nchains, N, probs, varnames, start, end, thin, datasets=None):
+    """The host finish of summary_batch(), pure numpy: pooled [D][5 p + 2 p nprobs] and chain_stats [D nchains][p][4] as
+    fmcmc_summary_groups_dev leaves them, summarised over N rows per chain  ->  the list of McmcSummary of `datasets` (default:
+    every row), each what summary() makes of that dataset alone: finish_statistics, type7_quantiles, _per_chain."""
+    pooled = np.asarray(pooled, dtype=np.float64)
+    probs = tuple(float(q) for q in probs)
+    p, nprobs, nchains, N = len(varnames), len(probs), int(nchains), int(N)
+    cs = np.asarray(chain_stats, dtype=np.float64).reshape(-1, nchains, p, 4)
+    out = []
+    for d in (range(pooled.shape[0]) if datasets is None else datasets):
+        ps, os_ = _pooled_parts(pooled[d], p, nprobs)
+        out.append(McmcSummary(finish_statistics(ps, nchains, N), type7_quantiles(os_, nchains * N, probs), probs, varnames,
+                               start, end, thin, nchains, per_chain=_per_chain(cs[d], N), ess=ps[:, 3].copy()))
+    return out
+
+
+def _batch_calls(ans):
+    """The grouped calls a (ragged) McmcBatch needs: one per distinct row count, (rows, datasets, mask or None)."""
+    D, counts = ans.nmodels, np.asarray(ans.nrows)
+    for nr in sorted(set(int(v) for v in counts)):
+        sel = np.nonzero(counts == nr)[0]
+        mask = None
+        if sel.size != D:
+            mask = np.zeros(D, dtype=np.int32)
+            mask[sel] = 1
+        yield nr, sel, mask
+
+
+def _batch_groups(ans, nr, mask, cols, probs, want_chains):
+    """One grouped call on the first nr rows of ans.history and ONE copy back: (pooled [D][.], chain_stats or None, columns)."""
+    import torch
+    full, D = ans.history, ans.nmodels
+    active = None if mask is None else torch.as_tensor(mask).to(full._samples.device)
+    pooled, chain_stats, _work, cs = enqueue_summary_groups(full, D, ans.nchains, 0, nr, cols, probs, active, want_chains)
+    if not want_chains:
+        return pooled.cpu().numpy(), None, cs
+    both = torch.cat([pooled.reshape(-1), chain_stats.reshape(-1)]).cpu().numpy()
+    return both[:pooled.numel()].reshape(D, -1), both[pooled.numel():].reshape(chain_stats.shape), cs
+
+
+def _raise_non_finite_batch(pooled_h, sel, p, cols, what):
+    for d in sel:
+        try:
+            _raise_non_finite(pooled_h[d, :5 * p].reshape(1, p, 5)[:, :, 4], cols, what)
+        except ValueError as e:
+            raise ValueError("dataset %d: %s" % (d, e)) from None
+
+
+def summary_batch(ans, quantiles=DEFAULT_QUANTILES, cols=None):
+    """summary(ans[d]) for every dataset d of an McmcBatch from ONE grouped call (fmcmc_summary_groups_dev) and one copy back:
+    the same numbers bit for bit, the same host finish.  On a ragged result (MCMC_batch(stop_each = ...)) each dataset is
+    summarised on its own rows with its own iteration labels, with one call per distinct row count -- at most one per bulk."""
+    from .mcmc import McmcBatch
+    if not isinstance(ans, McmcBatch):
+        raise TypeError("summary_batch() expects an McmcBatch (the result of MCMC_batch)")
+    _single_process()
+    probs = tuple(float(q) for q in np.atleast_1d(np.asarray(quantiles, dtype=np.float64)))
+    if len(probs) > abi.SUMMARY_MAX_PROBS:
+        raise ValueError("at most %d quantiles per call" % abi.SUMMARY_MAX_PROBS)
+    full = ans.history
+    out = [None] * ans.nmodels
+    for nr, sel, mask in _batch_calls(ans):
+        pooled_h, chain_h, cs = _batch_groups(ans, nr, mask, cols, probs, True)
+        _raise_non_finite_batch(pooled_h, sel, int(cs.size), cs, "summarise")
+        iters = full.iters[:nr]
+        for d, s in zip(sel, summary_batch_finish(pooled_h, chain_h, ans.nchains, nr, probs, _names(full, cs), int(iters[0]),
+                                                  int(iters[-1]), full.thin, datasets=sel)):
+            out[d] = s
+    return McmcSummaryBatch(out)
+
+
+def effective_size_batch(ans, cols=None):
+    """effective_size(ans[d]) for every dataset of an McmcBatch, [D][p], from the grouped call without quantiles."""
+    from .mcmc import McmcBatch
+    if not isinstance(ans, McmcBatch):
+        raise TypeError("effective_size_batch() expects an McmcBatch (the result of MCMC_batch)")
+    _single_process()
+    out = None
+    for nr, sel, mask in _batch_calls(ans):
+        pooled_h, _none, cs = _batch_groups(ans, nr, mask, cols, (), False)
+        p = int(cs.size)
+        _raise_non_finite_batch(pooled_h, sel, p, cs, "summarise")
+        if out is None:
+            out = np.empty((ans.nmodels, p))
+        out[sel] = pooled_h[sel, :5 * p].reshape(sel.size, p, 5)[:, :, 3]
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ HPD intervals

@@ -406,6 +406,22 @@ int64_t fmcmc_summary_pooled_len(int32_t p, int32_t nprobs);
 int fmcmc_summary_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N,
                       const int32_t* cols, int32_t p, const double* probs, int32_t nprobs, double* work,
                       double* chain_stats, double* pooled, void* hip_stream);
+/* The same summary for ngroups groups of chains_per_group consecutive chains, each group on its own (group g = chains
+ * g chains_per_group ..; one model on many datasets: a group = the chains of a dataset), enqueued once on the caller's stream.
+ * pooled is [ngroups][fmcmc_summary_pooled_len(p, nprobs)] (device): row g is bit for bit the `pooled` that fmcmc_summary_dev
+ * writes for the chains of group g alone (divisors and ranks over chains_per_group N values).  chain_stats (device, may be NULL):
+ * [ngroups chains_per_group][p][4], and work, fmcmc_summary_groups_work_len = ngroups chains_per_group p (72 + 4) doubles whose
+ * head is [series][72] (r_0 .. r_64, mean at 65, residual sd at 66, non-finite count at 67): both bit for bit those of the single
+ * call.  active[ngroups] (device int32, NULL = all): for a group whose entry is 0 no row of pooled, chain_stats or work is
+ * written.  probs as for fmcmc_summary_dev.  The order statistics of a (group, column) are selected by ONE workgroup that keeps
+ * the group's chains_per_group N keys in LDS while they are at most 19456 and re-reads them every pass beyond: correct at any
+ * size below 2^32 values per group (FMCMC_ERR_UNSUPPORTED from there), slow for a few large groups -- fmcmc_summary_dev per
+ * group is the form for those. */
+int64_t fmcmc_summary_groups_work_len(int64_t ngroups, int64_t chains_per_group, int32_t p, int32_t nprobs);
+int fmcmc_summary_groups_dev(const double* samples, int64_t ngroups, int64_t chains_per_group, int32_t k, int64_t S,
+                             int64_t row0, int64_t N, const int32_t* cols, int32_t p, const int32_t* active,
+                             const double* probs, int32_t nprobs, double* work, double* chain_stats, double* pooled,
+                             void* hip_stream);
 
 /* ---- Heidelberger-Welch diagnostic of every chain (coda::heidel.diag), the device part ---------------------------------------
  * Window, samples, S, cols as for fmcmc_summary_dev.  Rows are counted from row0: half_row is the first row of the window the
