@@ -23,6 +23,23 @@ def _t(a, dtype, device):
     return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(device).contiguous()
 
 
+def _call_stream(stream, dev, made=()):
+    """The stream of a call: `stream`, or torch's current stream of `dev`.  The one rule of every `stream=` of this module: with
+    stream = s the call starts behind torch's current stream as it stands at the call (s.wait_stream(current): what the caller
+    and this module prepared there -- inputs, NaN and zero fills of the outputs, contiguous copies -- is done before the first
+    launch), its results are ordered on s, and check=True waits for s.  made: tensors this module allocated on the current stream
+    for the call; they are recorded on s, so that the caching allocator does not hand their memory out again on the current stream
+    while s still works on them.  Nothing happens when s is the current stream.  Call it after the last preparation."""
+    cur = torch.cuda.current_stream(dev)
+    if stream is None or stream == cur:
+        return cur
+    stream.wait_stream(cur)
+    for t in made:
+        if t is not None:
+            t.record_stream(stream)
+    return stream
+
+
 class DeviceModel:
     """Shared read-only data of a log-posterior family, resident in HBM (fmcmc_model)."""
 
@@ -68,18 +85,22 @@ class DeviceModel:
 
     def logpost(self, theta, out=None, stream=None):
         """The family's canonical log-posterior of every row of theta [C, k] (a float64 tensor on this device) -> [C]
-        (fmcmc_logpost_dev): the value the sweeps evaluate, bit for bit, enqueued on `stream` (torch's current one)."""
+        (fmcmc_logpost_dev): the value the sweeps evaluate, bit for bit, enqueued on `stream` (torch's current one; the rule of
+        _call_stream: the call starts behind torch's current stream, a non-contiguous theta is copied there first)."""
         if not torch.is_tensor(theta) or theta.dtype != torch.float64 or theta.ndim != 2 or theta.shape[1] != self.k or \
                 not _on(theta, self.device):
             raise ValueError("DeviceModel.logpost: theta must be a float64 tensor of shape [C, %d] on %s; got %s" % (
                 self.k, self.device, _describe(theta)))
-        theta = theta.contiguous()
+        made = []
+        if not theta.is_contiguous():
+            theta = theta.contiguous()
+            made.append(theta)
         if out is None:
             out = torch.empty(theta.shape[0], dtype=torch.float64, device=self.device)
+            made.append(out)
         if theta.shape[0] == 0:
             return out
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device)
+        stream = _call_stream(stream, self.device, made)
         cm = self.c()
         with torch.cuda.device(self.device):
             rc = abi.lib().fmcmc_logpost_dev(C.byref(cm), theta.data_ptr(), theta.shape[0], out.data_ptr(),
@@ -281,7 +302,7 @@ class ChainState:
             if cols.shape[1] < nsteps:   # R: update_sequence[env$i, ] beyond the rows of the kernel's first call
                 raise IndexError("subscript out of bounds: the update plan of this kernel has %d rows" % cols.shape[1])
             cols = cols[:, :nsteps].contiguous()
-        self._cols_keep = cols
+        self._cols_keep = cols      # (alive while the call runs; a copy made here is among the call's _made_for_call)
         return abi.State(self.theta0.data_ptr(), self.f0.data_ptr(), self.abs_iter.data_ptr(),
                          self.Sigma.data_ptr(), self.mean_prev.data_ptr(), self.have_mean.data_ptr(),
                          self.nerrors.data_ptr(), self.fresh, 0, cols.data_ptr() if cols is not None else None,
@@ -308,6 +329,9 @@ def sweep(model, kernel, state, nsteps, burnin=0, thin=1, seed=0, chain_base=0,
     model: a DeviceModel (a closed-form family) or a DeviceFun (a batched user-defined log-posterior, called between the
     engine's launches with `stream` as torch's current stream).
 
+    stream: the stream of the call (None: torch's current stream).  With stream = s the call starts behind torch's current stream
+    as it stands at the call, its results are ordered on s, and check=True waits for s (_call_stream).
+
     Raises ValueError for argument errors (messages mirror the reference's stop() texts) and
     RuntimeError for chain errors ("fun(par) is undefined", R/mcmc.R:758-765)."""
     L = abi.lib()
@@ -320,21 +344,20 @@ def sweep(model, kernel, state, nsteps, burnin=0, thin=1, seed=0, chain_base=0,
         if rng_mode == abi.RNG_FED:
             raise ValueError("rng_mode = FED with scheme = 'random' needs state.scheme_cols (the plan R drew)")
         state.scheme_cols = torch.zeros((Cn, nsteps), dtype=torch.int32, device=dev)
-    if stream is None:
-        stream = torch.cuda.current_stream(dev)
+    if isinstance(model, DeviceFun) and k != model.k:
+        raise ValueError("Incorrect length of -initial-: the model has %d parameters, got %d." % (model.k, k))
+    cs = state.c(nsteps)
+    # (the output buffers above were made and filled on the current stream: the engine's stream starts behind them)
+    stream = _call_stream(stream, dev, _made_for_call(out, state))
     if isinstance(model, DeviceFun):
-        if k != model.k:
-            raise ValueError("Incorrect length of -initial-: the model has %d parameters, got %d." % (model.k, k))
-        # (the output buffers above were made on the current stream: the engine's stream starts behind them)
-        stream.wait_stream(torch.cuda.current_stream(dev))
-        rc = _run_fun_dev(model, kernel.c(), crun, state.c(nsteps), cout, stream)
+        rc = _run_fun_dev(model, kernel.c(), crun, cs, cout, stream)
     else:
-        cm, ck, cs = model.c(), kernel.c(), state.c(nsteps)
+        cm, ck = model.c(), kernel.c()
         with torch.cuda.device(dev):
             rc = L.fmcmc_mcmc_run_dev(C.byref(cm), C.byref(ck), C.byref(crun), C.byref(cs), C.byref(cout),
                                       C.c_void_p(stream.cuda_stream))
     return _finish_call(out, state, rc, "fmcmc_mcmc_run_fun_dev" if isinstance(model, DeviceFun) else "fmcmc_mcmc_run_dev",
-                        nsteps, burnin, thin, chain_base, check)
+                        nsteps, burnin, thin, chain_base, check, stream)
 
 
 def sweep_batch(batch, kernel, state, nsteps, burnin=0, thin=1, seed=0, chain_base=0,
@@ -346,7 +369,7 @@ def sweep_batch(batch, kernel, state, nsteps, burnin=0, thin=1, seed=0, chain_ba
     sweep()'s.  stream_data = True reads the datasets from global memory every step instead of holding each in LDS
     (FMCMC_BATCH_STREAM_DATA; the same bits).  active: None, or an int32 device tensor [D] -- the chains of a dataset whose
     entry is 0 do not run: their state, their rows of `into` and their entries of every output stay as they were (the
-    outputs this call allocates: zeros, NaN samples)."""
+    outputs this call allocates: zeros, NaN samples).  stream: as for sweep()."""
     L = abi.lib()
     dev = state.device
     if active is not None and (not torch.is_tensor(active) or active.dtype != torch.int32 or tuple(active.shape) != (batch.nmodels,)
@@ -362,14 +385,13 @@ def sweep_batch(batch, kernel, state, nsteps, burnin=0, thin=1, seed=0, chain_ba
         if crun.rng_mode == abi.RNG_FED:
             raise ValueError("rng_mode = FED with scheme = 'random' needs state.scheme_cols (the plan R drew)")
         state.scheme_cols = torch.zeros((Cn, nsteps), dtype=torch.int32, device=dev)
-    if stream is None:
-        stream = torch.cuda.current_stream(dev)
     cm, ck, cs = batch.c(), kernel.c(), state.c(nsteps)
+    stream = _call_stream(stream, dev, _made_for_call(out, state))
     with torch.cuda.device(dev):
         rc = L.fmcmc_mcmc_run_batch_sel_dev(C.byref(cm), batch.nmodels, batch.x_stride, batch.y_stride, C.byref(ck), C.byref(crun),
                                             C.byref(cs), C.byref(cout), active.data_ptr() if active is not None else None,
                                             abi.BATCH_STREAM_DATA if stream_data else 0, C.c_void_p(stream.cuda_stream))
-    return _finish_call(out, state, rc, "fmcmc_mcmc_run_batch_sel_dev", nsteps, burnin, thin, chain_base, check)
+    return _finish_call(out, state, rc, "fmcmc_mcmc_run_batch_sel_dev", nsteps, burnin, thin, chain_base, check, stream)
 
 
 def _call_buffers(state, nsteps, burnin, thin, seed, chain_base, want_logpost, want_draws, want_bits, fed_logu, fed_z, into, row0):
@@ -401,6 +423,9 @@ def _call_buffers(state, nsteps, burnin, thin, seed, chain_base, want_logpost, w
     out.status = torch.zeros(Cn, dtype=torch.int32, device=dev)
     out.status_step = torch.zeros(Cn, dtype=torch.int64, device=dev)
     out.status_theta = torch.zeros((Cn, k), **f64)
+    out._made = [out.accept_count, out.accept_bits, out.status, out.status_step, out.status_theta]
+    if into is None:
+        out._made += [out.samples, out.logpost, out.draws]
     rng_mode = abi.RNG_FED if fed_logu is not None else abi.RNG_PHILOX
     crun = abi.Run(Cn, nsteps, burnin, thin, seed & 0xFFFFFFFFFFFFFFFF, chain_base, state.step_base,
                    rng_mode, 0, fed_logu.data_ptr() if fed_logu is not None else None,
@@ -413,8 +438,17 @@ def _call_buffers(state, nsteps, burnin, thin, seed, chain_base, want_logpost, w
     return out, crun, cout
 
 
-def _finish_call(out, state, rc, entry, nsteps, burnin, thin, chain_base, check):
-    """The return code of an entry point raised as sweep() documents it; the state advanced, the result labelled."""
+def _made_for_call(out, state):
+    """the tensors _call_buffers and ChainState.c() allocated for this call (for _call_stream)"""
+    made = list(out._made)
+    if state._cols_keep is not None and state._cols_keep is not state.scheme_cols:
+        made.append(state._cols_keep)
+    return made
+
+
+def _finish_call(out, state, rc, entry, nsteps, burnin, thin, chain_base, check, stream=None):
+    """The return code of an entry point raised as sweep() documents it; the state advanced, the result labelled.  check: the
+    chains' statuses are read back, after the work on `stream`."""
     if rc in (abi.ERR_ARG, abi.ERR_UNSUPPORTED):
         raise ValueError(abi.last_error())
     if rc != abi.OK:
@@ -424,23 +458,25 @@ def _finish_call(out, state, rc, entry, nsteps, burnin, thin, chain_base, check)
     out.iters = burnin + thin * np.arange(1, max(kept_rows(nsteps, burnin, thin), 0) + 1)
     out.thin, out.nsteps, out.burnin = thin, nsteps, burnin
     if check:
-        raise_on_chain_error(out, chain_base)
+        raise_on_chain_error(out, chain_base, stream)
     return out
 
 
 def rng_stream(state, kernel, nsteps, seed=0, chain_base=0, logu=None, z=None, stream=None):
     """Canonical Philox stream of the next sweep of `state` in HBM (fmcmc_rng_stream_dev); pass the returned
-    tensors as fed_logu / fed_z to sweep(): bit-identical to the in-library stream, buffers reusable."""
+    tensors as fed_logu / fed_z to sweep(): bit-identical to the in-library stream, buffers reusable.  stream: as for sweep()."""
     L = abi.lib()
     dev = state.device
     Cn = state.theta0.shape[0]
     kz = kernel.kz
+    made = []
     if logu is None:
         logu = torch.empty((Cn, nsteps), dtype=torch.float64, device=dev)
+        made.append(logu)
     if z is None:
         z = torch.empty((Cn, nsteps, kz), dtype=torch.float64, device=dev)
-    if stream is None:
-        stream = torch.cuda.current_stream(dev)
+        made.append(z)
+    stream = _call_stream(stream, dev, made)
     # the variate family the kernel's own in-library stream draws (mh_engine.hip, launch_sweep): kernel_ram's qfun families
     # (fmcmc_kernel.ram_qfun: rt(k, k) / rnorm(k) / rt(k, df)), U(0,1) for the uniform kernels, N(0,1) otherwise
     if kernel.kind == abi.KERNEL_RAM:
@@ -534,7 +570,7 @@ def sweep_user(model, kernel, state, nsteps, burnin=0, thin=1, seed=0, chain_bas
     kernel.proposal(env) -> theta1 [C, k], the evaluation (model: a DeviceModel, evaluated by the engine, or a DeviceFun),
     kernel.logratio(env) -> [C] when the kernel has one, and one launch of the engine's accept / store step.  The keywords and
     the result are sweep()'s; fed_logu feeds the accept uniforms (env.rnorm / runif / rt then raise).  The callbacks run with
-    `stream` as torch's current stream; an exception raised in one ends the call and is raised again here."""
+    `stream` as torch's current stream (as for sweep()); an exception raised in one ends the call and is raised again here."""
     L = abi.lib()
     dev = state.device
     Cn, k = state.theta0.shape
@@ -542,11 +578,10 @@ def sweep_user(model, kernel, state, nsteps, burnin=0, thin=1, seed=0, chain_bas
         raise ValueError("Incorrect length of -initial-: the model has %d parameters, got %d." % (model.k, k))
     out, crun, cout = _call_buffers(state, nsteps, burnin, thin, seed, chain_base, want_logpost, want_draws, want_bits,
                                     fed_logu, None, into, row0)
-    if stream is None:
-        stream = torch.cuda.current_stream(dev)
-    # (the output buffers above were made on the current stream: the engine's stream starts behind them)
-    stream.wait_stream(torch.cuda.current_stream(dev))
-    env = UserEnv(kernel, model, state, nsteps, seed, chain_base, stream, fed_logu is not None)
+    cs = state.c(nsteps)
+    env = UserEnv(kernel, model, state, nsteps, seed, chain_base, None, fed_logu is not None)
+    # (the output buffers above and env.chain_ids were made on the current stream: the engine's stream starts behind them)
+    stream = env._stream = _call_stream(stream, dev, _made_for_call(out, state) + [env.chain_ids])
     caught, view = [], _Views(dev)
 
     def step_fn(user_fn, what, shape):
@@ -570,16 +605,19 @@ def sweep_user(model, kernel, state, nsteps, burnin=0, thin=1, seed=0, chain_bas
     prop_cb = step_fn(kernel.proposal, "proposal", (Cn, k))
     ratio_cb = step_fn(kernel.logratio, "logratio", (Cn,)) if kernel.logratio is not None else abi.STEP_FN()
     cm = None if isinstance(model, DeviceFun) else model.c()
-    cs = state.c(nsteps)
     with torch.cuda.device(dev):
         rc = L.fmcmc_mcmc_run_user_dev(C.byref(cm) if cm is not None else None, fun_cb, prop_cb, ratio_cb, None, k,
                                        C.byref(crun), C.byref(cs), C.byref(cout), C.c_void_p(stream.cuda_stream))
     if caught:
         raise caught[0]
-    return _finish_call(out, state, rc, "fmcmc_mcmc_run_user_dev", nsteps, burnin, thin, chain_base, check)
+    return _finish_call(out, state, rc, "fmcmc_mcmc_run_user_dev", nsteps, burnin, thin, chain_base, check, stream)
 
 
-def raise_on_chain_error(out, chain_base=0):
+def raise_on_chain_error(out, chain_base=0, stream=None):
+    """Raises the first chain error of a call's result.  stream: the stream the call ran on (None: torch's current one, which the
+    copy below waits for); the statuses are read after its work."""
+    if stream is not None:
+        stream.synchronize()
     st = out.status.cpu().numpy()
     bad = np.nonzero(st)[0]
     if bad.size:

@@ -29,10 +29,12 @@ def make_series(N, seed, non_finite=False):
     return np.ascontiguousarray(x)
 
 
-def device_call(name, x, N, mid, lens):
+def device_call(name, x, N, mid, lens, run=None):
     """One call L.<name>(samples, C, k, S, ROW0, N, cols, p, *mid, *buffers, stream 0) on x [C][k][S]: a buffer of doubles per
     entry of `lens` (None: a null pointer), NaN-filled and GUARD elements longer than asked, which must stay NaN.  Returns the
-    buffers as numpy arrays of their documented lengths."""
+    buffers as numpy arrays of their documented lengths.  run: None, or run(inputs, buffers, call) -> code, which makes the
+    call as call(hip_stream) on a stream of its choice (tests/test_gpu_streams.py); the device inputs and the buffers are its
+    to prepare, and the buffers must be NaN beyond what the call writes when it returns."""
     import torch
     from fmcmc_amd import _abi as abi
     Cn, k, S = x.shape
@@ -40,8 +42,9 @@ def device_call(name, x, N, mid, lens):
     xd = torch.as_tensor(x).cuda()
     cd = torch.as_tensor(np.asarray(COLS, dtype=np.int32)).cuda()
     bufs = [None if n is None else torch.full((int(n) + GUARD,), float("nan"), dtype=torch.float64, device="cuda") for n in lens]
-    rc = getattr(abi.lib(), name)(xd.data_ptr(), Cn, k, S, ROW0, N, cd.data_ptr(), len(COLS), *mid,
-                                  *[None if b is None else b.data_ptr() for b in bufs], None)
+    call = lambda stream: getattr(abi.lib(), name)(xd.data_ptr(), Cn, k, S, ROW0, N, cd.data_ptr(), len(COLS), *mid,
+                                                   *[None if b is None else b.data_ptr() for b in bufs], stream)
+    rc = call(None) if run is None else run([xd, cd], [b for b in bufs if b is not None], call)
     assert rc == abi.OK, (rc, abi.last_error())
     torch.cuda.synchronize()
     host = [None if b is None else b.cpu().numpy() for b in bufs]
@@ -54,7 +57,7 @@ def _lib():
     return abi.lib()
 
 
-def summary_case(N, non_finite=False):
+def summary_case(N, non_finite=False, run=None):
     """The five default probs, chain_stats asked for: slots 0..67 of every series' 72-double head of `work` (68..71 are never
     written), chain_stats and pooled."""
     L, nprobs = _lib(), len(PROBS)
@@ -62,14 +65,14 @@ def summary_case(N, non_finite=False):
     work, stats, pooled = device_call("fmcmc_summary_dev", make_series(N, 1000 + N, non_finite), N,
                                       (probs.ctypes.data_as(C.POINTER(C.c_double)), nprobs),
                                       (L.fmcmc_summary_work_len(CHAINS, len(COLS), nprobs), SERIES * 4,
-                                       L.fmcmc_summary_pooled_len(len(COLS), nprobs)))
+                                       L.fmcmc_summary_pooled_len(len(COLS), nprobs)), run)
     head = work[:SERIES * 72].reshape(SERIES, 72)
     if non_finite:
         return {"non_finite": _bits(head[:, 67]), "pooled_non_finite": _bits(pooled[:5 * len(COLS)].reshape(-1, 5)[:, 4])}
     return {"work": _bits(head[:, :68]).ravel(), "chain_stats": _bits(stats), "pooled": _bits(pooled)}
 
 
-def heidel_case(N, non_finite=False):
+def heidel_case(N, non_finite=False, run=None):
     """The windows heidel() takes of the iterations 1 .. N: all of `out`, and the non-finite slot of every series of `work`."""
     from fmcmc_amd.summary import heidel_candidates
     L = _lib()
@@ -77,12 +80,13 @@ def heidel_case(N, non_finite=False):
     rows = np.ascontiguousarray(rows, dtype=np.int64)
     work, out = device_call("fmcmc_heidel_dev", make_series(N, 2000 + N, non_finite), N,
                             (int(half), rows.ctypes.data_as(C.POINTER(C.c_int64)), int(rows.size)),
-                            (L.fmcmc_heidel_work_len(CHAINS, len(COLS), rows.size), L.fmcmc_heidel_out_len(CHAINS, len(COLS), rows.size)))
+                            (L.fmcmc_heidel_work_len(CHAINS, len(COLS), rows.size), L.fmcmc_heidel_out_len(CHAINS, len(COLS), rows.size)),
+                            run)
     nf = {"non_finite": _bits(work.reshape(SERIES, 72)[:, 67])}
     return nf if non_finite else dict(nf, out=_bits(out))
 
 
-def order_case(N, nprobs, non_finite=False):
+def order_case(N, nprobs, non_finite=False, run=None):
     """nprobs = 0: the one rank of the lower median; else the 2 nprobs ranks of evenly spaced probs from 0 to 1.  `out` and the
     non-finite counts."""
     from fmcmc_amd.summary import type7_order_ranks
@@ -90,17 +94,18 @@ def order_case(N, nprobs, non_finite=False):
     ranks = np.ascontiguousarray(type7_order_ranks(N, probs).ravel()[:1 if nprobs == 0 else None], dtype=np.int64)
     work, out = device_call("fmcmc_chain_order_dev", make_series(N, 3000 + N + nprobs, non_finite), N,
                             (ranks.ctypes.data_as(C.POINTER(C.c_int64)), int(ranks.size)),
-                            (_lib().fmcmc_chain_order_work_len(CHAINS, len(COLS), ranks.size), SERIES * ranks.size))
+                            (_lib().fmcmc_chain_order_work_len(CHAINS, len(COLS), ranks.size), SERIES * ranks.size), run)
     nf = {"non_finite": _bits(work)}
     return nf if non_finite else dict(nf, out=_bits(out))
 
 
-def raftery_case(N, q, j0, nj, non_finite=False):
+def raftery_case(N, q, j0, nj, non_finite=False, run=None):
     """The head (u, x_(lo), x_(hi), non-finite count per series) and the integer counts of the thinnings j0 .. j0 + nj - 1 (they
     cover the indicator words in `work`)."""
     L = _lib()
     _work, out = device_call("fmcmc_raftery_dev", make_series(N, 4000 + N, non_finite), N, (float(q), int(j0), int(nj)),
-                             (L.fmcmc_raftery_work_len(CHAINS, len(COLS), N), L.fmcmc_raftery_out_len(CHAINS, len(COLS), nj)))
+                             (L.fmcmc_raftery_work_len(CHAINS, len(COLS), N), L.fmcmc_raftery_out_len(CHAINS, len(COLS), nj)),
+                             run)
     head = out[:SERIES * 4].reshape(SERIES, 4)
     if non_finite:
         return {"non_finite": _bits(head[:, 3])}

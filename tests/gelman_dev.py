@@ -18,9 +18,11 @@ def pick_columns(k, p, seed):
     return (np.arange(k) if p == k else np.sort(np.random.default_rng(seed).choice(k, size=p, replace=False))).astype(np.int32)
 
 
-def device_partial(x, cols, row0, N, center=FIRST_ROW):
+def device_partial(x, cols, row0, N, center=FIRST_ROW, run=None):
     """One fmcmc_gelman_partial_dev call on x [C][k][S]: (work [C][p + p p], partial) as numpy; buffers NaN-filled, guards
-    checked.  center None passes a null pointer."""
+    checked.  center None passes a null pointer.  run: None, or run(inputs, buffers, call) -> code, which makes the call as
+    call(hip_stream) on a stream of its choice (tests/test_gpu_streams.py); the device inputs and the buffers are its to prepare,
+    and the buffers must be NaN beyond what the call writes when it returns."""
     import torch
     from fmcmc_amd import _abi as abi
     L = abi.lib()
@@ -36,8 +38,9 @@ def device_partial(x, cols, row0, N, center=FIRST_ROW):
     assert wlen == Cn * (p + p * p) and plen == 1 + 5 * p + 2 * p * p
     work = torch.full((wlen + GUARD,), float("nan"), dtype=torch.float64, device="cuda")
     part = torch.full((plen + GUARD,), float("nan"), dtype=torch.float64, device="cuda")
-    rc = L.fmcmc_gelman_partial_dev(xd.data_ptr(), Cn, k, S, row0, N, cd.data_ptr(), p, None if ctr is None else ctr.data_ptr(),
-                                    work.data_ptr(), part.data_ptr(), None)
+    call = lambda stream: L.fmcmc_gelman_partial_dev(xd.data_ptr(), Cn, k, S, row0, N, cd.data_ptr(), p,
+                                                     None if ctr is None else ctr.data_ptr(), work.data_ptr(), part.data_ptr(), stream)
+    rc = call(None) if run is None else run([xd, cd] + ([] if ctr is None else [ctr]), [work, part], call)
     assert rc == abi.OK, rc
     torch.cuda.synchronize()
     wh, ph = work.cpu().numpy(), part.cpu().numpy()
