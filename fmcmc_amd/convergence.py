@@ -399,3 +399,102 @@ class convergence_auto:
     history = property(lambda self: self._used.history)
     msg = property(lambda self: self._used.msg)
     last = property(lambda self: self._used.last)
+
+
+# ================================================================================================
+# Rank-normalised split R-hat (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021).  The definition is INTEGRATION.md §2.2;
+# the device computes it in csrc/diag_rank.hpp (summary.rhat), this is its restatement on the host.
+# ================================================================================================
+def split_chains(data):
+    """data [C][N][p] -> [2 C][N // 2][p]: split chain 2 c = the first N // 2 rows of chain c, 2 c + 1 its last N // 2 (an odd N
+    drops the middle row)."""
+    data = np.asarray(data, dtype=np.float64)
+    Cn, N, p = data.shape
+    nh = N // 2
+    return np.stack([data[:, :nh], data[:, N - nh:]], axis=1).reshape(2 * Cn, nh, p)
+
+
+def rank_z(values):
+    """values [m][n] -> (z [m][n], 2 r [m][n]): the average ranks r among all m n values (ties by numerical equality) and
+    z = qnorm((r - 0.375) / (m n + 0.25))."""
+    from scipy.special import ndtri
+    from scipy.stats import rankdata
+    v = np.asarray(values, dtype=np.float64) + 0.0
+    r = rankdata(v.ravel(), method="average").reshape(v.shape)
+    return ndtri((r - 0.375) / (v.size + 0.25)), 2.0 * r
+
+
+def rhat_host(data):
+    """The rank-normalised split R-hat of data [C][N][p] (or an McmcList / Mcmc) on the host: a namespace of bulk, tail, rhat,
+    median, each [p] (summary.rhat is the device form; the two share rhat_of_moments)."""
+    from types import SimpleNamespace
+    from .mcmc import Mcmc, McmcList
+    from .summary import rhat_max, rhat_of_moments
+    if isinstance(data, Mcmc):
+        data = McmcList([data])
+    if isinstance(data, McmcList):
+        data = data.as_array()
+    data = np.asarray(data, dtype=np.float64)
+    if data.ndim != 3 or data.shape[0] < 1 or data.shape[1] < 4:
+        raise ValueError("rhat_host: data [C][N][p] with N >= 4 rows are needed")
+    bad = ~np.isfinite(data)
+    if bad.any():
+        raise ValueError("%d non-finite value(s) among the rows to rank (columns %s)"
+                         % (int(bad.sum()), [j for j in range(data.shape[2]) if bad[:, :, j].any()]))
+    sp = split_chains(data)
+    m, nh, p = sp.shape
+    bulk, tail, med = np.empty(p), np.empty(p), np.empty(p)
+    for j in range(p):
+        x = sp[:, :, j] + 0.0
+        srt = np.sort(x.ravel())
+        med[j] = (srt[m * nh // 2 - 1] + srt[m * nh // 2]) / 2.0
+        for dest, v in ((bulk, x), (tail, np.abs(x - med[j]))):
+            z = rank_z(v)[0].astype(np.longdouble)
+            dest[j] = rhat_of_moments(z.mean(axis=1), z.var(axis=1, ddof=1), nh)
+    return SimpleNamespace(bulk=bulk, tail=tail, rhat=rhat_max(bulk, tail), median=med)
+
+
+class convergence_rhat:
+    """Auto-stop on the rank-normalised split R-hat: converged when the largest rhat = max(bulk, tail) over the free columns
+    is below `threshold` (1.01 is the usual one).  With `autoburnin` the rows are coda's window (_window: the second half of
+    the history, what convergence_gelman tests), else all rows.  NaN (a constant column) or fewer than 4 rows: not converged.
+    One chain is enough.  The chains of ONE process only: pooled ranks across GPUs are not built."""
+
+    def __init__(self, freq=1000, threshold=1.01, autoburnin=True):
+        self.freq, self.threshold, self.autoburnin = int(freq), float(threshold), bool(autoburnin)
+        self.flush()
+
+    def flush(self):
+        self.history = []  # (end iteration, value, rhat [p])
+        self.msg = ""
+        self.last = None
+
+    def check_device(self, chains, cols, group=None):
+        import torch.distributed as dist
+        from .summary import enqueue_rank_rhat, rhat_finish, _raise_non_finite
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            raise NotImplementedError("convergence_rhat ranks the values of ONE process: under torch.distributed with more than "
+                                      "one rank the chains are sharded and pooled ranks across GPUs are not implemented.")
+        self.msg = ""
+        row0, N = _window(chains.iters) if self.autoburnin else (0, int(chains.nrows))
+        if N < 4:
+            return False
+        out, _work, cols = enqueue_rank_rhat(chains, row0, N, cols)
+        fin = rhat_finish(out.cpu().numpy(), int(chains._samples.shape[0]), N // 2)
+        _raise_non_finite(fin.non_finite[None, :], cols, "rank")
+        val = float("nan") if np.isnan(fin.rhat).any() else float(fin.rhat.max())
+        self.history.append((int(chains.iters[-1]), val, fin.rhat.copy()))
+        self.last = val
+        self.msg = "Rank-normalised split R-hat: %.4f." % val
+        return bool(val < self.threshold)
+
+    def __call__(self, x):
+        import torch
+        from .mcmc import DeviceChains, Mcmc, McmcList
+        if isinstance(x, Mcmc):
+            x = McmcList([x])
+        if not isinstance(x, McmcList) or len(x) < 1:
+            raise TypeError("expected an McmcList object")
+        arr = np.ascontiguousarray(x.as_array().transpose(0, 2, 1))  # [C][k][S]
+        dc = DeviceChains(torch.as_tensor(arr).cuda(), None, None, x.iters, x.thin, x[0].varnames, 0, len(x))
+        return self.check_device(dc, np.arange(arr.shape[1]))

@@ -16,6 +16,7 @@
 // Every count is an integer, so neither the arrival order of the LDS atomics nor the launch changes a result.  Nothing here
 // writes `samples`.
 #include "diag_common.hpp"
+#include "diag_rank.hpp"            // the sort through HBM, the pooled ranks and the split R-hat entries (fmcmc_rank_*)
 
 namespace {
 

@@ -287,6 +287,16 @@ class DeviceChains:
         from .summary import gelman_diag
         return gelman_diag(self, confidence, autoburnin, multivariate, cols)
 
+    def rhat(self, autoburnin=False, cols=None):
+        """Rank-normalised split R-hat (Vehtari et al. 2021): bulk, tail and their maximum per column."""
+        from .summary import rhat
+        return rhat(self, autoburnin, cols)
+
+    def rank_scores(self, fold=False, cols=None):
+        """The rank-normalised scores behind rhat(), a device tensor [p][2 C][N // 2] (for rank plots)."""
+        from .summary import rank_scores
+        return rank_scores(self, fold, cols)
+
     def hpd_interval(self, prob=0.95, cols=None):
         """Highest-posterior-density interval of every chain on its own (coda::HPDinterval): lower, upper [C][p]."""
         from .summary import hpd_interval

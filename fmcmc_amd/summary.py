@@ -7,7 +7,8 @@ The first thing every example of the reference does with a result is `summary(an
 kept rows stay where the sweep left them: csrc/summary.hip reduces every (chain, column) series to its mean, variance and
 spectral density at zero (coda::spectrum0.ar), pools them over the chains and selects the exact order statistics the
 quantiles need; a few hundred numbers come back.  The host finish below is the type-7 interpolation and the standard errors.
-gelman_diag() is the one cross-chain diagnostic: csrc/gelman.hip reduces the window, gelman_diag_finish adds coda's upper limit.
+gelman_diag() is coda's cross-chain diagnostic: csrc/gelman.hip reduces the window, gelman_diag_finish adds coda's upper limit.
+rhat() / rank_scores() are the one diagnostic that is not coda's: the rank-normalised split R-hat (csrc/diag_rank.hpp).
 There is no CPU fallback.
 """
 import ctypes as C
@@ -1234,3 +1235,116 @@ def crosscorr(x, cols=None):
     N = int(dc.nrows)
     partial, _work, cols = enqueue_gelman(dc, 0, N, cols)
     return crosscorr_finish(partial.cpu().numpy(), int(cols.size), N)
+
+
+# ------------------------------------------------------------------------------------------------ rank-normalised split R-hat
+class RhatDiag:
+    """rhat() of a result: per column the rank-normalised split R-hat of Vehtari et al. (2021): bulk [p] (on the values), tail
+    [p] (on |x - median|), rhat [p] = max(bulk, tail) (NaN when either is: a constant column), median [p] = the fold point, the
+    mean of the two middle pooled values; nchains, niter = the chains and the rows of each the values came from, and the window
+    [start, end] of iteration labels."""
+    columns = ("Bulk", "Tail", "R-hat")
+
+    def __init__(self, bulk, tail, median, nchains, niter, varnames=None, start=None, end=None):
+        self.bulk = np.asarray(bulk, dtype=np.float64).reshape(-1)
+        self.tail = np.asarray(tail, dtype=np.float64).reshape(-1)
+        self.rhat = rhat_max(self.bulk, self.tail)
+        self.median = np.asarray(median, dtype=np.float64).reshape(-1)
+        self.nchains, self.niter = int(nchains), int(niter)
+        self.varnames = list(varnames) if varnames is not None else _par_names(range(self.bulk.size))
+        self.start, self.end = start, end
+
+    def __str__(self):
+        table = np.stack([self.bulk, self.tail, self.rhat], axis=1)
+        return "\n".join(["Rank-normalised split R-hat (%d chains of %d rows, split in two):" % (self.nchains, self.niter), "",
+                          _fmt_table(self.varnames, self.columns, table, _fmt_column_sig)]) + "\n"
+
+    def __repr__(self):
+        return "<RhatDiag nvar=%d max=%.4g>" % (self.bulk.size, np.max(self.rhat) if self.rhat.size else np.nan)
+
+
+def rhat_max(bulk, tail):
+    """max(bulk, tail), NaN where either is NaN."""
+    return np.where(np.isnan(bulk) | np.isnan(tail), np.nan, np.maximum(bulk, tail))
+
+
+def rhat_of_moments(means, variances, nh):
+    """Step 4 of the definition on the means and unbiased variances [..., m] of the scores of m split
+    chains of nh rows: B = nh var(means, ddof 1), W = mean(variances), sqrt((B / W + nh - 1) / nh), in np.longdouble, returned
+    as float64; NaN where W == 0."""
+    mu = np.asarray(means, dtype=np.longdouble)
+    s2 = np.asarray(variances, dtype=np.longdouble)
+    m, nh = mu.shape[-1], np.longdouble(nh)
+    dev = mu - mu.sum(axis=-1, keepdims=True) / m
+    B = nh * (dev * dev).sum(axis=-1) / (m - 1)
+    W = s2.sum(axis=-1) / m
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.sqrt((B / W + nh - 1) / nh)
+    return np.where(W == 0, np.nan, r).astype(np.float64)
+
+
+def rhat_finish(out, nchains, nh):
+    """The host finish of rhat(): `out` of fmcmc_rank_rhat_dev (per column the [2 C][2] means and variances of the bulk scores,
+    those of the tail scores, the non-finite count, med) -> a namespace of bulk, tail, rhat, median, non_finite, each [p]."""
+    m = 2 * int(nchains)
+    o = np.asarray(out, dtype=np.float64).reshape(-1, 4 * m + 2)
+    mom = o[:, :4 * m].reshape(-1, 2, m, 2)
+    r = rhat_of_moments(mom[..., 0], mom[..., 1], nh)           # [p][2]
+    return SimpleNamespace(bulk=r[:, 0], tail=r[:, 1], rhat=rhat_max(r[:, 0], r[:, 1]), median=o[:, 4 * m + 1].copy(),
+                           non_finite=o[:, 4 * m].copy())
+
+
+def _rank_window(dc, o, row0, N):
+    if row0 < 0 or N < 4 or row0 + N > dc.nrows:
+        raise ValueError("the window [%d, %d) needs at least four of the %d kept rows" % (row0, row0 + N, dc.nrows))
+    return _doubles(o, o.L.fmcmc_rank_work_len(o.Cn, o.p, int(N)))
+
+
+def enqueue_rank_rhat(dc, row0, N, cols):
+    """Enqueues one fmcmc_rank_rhat_dev call on the window [row0, row0 + N) of the kept rows of `dc` (current torch stream).
+    Returns the device tensors (out [p][8 C + 2], work) and the columns; nothing is synchronised."""
+    o = _open(dc, cols, "rank")
+    work = _rank_window(dc, o, row0, N)
+    out = _doubles(o, o.L.fmcmc_rank_rhat_out_len(o.Cn, o.p)).view(o.p, 8 * o.Cn + 2)
+    _windowed(o, o.L.fmcmc_rank_rhat_dev, row0, N, work.data_ptr(), out.data_ptr())
+    return out, work, o.cols
+
+
+def enqueue_rank_scores(dc, row0, N, cols, fold=False, what=0):
+    """Enqueues one fmcmc_rank_scores_dev call (current torch stream): returns the device tensors (scores [p][2 C][N / 2]:
+    z, or 2 r with what = 1; info [p][2] = non-finite count, med; work) and the columns; nothing is synchronised."""
+    o = _open(dc, cols, "rank")
+    work = _rank_window(dc, o, row0, N)
+    out = _doubles(o, o.p * 2 * o.Cn * (int(N) // 2)).view(o.p, 2 * o.Cn, int(N) // 2)
+    info = _doubles(o, 2 * o.p).view(o.p, 2)
+    _windowed(o, o.L.fmcmc_rank_scores_dev, row0, N, int(bool(fold)), int(what), work.data_ptr(), out.data_ptr(), info.data_ptr())
+    return out, info, work, o.cols
+
+
+def rank_scores(x, fold=False, cols=None):
+    """The rank-normalised scores z behind rhat(), for rank plots: a device tensor [p][2 C][N'] (split chain 2 c = the first
+    N' = N // 2 rows of chain c, 2 c + 1 its last N'), of the values or, with `fold`, of |x - median|."""
+    dc = _as_device_chains(x)
+    out, info, _work, cols = enqueue_rank_scores(dc, 0, int(dc.nrows), cols, fold)
+    _raise_non_finite(info[:, 0].cpu().numpy()[None, :], cols, "rank")
+    return out
+
+
+def rhat(x, autoburnin=False, cols=None):
+    """Rank-normalised split R-hat (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021; the `rhat` of Stan, posterior and
+    ArviZ) of a result: x a DeviceChains (read in place), an Mcmc or a McmcList (uploaded first); an McmcBatch gives a list of
+    RhatDiag, one call per dataset.  With `autoburnin` the rows are coda's window (the second half, as gelman_diag takes it).
+    The device sorts the pooled values of every column through HBM, ranks them with ties averaged, and reduces the scores of
+    every split chain to a mean and a variance (csrc/diag_rank.hpp); rhat_finish does the rest.  One chain is enough.  For an
+    odd number of rows the middle row takes part in nothing, the median included (posterior and ArviZ keep it there)."""
+    from .convergence import _window
+    from .mcmc import McmcBatch
+    if isinstance(x, McmcBatch):
+        return [rhat(x[d], autoburnin, cols) for d in range(len(x))]
+    dc = _as_device_chains(x)
+    row0, N = _window(dc.iters) if autoburnin else (0, int(dc.nrows))
+    out, _work, cols = enqueue_rank_rhat(dc, row0, N, cols)
+    Cn = int(dc._samples.shape[0])
+    fin = rhat_finish(out.cpu().numpy(), Cn, N // 2)
+    _raise_non_finite(fin.non_finite[None, :], cols, "rank")
+    return RhatDiag(fin.bulk, fin.tail, fin.median, Cn, N, _names(dc, cols), int(dc.iters[row0]), int(dc.iters[-1]))

@@ -513,6 +513,38 @@ int64_t fmcmc_autocov_out_len(int64_t nchains, int32_t p, int32_t nlags);
 int fmcmc_autocov_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N, const int32_t* cols,
                       int32_t p, const int64_t* lags, int32_t nlags, double* work, double* out, void* hip_stream);
 
+/* ---- pooled ranks of a column and the rank-normalised split R-hat (Vehtari et al. 2021), the device part ------------------------
+ * Window, samples, S, cols as for fmcmc_summary_dev; N >= 4 (FMCMC_ERR_ARG), no upper limit from an AR order.  With
+ * N' = floor(N / 2) the window of chain c is two split chains: 2 c = rows [0, N'), 2 c + 1 = rows [N - N', N) (an odd N drops
+ * its middle row, which takes part in nothing).  The M = 2 nchains N' values of a column are pooled; M < 2^32
+ * (FMCMC_ERR_UNSUPPORTED from there: the index of a value is a 32-bit word).  r = the 1-based average rank of a value among the
+ * M (ties by numerical equality: -0.0 ties with +0.0), so 2 r = 2 #less + #equal + 1 is an integer;
+ * z = fmh_qnorm((r - 0.375) / (M + 0.25)), the difference and the sum exact, one rounded division.
+ * med = (x_(M/2 - 1) + x_(M/2)) / 2 of the pooled values in ascending order (0-based; -0.0 read as +0.0).
+ *
+ * fmcmc_rank_scores_dev: out (device, p M doubles) = [p][2 nchains][N']: z (what = 0) or 2 r (what = 1, exact integers) of the
+ *   values x (fold = 0) or |x - med| (fold = 1).  info (device, 2 p doubles) = [p][2] = {count of non-finite values of the
+ *   column's window (the dropped row not counted), med}.
+ * fmcmc_rank_rhat_dev: out (device, fmcmc_rank_rhat_out_len(nchains, p) = p (8 nchains + 2) doubles), per column:
+ *   [2 nchains][2] = {mean, variance (divisor N' - 1)} of the z of every split chain for x (bulk), the same [2 nchains][2] for
+ *   |x - med| (tail), then the non-finite count and med.  R-hat follows on the host (fmcmc_amd/summary.py: rhat_finish).
+ *   The sums of a split chain have a fixed order (csrc/diag_rank.hpp: split_stats_kernel).
+ * work: device scratch of fmcmc_rank_work_len(nchains, p, N) doubles: 1280 + 3 M + 2 ceil(M / 2) + 128 T + 4 ceil(T / 2) with
+ *   T = ceil(M / 4096) tiles (two buffers of 64-bit keys and 32-bit indices, the tile x digit table of a pass, the scores); it
+ *   does not grow with p: the columns are processed one after another.  A call does not depend on what work held before.
+ * The pairs (key, index) are sorted by a stable least-significant-digit radix sort through global memory, 8 passes of 8 bits; a
+ * pass whose digit is the same in every key is skipped.  Per column and sort at most 31 kernels and one memset are enqueued
+ * (rhat: two sorts and two reductions a column).  The calls only enqueue on hip_stream, take every temporary from work, never
+ * synchronise and read `samples` only.  Every count is an integer: the same bits on every call, wherever the window sits.
+ * Argument errors are found before any device call and leave their text in fmcmc_last_error(). */
+int64_t fmcmc_rank_work_len(int64_t nchains, int32_t p, int64_t N);
+int64_t fmcmc_rank_rhat_out_len(int64_t nchains, int32_t p);
+int fmcmc_rank_scores_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N,
+                          const int32_t* cols, int32_t p, int32_t fold, int32_t what, double* work, double* out, double* info,
+                          void* hip_stream);
+int fmcmc_rank_rhat_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N,
+                        const int32_t* cols, int32_t p, double* work, double* out, void* hip_stream);
+
 /* Materialises the canonical Philox stream of a call in device memory, in the FED layout of fmcmc_run:
  * logu[C][nsteps] (entry i-1 = log accept-uniform of loop step i), z[C][nsteps][kz] (N(0,1) when student_df == 0;
  * Student-t with student_df degrees of freedom when student_df > 0 -- kernel_ram: kf for the default qfun rt(k, k),
