@@ -454,18 +454,93 @@ def rhat_host(data):
     return SimpleNamespace(bulk=bulk, tail=tail, rhat=rhat_max(bulk, tail), median=med)
 
 
+def autocov_sums(y, t0, t1):
+    """y [m][n] -> (S(t0) .. S(t1 - 1), the means [m]) of the definition: the biased autocovariances of
+    every row summed over the rows, every product and sum in np.longdouble."""
+    y = np.asarray(y, dtype=np.longdouble)
+    n = y.shape[1]
+    mu = y.sum(axis=1) / n
+    u = y - mu[:, None]
+    return np.array([(u[:, :n - t] * u[:, t:]).sum() / n for t in range(t0, t1)], dtype=np.longdouble), mu
+
+
+def ess_series_host(y):
+    """geyer_tau of the series y [m][n] on longdouble autocovariances, computed in the device's rounds of lags until the pair
+    test is decided: (the namespace of geyer_tau, S as far as it was needed)."""
+    from .summary import LagsNeeded, ess_lag_cap, geyer_tau
+    m, n = np.shape(y)
+    cap = ess_lag_cap(n)
+    S, t1 = np.zeros(0, dtype=np.longdouble), min(256, cap)
+    while True:
+        more, mu = autocov_sums(y, S.size, t1)
+        S = np.concatenate([S, more])
+        try:
+            return geyer_tau(S.astype(np.float64), m, n, mu.astype(np.float64)), S
+        except LagsNeeded:
+            t1 = min(max(512, 2 * t1), cap)
+
+
+def ess_host(data):
+    """The rank-normalised bulk and tail effective sample size of data [C][N][p] (or an McmcList / Mcmc) on the host: a
+    namespace of bulk, tail_q05, tail_q95, tail, mean, mcse_mean, tau_bulk, q05, q95, pooled_sd [p], lags [p][4] and counts
+    [p][2] (the pooled values that are <= q05, <= q95) (summary.ess is the device form; the two share geyer_tau).  The autocovariances are summed directly in np.longdouble."""
+    from types import SimpleNamespace
+    from .mcmc import Mcmc, McmcList
+    from .summary import type7_order_ranks, type7_quantiles
+    if isinstance(data, Mcmc):
+        data = McmcList([data])
+    if isinstance(data, McmcList):
+        data = data.as_array()
+    data = np.asarray(data, dtype=np.float64)
+    if data.ndim != 3 or data.shape[0] < 1 or data.shape[1] < 8:
+        raise ValueError("ess_host: data [C][N][p] with N >= 8 rows are needed")
+    bad = ~np.isfinite(data)
+    if bad.any():
+        raise ValueError("%d non-finite value(s) among the rows to rank (columns %s)"
+                         % (int(bad.sum()), [j for j in range(data.shape[2]) if bad[:, :, j].any()]))
+    sp = split_chains(data)
+    m, nh, p = sp.shape
+    M = m * nh
+    probs = [0.05, 0.95]
+    ranks = type7_order_ranks(M, probs)
+    ess, tau = np.full((p, 4), np.nan), np.full((p, 4), np.nan)
+    lags = np.zeros((p, 4), dtype=np.int64)
+    q, sd = np.empty((p, 2)), np.empty(p)
+    counts = np.zeros((p, 2), dtype=np.int64)
+    for j in range(p):
+        x = sp[:, :, j] + 0.0
+        srt = np.sort(x.ravel())
+        q[j] = type7_quantiles(srt[ranks], M, probs)
+        counts[j] = [(x <= q[j, 0]).sum(), (x <= q[j, 1]).sum()]
+        sd[j] = float(np.sqrt(x.astype(np.longdouble).var(ddof=1)))
+        series = (rank_z(x)[0], (x <= q[j, 0]).astype(np.float64), (x <= q[j, 1]).astype(np.float64), x)
+        for kind, y in enumerate(series):
+            g, _ = ess_series_host(y)
+            lags[j, kind] = g.K
+            if srt[0] != srt[-1]:                    # a constant column: NaN throughout
+                ess[j, kind], tau[j, kind] = g.ess, g.tau
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mcse = sd / np.sqrt(ess[:, 3])
+    return SimpleNamespace(bulk=ess[:, 0], tail_q05=ess[:, 1], tail_q95=ess[:, 2], tail=np.minimum(ess[:, 1], ess[:, 2]),
+                           mean=ess[:, 3], mcse_mean=mcse, tau_bulk=tau[:, 0], q05=q[:, 0].copy(), q95=q[:, 1].copy(),
+                           pooled_sd=sd, lags=lags, counts=counts)
+
+
 class convergence_rhat:
     """Auto-stop on the rank-normalised split R-hat: converged when the largest rhat = max(bulk, tail) over the free columns
     is below `threshold` (1.01 is the usual one).  With `autoburnin` the rows are coda's window (_window: the second half of
     the history, what convergence_gelman tests), else all rows.  NaN (a constant column) or fewer than 4 rows: not converged.
+    With `min_ess` (400 is the usual one) a check converges only if also the smallest of the bulk and tail effective sample
+    sizes (summary.ess) over the free columns reaches it; a NaN there, or fewer than 8 rows: not converged.
     One chain is enough.  The chains of ONE process only: pooled ranks across GPUs are not built."""
 
-    def __init__(self, freq=1000, threshold=1.01, autoburnin=True):
+    def __init__(self, freq=1000, threshold=1.01, autoburnin=True, min_ess=None):
         self.freq, self.threshold, self.autoburnin = int(freq), float(threshold), bool(autoburnin)
+        self.min_ess = None if min_ess is None else float(min_ess)
         self.flush()
 
     def flush(self):
-        self.history = []  # (end iteration, value, rhat [p])
+        self.history = []  # (end iteration, value, rhat [p]), and with min_ess: min(bulk, tail) ESS [p]
         self.msg = ""
         self.last = None
 
@@ -477,16 +552,26 @@ class convergence_rhat:
                                       "one rank the chains are sharded and pooled ranks across GPUs are not implemented.")
         self.msg = ""
         row0, N = _window(chains.iters) if self.autoburnin else (0, int(chains.nrows))
-        if N < 4:
+        if N < 4 or (self.min_ess is not None and N < 8):
             return False
         out, _work, cols = enqueue_rank_rhat(chains, row0, N, cols)
+        if self.min_ess is not None:                 # both calls are enqueued before the first copy waits for them
+            from .summary import enqueue_rank_ess, ess_finish
+            eout, _ework, _ = enqueue_rank_ess(chains, row0, N, cols)
         fin = rhat_finish(out.cpu().numpy(), int(chains._samples.shape[0]), N // 2)
         _raise_non_finite(fin.non_finite[None, :], cols, "rank")
         val = float("nan") if np.isnan(fin.rhat).any() else float(fin.rhat.max())
-        self.history.append((int(chains.iters[-1]), val, fin.rhat.copy()))
         self.last = val
         self.msg = "Rank-normalised split R-hat: %.4f." % val
-        return bool(val < self.threshold)
+        if self.min_ess is None:
+            self.history.append((int(chains.iters[-1]), val, fin.rhat.copy()))
+            return bool(val < self.threshold)
+        efin = ess_finish(eout.cpu().numpy(), int(chains._samples.shape[0]), N)
+        both = np.minimum(efin.bulk, efin.tail)
+        least = float("nan") if np.isnan(both).any() else float(both.min())
+        self.history.append((int(chains.iters[-1]), val, fin.rhat.copy(), both.copy()))
+        self.msg += " Smallest ESS: %.1f." % least
+        return bool(val < self.threshold and least >= self.min_ess)
 
     def __call__(self, x):
         import torch

@@ -17,6 +17,7 @@
 // writes `samples`.
 #include "diag_common.hpp"
 #include "diag_rank.hpp"            // the sort through HBM, the pooled ranks and the split R-hat entries (fmcmc_rank_*)
+#include "diag_ess.hpp"             // on top of it: the all-lag autocovariances and the bulk / tail ESS (fmcmc_rank_ess_*)
 
 namespace {
 

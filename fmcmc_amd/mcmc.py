@@ -292,6 +292,11 @@ class DeviceChains:
         from .summary import rhat
         return rhat(self, autoburnin, cols)
 
+    def ess(self, autoburnin=False, cols=None):
+        """Rank-normalised bulk and tail effective sample size (Vehtari et al. 2021), ess_mean and mcse_mean per column."""
+        from .summary import ess
+        return ess(self, autoburnin, cols)
+
     def rank_scores(self, fold=False, cols=None):
         """The rank-normalised scores behind rhat(), a device tensor [p][2 C][N // 2] (for rank plots)."""
         from .summary import rank_scores

@@ -8,7 +8,8 @@ kept rows stay where the sweep left them: csrc/summary.hip reduces every (chain,
 spectral density at zero (coda::spectrum0.ar), pools them over the chains and selects the exact order statistics the
 quantiles need; a few hundred numbers come back.  The host finish below is the type-7 interpolation and the standard errors.
 gelman_diag() is coda's cross-chain diagnostic: csrc/gelman.hip reduces the window, gelman_diag_finish adds coda's upper limit.
-rhat() / rank_scores() are the one diagnostic that is not coda's: the rank-normalised split R-hat (csrc/diag_rank.hpp).
+rhat() / rank_scores() / ess() are the diagnostics that are not coda's: the rank-normalised split R-hat (csrc/diag_rank.hpp) and
+the rank-normalised bulk and tail effective sample size that is read beside it (csrc/diag_ess.hpp).
 There is no CPU fallback.
 """
 import ctypes as C
@@ -1348,3 +1349,159 @@ def rhat(x, autoburnin=False, cols=None):
     fin = rhat_finish(out.cpu().numpy(), Cn, N // 2)
     _raise_non_finite(fin.non_finite[None, :], cols, "rank")
     return RhatDiag(fin.bulk, fin.tail, fin.median, Cn, N, _names(dc, cols), int(dc.iters[row0]), int(dc.iters[-1]))
+
+
+# ------------------------------------------------------------------------------------------------ rank-normalised bulk / tail ESS
+ESS_KINDS = ("bulk", "q05", "q95", "mean")         # the four series of a column, in the order of fmcmc_rank_ess_dev's `out`
+ESS_INFO = 7                                       # non-finite count, q05, q95, pooled mean, pooled sd, least, largest value
+
+
+class LagsNeeded(ValueError):
+    """geyer_tau was given fewer lags than its pair test asks for."""
+
+
+def ess_lag_cap(n):
+    """The number of lags 0 .. n - 3 the definition may use."""
+    return int(n) - 2
+
+
+def geyer_tau(S, m, n, means, variances=None):
+    """The finish of the definition: S = S(0) .. S(L - 1), the autocovariances of m split chains of n rows
+    summed over the chains, and the chains' means -> a namespace of tau, ess = m n / tau, K (the pairs kept), W, V.  Everything up
+    to the cut is float64, plain IEEE operations in the written order: geyer_scan_kernel (csrc/diag_ess.hpp) evaluates the same
+    expressions, so the device never stops before a lag this function asks for.  Raises LagsNeeded when it does need one that S
+    does not hold.  `variances` (the chains' unbiased variances, which callers have at hand) take no part: W comes from S(0)."""
+    S = np.asarray(S, dtype=np.float64).ravel()
+    m, n, L = int(m), int(n), int(S.size)
+    cap = ess_lag_cap(n)
+    if n < 4 or L < 2 or L > cap:
+        raise ValueError("geyer_tau: n = %d rows and %d lags; n >= 4 and between 2 and n - 2 lags are needed" % (n, L))
+    dm, dn = np.float64(m), np.float64(n)
+    grand = np.float64(0.0)
+    for v in np.asarray(means, dtype=np.float64).ravel():
+        grand = grand + v
+    grand = grand / dm
+    d2 = np.float64(0.0)
+    for v in np.asarray(means, dtype=np.float64).ravel():
+        d = v - grand
+        d2 = d2 + d * d
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        W = S[0] / dm * dn / (dn - 1.0)
+        V = S[0] / dm + d2 / (dm - 1.0) if m > 1 else S[0] / dm
+        rho = 1.0 - (W - S / dm) / V
+    rho[0] = 1.0
+    have = L // 2                                   # pairs with both lags in S
+    jcap = cap // 2                                 # the first j with 2 j + 1 > n - 3
+    P = rho[0:2 * have:2] + rho[1:2 * have:2]
+    upto = min(have, jcap)
+    bad = np.flatnonzero(~(P[1:upto] >= 0.0))
+    if bad.size:
+        K = int(bad[0]) + 1
+    elif have >= jcap:
+        K = jcap
+    else:
+        raise LagsNeeded("geyer_tau: the pair test is undecided after %d lags of at most %d" % (L, cap))
+    tau = -1.0 + 2.0 * np.sum(np.minimum.accumulate(P[:K]))
+    if 2 * K <= n - 3:
+        if 2 * K >= L:
+            raise LagsNeeded("geyer_tau: lag %d is needed, %d lags were given" % (2 * K, L))
+        if rho[2 * K] > 0.0:
+            tau = tau + rho[2 * K]
+    tau = max(tau, 1.0 / np.log10(dm * dn))
+    if not V > 0.0:
+        tau = np.float64(np.nan)
+    return SimpleNamespace(tau=float(tau), ess=float(dm * dn / tau), K=K, W=float(W), V=float(V))
+
+
+def ess_finish(out, nchains, N):
+    """The host finish of ess(): `out` of fmcmc_rank_ess_dev -> a namespace of bulk, tail_q05, tail_q95, tail, mean, mcse_mean,
+    tau_bulk, q05, q95, non_finite, pooled_mean, pooled_sd [p], lags, computed, device_lags [p][4] (K of geyer_tau, the lags L
+    the device computed and the K it stopped at, per series in the order of ESS_KINDS).  A column whose values are all equal
+    gives NaN for every ESS.  Raises LagsNeeded if the device stopped before a lag the finish needs."""
+    m, n = 2 * int(nchains), int(N) // 2
+    cap = ess_lag_cap(n)
+    kl = 2 * m + 2 + cap
+    o = np.asarray(out, dtype=np.float64).reshape(-1, len(ESS_KINDS) * kl + ESS_INFO)
+    p = o.shape[0]
+    info = o[:, len(ESS_KINDS) * kl:]
+    ess = np.full((p, 4), np.nan)
+    tau = np.full((p, 4), np.nan)
+    lags = np.zeros((p, 4), dtype=np.int64)
+    computed = np.zeros((p, 4), dtype=np.int64)
+    device_lags = np.zeros((p, 4), dtype=np.int64)
+    for j in range(p):
+        if info[j, 0] != 0:
+            continue                                 # non-finite values: the caller raises
+        for kind in range(4):
+            part = o[j, kind * kl:(kind + 1) * kl]
+            L = int(part[2 * m])
+            computed[j, kind], device_lags[j, kind] = L, int(part[2 * m + 1])
+            g = geyer_tau(part[2 * m + 2:2 * m + 2 + L], m, n, part[0:2 * m:2], part[1:2 * m:2])
+            lags[j, kind] = g.K
+            if info[j, 5] != info[j, 6]:
+                ess[j, kind], tau[j, kind] = g.ess, g.tau
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mcse = info[:, 4] / np.sqrt(ess[:, 3])
+    return SimpleNamespace(bulk=ess[:, 0], tail_q05=ess[:, 1], tail_q95=ess[:, 2], tail=np.minimum(ess[:, 1], ess[:, 2]),
+                           mean=ess[:, 3], mcse_mean=mcse, tau_bulk=tau[:, 0], q05=info[:, 1].copy(), q95=info[:, 2].copy(),
+                           non_finite=info[:, 0].copy(), pooled_mean=info[:, 3].copy(), pooled_sd=info[:, 4].copy(),
+                           lags=lags, computed=computed, device_lags=device_lags)
+
+
+class EssDiag:
+    """ess() of a result, per column: bulk (the ESS of the rank-normalised values), tail = min(tail_q05, tail_q95) (the ESS of
+    the indicators x <= q05, x <= q95; q05, q95 the type-7 quantiles of the pooled values), mean (the ESS of the values) and
+    mcse_mean = pooled sd / sqrt(mean); tau_bulk = m n / bulk; lags [p][4] = the pairs K kept for bulk, q05, q95, mean; NaN for
+    a constant column (and for an indicator that is constant).  nchains, niter = the chains and the rows of each the values came
+    from, and the window [start, end] of iteration labels."""
+    columns = ("Bulk", "Tail", "Mean", "MCSE")
+
+    def __init__(self, fin, nchains, niter, varnames=None, start=None, end=None):
+        for name in ("bulk", "tail", "tail_q05", "tail_q95", "mean", "mcse_mean", "tau_bulk", "q05", "q95"):
+            setattr(self, name, np.asarray(getattr(fin, name), dtype=np.float64).reshape(-1))
+        self.lags = np.asarray(fin.lags, dtype=np.int64).reshape(-1, 4)
+        self.nchains, self.niter = int(nchains), int(niter)
+        self.varnames = list(varnames) if varnames is not None else _par_names(range(self.bulk.size))
+        self.start, self.end = start, end
+
+    def __str__(self):
+        table = np.stack([self.bulk, self.tail, self.mean, self.mcse_mean], axis=1)
+        return "\n".join(["Rank-normalised effective sample size (%d chains of %d rows, split in two):"
+                          % (self.nchains, self.niter), "",
+                          _fmt_table(self.varnames, self.columns, table, _fmt_column_sig)]) + "\n"
+
+    def __repr__(self):
+        both = np.minimum(self.bulk, self.tail)
+        return "<EssDiag nvar=%d min=%.4g>" % (self.bulk.size, np.min(both) if both.size else np.nan)
+
+
+def enqueue_rank_ess(dc, row0, N, cols):
+    """Enqueues one fmcmc_rank_ess_dev call on the window [row0, row0 + N) of the kept rows of `dc` (current torch stream).
+    Returns the device tensors (out [p][4 (4 C + 2 + N // 2 - 2) + 7], work) and the columns; nothing is synchronised."""
+    o = _open(dc, cols, "rank")
+    if row0 < 0 or N < 8 or row0 + N > dc.nrows:
+        raise ValueError("the window [%d, %d) needs at least eight of the %d kept rows" % (row0, row0 + N, dc.nrows))
+    work = _doubles(o, o.L.fmcmc_rank_ess_work_len(o.Cn, o.p, int(N)))
+    out = _doubles(o, o.L.fmcmc_rank_ess_out_len(o.Cn, o.p, int(N))).view(o.p, -1)
+    _windowed(o, o.L.fmcmc_rank_ess_dev, row0, N, work.data_ptr(), out.data_ptr())
+    return out, work, o.cols
+
+
+def ess(x, autoburnin=False, cols=None):
+    """Rank-normalised bulk and tail effective sample size (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021; `ess_bulk`,
+    `ess_tail`, `ess_mean`, `mcse_mean` of posterior) of a result, to be read beside rhat(): x a DeviceChains (read in place),
+    an Mcmc or a McmcList (uploaded first); an McmcBatch gives a list of EssDiag, one call per dataset.  With `autoburnin` the
+    rows are coda's window (the second half).  The device sorts and ranks the pooled values as rhat() does, sums the
+    autocovariances of every split chain at every lag up to Geyer's cut on the fp64 matrix cores and finds the cut itself
+    (csrc/diag_ess.hpp); ess_finish does the rest.  At least 8 rows; one chain is enough."""
+    from .convergence import _window
+    from .mcmc import McmcBatch
+    if isinstance(x, McmcBatch):
+        return [ess(x[d], autoburnin, cols) for d in range(len(x))]
+    dc = _as_device_chains(x)
+    row0, N = _window(dc.iters) if autoburnin else (0, int(dc.nrows))
+    out, _work, cols = enqueue_rank_ess(dc, row0, N, cols)
+    Cn = int(dc._samples.shape[0])
+    fin = ess_finish(out.cpu().numpy(), Cn, N)
+    _raise_non_finite(fin.non_finite[None, :], cols, "rank")
+    return EssDiag(fin, Cn, N, _names(dc, cols), int(dc.iters[row0]), int(dc.iters[-1]))

@@ -545,6 +545,30 @@ int fmcmc_rank_scores_dev(const double* samples, int64_t nchains, int32_t k, int
 int fmcmc_rank_rhat_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N,
                         const int32_t* cols, int32_t p, double* work, double* out, void* hip_stream);
 
+/* ---- rank-normalised bulk and tail effective sample size (Vehtari et al. 2021), the device part -------------------------------
+ * Window, samples, S, cols, the split into m = 2 nchains chains of n = floor(N / 2) rows and M = m n < 2^32 as for
+ * fmcmc_rank_rhat_dev; N >= 8 (FMCMC_ERR_ARG below).  Per column four series y [m][n] are reduced, in this order: bulk (the
+ * scores z of fmcmc_rank_scores_dev), q05 and q95 (1.0 where x <= q, else 0.0; q = R's type-7 quantile at 0.05 / 0.95 of the M
+ * pooled values in ascending order, -0.0 read as +0.0: x_lo, or (1 - h) x_lo + h x_hi, two rounded products and a rounded sum),
+ * mean (the values).  Of every series: mean_s, var_s of every split chain (as fmcmc_rank_rhat_dev sums them),
+ * c_s(t) = (1 / n) sum_{i < n - t} (y_{s,i} - mean_s)(y_{s,i+t} - mean_s) (a rounded difference a value; the products are summed
+ * by v_mfma_f64_16x16x4 in an order that (n, t) fix: the same bits on every call, wherever the window sits and whatever other
+ * columns the call holds; |error| <= gamma(n + 8) sum |u_i| |u_{i+t}| / n), S(t) = sum_s c_s(t) in the order s = 0, 1, ...
+ * The lags come in rounds [0, 256), [256, 512), [512, 1024), ... up to the cap L_cap = n - 2 (lags 0 .. n - 3).  After every round
+ * the device runs the pair test of the definition in float64, the same expressions in the same order as
+ * fmcmc_amd/summary.py: geyer_tau; the rounds after the one that finds the cut K return at once.
+ * out (device, fmcmc_rank_ess_out_len(nchains, p, N) = p (4 (2 m + 2 + L_cap) + 7) doubles), per column: for each of the four
+ *   series {[m][2] = mean_s, var_s; L = the lags computed; K; S(0) .. S(L_cap - 1), written below L only}, then {count of
+ *   non-finite values, q05, q95, pooled mean, pooled sd (divisor M - 1), least value, largest value}.
+ * work: device scratch of fmcmc_rank_ess_work_len(nchains, p, N) doubles (= fmcmc_rank_work_len: the c_s(t) of a round live in
+ *   the sort's key buffers, which are dead by then).
+ * At most 30 + 4 (2 + 3 R) kernels and one memset a column for R rounds, R <= log2(n / 256) + 3, all on hip_stream; nothing is
+ * synchronised and `samples` is only read.  Argument errors are found before any device call. */
+int64_t fmcmc_rank_ess_work_len(int64_t nchains, int32_t p, int64_t N);
+int64_t fmcmc_rank_ess_out_len(int64_t nchains, int32_t p, int64_t N);
+int fmcmc_rank_ess_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N,
+                       const int32_t* cols, int32_t p, double* work, double* out, void* hip_stream);
+
 /* Materialises the canonical Philox stream of a call in device memory, in the FED layout of fmcmc_run:
  * logu[C][nsteps] (entry i-1 = log accept-uniform of loop step i), z[C][nsteps][kz] (N(0,1) when student_df == 0;
  * Student-t with student_df degrees of freedom when student_df > 0 -- kernel_ram: kf for the default qfun rt(k, k),
