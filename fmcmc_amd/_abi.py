@@ -36,7 +36,8 @@ EXPORTS = ["fmcmc_abi_version", "fmcmc_last_error", "fmcmc_last_kernel", "fmcmc_
            "fmcmc_mcmc_run_batch_sel_dev", "fmcmc_gelman_groups_work_len", "fmcmc_gelman_groups_dev",
            "fmcmc_summary_groups_work_len", "fmcmc_summary_groups_dev",
            "fmcmc_rank_work_len", "fmcmc_rank_rhat_out_len", "fmcmc_rank_scores_dev", "fmcmc_rank_rhat_dev",
-           "fmcmc_rank_ess_work_len", "fmcmc_rank_ess_out_len", "fmcmc_rank_ess_dev"]
+           "fmcmc_rank_ess_work_len", "fmcmc_rank_ess_out_len", "fmcmc_rank_ess_dev",
+           "fmcmc_rank_groups_max_values", "fmcmc_rank_rhat_groups_work_len", "fmcmc_rank_rhat_groups_dev"]
 BATCH_STREAM_DATA = 1          # fmcmc_mcmc_run_batch_*: flags bit, read the datasets from global memory every step
 SUMMARY_MAX_PROBS = 16
 CHAIN_ORDER_MAX_RANKS = 2 * SUMMARY_MAX_PROBS
@@ -227,6 +228,14 @@ def lib():
         L.fmcmc_rank_ess_dev.restype = C.c_int
         L.fmcmc_rank_ess_dev.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fmcmc_rank_groups_max_values.restype = C.c_int64
+        L.fmcmc_rank_groups_max_values.argtypes = []
+        L.fmcmc_rank_rhat_groups_work_len.restype = C.c_int64
+        L.fmcmc_rank_rhat_groups_work_len.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int64]
+        L.fmcmc_rank_rhat_groups_dev.restype = C.c_int
+        L.fmcmc_rank_rhat_groups_dev.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                                 C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]
         L.fmcmc_rng_stream_dev.restype = C.c_int
         L.fmcmc_rng_stream_dev.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                            C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -532,7 +532,9 @@ class convergence_rhat:
     the history, what convergence_gelman tests), else all rows.  NaN (a constant column) or fewer than 4 rows: not converged.
     With `min_ess` (400 is the usual one) a check converges only if also the smallest of the bulk and tail effective sample
     sizes (summary.ess) over the free columns reaches it; a NaN there, or fewer than 8 rows: not converged.
-    One chain is enough.  The chains of ONE process only: pooled ranks across GPUs are not built."""
+    One chain is enough.  The chains of ONE process only: pooled ranks across GPUs are not built.
+    MCMC_batch(stop_each = convergence_rhat(...)) reads the four settings and gives every dataset this verdict from one grouped
+    call per check (mcmc._batch_rhat_check, summary.rhat_batch_verdicts); the object itself is left as it was."""
 
     def __init__(self, freq=1000, threshold=1.01, autoburnin=True, min_ess=None):
         self.freq, self.threshold, self.autoburnin = int(freq), float(threshold), bool(autoburnin)

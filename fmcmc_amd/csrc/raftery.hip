@@ -18,6 +18,7 @@
 #include "diag_common.hpp"
 #include "diag_rank.hpp"            // the sort through HBM, the pooled ranks and the split R-hat entries (fmcmc_rank_*)
 #include "diag_ess.hpp"             // on top of it: the all-lag autocovariances and the bulk / tail ESS (fmcmc_rank_ess_*)
+#include "diag_rank_groups.hpp"     // the split R-hat of many small groups of chains, sorted in LDS (fmcmc_rank_rhat_groups_*)
 
 namespace {
 

@@ -643,6 +643,12 @@ class McmcBatch:
         from .summary import effective_size_batch
         return effective_size_batch(self, cols)
 
+    def rhat(self, autoburnin=False, cols=None):
+        """rhat(ans[d]) of every dataset (a list of RhatDiag with the stacked bulk, tail, rhat and median [D][p]) from one
+        grouped call on the device; on a ragged result every dataset is ranked on its own rows."""
+        from .summary import rhat_batch
+        return rhat_batch(self, autoburnin, cols)
+
 
 def batch_initial(initial, nmodels, nchains):
     """`initial` of MCMC_batch() as the [D x nchains][k] matrix of the call (dataset by dataset) and the parameter names:
@@ -699,18 +705,25 @@ def MCMC_batch(initial, batch, nsteps, nchains=1, burnin=0, thin=1, kernel=None,
     (summary.enqueue_gelman_groups), the host finishes them, and a dataset whose statistic (mpsrf; psrf at one free parameter)
     is below the threshold is frozen: the next bulks skip its chains (engine.sweep_batch(active = ...)), whose state and rows
     stay as they are.  Every dataset's rows, statistics and stop bulk are those of MCMC(fun = batch[d], conv_checker = ...)
-    run with its chains' global ids.  The checker object is only read (freq, threshold, check_invariant)."""
+    run with its chains' global ids.  The checker object is only read (freq, threshold, check_invariant).
+
+    stop_each = convergence_rhat(freq, threshold, autoburnin, min_ess): the same loop on the rank-normalised split R-hat, one
+    chain per dataset is enough.  After each bulk ONE grouped call ranks the datasets that still run
+    (summary.enqueue_rank_rhat_groups); a dataset stops when the largest max(bulk, tail) over its free columns is below the
+    threshold, and with min_ess only if also its smallest effective sample size reaches it (computed per dataset, for those
+    whose R-hat passed).  rhat_history holds the R-hat values."""
     from .models import ModelBatch
     if conv_checker is not None:
         raise ValueError("MCMC_batch runs without a -conv_checker-: the datasets would stop at different times. Pass "
                          "stop_each = convergence_gelman(...) to stop every dataset on its own, or check gelman_diag(ans) "
                          "and continue with initial = ans.")
     if stop_each is not None:
-        from .convergence import convergence_gelman
-        if not isinstance(stop_each, convergence_gelman):
-            raise TypeError("-stop_each- must be a convergence_gelman(freq, threshold, check_invariant): the single-chain "
-                            "checkers have no batched form.")
-        if nchains < 2:
+        from .convergence import convergence_gelman, convergence_rhat
+        if not isinstance(stop_each, (convergence_gelman, convergence_rhat)):
+            raise TypeError("-stop_each- must be a convergence_gelman(freq, threshold, check_invariant) or a "
+                            "convergence_rhat(freq, threshold, autoburnin, min_ess): the single-chain checkers have no "
+                            "batched form.")
+        if isinstance(stop_each, convergence_gelman) and nchains < 2:
             raise ValueError("Convergence test with the Gelman is only available when `nchains` > 1L.")
     if not isinstance(batch, ModelBatch):
         raise TypeError("-batch- must be a model_batch(...) of the engine's closed-form families.")
@@ -747,10 +760,55 @@ def MCMC_batch(initial, batch, nsteps, nchains=1, burnin=0, thin=1, kernel=None,
     return McmcBatch(dc, D, nchains, steps=np.full(D, nsteps, dtype=np.int64))
 
 
+def _batch_rhat_check(hist, D, nchains, free, active, mask, checker):
+    """One check of MCMC_batch(stop_each = convergence_rhat(...)): the datasets of `active` (bool [D]; mask: the same as a
+    device tensor, None = all) tested on the window of `hist` by ONE grouped call -> (values [D], passed [D]), per dataset
+    what convergence_rhat.check_device makes of its chains alone.  With min_ess the effective sample sizes of a dataset whose
+    R-hat passed are computed on its slice (summary.enqueue_rank_ess): they can only take a pass back."""
+    from .convergence import _window
+    from .summary import (enqueue_rank_ess, enqueue_rank_rhat, enqueue_rank_rhat_groups, ess_finish, rank_groups_fit,
+                          rhat_batch_verdicts, rhat_finish, rhat_groups_finish, _raise_non_finite)
+    row0, N = _window(hist.iters) if checker.autoburnin else (0, int(hist.nrows))
+    if N < 4 or (checker.min_ess is not None and N < 8):
+        return np.full(D, np.nan), np.zeros(D, dtype=bool)
+    run = np.nonzero(active)[0]
+    rhat = np.full((D, int(free.size)), np.nan)
+    non_finite = np.zeros((D, int(free.size)))
+
+    def slice_of(d):
+        sl = slice(d * nchains, (d + 1) * nchains)
+        return DeviceChains(hist._samples[sl], None, None, hist.iters, hist.thin, hist.names, d * nchains, nchains, nrows=hist.nrows)
+
+    if rank_groups_fit(nchains, N):
+        out, _scores, _work, cols = enqueue_rank_rhat_groups(hist, D, nchains, row0, N, free, mask)
+        fin = rhat_groups_finish(out.cpu().numpy()[run], nchains, N // 2)
+        rhat[run], non_finite[run] = fin.rhat, fin.non_finite
+    else:                                            # (a group too large for the grouped call: dataset by dataset)
+        outs = [enqueue_rank_rhat(slice_of(d), row0, N, free) for d in run]
+        cols = free if not outs else outs[0][2]
+        for d, (out, _work, _cols) in zip(run, outs):
+            fin = rhat_finish(out.cpu().numpy(), nchains, N // 2)
+            rhat[d], non_finite[d] = fin.rhat, fin.non_finite
+    for d in run:
+        try:
+            _raise_non_finite(non_finite[d][None, :], cols, "rank")
+        except ValueError as e:
+            raise ValueError("dataset %d: %s" % (d, e)) from None
+    vals, passed = rhat_batch_verdicts(rhat, checker.threshold, active)
+    if checker.min_ess is not None:
+        cand = np.nonzero(passed)[0]
+        eouts = [enqueue_rank_ess(slice_of(d), row0, N, free)[0] for d in cand]     # all enqueued before the first copy waits
+        for d, eout in zip(cand, eouts):
+            efin = ess_finish(eout.cpu().numpy(), nchains, N)
+            both = np.minimum(efin.bulk, efin.tail)
+            passed[d] = bool(not np.isnan(both).any() and both.min() >= checker.min_ess)
+    return vals, passed
+
+
 def _batch_stop_each(gm, kernel, st, D, nchains, nsteps, burnin, thin, seed, names, keep_logpost, keep_draws, checker, verbose):
     """The auto-stop loop of MCMC_batch(stop_each = ...): MCMC_with_conv_checker's loop with a verdict per dataset."""
     import torch
-    from .convergence import _window, convergence_gelman
+    from .convergence import _window, convergence_gelman, convergence_rhat
     from .summary import enqueue_gelman_groups
     dev, Cn, k = gm.device, D * nchains, int(st.theta0.shape[1])
     bulks = bulk_plan(nsteps, burnin, checker.freq)
@@ -760,7 +818,9 @@ def _batch_stop_each(gm, kernel, st, D, nchains, nsteps, burnin, thin, seed, nam
     hist = DeviceChains(nan(Cn, k, capacity), nan(Cn, capacity) if keep_logpost else None,
                         nan(Cn, k, capacity) if keep_draws else None, np.zeros(0, dtype=np.int64), thin, names, 0, Cn, nrows=0)
     hist.accept_count = torch.zeros(Cn, dtype=torch.int64, device=dev)
-    own = convergence_gelman(checker.freq, checker.threshold, checker.check_invariant)   # (the caller's object is only read)
+    by_rank = isinstance(checker, convergence_rhat)
+    # (the caller's object is only read)
+    own = None if by_rank else convergence_gelman(checker.freq, checker.threshold, checker.check_invariant)
     free = np.nonzero(~kernel.fixed)[0]
     p = int(free.size)
     active = np.ones(D, dtype=bool)
@@ -786,7 +846,10 @@ def _batch_stop_each(gm, kernel, st, D, nchains, nsteps, burnin, thin, seed, nam
         nrows[active], steps[active] = hist.nrows, steps[active] + nb
         total = int(sum(bulks[:bi + 1]))
         vals = np.full(D, np.nan)
-        row0, N = _window(hist.iters)
+        if by_rank:
+            vals, passed = _batch_rhat_check(hist, D, nchains, free, active, mask, checker)
+            converged |= passed
+        row0, N = (0, 0) if by_rank else _window(hist.iters)
         if N >= 2:
             partials, _work, _cols = enqueue_gelman_groups(hist, D, nchains, row0, N, free, mask)
             ph = partials.cpu().numpy()

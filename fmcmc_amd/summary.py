@@ -1333,15 +1333,15 @@ def rank_scores(x, fold=False, cols=None):
 
 def rhat(x, autoburnin=False, cols=None):
     """Rank-normalised split R-hat (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021; the `rhat` of Stan, posterior and
-    ArviZ) of a result: x a DeviceChains (read in place), an Mcmc or a McmcList (uploaded first); an McmcBatch gives a list of
-    RhatDiag, one call per dataset.  With `autoburnin` the rows are coda's window (the second half, as gelman_diag takes it).
+    ArviZ) of a result: x a DeviceChains (read in place), an Mcmc or a McmcList (uploaded first); an McmcBatch gives a
+    RhatDiagBatch, one RhatDiag per dataset from one grouped call (rhat_batch).  With `autoburnin` the rows are coda's window (the second half, as gelman_diag takes it).
     The device sorts the pooled values of every column through HBM, ranks them with ties averaged, and reduces the scores of
     every split chain to a mean and a variance (csrc/diag_rank.hpp); rhat_finish does the rest.  One chain is enough.  For an
     odd number of rows the middle row takes part in nothing, the median included (posterior and ArviZ keep it there)."""
     from .convergence import _window
     from .mcmc import McmcBatch
     if isinstance(x, McmcBatch):
-        return [rhat(x[d], autoburnin, cols) for d in range(len(x))]
+        return rhat_batch(x, autoburnin, cols)
     dc = _as_device_chains(x)
     row0, N = _window(dc.iters) if autoburnin else (0, int(dc.nrows))
     out, _work, cols = enqueue_rank_rhat(dc, row0, N, cols)
@@ -1349,6 +1349,114 @@ def rhat(x, autoburnin=False, cols=None):
     fin = rhat_finish(out.cpu().numpy(), Cn, N // 2)
     _raise_non_finite(fin.non_finite[None, :], cols, "rank")
     return RhatDiag(fin.bulk, fin.tail, fin.median, Cn, N, _names(dc, cols), int(dc.iters[row0]), int(dc.iters[-1]))
+
+
+# ------------------------------------------------------------------------------------------------ R-hat of an McmcBatch
+def rank_groups_fit(chains_per_group, N):
+    """Does a group of chains_per_group chains x N rows fit the grouped call: M = 2 chains_per_group (N // 2) pooled values of
+    a column at most fmcmc_rank_groups_max_values() (the keys of a group are sorted in LDS)."""
+    return 2 * int(chains_per_group) * (int(N) // 2) <= int(abi.lib().fmcmc_rank_groups_max_values())
+
+
+def enqueue_rank_rhat_groups(dc, ngroups, chains_per_group, row0, N, cols, active=None, want_scores=False):
+    """The one call site of fmcmc_rank_rhat_groups_dev (current torch stream): the window [row0, row0 + N) of the rows of `dc`,
+    whose chains are ngroups groups of chains_per_group consecutive chains (McmcBatch: a group = a dataset), each group ranked
+    on its own.  active: None or an int32 device tensor [ngroups]; the rows of the groups whose entry is 0 keep their NaN
+    prefill.  Returns the device tensors (out [ngroups][p][8 chains_per_group + 2], scores [ngroups][p][2][2 chains_per_group]
+    [N // 2] or None, work) and the columns; nothing is synchronised."""
+    import torch
+    o = _open(dc, cols, "rank")
+    ngroups, cpg = int(ngroups), int(chains_per_group)
+    if ngroups < 1 or cpg < 1 or ngroups * cpg != o.Cn:
+        raise ValueError("%d groups of %d chains are not the %d chains of the result" % (ngroups, cpg, o.Cn))
+    if row0 < 0 or N < 4 or row0 + N > dc.nrows:
+        raise ValueError("the window [%d, %d) needs at least four of the %d kept rows" % (row0, row0 + N, dc.nrows))
+    if active is not None and (not torch.is_tensor(active) or active.dtype != torch.int32 or tuple(active.shape) != (ngroups,)
+                               or not active.is_contiguous() or active.device != o.dev):
+        raise ValueError("`active` must be a contiguous int32 tensor of shape [%d] on %s" % (ngroups, o.dev))
+    nan = float("nan")
+    out = torch.full((ngroups, o.p, 8 * cpg + 2), nan, dtype=torch.float64, device=o.dev)
+    scores = torch.full((ngroups, o.p, 2, 2 * cpg, int(N) // 2), nan, dtype=torch.float64, device=o.dev) if want_scores else None
+    work = _doubles(o, max(int(o.L.fmcmc_rank_rhat_groups_work_len(ngroups, cpg, o.p, int(N))), 1))
+    with torch.cuda.device(o.dev):
+        rc = o.L.fmcmc_rank_rhat_groups_dev(o.smp.data_ptr(), ngroups, cpg, o.k, o.cap, int(row0), int(N), o.cols_d.data_ptr(), o.p,
+                                            active.data_ptr() if active is not None else None, work.data_ptr(),
+                                            scores.data_ptr() if want_scores else None, out.data_ptr(), _stream(o.dev))
+    if rc != abi.OK:
+        raise (NotImplementedError if rc == abi.ERR_UNSUPPORTED else ValueError if rc == abi.ERR_ARG else RuntimeError)(
+            abi.last_error())
+    return out, scores, work, o.cols
+
+
+class RhatDiagBatch(list):
+    """rhat() of an McmcBatch: a list of D RhatDiag, one per dataset (what rhat(ans[d]) returns), with the stacked arrays bulk,
+    tail, rhat and median, each [D][p]."""
+
+    def __init__(self, diags):
+        super().__init__(diags)
+        stack = lambda get: np.stack([get(r) for r in self]) if len(self) else np.zeros((0, 0))
+        self.bulk, self.tail = stack(lambda r: r.bulk), stack(lambda r: r.tail)
+        self.rhat, self.median = stack(lambda r: r.rhat), stack(lambda r: r.median)
+
+    def __repr__(self):
+        return "<RhatDiagBatch ndatasets=%d nvar=%d>" % (len(self), self.bulk.shape[1])
+
+
+def rhat_groups_finish(out, chains_per_group, nh):
+    """The host finish of the grouped call, pure numpy: out [D][p][8 chains_per_group + 2] as fmcmc_rank_rhat_groups_dev leaves
+    it -> a namespace of bulk, tail, rhat, median, non_finite, each [D][p]: row d is rhat_finish(out[d])."""
+    o = np.asarray(out, dtype=np.float64)
+    D, p = o.shape[0], o.shape[1]
+    fin = rhat_finish(o.reshape(D * p, -1), chains_per_group, nh)
+    return SimpleNamespace(**{f: getattr(fin, f).reshape(D, p) for f in ("bulk", "tail", "rhat", "median", "non_finite")})
+
+
+def rhat_batch(ans, autoburnin=False, cols=None):
+    """rhat(ans[d]) for every dataset d of an McmcBatch from ONE grouped call (fmcmc_rank_rhat_groups_dev) and one copy back: the
+    same moments bit for bit, the same host finish.  On a ragged result (MCMC_batch(stop_each = ...)) each dataset is ranked on
+    its own rows (its own autoburnin window) with its own iteration labels, with one call per distinct row count.  A row count
+    at which a dataset's pooled values do not fit the grouped call (rank_groups_fit) is served dataset by dataset."""
+    import torch
+    from .convergence import _window
+    from .mcmc import McmcBatch
+    if not isinstance(ans, McmcBatch):
+        raise TypeError("rhat_batch() expects an McmcBatch (the result of MCMC_batch)")
+    _single_process()
+    full, D, Cm = ans.history, ans.nmodels, ans.nchains
+    diags = [None] * D
+    for nr, sel, mask in _batch_calls(ans):
+        iters = full.iters[:nr]
+        row0, N = _window(iters) if autoburnin else (0, nr)
+        if N < 4 or not rank_groups_fit(Cm, N):           # (too few rows: the single form's text)
+            for d in sel:
+                try:
+                    diags[d] = rhat(ans[int(d)], autoburnin, cols)
+                except ValueError as e:
+                    raise ValueError("dataset %d: %s" % (d, e)) from None
+            continue
+        active = None if mask is None else torch.as_tensor(mask).to(full._samples.device)
+        out, _scores, _work, cs = enqueue_rank_rhat_groups(full, D, Cm, row0, N, cols, active)
+        fin = rhat_groups_finish(out.cpu().numpy()[sel], Cm, N // 2)
+        for i, d in enumerate(sel):
+            try:
+                _raise_non_finite(fin.non_finite[i][None, :], cs, "rank")
+            except ValueError as e:
+                raise ValueError("dataset %d: %s" % (d, e)) from None
+            diags[d] = RhatDiag(fin.bulk[i], fin.tail[i], fin.median[i], Cm, N, _names(full, cs), int(iters[row0]), int(iters[-1]))
+    return RhatDiagBatch(diags)
+
+
+def rhat_batch_verdicts(rhat, threshold, tested=None):
+    """The verdict of convergence_rhat per dataset, pure numpy: rhat [D][p] (max(bulk, tail) of every free column) -> (values
+    [D], passed [D]): the value of a dataset is the largest of its row, NaN when any of them is; it passes when the value is
+    below the threshold (a NaN never does).  Datasets outside `tested` (a bool mask [D]) have the value NaN and do not pass."""
+    r = np.asarray(rhat, dtype=np.float64)
+    r = r.reshape(r.shape[0], -1)
+    with np.errstate(invalid="ignore"):
+        vals = np.where(np.isnan(r).any(axis=1), np.nan, np.max(np.where(np.isnan(r), -np.inf, r), axis=1, initial=-np.inf))
+        if tested is not None:
+            vals = np.where(np.asarray(tested, dtype=bool), vals, np.nan)
+        return vals, vals < float(threshold)
 
 
 # ------------------------------------------------------------------------------------------------ rank-normalised bulk / tail ESS

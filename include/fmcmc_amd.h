@@ -544,6 +544,29 @@ int fmcmc_rank_scores_dev(const double* samples, int64_t nchains, int32_t k, int
                           void* hip_stream);
 int fmcmc_rank_rhat_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N,
                         const int32_t* cols, int32_t p, double* work, double* out, void* hip_stream);
+/* fmcmc_rank_rhat_dev for ngroups groups of chains_per_group consecutive chains, each group on its own (group g = chains
+ * g chains_per_group ..; one model on many datasets: a group = the chains of a dataset), in ONE kernel on the caller's stream.
+ * samples, S, row0, N, cols, active and the grouping as for fmcmc_gelman_groups_dev and fmcmc_summary_groups_dev; N >= 4.
+ * One workgroup takes one (group, column): it keeps the M = 2 chains_per_group floor(N / 2) keys of the column in LDS, sorts them
+ * there, looks every value's rank up in the sorted keys and reduces the scores of every split chain in the order of
+ * fmcmc_rank_rhat_dev (csrc/diag_rank_groups.hpp).  M <= fmcmc_rank_groups_max_values() = 8192 (FMCMC_ERR_UNSUPPORTED beyond,
+ * before any device call: fmcmc_rank_rhat_dev per group is the form for larger groups).
+ * out (device, ngroups p (8 chains_per_group + 2) doubles) = [ngroups][p][8 chains_per_group + 2]: row g is bit for bit the
+ *   `out` that fmcmc_rank_rhat_dev writes for the chains of group g alone: the moments, the non-finite count and med, a column
+ *   index outside k (all of its values count as non-finite) and -0.0 read as +0.0 included.
+ * scores (device, may be NULL): [ngroups][p][2][M], the bulk z then the tail z of every group and column, each in the element
+ *   order of fmcmc_rank_scores_dev ([2 chains_per_group][N']) and bit for bit its values (fold = 0, then fold = 1).
+ * active[ngroups] (device int32, NULL = all): for a group whose entry is 0 no element of out or scores is written.
+ * work: device scratch of fmcmc_rank_rhat_groups_work_len doubles: 1, which the call does not touch (everything lives in LDS,
+ *   with or without scores); the length is 0 for arguments the call refuses.  A call does not depend on what work held.
+ * The call only enqueues on hip_stream, never synchronises and reads `samples` only.  Every count is an integer and every sum
+ * has a fixed order: the same bits on every call, wherever a group sits in the launch and whatever other columns the call holds.
+ * Argument errors are found before any device call and leave their text in fmcmc_last_error(). */
+int64_t fmcmc_rank_groups_max_values(void);
+int64_t fmcmc_rank_rhat_groups_work_len(int64_t ngroups, int64_t chains_per_group, int32_t p, int64_t N);
+int fmcmc_rank_rhat_groups_dev(const double* samples, int64_t ngroups, int64_t chains_per_group, int32_t k, int64_t S,
+                               int64_t row0, int64_t N, const int32_t* cols, int32_t p, const int32_t* active, double* work,
+                               double* scores, double* out, void* hip_stream);
 
 /* ---- rank-normalised bulk and tail effective sample size (Vehtari et al. 2021), the device part -------------------------------
  * Window, samples, S, cols, the split into m = 2 nchains chains of n = floor(N / 2) rows and M = m n < 2^32 as for
