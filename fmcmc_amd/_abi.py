@@ -37,7 +37,8 @@ EXPORTS = ["fmcmc_abi_version", "fmcmc_last_error", "fmcmc_last_kernel", "fmcmc_
            "fmcmc_summary_groups_work_len", "fmcmc_summary_groups_dev",
            "fmcmc_rank_work_len", "fmcmc_rank_rhat_out_len", "fmcmc_rank_scores_dev", "fmcmc_rank_rhat_dev",
            "fmcmc_rank_ess_work_len", "fmcmc_rank_ess_out_len", "fmcmc_rank_ess_dev",
-           "fmcmc_rank_groups_max_values", "fmcmc_rank_rhat_groups_work_len", "fmcmc_rank_rhat_groups_dev"]
+           "fmcmc_rank_groups_max_values", "fmcmc_rank_rhat_groups_work_len", "fmcmc_rank_rhat_groups_dev",
+           "fmcmc_rank_ess_groups_work_len", "fmcmc_rank_ess_groups_out_len", "fmcmc_rank_ess_groups_dev"]
 BATCH_STREAM_DATA = 1          # fmcmc_mcmc_run_batch_*: flags bit, read the datasets from global memory every step
 SUMMARY_MAX_PROBS = 16
 CHAIN_ORDER_MAX_RANKS = 2 * SUMMARY_MAX_PROBS
@@ -236,6 +237,13 @@ def lib():
         L.fmcmc_rank_rhat_groups_dev.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
                                                  C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p]
+        L.fmcmc_rank_ess_groups_work_len.restype = C.c_int64
+        L.fmcmc_rank_ess_groups_work_len.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int64]
+        L.fmcmc_rank_ess_groups_out_len.restype = C.c_int64
+        L.fmcmc_rank_ess_groups_out_len.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int64]
+        L.fmcmc_rank_ess_groups_dev.restype = C.c_int
+        L.fmcmc_rank_ess_groups_dev.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                                C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.fmcmc_rng_stream_dev.restype = C.c_int
         L.fmcmc_rng_stream_dev.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                            C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -27,6 +27,10 @@
 // sum is not bit for bit a host sum; it is a function of (n, lag, the series) alone: no atomics, no dependence on the launch,
 // the window's place or the other columns.  |c - exact| <= gamma(n + 8) sum |u_i| |u_{i+t}| / n for ANY order of the n - t
 // products, each rounded once, u as the device centres it (one rounded subtraction a value, the mean of split_stats_kernel).
+//
+// What the grouped form (diag_ess_groups.hpp: one workgroup does all of this for a small group's column) computes with the same
+// code lives in __device__ functions that the kernels here call: ess_quantile, ess_indicator, ess_autocov_block (the body of
+// ess_autocov_kernel), geyer_rho, geyer_head, geyer_pairs, geyer_cut (the three steps of geyer_scan_kernel) and ess_next_round.
 #pragma once
 #include "diag_rank.hpp"
 
@@ -52,6 +56,11 @@ inline long long ess_kind_len(long long m, long long n) { return 2 * m + 2 + ess
 inline long long ess_col_len(long long m, long long n) { return ESS_KINDS * ess_kind_len(m, n) + ESS_INFO; }
 
 // q05, q95 (R's type 7 on the M sorted values, the arithmetic of summary.py: type7_quantiles), the least and the largest value.
+__device__ __forceinline__ double ess_quantile(const unsigned long long* key, const EssQuant& t, int i) {
+  const double xlo = value_of(key[t.lo[i]]), xhi = value_of(key[t.hi[i]]);
+  return (t.between[i] && xhi != xlo) ? (1.0 - t.h[i]) * xlo + t.h[i] * xhi : xlo;
+}
+
 __global__ void ess_quant_kernel(unsigned int* hdr, const unsigned long long* keyA, const unsigned long long* keyB,
                                  unsigned int M, EssQuant t, double* __restrict__ info) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
@@ -59,8 +68,7 @@ __global__ void ess_quant_kernel(unsigned int* hdr, const unsigned long long* ke
   double* hd = reinterpret_cast<double*>(hdr);
   info[0] = (double)hdr[H_NF];
   for (int i = 0; i < 2; i++) {
-    const double xlo = value_of(key[t.lo[i]]), xhi = value_of(key[t.hi[i]]);
-    const double q = (t.between[i] && xhi != xlo) ? (1.0 - t.h[i]) * xlo + t.h[i] * xhi : xlo;
+    const double q = ess_quantile(key, t, i);
     hd[E_Q + i] = q;
     info[1 + i] = q;
   }
@@ -69,6 +77,8 @@ __global__ void ess_quant_kernel(unsigned int* hdr, const unsigned long long* ke
 }
 
 // kind 1, 2: y = 1.0 where x <= q05 / q95, else 0.0; kind 3: y = x.  Element e = s n + r as rank_gather_kernel reads it.
+__device__ __forceinline__ double ess_indicator(int kind, double x, double q) { return kind == 3 ? x : (x <= q ? 1.0 : 0.0); }
+
 __global__ __launch_bounds__(RT_THREADS) void ess_fill_kernel(const double* __restrict__ samples, long long S, int k,
                                                               long long row0, long long N, const int* __restrict__ cols, int j,
                                                               int kind, unsigned int M, const unsigned int* __restrict__ hdr,
@@ -84,41 +94,31 @@ __global__ __launch_bounds__(RT_THREADS) void ess_fill_kernel(const double* __re
       const unsigned int s = (unsigned int)e / Nh, r = (unsigned int)e - s * Nh;
       const long long row = row0 + ((s & 1u) ? N - Nh + r : (long long)r);
       const double x = col_ok ? samples[((long long)(s >> 1) * k + col) * S + row] : fmh_nan();
-      y[e] = kind == 3 ? x : (x <= q ? 1.0 : 0.0);
+      y[e] = ess_indicator(kind, x, q);
     }
   }
 }
 
 typedef double ess_d4 __attribute__((ext_vector_type(4)));
 
-// c[s (T1 - T0) + t - T0] = c_s(t) for the lags t in [T0, T1) of split chain s = blockIdx.x / nblk, 256 lags a workgroup.
-__global__ __launch_bounds__(RT_THREADS) void ess_autocov_kernel(const unsigned int* __restrict__ hdr,
-                                                                 const double* __restrict__ y,
-                                                                 const double* __restrict__ stats, unsigned int n,
-                                                                 unsigned int T0, unsigned int T1, unsigned int nblk,
-                                                                 double* __restrict__ c) {
-  __shared__ double s_a[EA_T + 16];                  // up[tile + i]
-  // up[tile + L0 + i] at i + 2 (i / 16): the lanes of a half wavefront read i = i0 + kk + 16 b, b < 16, kk < 2, which are the 32
-  // double slots 18 b + kk + const: 18 b mod 32 runs through the even slots once, kk picks even or odd
-  __shared__ double s_b[EA_B];
-  __shared__ double s_p[RT_WAVES][256];
-  if (T0 != 0u && hdr[E_DONE]) return;
+// The 256 lags L0 - 15 .. L0 + 240 of one split chain by the RT_THREADS threads of a workgroup: x(g) = row g of the series,
+// g in [0, nn); s_a [EA_T + 16], s_b [EA_B], s_p [RT_WAVES * 256] in LDS.  Returns c(lag) = the sum / nn and the lag of the
+// calling thread.  Every barrier here is met by the whole workgroup: the trip counts depend on (nn, L0) alone.
+template <typename Row>
+__device__ __forceinline__ double ess_autocov_block(Row x, double mean, long long nn, long long L0, double* s_a, double* s_b,
+                                                    double* s_p, long long* lag_out) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kk = lane >> 4, col = lane & 15;
-  const unsigned int s = blockIdx.x / nblk, jb = blockIdx.x - s * nblk;
-  const long long L0 = (long long)T0 + (long long)EA_LAGS * jb + 15;
-  const long long nn = n, total = nn - L0 + EA_FRONT;  // rows of q: from there on B is zeros for every lag of the block
-  const double mean = stats[2 * (long long)s];
-  const double* __restrict__ x = y + (long long)s * nn;
+  const long long total = nn - L0 + EA_FRONT;        // rows of q: from there on B is zeros for every lag of the block
   ess_d4 acc = {0.0, 0.0, 0.0, 0.0};
   for (long long tile = 0; tile < total; tile += EA_T) {
     __syncthreads();
     for (int i = tid; i < EA_T + 16; i += RT_THREADS) {
       const long long g = tile + i - EA_FRONT;
-      s_a[i] = (g >= 0 && g < nn) ? x[g] - mean : 0.0;
+      s_a[i] = (g >= 0 && g < nn) ? x(g) - mean : 0.0;
     }
     for (int i = tid; i < EA_T + EA_LAGS; i += RT_THREADS) {
       const long long g = tile + L0 + i - EA_FRONT;
-      s_b[i + 2 * (i >> 4)] = (g >= 0 && g < nn) ? x[g] - mean : 0.0;
+      s_b[i + 2 * (i >> 4)] = (g >= 0 && g < nn) ? x(g) - mean : 0.0;
     }
     __syncthreads();
     const long long left = total - tile;             // rows of q that are left: the rest of the tile multiplies zeros
@@ -131,14 +131,33 @@ __global__ __launch_bounds__(RT_THREADS) void ess_autocov_kernel(const unsigned 
   }
   // D register r of lane l is row a = 4 r + l / 16, column b = l % 16: lag L0 + 16 b - a
 #pragma unroll
-  for (int r = 0; r < 4; r++) s_p[wave][lane * 4 + r] = acc[r];
+  for (int r = 0; r < 4; r++) s_p[wave * 256 + lane * 4 + r] = acc[r];
   __syncthreads();
-  {
-    const int l = tid >> 2, r = tid & 3;
-    const long long lag = L0 + 16 * (l & 15) - (4 * r + (l >> 4));
-    const double sum = ((s_p[0][tid] + s_p[1][tid]) + s_p[2][tid]) + s_p[3][tid];
-    if (lag < (long long)T1) c[(long long)s * (T1 - T0) + (lag - T0)] = sum / (double)nn;
-  }
+  const int l = tid >> 2, r = tid & 3;
+  *lag_out = L0 + 16 * (l & 15) - (4 * r + (l >> 4));
+  const double sum = ((s_p[tid] + s_p[256 + tid]) + s_p[512 + tid]) + s_p[768 + tid];
+  return sum / (double)nn;
+}
+
+// c[s (T1 - T0) + t - T0] = c_s(t) for the lags t in [T0, T1) of split chain s = blockIdx.x / nblk, 256 lags a workgroup.
+__global__ __launch_bounds__(RT_THREADS) void ess_autocov_kernel(const unsigned int* __restrict__ hdr,
+                                                                 const double* __restrict__ y,
+                                                                 const double* __restrict__ stats, unsigned int n,
+                                                                 unsigned int T0, unsigned int T1, unsigned int nblk,
+                                                                 double* __restrict__ c) {
+  __shared__ double s_a[EA_T + 16];                  // up[tile + i]
+  // up[tile + L0 + i] at i + 2 (i / 16): the lanes of a half wavefront read i = i0 + kk + 16 b, b < 16, kk < 2, which are the 32
+  // double slots 18 b + kk + const: 18 b mod 32 runs through the even slots once, kk picks even or odd
+  __shared__ double s_b[EA_B];
+  __shared__ double s_p[RT_WAVES * 256];
+  if (T0 != 0u && hdr[E_DONE]) return;
+  const unsigned int s = blockIdx.x / nblk, jb = blockIdx.x - s * nblk;
+  const long long L0 = (long long)T0 + (long long)EA_LAGS * jb + 15;
+  const long long nn = n;
+  const double* __restrict__ x = y + (long long)s * nn;
+  long long lag;
+  const double cv = ess_autocov_block([&](long long g) { return x[g]; }, stats[2 * (long long)s], nn, L0, s_a, s_b, s_p, &lag);
+  if (lag < (long long)T1) c[(long long)s * (T1 - T0) + (lag - T0)] = cv;
 }
 
 // rho_t of the definition, plain IEEE operations in the written order (the unit is built without contraction): the same
@@ -159,8 +178,43 @@ __global__ __launch_bounds__(RT_THREADS) void ess_sum_kernel(const unsigned int*
   S[t] = sum;
 }
 
-// One workgroup after every round: the pair test on the new lags.  kout = {L, K} of the series, S = its S(t); info: the
-// column's {.., pooled mean, pooled sd, ..} when the series is the values themselves, else null.
+// The head of the pair test, by one thread: W, V of the series from the split chains' means and S(0); info: the column's
+// {.., pooled mean, pooled sd, ..} when the series is the values themselves, else null.
+__device__ __forceinline__ void geyer_head(const double* stats, unsigned int m, unsigned int n, double S0, double* W, double* V,
+                                           double* info) {
+  const double dm = (double)m, dn = (double)n;
+  double grand = 0.0, d2 = 0.0;
+  for (unsigned int s = 0; s < m; s++) grand += stats[2 * (long long)s];
+  grand = grand / dm;
+  for (unsigned int s = 0; s < m; s++) {
+    const double d = stats[2 * (long long)s] - grand;
+    d2 += d * d;
+  }
+  *W = S0 / dm * dn / (dn - 1.0);
+  *V = S0 / dm + d2 / (dm - 1.0);
+  if (info) {
+    info[3] = grand;
+    info[4] = sqrt((dn * S0 + dn * d2) / (dm * dn - 1.0));
+  }
+}
+
+// The pairs whose lags lie in [T0, T1), a thread a pair: the first failing one into *first (LDS, an integer minimum).
+__device__ __forceinline__ void geyer_pairs(const double* S, unsigned int T0, unsigned int T1, double dm, double W, double V,
+                                            unsigned int* first) {
+  const unsigned int j0 = T0 < 2u ? 1u : T0 / 2u;
+  for (unsigned int j = j0 + threadIdx.x; 2u * j + 1u < T1; j += RT_THREADS) {
+    const double P = geyer_rho(S, 2u * j, dm, W, V) + geyer_rho(S, 2u * j + 1u, dm, W, V);
+    if (!(P >= 0.0)) atomicMin(first, j);
+  }
+}
+
+// The cut after the round that ended at T1, 0: not known yet.  The cap: the first j with 2 j + 1 > n - 3.
+__device__ __forceinline__ unsigned int geyer_cut(unsigned int first, unsigned int T1, unsigned int cap) {
+  return first != 0xffffffffu ? first : (T1 == cap ? cap / 2u : 0u);
+}
+
+// One workgroup after every round: the pair test on the new lags.  kout = {L, K} of the series, S = its S(t); info as
+// geyer_head takes it.
 __global__ __launch_bounds__(RT_THREADS) void geyer_scan_kernel(unsigned int* hdr, const double* __restrict__ stats,
                                                                 unsigned int m, unsigned int n, unsigned int T0,
                                                                 unsigned int T1, unsigned int cap, double* kout,
@@ -170,37 +224,22 @@ __global__ __launch_bounds__(RT_THREADS) void geyer_scan_kernel(unsigned int* hd
   const int tid = threadIdx.x;
   double* hd = reinterpret_cast<double*>(hdr);
   if (tid == 0) s_k = 0xffffffffu;
-  const double dm = (double)m, dn = (double)n;
-  if (T0 == 0u && tid == 0) {
-    double grand = 0.0, d2 = 0.0;
-    for (unsigned int s = 0; s < m; s++) grand += stats[2 * (long long)s];
-    grand = grand / dm;
-    for (unsigned int s = 0; s < m; s++) {
-      const double d = stats[2 * (long long)s] - grand;
-      d2 += d * d;
-    }
-    const double S0 = S[0];
-    hd[E_W] = S0 / dm * dn / (dn - 1.0);
-    hd[E_V] = S0 / dm + d2 / (dm - 1.0);
-    if (info) {
-      info[3] = grand;
-      info[4] = sqrt((dn * S0 + dn * d2) / (dm * dn - 1.0));
-    }
-  }
+  if (T0 == 0u && tid == 0) geyer_head(stats, m, n, S[0], hd + E_W, hd + E_V, info);
   __syncthreads();
-  const double W = hd[E_W], V = hd[E_V];
-  const unsigned int j0 = T0 < 2u ? 1u : T0 / 2u;
-  for (unsigned int j = j0 + tid; 2u * j + 1u < T1; j += RT_THREADS) {
-    const double P = geyer_rho(S, 2u * j, dm, W, V) + geyer_rho(S, 2u * j + 1u, dm, W, V);
-    if (!(P >= 0.0)) atomicMin(&s_k, j);
-  }
+  geyer_pairs(S, T0, T1, (double)m, hd[E_W], hd[E_V], &s_k);
   __syncthreads();
   if (tid == 0) {
-    const unsigned int K = s_k != 0xffffffffu ? s_k : (T1 == cap ? cap / 2u : 0u);   // the cap: the first j with 2 j + 1 > n - 3
+    const unsigned int K = geyer_cut(s_k, T1, cap);
     hdr[E_DONE] = K ? 1u : 0u;
     kout[0] = (double)T1;
     if (K) kout[1] = (double)K;
   }
+}
+
+// The rounds of lags after [T0, T1): [0, 256), [256, 512), [512, 1024), ... up to the cap.
+__host__ __device__ inline unsigned int ess_next_round(unsigned int T1, unsigned int cap) {
+  unsigned int nx = T1 < 512u ? 512u : (T1 > cap / 2u ? cap : 2u * T1);
+  return nx > cap ? cap : nx;
 }
 
 // stats, then every round, of the series in b.z; o: the series' part of `out`.
@@ -217,8 +256,7 @@ inline int ess_series(const char* who, unsigned int m, unsigned int n, const Ran
                        o + 2 * (long long)m + 2, info);
     if (T1 == cap) break;
     T0 = T1;
-    T1 = T1 < 512u ? 512u : (T1 > cap / 2u ? cap : 2u * T1);
-    if (T1 > cap) T1 = cap;
+    T1 = ess_next_round(T1, cap);
   }
   return rank_launched(who);
 }

@@ -19,6 +19,7 @@
 #include "diag_rank.hpp"            // the sort through HBM, the pooled ranks and the split R-hat entries (fmcmc_rank_*)
 #include "diag_ess.hpp"             // on top of it: the all-lag autocovariances and the bulk / tail ESS (fmcmc_rank_ess_*)
 #include "diag_rank_groups.hpp"     // the split R-hat of many small groups of chains, sorted in LDS (fmcmc_rank_rhat_groups_*)
+#include "diag_ess_groups.hpp"      // the bulk / tail ESS of many small groups, one workgroup a (group, column) (fmcmc_rank_ess_groups_*)
 
 namespace {
 

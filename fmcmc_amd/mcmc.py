@@ -649,6 +649,12 @@ class McmcBatch:
         from .summary import rhat_batch
         return rhat_batch(self, autoburnin, cols)
 
+    def ess(self, autoburnin=False, cols=None):
+        """ess(ans[d]) of every dataset (a list of EssDiag with the stacked bulk, tail, mean, mcse_mean, ... [D][p] and lags
+        [D][p][4]) from one grouped call on the device; on a ragged result every dataset has its own rows."""
+        from .summary import ess_batch
+        return ess_batch(self, autoburnin, cols)
+
 
 def batch_initial(initial, nmodels, nchains):
     """`initial` of MCMC_batch() as the [D x nchains][k] matrix of the call (dataset by dataset) and the parameter names:
@@ -710,8 +716,8 @@ def MCMC_batch(initial, batch, nsteps, nchains=1, burnin=0, thin=1, kernel=None,
     stop_each = convergence_rhat(freq, threshold, autoburnin, min_ess): the same loop on the rank-normalised split R-hat, one
     chain per dataset is enough.  After each bulk ONE grouped call ranks the datasets that still run
     (summary.enqueue_rank_rhat_groups); a dataset stops when the largest max(bulk, tail) over its free columns is below the
-    threshold, and with min_ess only if also its smallest effective sample size reaches it (computed per dataset, for those
-    whose R-hat passed).  rhat_history holds the R-hat values."""
+    threshold, and with min_ess only if also its smallest effective sample size reaches it (one more grouped call, masked
+    to those whose R-hat passed: summary.enqueue_rank_ess_groups).  rhat_history holds the R-hat values."""
     from .models import ModelBatch
     if conv_checker is not None:
         raise ValueError("MCMC_batch runs without a -conv_checker-: the datasets would stop at different times. Pass "
@@ -763,11 +769,13 @@ def MCMC_batch(initial, batch, nsteps, nchains=1, burnin=0, thin=1, kernel=None,
 def _batch_rhat_check(hist, D, nchains, free, active, mask, checker):
     """One check of MCMC_batch(stop_each = convergence_rhat(...)): the datasets of `active` (bool [D]; mask: the same as a
     device tensor, None = all) tested on the window of `hist` by ONE grouped call -> (values [D], passed [D]), per dataset
-    what convergence_rhat.check_device makes of its chains alone.  With min_ess the effective sample sizes of a dataset whose
-    R-hat passed are computed on its slice (summary.enqueue_rank_ess): they can only take a pass back."""
+    what convergence_rhat.check_device makes of its chains alone.  With min_ess the effective sample sizes of the datasets whose
+    R-hat passed come from ONE more grouped call masked to them (summary.enqueue_rank_ess_groups; dataset by dataset on its slice,
+    summary.enqueue_rank_ess, where a group does not fit): they can only take a pass back."""
     from .convergence import _window
-    from .summary import (enqueue_rank_ess, enqueue_rank_rhat, enqueue_rank_rhat_groups, ess_finish, rank_groups_fit,
-                          rhat_batch_verdicts, rhat_finish, rhat_groups_finish, _raise_non_finite)
+    from .summary import (enqueue_rank_ess, enqueue_rank_ess_groups, enqueue_rank_rhat, enqueue_rank_rhat_groups, ess_finish,
+                          ess_groups_finish, rank_groups_fit, rhat_batch_verdicts, rhat_finish, rhat_groups_finish,
+                          _raise_non_finite)
     row0, N = _window(hist.iters) if checker.autoburnin else (0, int(hist.nrows))
     if N < 4 or (checker.min_ess is not None and N < 8):
         return np.full(D, np.nan), np.zeros(D, dtype=bool)
@@ -797,11 +805,20 @@ def _batch_rhat_check(hist, D, nchains, free, active, mask, checker):
     vals, passed = rhat_batch_verdicts(rhat, checker.threshold, active)
     if checker.min_ess is not None:
         cand = np.nonzero(passed)[0]
-        eouts = [enqueue_rank_ess(slice_of(d), row0, N, free)[0] for d in cand]     # all enqueued before the first copy waits
-        for d, eout in zip(cand, eouts):
-            efin = ess_finish(eout.cpu().numpy(), nchains, N)
+        if cand.size and rank_groups_fit(nchains, N):    # one grouped call, masked to the datasets whose R-hat passed
+            import torch
+            emask = np.zeros(D, dtype=np.int32)
+            emask[cand] = 1
+            eout, _work, _cols = enqueue_rank_ess_groups(hist, D, nchains, row0, N, free, torch.as_tensor(emask).to(hist._samples.device))
+            efin = ess_groups_finish(eout[torch.as_tensor(cand).to(eout.device)].cpu().numpy(), nchains, N)
             both = np.minimum(efin.bulk, efin.tail)
-            passed[d] = bool(not np.isnan(both).any() and both.min() >= checker.min_ess)
+            passed[cand] = ~np.isnan(both).any(axis=1) & (both.min(axis=1) >= checker.min_ess)
+        else:
+            eouts = [enqueue_rank_ess(slice_of(d), row0, N, free)[0] for d in cand]     # all enqueued before the first copy waits
+            for d, eout in zip(cand, eouts):
+                efin = ess_finish(eout.cpu().numpy(), nchains, N)
+                both = np.minimum(efin.bulk, efin.tail)
+                passed[d] = bool(not np.isnan(both).any() and both.min() >= checker.min_ess)
     return vals, passed
 
 

@@ -1598,14 +1598,14 @@ def enqueue_rank_ess(dc, row0, N, cols):
 def ess(x, autoburnin=False, cols=None):
     """Rank-normalised bulk and tail effective sample size (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021; `ess_bulk`,
     `ess_tail`, `ess_mean`, `mcse_mean` of posterior) of a result, to be read beside rhat(): x a DeviceChains (read in place),
-    an Mcmc or a McmcList (uploaded first); an McmcBatch gives a list of EssDiag, one call per dataset.  With `autoburnin` the
+    an Mcmc or a McmcList (uploaded first); an McmcBatch gives an EssDiagBatch, one EssDiag per dataset from one grouped call (ess_batch).  With `autoburnin` the
     rows are coda's window (the second half).  The device sorts and ranks the pooled values as rhat() does, sums the
     autocovariances of every split chain at every lag up to Geyer's cut on the fp64 matrix cores and finds the cut itself
     (csrc/diag_ess.hpp); ess_finish does the rest.  At least 8 rows; one chain is enough."""
     from .convergence import _window
     from .mcmc import McmcBatch
     if isinstance(x, McmcBatch):
-        return [ess(x[d], autoburnin, cols) for d in range(len(x))]
+        return ess_batch(x, autoburnin, cols)
     dc = _as_device_chains(x)
     row0, N = _window(dc.iters) if autoburnin else (0, int(dc.nrows))
     out, _work, cols = enqueue_rank_ess(dc, row0, N, cols)
@@ -1613,3 +1613,213 @@ def ess(x, autoburnin=False, cols=None):
     fin = ess_finish(out.cpu().numpy(), Cn, N)
     _raise_non_finite(fin.non_finite[None, :], cols, "rank")
     return EssDiag(fin, Cn, N, _names(dc, cols), int(dc.iters[row0]), int(dc.iters[-1]))
+
+
+# ------------------------------------------------------------------------------------------------ ESS of an McmcBatch
+ESS_FIELDS = ("bulk", "tail_q05", "tail_q95", "tail", "mean", "mcse_mean", "tau_bulk", "q05", "q95", "non_finite", "pooled_mean",
+              "pooled_sd", "lags", "computed", "device_lags")
+
+
+def enqueue_rank_ess_groups(dc, ngroups, chains_per_group, row0, N, cols, active=None):
+    """The one call site of fmcmc_rank_ess_groups_dev (current torch stream): the window [row0, row0 + N) of the rows of `dc`,
+    whose chains are ngroups groups of chains_per_group consecutive chains (McmcBatch: a group = a dataset), each group on its
+    own.  active: None or an int32 device tensor [ngroups]; the rows of the groups whose entry is 0 keep their NaN prefill.
+    Returns the device tensors (out [ngroups][p][4 (4 chains_per_group + 2 + N // 2 - 2) + 7], NaN where the call wrote nothing;
+    work) and the columns; nothing is synchronised."""
+    import torch
+    o = _open(dc, cols, "rank")
+    ngroups, cpg = int(ngroups), int(chains_per_group)
+    if ngroups < 1 or cpg < 1 or ngroups * cpg != o.Cn:
+        raise ValueError("%d groups of %d chains are not the %d chains of the result" % (ngroups, cpg, o.Cn))
+    if row0 < 0 or N < 8 or row0 + N > dc.nrows:
+        raise ValueError("the window [%d, %d) needs at least eight of the %d kept rows" % (row0, row0 + N, dc.nrows))
+    if active is not None and (not torch.is_tensor(active) or active.dtype != torch.int32 or tuple(active.shape) != (ngroups,)
+                               or not active.is_contiguous() or active.device != o.dev):
+        raise ValueError("`active` must be a contiguous int32 tensor of shape [%d] on %s" % (ngroups, o.dev))
+    m, n = 2 * cpg, int(N) // 2
+    out = torch.full((ngroups, o.p, len(ESS_KINDS) * (2 * m + 2 + ess_lag_cap(n)) + ESS_INFO), float("nan"), dtype=torch.float64,
+                     device=o.dev)
+    work = _doubles(o, o.L.fmcmc_rank_ess_groups_work_len(ngroups, cpg, o.p, int(N)))
+    with torch.cuda.device(o.dev):
+        rc = o.L.fmcmc_rank_ess_groups_dev(o.smp.data_ptr(), ngroups, cpg, o.k, o.cap, int(row0), int(N), o.cols_d.data_ptr(), o.p,
+                                           active.data_ptr() if active is not None else None, work.data_ptr(), out.data_ptr(),
+                                           _stream(o.dev))
+    if rc != abi.OK:
+        raise (NotImplementedError if rc == abi.ERR_UNSUPPORTED else ValueError if rc == abi.ERR_ARG else RuntimeError)(
+            abi.last_error())
+    return out, work, o.cols
+
+
+def geyer_tau_rows(S, L, m, n, means):
+    """geyer_tau on many series at once: S [R][>= max(L)] (row r holds S(0) .. S(L[r] - 1); what lies beyond is not looked at),
+    L [R] the lags each row holds, means [R][m] -> (tau, ess, K, W, V), each [R], row r bit for bit what
+    geyer_tau(S[r, :L[r]], m, n, means[r]) returns.  Every step is the same IEEE operation element by element; the one reduction
+    whose order depends on its length, np.sum over the K kept pairs, is taken over the rows that share K (a row of a C-contiguous
+    [rows][K] array is summed as the 1-D array it is).  The first row, in order, at which geyer_tau would raise, raises the same."""
+    S = np.asarray(S, dtype=np.float64)
+    L = np.asarray(L, dtype=np.int64).reshape(-1)
+    mu = np.asarray(means, dtype=np.float64).reshape(L.size, -1)
+    R, m, n = int(L.size), int(m), int(n)
+    cap = ess_lag_cap(n)
+    if R == 0:
+        return (np.zeros(0),) * 2 + (np.zeros(0, dtype=np.int64),) + (np.zeros(0),) * 2
+    wrong = np.flatnonzero((L < 2) | (L > cap)) if n >= 4 else np.arange(R)
+    # (errors: row -> text; the earliest row raises at the end of the steps that can find one)
+    errors = {int(r): ValueError("geyer_tau: n = %d rows and %d lags; n >= 4 and between 2 and n - 2 lags are needed" % (n, L[r]))
+              for r in wrong[:1]}
+    ok = np.ones(R, dtype=bool)
+    ok[wrong] = False
+    Lmax = int(L[ok].max()) if ok.any() else 2
+    Lmax += Lmax % 2                                 # (pairs: an even width, padded below)
+    Sx = np.full((R, Lmax + 1), np.nan)
+    w = min(Lmax + 1, S.shape[1])
+    Sx[:, :w] = S[:, :w]
+    Sx[np.arange(Lmax + 1)[None, :] >= L[:, None]] = np.nan
+    dm, dn = np.float64(m), np.float64(n)
+    grand = np.zeros(R)
+    for s in range(m):
+        grand = grand + mu[:, s]
+    grand = grand / dm
+    d2 = np.zeros(R)
+    for s in range(m):
+        d = mu[:, s] - grand
+        d2 = d2 + d * d
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        W = Sx[:, 0] / dm * dn / (dn - 1.0)
+        V = Sx[:, 0] / dm + d2 / (dm - 1.0) if m > 1 else Sx[:, 0] / dm
+        rho = 1.0 - (W[:, None] - Sx / dm) / V[:, None]
+    rho[:, 0] = 1.0
+    have = L // 2
+    jcap = cap // 2
+    P = rho[:, 0:Lmax:2] + rho[:, 1:Lmax:2]          # [R][Lmax / 2]; row r is geyer_tau's P below have[r]
+    upto = np.minimum(have, jcap)
+    jj = np.arange(P.shape[1])[None, :]
+    fails = ~(P >= 0.0) & (jj >= 1) & (jj < upto[:, None])
+    cut = fails.any(axis=1)
+    K = np.where(cut, fails.argmax(axis=1), jcap).astype(np.int64)
+    for r in np.flatnonzero(ok & ~cut & (have < jcap))[:1]:
+        errors.setdefault(int(r), LagsNeeded("geyer_tau: the pair test is undecided after %d lags of at most %d" % (L[r], cap)))
+    ok &= cut | (have >= jcap)
+    for r in np.flatnonzero(ok & (2 * K <= n - 3) & (2 * K >= L))[:1]:
+        errors.setdefault(int(r), LagsNeeded("geyer_tau: lag %d is needed, %d lags were given" % (2 * K[r], L[r])))
+    if errors:
+        raise errors[min(errors)]
+    tau = np.empty(R)
+    run = np.minimum.accumulate(P, axis=1)
+    for Kv in np.unique(K):
+        rows = np.flatnonzero(K == Kv)
+        tau[rows] = -1.0 + 2.0 * np.sum(np.ascontiguousarray(run[rows, :Kv]), axis=1)
+    end = 2 * K <= n - 3
+    at = np.where(end, 2 * K, 0)
+    last = rho[np.arange(R), np.minimum(at, Lmax)]
+    with np.errstate(invalid="ignore"):
+        tau = np.where(end & (last > 0.0), tau + last, tau)
+        floor = 1.0 / np.log10(dm * dn)
+        tau = np.where(floor > tau, floor, tau)
+        tau = np.where(V > 0.0, tau, np.nan)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return tau, dm * dn / tau, K, W, V
+
+
+def ess_rows_finish(out, nchains, N):
+    """ess_finish on any number of columns at once through geyer_tau_rows: out [R][.] (the layout of fmcmc_rank_ess_dev's
+    column) -> the namespace of ess_finish, each field with R rows and bit for bit what ess_finish(out[r]) gives.  A row that is
+    still its NaN prefill (a masked group) gives NaN in every float field and 0 in the integer ones."""
+    m, n = 2 * int(nchains), int(N) // 2
+    cap = ess_lag_cap(n)
+    kl = 2 * m + 2 + cap
+    o = np.asarray(out, dtype=np.float64).reshape(-1, len(ESS_KINDS) * kl + ESS_INFO)
+    R = o.shape[0]
+    info = o[:, len(ESS_KINDS) * kl:]
+    ess = np.full((R, 4), np.nan)
+    tau = np.full((R, 4), np.nan)
+    lags = np.zeros((R, 4), dtype=np.int64)
+    computed = np.zeros((R, 4), dtype=np.int64)
+    device_lags = np.zeros((R, 4), dtype=np.int64)
+    live = np.flatnonzero(info[:, 0] == 0)           # (non-finite values: the caller raises; NaN: the row was not written)
+    if live.size:
+        # series (row, kind), row after row; only the lags below the largest L are gathered from the wide rows
+        ol = o if live.size == R else o[live]
+        piece = lambda a, b: np.stack([ol[:, kind * kl + a:kind * kl + b] for kind in range(4)], axis=1).reshape(live.size * 4, b - a)
+        head = piece(0, 2 * m + 2)
+        L = head[:, 2 * m].astype(np.int64)
+        Lmax = int(min(max(int(L.max()), 2), cap))
+        g_tau, g_ess, g_K, _W, _V = geyer_tau_rows(piece(2 * m + 2, min(2 * m + 2 + Lmax + 2, kl)), L, m, n, head[:, 0:2 * m:2])
+        computed[live], device_lags[live] = L.reshape(-1, 4), head[:, 2 * m + 1].astype(np.int64).reshape(-1, 4)
+        lags[live] = g_K.reshape(-1, 4)
+        varies = (info[live, 5] != info[live, 6])[:, None]
+        ess[live] = np.where(varies, g_ess.reshape(-1, 4), np.nan)
+        tau[live] = np.where(varies, g_tau.reshape(-1, 4), np.nan)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mcse = info[:, 4] / np.sqrt(ess[:, 3])
+    return SimpleNamespace(bulk=ess[:, 0], tail_q05=ess[:, 1], tail_q95=ess[:, 2], tail=np.minimum(ess[:, 1], ess[:, 2]),
+                           mean=ess[:, 3], mcse_mean=mcse, tau_bulk=tau[:, 0], q05=info[:, 1].copy(), q95=info[:, 2].copy(),
+                           non_finite=info[:, 0].copy(), pooled_mean=info[:, 3].copy(), pooled_sd=info[:, 4].copy(),
+                           lags=lags, computed=computed, device_lags=device_lags)
+
+
+def ess_groups_finish(out, chains_per_group, N):
+    """The host finish of the grouped call, pure numpy: out [D][p][.] as fmcmc_rank_ess_groups_dev leaves it -> the fields of
+    ess_finish with a leading [D] axis: row d is ess_finish(out[d]), to the bit (ess_rows_finish)."""
+    o = np.asarray(out, dtype=np.float64)
+    D, p = o.shape[0], o.shape[1]
+    fin = ess_rows_finish(o.reshape(D * p, -1), chains_per_group, N)
+    return SimpleNamespace(**{f: getattr(fin, f).reshape((D, p) + getattr(fin, f).shape[1:]) for f in ESS_FIELDS})
+
+
+def _ess_row(fin, i):
+    """dataset i of ess_groups_finish as the namespace ess_finish gives"""
+    return SimpleNamespace(**{f: getattr(fin, f)[i] for f in ESS_FIELDS})
+
+
+class EssDiagBatch(list):
+    """ess() of an McmcBatch: a list of D EssDiag, one per dataset (what ess(ans[d]) returns), with the stacked arrays bulk,
+    tail, tail_q05, tail_q95, mean, mcse_mean, tau_bulk, q05, q95, each [D][p], and lags [D][p][4]."""
+    fields = ("bulk", "tail", "tail_q05", "tail_q95", "mean", "mcse_mean", "tau_bulk", "q05", "q95", "lags")
+
+    def __init__(self, diags):
+        super().__init__(diags)
+        for name in self.fields:
+            setattr(self, name, np.stack([getattr(r, name) for r in self]) if len(self) else np.zeros((0, 0)))
+
+    def __repr__(self):
+        return "<EssDiagBatch ndatasets=%d nvar=%d>" % (len(self), self.bulk.shape[1])
+
+
+def ess_batch(ans, autoburnin=False, cols=None):
+    """ess(ans[d]) for every dataset d of an McmcBatch from ONE grouped call (fmcmc_rank_ess_groups_dev) and one copy back: the
+    same `out` bit for bit, and a host finish that equals ess_finish to the bit.  On a ragged result (MCMC_batch(stop_each = ...))
+    each dataset has its own rows (its own autoburnin window) and iteration labels, with one call per distinct row count.  A row
+    count with fewer than 8 rows, or at which a dataset's pooled values do not fit the grouped call (rank_groups_fit), is served
+    dataset by dataset."""
+    import torch
+    from .convergence import _window
+    from .mcmc import McmcBatch
+    if not isinstance(ans, McmcBatch):
+        raise TypeError("ess_batch() expects an McmcBatch (the result of MCMC_batch)")
+    _single_process()
+    full, D, Cm = ans.history, ans.nmodels, ans.nchains
+    diags = [None] * D
+    for nr, sel, mask in _batch_calls(ans):
+        iters = full.iters[:nr]
+        row0, N = _window(iters) if autoburnin else (0, nr)
+        if N < 8 or not rank_groups_fit(Cm, N):           # (too few rows: the single form's text)
+            for d in sel:
+                try:
+                    diags[d] = ess(ans[int(d)], autoburnin, cols)
+                except ValueError as e:
+                    raise ValueError("dataset %d: %s" % (d, e)) from None
+            continue
+        active = None if mask is None else torch.as_tensor(mask).to(full._samples.device)
+        out, _work, cs = enqueue_rank_ess_groups(full, D, Cm, row0, N, cols, active)
+        if mask is not None:                              # (only the rows of the datasets of this call are copied back)
+            out = out[torch.as_tensor(sel).to(out.device)]
+        fin = ess_groups_finish(out.cpu().numpy(), Cm, N)
+        names, start, end = _names(full, cs), int(iters[row0]), int(iters[-1])
+        for i, d in enumerate(sel):
+            try:
+                _raise_non_finite(fin.non_finite[i][None, :], cs, "rank")
+            except ValueError as e:
+                raise ValueError("dataset %d: %s" % (d, e)) from None
+            diags[d] = EssDiag(_ess_row(fin, i), Cm, N, names, start, end)
+    return EssDiagBatch(diags)

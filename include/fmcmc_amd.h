@@ -591,6 +591,28 @@ int64_t fmcmc_rank_ess_work_len(int64_t nchains, int32_t p, int64_t N);
 int64_t fmcmc_rank_ess_out_len(int64_t nchains, int32_t p, int64_t N);
 int fmcmc_rank_ess_dev(const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N,
                        const int32_t* cols, int32_t p, double* work, double* out, void* hip_stream);
+/* fmcmc_rank_ess_dev for ngroups groups of chains_per_group consecutive chains, each group on its own, in ONE kernel on the
+ * caller's stream, whatever the number of groups.  samples, S, row0, N, cols, active and the grouping as for
+ * fmcmc_rank_rhat_groups_dev; N >= 8 (FMCMC_ERR_ARG below).  One workgroup takes one (group, column): it sorts the
+ * M = 2 chains_per_group floor(N / 2) keys of the column in LDS, writes the column's info and scores, and takes the four series
+ * through the stats, the rounds of lags on the fp64 matrix core and the pair test, leaving its loop when the cut is known
+ * (csrc/diag_ess_groups.hpp).  M <= fmcmc_rank_groups_max_values() = 8192 (FMCMC_ERR_UNSUPPORTED beyond, before any device call:
+ * fmcmc_rank_ess_dev per group is the form for larger groups); more than 2^31 - 1 (group, column) pairs are FMCMC_ERR_UNSUPPORTED.
+ * out (device, fmcmc_rank_ess_groups_out_len = ngroups p (4 (2 m + 2 + L_cap) + 7) doubles, m = 2 chains_per_group,
+ *   L_cap = floor(N / 2) - 2) = [ngroups][p][.]: row (g, j) has the layout of a column of fmcmc_rank_ess_dev's `out`, and every
+ *   element that call writes for the chains of group g alone has the same bits here: the stats, L, K, S(t) below L, the info; NaN
+ *   keys, -0.0 read as +0.0, a column index outside k and a constant column included.  S(t) at and above L is not written.
+ * active[ngroups] (device int32, NULL = all): for a group whose entry is 0 no element of out or work is written.
+ * work: device scratch of fmcmc_rank_ess_groups_work_len = ngroups p M doubles: the scores of every (group, column), written and
+ *   read by its own workgroup.  A call does not depend on what work held.  Both lengths are 0 for arguments the call refuses.
+ * The call only enqueues on hip_stream, never synchronises and reads `samples` only.  Every count is an integer and every sum
+ * has a fixed order: the same bits on every call, wherever a group sits in the launch and whatever other columns the call holds.
+ * Argument errors are found before any device call and leave their text in fmcmc_last_error(). */
+int64_t fmcmc_rank_ess_groups_work_len(int64_t ngroups, int64_t chains_per_group, int32_t p, int64_t N);
+int64_t fmcmc_rank_ess_groups_out_len(int64_t ngroups, int64_t chains_per_group, int32_t p, int64_t N);
+int fmcmc_rank_ess_groups_dev(const double* samples, int64_t ngroups, int64_t chains_per_group, int32_t k, int64_t S,
+                              int64_t row0, int64_t N, const int32_t* cols, int32_t p, const int32_t* active, double* work,
+                              double* out, void* hip_stream);
 
 /* Materialises the canonical Philox stream of a call in device memory, in the FED layout of fmcmc_run:
  * logu[C][nsteps] (entry i-1 = log accept-uniform of loop step i), z[C][nsteps][kz] (N(0,1) when student_df == 0;
