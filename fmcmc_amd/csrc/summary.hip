@@ -822,3 +822,5 @@ int fmcmc_autocov_dev(const double* samples, int64_t nchains, int32_t k, int64_t
 }
 
 }  // extern "C"
+
+#include "diag_waic.hpp"   // fmcmc_waic_dev, fmcmc_waic_groups_dev (block_sum and diag_common.hpp come from above)

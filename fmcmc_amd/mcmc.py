@@ -297,6 +297,11 @@ class DeviceChains:
         from .summary import ess
         return ess(self, autoburnin, cols)
 
+    def waic(self, model, autoburnin=False):
+        """WAIC of the rows under `model` (a gaussian_linreg / logistic / iid_normal object): a WaicResult."""
+        from .summary import waic
+        return waic(self, model, autoburnin)
+
     def rank_scores(self, fold=False, cols=None):
         """The rank-normalised scores behind rhat(), a device tensor [p][2 C][N // 2] (for rank plots)."""
         from .summary import rank_scores
@@ -654,6 +659,12 @@ class McmcBatch:
         [D][p][4]) from one grouped call on the device; on a ragged result every dataset has its own rows."""
         from .summary import ess_batch
         return ess_batch(self, autoburnin, cols)
+
+    def waic(self, models, autoburnin=False):
+        """waic(ans[d], models[d]) of every dataset (a list of WaicResult with the stacked elpd_waic, p_waic, ... [D] and
+        pointwise [D][n][4]) from one grouped call on the device; on a ragged result every dataset has its own rows."""
+        from .summary import waic_batch
+        return waic_batch(self, models, autoburnin)
 
 
 def batch_initial(initial, nmodels, nchains):

@@ -1823,3 +1823,253 @@ def ess_batch(ans, autoburnin=False, cols=None):
                 raise ValueError("dataset %d: %s" % (d, e)) from None
             diags[d] = EssDiag(_ess_row(fin, i), Cm, N, names, start, end)
     return EssDiagBatch(diags)
+
+
+# ------------------------------------------------------------------------------------------------ WAIC
+WAIC_POINT = ("elpd_waic", "p_waic", "lppd", "mean")           # the columns of `pointwise`, in the order of fmcmc_waic_dev's `point`
+WAIC_TOTAL = ("elpd_waic", "p_waic", "lppd", "waic", "se_elpd", "se_p", "se_lppd", "n_high", "bad_draws", "bad_points")
+WAIC_HIGH = 0.4                                                 # loo's warning threshold for p_waic_i
+WAIC_PART_ROWS, WAIC_MAX_PARTS, WAIC_MAX_PARTS_SMALL, WAIC_SMALL_N = 512, 64, 256, 1024   # csrc/diag_waic.hpp
+
+
+def waic_parts(nchains, N, n):
+    """(units a part, parts) of fmcmc_waic_dev's split of the draws (include/fmcmc_amd.h): a unit is one tile of 16 rows of one
+    chain, chain after chain."""
+    U = int(nchains) * ((int(N) + 15) // 16)
+    cap = WAIC_MAX_PARTS_SMALL if n <= WAIC_SMALL_N else WAIC_MAX_PARTS
+    upp = max(WAIC_PART_ROWS // 16, -(-U // cap))
+    return upp, -(-U // upp)
+
+
+def _waic_model(model):
+    from .models import LogPosterior
+    if not isinstance(model, LogPosterior):
+        raise TypeError("waic() needs one of the closed-form families (gaussian_linreg, logistic, iid_normal): a %s returns the "
+                        "summed log-posterior and has no pointwise form." % type(model).__name__)
+    return model
+
+
+def waic_loglik(model, draws, dtype=np.float64):
+    """The pointwise log-likelihood l [S][n] of the definition for draws [S][k], in `dtype`: the likelihood
+    alone, without the prior_div term and without the guard."""
+    model = _waic_model(model)
+    th = np.asarray(draws, dtype=dtype)
+    if th.ndim != 2 or th.shape[1] != model.k:
+        raise ValueError("draws must be [S][%d] for this family; got shape %s" % (model.k, th.shape))
+    ic, p, n = int(model.intercept), model.p, int(model.y.shape[0])
+    y = model.y.astype(dtype)
+    eta = np.zeros((th.shape[0], n), dtype=dtype)
+    if model.family == abi.FAM_IID_NORMAL:
+        eta = eta + th[:, :1]
+        sigma = th[:, 1]
+    else:
+        if ic:
+            eta = eta + th[:, :1]
+        if p:
+            eta = eta + th[:, ic:ic + p] @ model.X.astype(dtype).T
+        sigma = th[:, ic + p] if model.family == abi.FAM_GAUSSIAN_LINREG else None
+    with np.errstate(all="ignore"):
+        if model.family == abi.FAM_LOGISTIC:
+            t = np.where(y[None, :] != 0, eta, -eta)
+            return np.where(t < 0, t, dtype(0)) - np.log1p(np.exp(-np.abs(t)))
+        r = y[None, :] - eta
+        half_log_2pi = np.log(np.sqrt(dtype(2) * np.arccos(dtype(-1))))
+        return -(np.log(sigma) + half_log_2pi)[:, None] - dtype(0.5) * r * r / (sigma * sigma)[:, None]
+
+
+def _se(v):
+    """sqrt(n var(v)) with divisor n - 1 (NaN for n = 1), in the dtype of v"""
+    n = v.shape[-1]
+    with np.errstate(all="ignore"):
+        d = v - v.mean(axis=-1, keepdims=True)
+        return np.sqrt(n * ((d * d).sum(axis=-1) / v.dtype.type(n - 1)))
+
+
+def waic_host(model, draws, dtype=np.float64):
+    """The plain numpy restatement of waic() on draws [S][k]: the CPU reference and the documentation of the definition.  With
+    dtype = np.longdouble it is the truth the tests hold the device to.  Returns a namespace with pointwise [n][4] = {elpd_i,
+    p_waic_i, lppd_i, mean_i} and the totals elpd_waic, p_waic, lppd, waic, se_elpd, se_p, se_lppd, n_high, bad_draws,
+    bad_points, all in `dtype`."""
+    model = _waic_model(model)
+    th = np.asarray(draws, dtype=dtype)
+    l = np.ascontiguousarray(waic_loglik(model, th, dtype).T)        # [n][S]: the sums run along a row (numpy: pairwise)
+    S = l.shape[1]
+    if S < 2:
+        raise ValueError("WAIC needs at least 2 draws; got %d" % S)
+    with np.errstate(all="ignore"):
+        top = l.max(axis=1)
+        lppd = top + np.log(np.exp(l - top[:, None]).sum(axis=1) / dtype(S))
+        mean = l[:, 0] + (l - l[:, :1]).sum(axis=1) / dtype(S)       # (shifted by the first draw: equal draws give it back)
+        p_waic = ((l - mean[:, None]) ** 2).sum(axis=1) / dtype(S - 1)
+    point = np.stack([lppd - p_waic, p_waic, lppd, mean], axis=1)
+    bad = ~np.isfinite(th).all(axis=1)
+    if model.family != abi.FAM_LOGISTIC:
+        bad |= ~(th[:, -1] > 0)
+    tot = point[:, :3].sum(axis=0)
+    se = [_se(point[:, q]) for q in range(3)]
+    return SimpleNamespace(pointwise=point, elpd_waic=tot[0], p_waic=tot[1], lppd=tot[2], waic=dtype(-2) * tot[0], se_elpd=se[0],
+                           se_p=se[1], se_lppd=se[2], n_high=int((point[:, 1] > WAIC_HIGH).sum()), bad_draws=int(bad.sum()),
+                           bad_points=int((~np.isfinite(point).all(axis=1)).sum()))
+
+
+class WaicResult:
+    """waic() of a result: elpd_waic, p_waic, lppd, waic = -2 elpd_waic, their standard errors se_elpd, se_p, se_lppd (se_waic =
+    2 se_elpd), n_high = the observations with p_waic_i > 0.4, and pointwise [n][4] = {elpd_i, p_waic_i, lppd_i, mean_i} (numpy;
+    pointwise_dev is the device tensor it was copied from, or None).  ndraws = the S draws, nobs = the n observations."""
+
+    def __init__(self, pointwise, total, ndraws, pointwise_dev=None):
+        self.pointwise = np.asarray(pointwise, dtype=np.float64).reshape(-1, 4)
+        self.pointwise_dev = pointwise_dev
+        total = np.asarray(total, dtype=np.float64).reshape(10)
+        for name, v in zip(WAIC_TOTAL[:7], total):
+            setattr(self, name, float(v))
+        self.se_waic = 2.0 * self.se_elpd
+        self.n_high, self.bad_draws, self.bad_points = (int(v) if np.isfinite(v) else -1 for v in total[7:])
+        self.ndraws, self.nobs = int(ndraws), int(self.pointwise.shape[0])
+
+    def __str__(self):
+        rows = [("elpd_waic", self.elpd_waic, self.se_elpd), ("p_waic", self.p_waic, self.se_p), ("waic", self.waic, self.se_waic)]
+        out = ["", "Computed from %d by %d log-likelihood matrix" % (self.ndraws, self.nobs), "",
+               "%-9s %9s %6s" % ("", "Estimate", "SE")]
+        out += ["%-9s %9.1f %6.1f" % r for r in rows]
+        if self.n_high > 0:
+            out += ["", "%d (%.1f%%) p_waic estimates greater than 0.4. We recommend trying loo instead."
+                    % (self.n_high, 100.0 * self.n_high / self.nobs)]
+        return "\n".join(out) + "\n"
+
+    def __repr__(self):
+        return "<WaicResult elpd_waic=%.4g p_waic=%.4g n=%d>" % (self.elpd_waic, self.p_waic, self.nobs)
+
+
+class WaicBatch(list):
+    """waic() of an McmcBatch: a list of D WaicResult, one per dataset (what waic(ans[d], models[d]) returns), with the stacked
+    arrays elpd_waic, p_waic, lppd, waic, se_elpd, se_p, se_lppd, se_waic, n_high, each [D], and pointwise [D][n][4]."""
+    fields = WAIC_TOTAL[:8] + ("se_waic",)
+
+    def __init__(self, results):
+        super().__init__(results)
+        for name in self.fields:
+            setattr(self, name, np.array([getattr(r, name) for r in self]))
+        self.pointwise = np.stack([r.pointwise for r in self]) if len(self) else np.zeros((0, 0, 4))
+
+    def __repr__(self):
+        return "<WaicBatch ndatasets=%d n=%d>" % (len(self), self.pointwise.shape[1])
+
+
+def _waic_rc(rc):
+    if rc != abi.OK:
+        raise (NotImplementedError if rc == abi.ERR_UNSUPPORTED else ValueError if rc == abi.ERR_ARG else RuntimeError)(
+            abi.last_error())
+
+
+def enqueue_waic_groups(dc, dm, ngroups, chains_per_group, row0, N, active=None):
+    """The one call site of fmcmc_waic_groups_dev (current torch stream): the window [row0, row0 + N) of the rows of `dc`, whose
+    chains are ngroups groups of chains_per_group consecutive chains, group g on dataset g of the device model dm (a DeviceModel
+    for one group, a DeviceModelBatch beyond).  active: None or an int32 device tensor [ngroups]; the rows of the groups whose
+    entry is 0 keep their NaN prefill.  Returns the device tensors (point [ngroups][n][4], total [ngroups][10], work); nothing
+    is synchronised."""
+    import torch
+    o = _open(dc, None, "score")
+    ngroups, cpg = int(ngroups), int(chains_per_group)
+    if ngroups < 1 or cpg < 1 or ngroups * cpg != o.Cn:
+        raise ValueError("%d groups of %d chains are not the %d chains of the result" % (ngroups, cpg, o.Cn))
+    if getattr(dm, "nmodels", 1) != ngroups:
+        raise ValueError("%d datasets for %d groups of chains" % (getattr(dm, "nmodels", 1), ngroups))
+    if dm.device != o.dev and (dm.device.index is not None or dm.device.type != o.dev.type):
+        raise ValueError("the model's data are on %s, the draws on %s" % (dm.device, o.dev))
+    if o.k != dm.k:
+        raise ValueError("the result has k = %d parameters, the model's family has %d" % (o.k, dm.k))
+    if row0 < 0 or N < 1 or row0 + N > dc.nrows:
+        raise ValueError("the window [%d, %d) is outside the %d kept rows" % (row0, row0 + N, dc.nrows))
+    if cpg * int(N) < 2:
+        raise ValueError("WAIC needs at least 2 draws; got %d" % (cpg * int(N)))
+    if active is not None and (not torch.is_tensor(active) or active.dtype != torch.int32 or tuple(active.shape) != (ngroups,)
+                               or not active.is_contiguous() or active.device != o.dev):
+        raise ValueError("`active` must be a contiguous int32 tensor of shape [%d] on %s" % (ngroups, o.dev))
+    cm = dm.c()
+    point = torch.full((ngroups, dm.n, 4), float("nan"), dtype=torch.float64, device=o.dev)
+    total = torch.full((ngroups, 10), float("nan"), dtype=torch.float64, device=o.dev)
+    work = _doubles(o, o.L.fmcmc_waic_work_len(C.byref(cm), ngroups, cpg, int(N)))
+    with torch.cuda.device(o.dev):
+        rc = o.L.fmcmc_waic_groups_dev(C.byref(cm), getattr(dm, "x_stride", 0), getattr(dm, "y_stride", 0), o.smp.data_ptr(),
+                                       ngroups, cpg, o.k, o.cap, int(row0), int(N),
+                                       active.data_ptr() if active is not None else None, work.data_ptr(), point.data_ptr(),
+                                       total.data_ptr(), _stream(o.dev))
+    _waic_rc(rc)
+    return point, total, work
+
+
+def _raise_bad_draws(total_row):
+    if total_row[8] != 0:
+        raise ValueError("%d draw(s) with a parameter that is not finite or a sigma that is not > 0 among the rows to score"
+                         % int(total_row[8]))
+
+
+def waic(x, model, autoburnin=False):
+    """The widely applicable information criterion (Watanabe 2010; Gelman, Hwang and Vehtari 2014; loo::waic) of a result under
+    the model it was sampled from, or another one of the same parameters: x a DeviceChains (read in place), an Mcmc or a McmcList
+    (uploaded first), model a gaussian_linreg / logistic / iid_normal object; an McmcBatch with a model_batch gives a WaicBatch,
+    one WaicResult per dataset from one grouped call (waic_batch).  With `autoburnin` the rows are coda's window (the second
+    half).  The S x n matrix of pointwise log-likelihoods is never formed: the device turns tiles of it into four running
+    numbers per observation (csrc/diag_waic.hpp)."""
+    from .convergence import _window
+    from .mcmc import McmcBatch
+    if isinstance(x, McmcBatch):
+        return waic_batch(x, model, autoburnin)
+    model = _waic_model(model)
+    dc = _as_device_chains(x)
+    row0, N = _window(dc.iters) if autoburnin else (0, int(dc.nrows))
+    Cn = int(dc._samples.shape[0])
+    point, total, _work = enqueue_waic_groups(dc, model.device_model(dc._samples.device), 1, Cn, row0, N)
+    th = total[0].cpu().numpy()
+    _raise_bad_draws(th)
+    return WaicResult(point[0].cpu().numpy(), th, Cn * N, point[0])
+
+
+def waic_batch(ans, models, autoburnin=False):
+    """waic(ans[d], models[d]) for every dataset d of an McmcBatch from ONE grouped call (fmcmc_waic_groups_dev): the same bits.
+    On a ragged result (MCMC_batch(stop_each = ...)) each dataset has its own rows, with one call per distinct row count."""
+    import torch
+    from .convergence import _window
+    from .mcmc import McmcBatch
+    from .models import ModelBatch
+    if not isinstance(ans, McmcBatch):
+        raise TypeError("waic_batch() expects an McmcBatch (the result of MCMC_batch)")
+    if not isinstance(models, ModelBatch):
+        raise TypeError("waic_batch() needs the model_batch the datasets came from (a %s has no pointwise form per dataset)"
+                        % type(models).__name__)
+    _single_process()
+    full, D, Cm = ans.history, ans.nmodels, ans.nchains
+    if models.nmodels != D:
+        raise ValueError("%d datasets in the model batch, %d in the result" % (models.nmodels, D))
+    dm = models.device_model(full._samples.device)
+    out = [None] * D
+    for nr, sel, mask in _batch_calls(ans):
+        row0, N = _window(full.iters[:nr]) if autoburnin else (0, nr)
+        active = None if mask is None else torch.as_tensor(mask).to(full._samples.device)
+        point, total, _work = enqueue_waic_groups(full, dm, D, Cm, row0, N, active)
+        ph, th = point.cpu().numpy(), total.cpu().numpy()
+        for d in sel:
+            try:
+                _raise_bad_draws(th[d])
+            except ValueError as e:
+                raise ValueError("dataset %d: %s" % (d, e)) from None
+            out[d] = WaicResult(ph[d], th[d], Cm * N, point[d])
+    return WaicBatch(out)
+
+
+def waic_compare(a, b):
+    """The difference of two models on the same observations, as loo::loo_compare forms it: elpd_diff = sum_i (elpd_i of a - elpd_i
+    of b) and se_diff = sqrt(n var of the pointwise differences) (divisor n - 1), from the pointwise arrays in longdouble.  Two
+    WaicResult (or waic_host results) give two numbers, two WaicBatch arrays [D]."""
+    pa, pb = (np.asarray(r.pointwise, dtype=np.longdouble) for r in (a, b))
+    if pa.ndim != pb.ndim or pa.shape[:-2] != pb.shape[:-2]:
+        raise ValueError("waic_compare: a single result against a batch, or batches of different sizes")
+    if pa.shape[-2] != pb.shape[-2]:
+        raise ValueError("waic_compare: the models score different numbers of observations (%d and %d)"
+                         % (pa.shape[-2], pb.shape[-2]))
+    d = pa[..., 0] - pb[..., 0]
+    diff, se = d.sum(axis=-1), _se(d)
+    if d.ndim == 1:
+        return SimpleNamespace(elpd_diff=float(diff), se_diff=float(se))
+    return SimpleNamespace(elpd_diff=diff.astype(np.float64), se_diff=se.astype(np.float64))

@@ -614,6 +614,46 @@ int fmcmc_rank_ess_groups_dev(const double* samples, int64_t ngroups, int64_t ch
                               int64_t row0, int64_t N, const int32_t* cols, int32_t p, const int32_t* active, double* work,
                               double* out, void* hip_stream);
 
+/* ---- WAIC and the pointwise log-likelihood of the closed-form families (Watanabe 2010; loo::waic), the device part -------------
+ * The draws are the rows [row0, row0 + N) of the nchains chains of `samples` ([C][k][S], S the row stride): S' = nchains N >= 2
+ * draws, every one of the k parameters read; k must be the family's parameter count (FMCMC_ERR_ARG), at most FMCMC_MAX_K.  `m`
+ * holds DEVICE pointers X [p][n], y [n] as for fmcmc_mcmc_run_dev.  Per draw s and observation i, l = log p(y_i | theta_s), the
+ * likelihood alone (no prior_div term, no guard):
+ *   gaussian_linreg  l = -(log sigma + ln sqrt(2 pi)) - 0.5 (y_i - b0 - x_i b)^2 / sigma^2; iid_normal the same with mu = theta_0,
+ *                    sigma = theta_1; evaluated as fma(-w, r r, a), a = -(fmh_log(sigma) + ln sqrt(2 pi)), w = 0.5 / (sigma sigma),
+ *                    r = the fma chain of v_mfma_f64_16x16x4 over (b0, b, 1) . (1, x_i, -y_i);
+ *   logistic         t = eta where y_i != 0, else -eta; l = min(t, 0) - fmh_log1p(fmh_exp(-|t|)).
+ * point (device, [n][4]) = {elpd_i, p_waic_i, lppd_i, mean_i}: lppd_i = log((1 / S') sum_s exp l), mean_i = (1 / S') sum_s l,
+ *   p_waic_i = sum_s (l - mean_i)^2 / (S' - 1), elpd_i = lppd_i - p_waic_i.
+ * total (device, [10]) = {elpd_waic, p_waic, lppd (the sums of the pointwise values), waic = -2 elpd_waic, se_elpd, se_p, se_lppd
+ *   (sqrt(n var) of the pointwise values, divisor n - 1: NaN for n = 1), n_high (observations with p_waic_i > 0.4), bad_draws
+ *   (draws with a parameter that is not finite or a sigma that is not > 0), bad_points (observations whose four numbers are not
+ *   all finite)}; the counts are exact doubles.  A call with bad_draws > 0 is not repaired: its numbers mean nothing.
+ * The split of the draws into parts, whose partial results {max, sum of exp, mean, M2} are merged in part order (log-sum-exp, and
+ * Chan's update): with T = ceil(N / 16) tiles of 16 rows a chain, unit u = c T + t is tile t of chain c, U = nchains T; a part is
+ * upp = max(fmcmc_waic_part_rows() / 16, ceil(U / cap)) consecutive units, cap = 256 while n <= 1024 and 64 beyond;
+ * fmcmc_waic_parts(nchains, N, n) = ceil(U / upp) <= cap.  The rule reads (nchains, N, n) only -- never the device, the
+ * occupancy or the number of groups --, no float atomics are used and every merge has a fixed order: the same bits on every
+ * call and every gfx950, wherever the window sits in `samples`.
+ * work: device scratch of fmcmc_waic_work_len(m, ngroups, chains_per_group, N) doubles (0 for arguments the call refuses): for
+ *   the Gaussian families a and w of every draw (16 bytes a draw), the bad-draw count of every 256 draws, and the partials
+ *   [ngroups][parts][n][4] (20 MB at n = 10^4 with 64 parts).  A call does not depend on what work held.
+ * fmcmc_waic_groups_dev: ngroups groups of chains_per_group consecutive chains, group g on dataset g (X, y of m0 are those of
+ *   dataset 0, dataset g lies x_stride / y_stride doubles behind: fmcmc_mcmc_run_batch_dev's layout); point [ngroups][n][4] and
+ *   total [ngroups][10]; row g is bit for bit what fmcmc_waic_dev writes for the chains of group g and dataset g alone (it is the
+ *   same code: fmcmc_waic_dev is the call with one group).  active[ngroups] (device int32, NULL = all) as for
+ *   fmcmc_gelman_groups_dev: for a group whose entry is 0 no element of point, total or work is written.  At most 65535 groups.
+ * Four kernels are enqueued on hip_stream; nothing is synchronised, `samples` and the model are only read, nothing is written
+ * past the documented lengths.  Argument errors are found before any device call and leave their text in fmcmc_last_error(). */
+int64_t fmcmc_waic_part_rows(void);
+int64_t fmcmc_waic_parts(int64_t nchains, int64_t N, int64_t n);
+int64_t fmcmc_waic_work_len(const fmcmc_model* m, int64_t ngroups, int64_t chains_per_group, int64_t N);
+int fmcmc_waic_dev(const fmcmc_model* m, const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N,
+                   double* work, double* point /* [n][4] */, double* total /* [10] */, void* hip_stream);
+int fmcmc_waic_groups_dev(const fmcmc_model* m0, int64_t x_stride, int64_t y_stride, const double* samples, int64_t ngroups,
+                          int64_t chains_per_group, int32_t k, int64_t S, int64_t row0, int64_t N, const int32_t* active,
+                          double* work, double* point /* [G][n][4] */, double* total /* [G][10] */, void* hip_stream);
+
 /* Materialises the canonical Philox stream of a call in device memory, in the FED layout of fmcmc_run:
  * logu[C][nsteps] (entry i-1 = log accept-uniform of loop step i), z[C][nsteps][kz] (N(0,1) when student_df == 0;
  * Student-t with student_df degrees of freedom when student_df > 0 -- kernel_ram: kf for the default qfun rt(k, k),
