@@ -39,7 +39,10 @@ EXPORTS = ["fmcmc_abi_version", "fmcmc_last_error", "fmcmc_last_kernel", "fmcmc_
            "fmcmc_rank_ess_work_len", "fmcmc_rank_ess_out_len", "fmcmc_rank_ess_dev",
            "fmcmc_rank_groups_max_values", "fmcmc_rank_rhat_groups_work_len", "fmcmc_rank_rhat_groups_dev",
            "fmcmc_rank_ess_groups_work_len", "fmcmc_rank_ess_groups_out_len", "fmcmc_rank_ess_groups_dev",
-           "fmcmc_waic_part_rows", "fmcmc_waic_parts", "fmcmc_waic_work_len", "fmcmc_waic_dev", "fmcmc_waic_groups_dev"]
+           "fmcmc_waic_part_rows", "fmcmc_waic_parts", "fmcmc_waic_work_len", "fmcmc_waic_dev", "fmcmc_waic_groups_dev",
+           "fmcmc_loo_tail_len", "fmcmc_loo_plan", "fmcmc_loo_work_len", "fmcmc_loo_state_offset", "fmcmc_loo_dev",
+           "fmcmc_loo_groups_dev"]
+LOO_PLAN_LEN = 16              # FMCMC_LOO_PLAN_LEN
 BATCH_STREAM_DATA = 1          # fmcmc_mcmc_run_batch_*: flags bit, read the datasets from global memory every step
 SUMMARY_MAX_PROBS = 16
 CHAIN_ORDER_MAX_RANKS = 2 * SUMMARY_MAX_PROBS
@@ -258,6 +261,21 @@ def lib():
         L.fmcmc_waic_groups_dev.argtypes = [C.POINTER(Model), C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
                                             C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]
+        L.fmcmc_loo_tail_len.restype = C.c_int64
+        L.fmcmc_loo_tail_len.argtypes = [C.c_int64]
+        L.fmcmc_loo_plan.restype = C.c_int
+        L.fmcmc_loo_plan.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
+        L.fmcmc_loo_work_len.restype = C.c_int64
+        L.fmcmc_loo_work_len.argtypes = [C.POINTER(Model), C.c_int64, C.c_int64, C.c_int64]
+        L.fmcmc_loo_state_offset.restype = C.c_int64
+        L.fmcmc_loo_state_offset.argtypes = [C.POINTER(Model), C.c_int64, C.c_int64, C.c_int64]
+        L.fmcmc_loo_dev.restype = C.c_int
+        L.fmcmc_loo_dev.argtypes = [C.POINTER(Model), C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fmcmc_loo_groups_dev.restype = C.c_int
+        L.fmcmc_loo_groups_dev.argtypes = [C.POINTER(Model), C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
+                                           C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
         L.fmcmc_rng_stream_dev.restype = C.c_int
         L.fmcmc_rng_stream_dev.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                            C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -302,6 +302,11 @@ class DeviceChains:
         from .summary import waic
         return waic(self, model, autoburnin)
 
+    def loo(self, model, autoburnin=False):
+        """PSIS-LOO of the rows under `model`, with the Pareto k of every observation: a LooResult."""
+        from .summary import loo
+        return loo(self, model, autoburnin)
+
     def rank_scores(self, fold=False, cols=None):
         """The rank-normalised scores behind rhat(), a device tensor [p][2 C][N // 2] (for rank plots)."""
         from .summary import rank_scores
@@ -665,6 +670,12 @@ class McmcBatch:
         pointwise [D][n][4]) from one grouped call on the device; on a ragged result every dataset has its own rows."""
         from .summary import waic_batch
         return waic_batch(self, models, autoburnin)
+
+    def loo(self, models, autoburnin=False):
+        """loo(ans[d], models[d]) of every dataset (a list of LooResult with the stacked elpd_loo, p_loo, pareto_k, ...) from one
+        grouped device call; on a ragged batch one call per distinct row count: a LooBatch."""
+        from .summary import loo_batch
+        return loo_batch(self, models, autoburnin)
 
 
 def batch_initial(initial, nmodels, nchains):

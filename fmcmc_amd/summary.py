@@ -2073,3 +2073,285 @@ def waic_compare(a, b):
     if d.ndim == 1:
         return SimpleNamespace(elpd_diff=float(diff), se_diff=float(se))
     return SimpleNamespace(elpd_diff=diff.astype(np.float64), se_diff=se.astype(np.float64))
+
+
+# ------------------------------------------------------------------------------------------------ PSIS-LOO
+LOO_POINT = ("elpd_loo", "p_loo", "lppd", "pareto_k", "n_eff", "cutoff")     # the columns of `pointwise` (fmcmc_loo_dev's `point`)
+LOO_TOTAL = ("elpd_loo", "p_loo", "lppd", "looic", "se_elpd", "se_p", "se_lppd", "n_k_bad", "n_k_very_bad", "max_k", "bad_draws",
+             "bad_points")
+LOO_MAX_TAIL = 16384                                             # csrc/diag_loo.hpp: LOO_MAX_M
+
+
+def loo_tail_len(S):
+    """M = ceil(min(0.2 S, 3 sqrt(S))) in integers: loo's tail length with r_eff = 1 (fmcmc_loo_tail_len)."""
+    import math
+    S = int(S)
+    b = math.isqrt(9 * S)
+    return min((S + 4) // 5, b + (b * b < 9 * S))
+
+
+def loo_k_threshold(S):
+    """tau(S) = min(1 - 1 / log10 S, 0.7): the Pareto k above which the estimate of an observation is not to be trusted"""
+    import math
+    return min(1.0 - 1.0 / math.log10(S), 0.7)
+
+
+def loo_plan(nchains, N, n):
+    """fmcmc_loo_plan as a namespace: M, ustride / sub_units / sub_rows (the subsample: every ustride-th unit of 16 rows), rank
+    (the threshold's rank in the subsample), target (the draws expected above it), cap (an observation's buffer) and forms (the
+    tail lengths at which a kernel or its launch changes form).  A function of (nchains, N, n) alone; no device needed."""
+    out = (C.c_int64 * abi.LOO_PLAN_LEN)()
+    _waic_rc(abi.lib().fmcmc_loo_plan(int(nchains), int(N), int(n), out))
+    v = [int(x) for x in out]
+    return SimpleNamespace(M=v[0], ustride=v[1], sub_units=v[2], sub_rows=v[3], rank=v[4], target=v[5], cap=v[6],
+                           forms=tuple(v[8:8 + v[7]]))
+
+
+def loo_gpdfit(x):
+    """Zhang and Stephens' (2009) fit of the generalised Pareto distribution to x (ascending, >= 0) as loo::gpdfit forms it, with
+    loo's weakly informative prior on k: (k, sigma), in the dtype of x."""
+    import math
+    x = np.asarray(x)
+    dt = x.dtype.type
+    M = x.shape[0]
+    G = 30 + math.isqrt(M)
+    with np.errstate(all="ignore"):
+        xstar = x[(M + 2) // 4 - 1]
+        j = np.arange(1, G + 1).astype(x.dtype)
+        theta = dt(1) / x[-1] + (dt(1) - np.sqrt(dt(G) / (j - dt(0.5)))) / (dt(3) * xstar)
+        kappa = np.log1p(-theta[:, None] * x[None, :]).sum(axis=1) / dt(M)
+        ell = dt(M) * (np.log(-theta / kappa) - kappa - dt(1))
+        w = np.exp(ell - ell.max())
+        that = (theta * w).sum() / w.sum()
+        kraw = np.log1p(-that * x).sum() / dt(M)
+        return (dt(M) * kraw + dt(5)) / dt(M + 10), -kraw / that
+
+
+def _loo_smooth(tl, cut):
+    """The tail tl (log ratios after the shift, ascending, [M]) and the cutoff: (k, the smoothed tail), INTEGRATION.md 2.2 step
+    2 and 3; k = +Inf and the tail as it is where nothing is smoothed."""
+    dt = tl.dtype.type
+    M = tl.shape[0]
+    inf = dt(np.inf)
+    if M < 5 or tl[-1] - tl[0] < dt(np.finfo(np.float64).eps) / dt(100):
+        return inf, tl
+    with np.errstate(all="ignore"):
+        ecut = np.exp(cut)
+        k, sigma = loo_gpdfit(np.exp(tl) - ecut)
+        if not np.isfinite(k):
+            return inf, tl
+        p = (np.arange(1, M + 1).astype(tl.dtype) - dt(0.5)) / dt(M)
+        return k, np.log(ecut + sigma * np.expm1(-k * np.log1p(-p)) / k)
+
+
+def loo_host(model, draws, dtype=np.float64):
+    """The plain numpy restatement of loo() on draws [S][k]: the CPU reference and the executable form of the definition
+    (INTEGRATION.md 2.2).  With dtype = np.longdouble it is the truth the tests hold the device to.  Returns a namespace with
+    pointwise [n][6] = {elpd_loo_i, p_loo_i, lppd_i, pareto_k_i, n_eff_i, cutoff_i}, pareto_k, n_eff, tail [n][M] (the M largest
+    -l, ascending, before the smoothing), smoothed [n][M] (the tail's log weights after the shift and the smoothing, before the
+    cap at 0), the totals of LOO_TOTAL and tail_len, k_threshold."""
+    model = _waic_model(model)
+    th = np.asarray(draws, dtype=dtype)
+    l = np.ascontiguousarray(waic_loglik(model, th, dtype).T)        # [n][S]
+    n, S = l.shape
+    if S < 2:
+        raise ValueError("LOO needs at least 2 draws; got %d" % S)
+    M = loo_tail_len(S)
+    point = np.zeros((n, 6), dtype=dtype)
+    tail, smoothed = np.zeros((n, M), dtype=dtype), np.zeros((n, M), dtype=dtype)
+    with np.errstate(all="ignore"):
+        for i in range(n):
+            r = np.partition(-l[i], S - M - 1)                       # [S - M - 1] the cutoff, behind it the tail
+            rest, cutoff, tl = r[:S - M - 1], r[S - M - 1], np.sort(r[S - M:])
+            R = tl[-1]
+            tail[i] = tl
+            k, sm = _loo_smooth(tl - R, cutoff - R)
+            smoothed[i] = sm
+            lw = np.concatenate([rest - R, [cutoff - R], np.minimum(sm, dtype(0))])
+            ls = -np.concatenate([rest, [cutoff], tl])               # the l of the same draws
+            a = ls + lw
+            num = a.max() + np.log(np.exp(a - a.max()).sum())
+            den = np.exp(lw).sum()                                   # (max lw = 0 up to the smoothing)
+            top = l[i].max()
+            lppd = top + np.log(np.exp(l[i] - top).sum() / dtype(S))
+            elpd = num - np.log(den)
+            point[i] = (elpd, lppd - elpd, lppd, k, den * den / np.exp(dtype(2) * lw).sum(), cutoff)
+    bad = ~np.isfinite(th).all(axis=1)
+    if model.family != abi.FAM_LOGISTIC:
+        bad |= ~(th[:, -1] > 0)
+    tot = point[:, :3].sum(axis=0)
+    se = [_se(point[:, q]) for q in range(3)]
+    tau = loo_k_threshold(S)
+    kk = point[:, 3]
+    okp = np.isfinite(point[:, [0, 1, 2, 4]]).all(axis=1) & ~np.isnan(kk)
+    return SimpleNamespace(pointwise=point, pareto_k=kk, n_eff=point[:, 4], tail=tail, smoothed=smoothed, elpd_loo=tot[0],
+                           p_loo=tot[1], lppd=tot[2], looic=dtype(-2) * tot[0], se_elpd=se[0], se_p=se[1], se_lppd=se[2],
+                           n_k_bad=int((kk > tau).sum()), n_k_very_bad=int((kk > 1).sum()), max_k=kk.max(),
+                           bad_draws=int(bad.sum()), bad_points=int((~okp).sum()), tail_len=M, k_threshold=tau)
+
+
+class LooResult:
+    """loo() of a result: elpd_loo, p_loo, lppd, looic = -2 elpd_loo, their standard errors se_elpd, se_p, se_lppd (se_looic =
+    2 se_elpd), pareto_k [n] and n_eff [n], n_k_bad / n_k_very_bad = the observations with k > k_threshold = min(1 - 1 / log10 S,
+    0.7) / with k > 1, max_k, and pointwise [n][6] = {elpd_i, p_loo_i, lppd_i, pareto_k_i, n_eff_i, cutoff_i} (numpy;
+    pointwise_dev is the device tensor it was copied from, or None).  ndraws = the S draws, nobs = the n observations."""
+
+    def __init__(self, pointwise, total, ndraws, pointwise_dev=None):
+        self.pointwise = np.asarray(pointwise, dtype=np.float64).reshape(-1, 6)
+        self.pointwise_dev = pointwise_dev
+        total = np.asarray(total, dtype=np.float64).reshape(12)
+        for name, v in zip(LOO_TOTAL[:7], total):
+            setattr(self, name, float(v))
+        self.se_looic = 2.0 * self.se_elpd
+        self.max_k = float(total[9])
+        self.n_k_bad, self.n_k_very_bad, self.bad_draws, self.bad_points = (
+            int(v) if np.isfinite(v) else -1 for v in (total[7], total[8], total[10], total[11]))
+        self.pareto_k, self.n_eff = self.pointwise[:, 3], self.pointwise[:, 4]
+        self.ndraws, self.nobs = int(ndraws), int(self.pointwise.shape[0])
+        self.tail_len, self.k_threshold = loo_tail_len(self.ndraws), loo_k_threshold(self.ndraws)
+
+    def k_table(self):
+        """loo's table: (label, count, percent, least n_eff) for k <= threshold (good), (threshold, 1] (bad), > 1 (very bad)"""
+        k, tau = self.pareto_k, self.k_threshold
+        rows = []
+        for label, sel in (("(-Inf, %.2g]   (good)" % tau, k <= tau), ("(%.2g, 1]   (bad)" % tau, (k > tau) & (k <= 1)),
+                           ("(1, Inf)   (very bad)", k > 1)):
+            c = int(sel.sum())
+            rows.append((label, c, 100.0 * c / max(1, self.nobs), float(self.n_eff[sel].min()) if c else float("nan")))
+        return rows
+
+    def __str__(self):
+        rows = [("elpd_loo", self.elpd_loo, self.se_elpd), ("p_loo", self.p_loo, self.se_p), ("looic", self.looic, self.se_looic)]
+        out = ["", "Computed from %d by %d log-likelihood matrix" % (self.ndraws, self.nobs), "",
+               "%-9s %9s %6s" % ("", "Estimate", "SE")]
+        out += ["%-9s %9.1f %6.1f" % r for r in rows]
+        out += ["------", "MCSE and r_eff are not computed (r_eff = 1).", ""]
+        if self.n_k_bad == 0:
+            out += ["All Pareto k estimates are good (k < %.2g)." % self.k_threshold]
+        else:
+            out += ["Pareto k diagnostic values:", "%-26s %6s %6s %10s" % ("", "Count", "Pct.", "Min. n_eff")]
+            out += ["%-26s %6d %5.1f%% %10s" % (lab, c, pct, "<NA>" if c == 0 else "%.0f" % ne)
+                    for lab, c, pct, ne in self.k_table()]
+        return "\n".join(out) + "\n"
+
+    def __repr__(self):
+        return "<LooResult elpd_loo=%.4g p_loo=%.4g max_k=%.3g n=%d>" % (self.elpd_loo, self.p_loo, self.max_k, self.nobs)
+
+
+class LooBatch(list):
+    """loo() of an McmcBatch: a list of D LooResult, one per dataset (what loo(ans[d], models[d]) returns), with the stacked
+    arrays elpd_loo, p_loo, lppd, looic, se_elpd, se_p, se_lppd, se_looic, n_k_bad, n_k_very_bad, max_k, each [D], and
+    pointwise [D][n][6], pareto_k [D][n], n_eff [D][n]."""
+    fields = LOO_TOTAL[:10] + ("se_looic",)
+
+    def __init__(self, results):
+        super().__init__(results)
+        for name in self.fields:
+            setattr(self, name, np.array([getattr(r, name) for r in self]))
+        self.pointwise = np.stack([r.pointwise for r in self]) if len(self) else np.zeros((0, 0, 6))
+        self.pareto_k, self.n_eff = self.pointwise[..., 3], self.pointwise[..., 4]
+
+    def __repr__(self):
+        return "<LooBatch ndatasets=%d n=%d>" % (len(self), self.pointwise.shape[1])
+
+
+def enqueue_loo_groups(dc, dm, ngroups, chains_per_group, row0, N, active=None, want_tail=False):
+    """The one call site of fmcmc_loo_groups_dev (current torch stream), with the arguments of enqueue_waic_groups.  Returns the
+    device tensors (point [ngroups][n][6], total [ngroups][12], work, tail [ngroups][n][M] or None); nothing is synchronised."""
+    import torch
+    o = _open(dc, None, "score")
+    ngroups, cpg = int(ngroups), int(chains_per_group)
+    if ngroups < 1 or cpg < 1 or ngroups * cpg != o.Cn:
+        raise ValueError("%d groups of %d chains are not the %d chains of the result" % (ngroups, cpg, o.Cn))
+    if getattr(dm, "nmodels", 1) != ngroups:
+        raise ValueError("%d datasets for %d groups of chains" % (getattr(dm, "nmodels", 1), ngroups))
+    if dm.device != o.dev and (dm.device.index is not None or dm.device.type != o.dev.type):
+        raise ValueError("the model's data are on %s, the draws on %s" % (dm.device, o.dev))
+    if o.k != dm.k:
+        raise ValueError("the result has k = %d parameters, the model's family has %d" % (o.k, dm.k))
+    if row0 < 0 or N < 1 or row0 + N > dc.nrows:
+        raise ValueError("the window [%d, %d) is outside the %d kept rows" % (row0, row0 + N, dc.nrows))
+    if cpg * int(N) < 2:
+        raise ValueError("LOO needs at least 2 draws; got %d" % (cpg * int(N)))
+    M = loo_tail_len(cpg * int(N))
+    if M > LOO_MAX_TAIL:
+        raise NotImplementedError("%d draws ask for a tail of %d; supported are tails up to %d" % (cpg * int(N), M, LOO_MAX_TAIL))
+    if active is not None and (not torch.is_tensor(active) or active.dtype != torch.int32 or tuple(active.shape) != (ngroups,)
+                               or not active.is_contiguous() or active.device != o.dev):
+        raise ValueError("`active` must be a contiguous int32 tensor of shape [%d] on %s" % (ngroups, o.dev))
+    cm = dm.c()
+    point = torch.full((ngroups, dm.n, 6), float("nan"), dtype=torch.float64, device=o.dev)
+    total = torch.full((ngroups, 12), float("nan"), dtype=torch.float64, device=o.dev)
+    tail = torch.full((ngroups, dm.n, M), float("nan"), dtype=torch.float64, device=o.dev) if want_tail else None
+    work = _doubles(o, o.L.fmcmc_loo_work_len(C.byref(cm), ngroups, cpg, int(N)))
+    with torch.cuda.device(o.dev):
+        rc = o.L.fmcmc_loo_groups_dev(C.byref(cm), getattr(dm, "x_stride", 0), getattr(dm, "y_stride", 0), o.smp.data_ptr(),
+                                      ngroups, cpg, o.k, o.cap, int(row0), int(N),
+                                      active.data_ptr() if active is not None else None, work.data_ptr(), point.data_ptr(),
+                                      tail.data_ptr() if tail is not None else None, total.data_ptr(), _stream(o.dev))
+    _waic_rc(rc)
+    return point, total, work, tail
+
+
+def _raise_bad_loo_draws(total_row):
+    if total_row[10] != 0:
+        raise ValueError("%d draw(s) with a parameter that is not finite or a sigma that is not > 0 among the rows to score"
+                         % int(total_row[10]))
+
+
+def loo(x, model, autoburnin=False):
+    """Pareto-smoothed importance-sampling leave-one-out cross-validation (Vehtari, Gelman and Gabry 2017; loo::loo with r_eff =
+    1) of a result under the model it was sampled from, or another one of the same parameters, with the Pareto k of every
+    observation: the arguments of waic(); a LooResult, or a LooBatch for an McmcBatch with a model_batch.  The S x n matrix of
+    pointwise log-likelihoods is never formed: the device selects the M largest importance ratios of every observation exactly
+    (csrc/diag_loo.hpp)."""
+    from .convergence import _window
+    from .mcmc import McmcBatch
+    if isinstance(x, McmcBatch):
+        return loo_batch(x, model, autoburnin)
+    model = _waic_model(model)
+    dc = _as_device_chains(x)
+    row0, N = _window(dc.iters) if autoburnin else (0, int(dc.nrows))
+    Cn = int(dc._samples.shape[0])
+    point, total, _work, _tail = enqueue_loo_groups(dc, model.device_model(dc._samples.device), 1, Cn, row0, N)
+    th = total[0].cpu().numpy()
+    _raise_bad_loo_draws(th)
+    return LooResult(point[0].cpu().numpy(), th, Cn * N, point[0])
+
+
+def loo_batch(ans, models, autoburnin=False):
+    """loo(ans[d], models[d]) for every dataset d of an McmcBatch from ONE grouped call (fmcmc_loo_groups_dev): the same bits.
+    On a ragged result (MCMC_batch(stop_each = ...)) each dataset has its own rows, with one call per distinct row count."""
+    import torch
+    from .convergence import _window
+    from .mcmc import McmcBatch
+    from .models import ModelBatch
+    if not isinstance(ans, McmcBatch):
+        raise TypeError("loo_batch() expects an McmcBatch (the result of MCMC_batch)")
+    if not isinstance(models, ModelBatch):
+        raise TypeError("loo_batch() needs the model_batch the datasets came from (a %s has no pointwise form per dataset)"
+                        % type(models).__name__)
+    _single_process()
+    full, D, Cm = ans.history, ans.nmodels, ans.nchains
+    if models.nmodels != D:
+        raise ValueError("%d datasets in the model batch, %d in the result" % (models.nmodels, D))
+    dm = models.device_model(full._samples.device)
+    out = [None] * D
+    for nr, sel, mask in _batch_calls(ans):
+        row0, N = _window(full.iters[:nr]) if autoburnin else (0, nr)
+        active = None if mask is None else torch.as_tensor(mask).to(full._samples.device)
+        point, total, _work, _tail = enqueue_loo_groups(full, dm, D, Cm, row0, N, active)
+        ph, th = point.cpu().numpy(), total.cpu().numpy()
+        for d in sel:
+            try:
+                _raise_bad_loo_draws(th[d])
+            except ValueError as e:
+                raise ValueError("dataset %d: %s" % (d, e)) from None
+            out[d] = LooResult(ph[d], th[d], Cm * N, point[d])
+    return LooBatch(out)
+
+
+def loo_compare(a, b):
+    """The difference of two models on the same observations, as loo::loo_compare forms it: the arithmetic of waic_compare on
+    column 0 (elpd_loo_i) of the pointwise arrays.  Two LooResult (or loo_host results) give two numbers, two LooBatch arrays [D]."""
+    return waic_compare(a, b)

@@ -654,6 +654,44 @@ int fmcmc_waic_groups_dev(const fmcmc_model* m0, int64_t x_stride, int64_t y_str
                           int64_t chains_per_group, int32_t k, int64_t S, int64_t row0, int64_t N, const int32_t* active,
                           double* work, double* point /* [G][n][4] */, double* total /* [G][10] */, void* hip_stream);
 
+/* ---- PSIS-LOO with Pareto-k diagnostics (Vehtari, Gelman, Gabry 2017; loo::loo with r_eff = 1), the device part ------------------
+ * Draws, model, families and the evaluation of l as for fmcmc_waic_dev; the definition is INTEGRATION.md 2.2 (fmcmc_amd/summary.py:
+ * loo_host is its executable form).  With r = -l: fmcmc_loo_tail_len(S') = M = ceil(min(0.2 S', 3 sqrt(S'))) (in integers; 0 for
+ * S' < 1); the tail of an observation is its M largest r, the cutoff its (M + 1)-th largest, both EXACTLY what a full sort of the
+ * device's own r gives, ties included.
+ * point (device, [n][6]) = {elpd_loo_i, p_loo_i = lppd_i - elpd_loo_i, lppd_i, pareto_k_i (+Inf: not smoothed), n_eff_i = 1 / sum
+ *   of the squared normalised weights, cutoff_i (the (M + 1)-th largest r, unshifted)}.
+ * tail (device, [n][M], or NULL) = the M largest r of every observation, ascending, before the smoothing.
+ * total (device, [12]) = {elpd_loo, p_loo, lppd, looic = -2 elpd_loo, se_elpd, se_p, se_lppd (as for WAIC), n_k_bad (pareto_k >
+ *   min(1 - 1 / log10 S', 0.7)), n_k_very_bad (pareto_k > 1), max_k, bad_draws, bad_points (observations whose elpd, p_loo, lppd
+ *   or n_eff is not finite or whose pareto_k is NaN)}; the counts are exact doubles.
+ * fmcmc_loo_plan(chains_per_group, N, n, out): the plan, a function of its three arguments alone.  out[0] = M; the subsample is
+ *   the units u = 0, out[1], 2 out[1], ... (a unit: WAIC's tile of 16 rows, u = c T + t), out[2] units with out[3] rows; the
+ *   threshold of an observation is the out[4]-th largest r of its subsample, chosen so that out[5] draws are expected above it;
+ *   out[6] = the capacity of an observation's buffer (the power of two >= 3 M).  An observation whose count of draws above the
+ *   threshold is in [M + 1 - ties, out[6]] is served from its buffer; any other takes the exact fallback (a radix select over all
+ *   draws).  With out[1] = 1 the subsample is every draw and the threshold is exact.  out[7] = the number of tail lengths at
+ *   which a kernel or its launch changes form, out[8 ...] those M (5: the fit and the smoothing start; 8193: the finishing
+ *   kernel's LDS passes 64 KB); the rest of the FMCMC_LOO_PLAN_LEN entries are 0.
+ * work: device scratch of fmcmc_loo_work_len(...) doubles (0 for arguments the call refuses): WAIC's, then per observation the
+ *   subsample (16 out[2] keys), the buffer (out[6] keys), 8 state words {threshold key, count above, count equal, 1 if the
+ *   fallback served it, ...} at fmcmc_loo_state_offset(...) + 8 (g n + i) (8-byte integers; what a call leaves there may be read),
+ *   and a 256-bin histogram.  A call does not depend on what work held.
+ * Tails up to M = 16384 (S' <= 29826161); beyond: FMCMC_ERR_UNSUPPORTED.  fmcmc_loo_groups_dev, active, the streams, the checks
+ * and the bit-for-bit equality of a group with its single call are those of fmcmc_waic_groups_dev. */
+#define FMCMC_LOO_PLAN_LEN 16
+int64_t fmcmc_loo_tail_len(int64_t S);
+int fmcmc_loo_plan(int64_t chains_per_group, int64_t N, int64_t n, int64_t out[FMCMC_LOO_PLAN_LEN]);
+int64_t fmcmc_loo_work_len(const fmcmc_model* m, int64_t ngroups, int64_t chains_per_group, int64_t N);
+int64_t fmcmc_loo_state_offset(const fmcmc_model* m, int64_t ngroups, int64_t chains_per_group, int64_t N);
+int fmcmc_loo_dev(const fmcmc_model* m, const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N,
+                  double* work, double* point /* [n][6] */, double* tail /* [n][M] or NULL */, double* total /* [12] */,
+                  void* hip_stream);
+int fmcmc_loo_groups_dev(const fmcmc_model* m0, int64_t x_stride, int64_t y_stride, const double* samples, int64_t ngroups,
+                         int64_t chains_per_group, int32_t k, int64_t S, int64_t row0, int64_t N, const int32_t* active,
+                         double* work, double* point /* [G][n][6] */, double* tail /* [G][n][M] or NULL */,
+                         double* total /* [G][12] */, void* hip_stream);
+
 /* Materialises the canonical Philox stream of a call in device memory, in the FED layout of fmcmc_run:
  * logu[C][nsteps] (entry i-1 = log accept-uniform of loop step i), z[C][nsteps][kz] (N(0,1) when student_df == 0;
  * Student-t with student_df degrees of freedom when student_df > 0 -- kernel_ram: kf for the default qfun rt(k, k),
