@@ -41,7 +41,9 @@ EXPORTS = ["fmcmc_abi_version", "fmcmc_last_error", "fmcmc_last_kernel", "fmcmc_
            "fmcmc_rank_ess_groups_work_len", "fmcmc_rank_ess_groups_out_len", "fmcmc_rank_ess_groups_dev",
            "fmcmc_waic_part_rows", "fmcmc_waic_parts", "fmcmc_waic_work_len", "fmcmc_waic_dev", "fmcmc_waic_groups_dev",
            "fmcmc_loo_tail_len", "fmcmc_loo_plan", "fmcmc_loo_work_len", "fmcmc_loo_state_offset", "fmcmc_loo_dev",
-           "fmcmc_loo_groups_dev"]
+           "fmcmc_loo_groups_dev",
+           "fmcmc_pointwise_block_rows", "fmcmc_waic_fun_work_len", "fmcmc_waic_fun_dev", "fmcmc_loo_fun_work_len",
+           "fmcmc_loo_fun_state_offset", "fmcmc_loo_fun_dev"]
 LOO_PLAN_LEN = 16              # FMCMC_LOO_PLAN_LEN
 BATCH_STREAM_DATA = 1          # fmcmc_mcmc_run_batch_*: flags bit, read the datasets from global memory every step
 SUMMARY_MAX_PROBS = 16
@@ -52,6 +54,8 @@ AUTOCOV_MAX_LAGS = 32          # lags per fmcmc_autocov_dev call
 
 # fmcmc_logpost_fn: out[c] = log f(theta[c][0..k-1]) for c < nchains; 0 = ok (theta, out, hip_stream, user: addresses)
 LOGPOST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p)
+# fmcmc_pointwise_fn: ll[b][i] = log p(y_i | theta[b][0..k-1]) for b < B, i < n; 0 = ok (theta, B, k, n, ll, hip_stream, user)
+POINTWISE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
 
 
 class StepEnv(C.Structure):
@@ -276,6 +280,17 @@ def lib():
         L.fmcmc_loo_groups_dev.argtypes = [C.POINTER(Model), C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
                                            C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p]
+        for name in ("fmcmc_pointwise_block_rows", "fmcmc_waic_fun_work_len", "fmcmc_loo_fun_work_len",
+                     "fmcmc_loo_fun_state_offset"):
+            getattr(L, name).restype = C.c_int64
+            getattr(L, name).argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64]
+        L.fmcmc_waic_fun_dev.restype = C.c_int
+        L.fmcmc_waic_fun_dev.argtypes = [POINTWISE_FN, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int64,
+                                         C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fmcmc_loo_fun_dev.restype = C.c_int
+        L.fmcmc_loo_fun_dev.argtypes = [POINTWISE_FN, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int64,
+                                        C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]
         L.fmcmc_rng_stream_dev.restype = C.c_int
         L.fmcmc_rng_stream_dev.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                            C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]

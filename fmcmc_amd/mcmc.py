@@ -297,15 +297,16 @@ class DeviceChains:
         from .summary import ess
         return ess(self, autoburnin, cols)
 
-    def waic(self, model, autoburnin=False):
-        """WAIC of the rows under `model` (a gaussian_linreg / logistic / iid_normal object): a WaicResult."""
+    def waic(self, model, autoburnin=False, block_rows=None):
+        """WAIC of the rows under `model` (a gaussian_linreg / logistic / iid_normal object, or a pointwise_fun, whose fn gets
+        blocks of at most block_rows draws): a WaicResult."""
         from .summary import waic
-        return waic(self, model, autoburnin)
+        return waic(self, model, autoburnin, block_rows)
 
-    def loo(self, model, autoburnin=False):
-        """PSIS-LOO of the rows under `model`, with the Pareto k of every observation: a LooResult."""
+    def loo(self, model, autoburnin=False, block_rows=None):
+        """PSIS-LOO of the rows under `model` (as for waic()), with the Pareto k of every observation: a LooResult."""
         from .summary import loo
-        return loo(self, model, autoburnin)
+        return loo(self, model, autoburnin, block_rows)
 
     def rank_scores(self, fold=False, cols=None):
         """The rank-normalised scores behind rhat(), a device tensor [p][2 C][N // 2] (for rank plots)."""

@@ -135,6 +135,40 @@ def batched_fun(fn, k, names=None):
     return BatchedFun(fn, k, names)
 
 
+class PointwiseFun:
+    """A user-defined pointwise log-likelihood for waic() and loo(): fn(theta) takes the float64 tensor [B, k] of B draws on the
+    device (read-only: it is the library's buffer) and returns the float64 tensor [B, n] of log p(y_i | theta_b) on the same
+    device, the likelihood alone (no prior), enqueued on the current torch stream.  The draws come in blocks of rows; fn is called
+    once per block."""
+
+    def __init__(self, fn, n, k, names=None):
+        if not callable(fn):
+            raise TypeError("pointwise_fun: -fn- must be callable.")
+        n, k = int(n), int(k)
+        if not 1 <= k <= abi.MAX_K:
+            raise ValueError("pointwise_fun: k = %d outside [1, %d]." % (k, abi.MAX_K))
+        if n < 1:
+            raise ValueError("pointwise_fun: n = %d observations; at least 1 is needed." % n)
+        if names is not None and len(names) != k:
+            raise ValueError("pointwise_fun: %d names for k = %d parameters." % (len(names), k))
+        self.fn, self.names = fn, (list(names) if names is not None else None)
+        self._n, self._k = n, k
+
+    @property
+    def k(self):
+        return self._k
+
+    @property
+    def n(self):
+        return self._n
+
+
+def pointwise_fun(fn, n, k, names=None):
+    """A user-defined model for waic() / loo(): fn(theta [B, k] float64 tensor on the device) -> [B, n] float64 tensor on the
+    same device, log p(y_i | theta_b) of the n observations.  names: optional parameter names."""
+    return PointwiseFun(fn, n, k, names)
+
+
 class ModelBatch:
     """One closed-form family fitted to D datasets of one shape (model_batch): what MCMC_batch() samples in one launch.
     batch[d] is dataset d's LogPosterior; the data go to HBM once per device, as X [D][p][n] and y [D][n]."""

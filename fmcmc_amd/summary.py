@@ -1842,20 +1842,42 @@ def waic_parts(nchains, N, n):
 
 
 def _waic_model(model):
-    from .models import LogPosterior
-    if not isinstance(model, LogPosterior):
-        raise TypeError("waic() needs one of the closed-form families (gaussian_linreg, logistic, iid_normal): a %s returns the "
-                        "summed log-posterior and has no pointwise form." % type(model).__name__)
+    """a closed-form family or a PointwiseFun, as it is; anything else has no pointwise form"""
+    from .models import LogPosterior, PointwiseFun
+    if not isinstance(model, (LogPosterior, PointwiseFun)):
+        raise TypeError("waic() and loo() need one of the closed-form families (gaussian_linreg, logistic, iid_normal) or a "
+                        "pointwise_fun(fn, n, k): a %s returns the summed log-posterior and has no pointwise form; give the "
+                        "log-likelihood of every observation as a pointwise_fun." % type(model).__name__)
     return model
+
+
+def _pointwise_loglik(model, th, dtype):
+    """fn of a PointwiseFun on CPU tensors: l [S][n] in `dtype` (fn itself computes in float64)"""
+    import torch
+    t = torch.as_tensor(np.ascontiguousarray(th, dtype=np.float64))
+    l = model.fn(t)
+    if not torch.is_tensor(l) or l.dtype != torch.float64 or tuple(l.shape) != (t.shape[0], model.n) or l.device != t.device:
+        raise ValueError("pointwise_fun: fn(theta) must return a float64 tensor of shape [%d, %d] on %s; got %s"
+                         % (t.shape[0], model.n, t.device, _describe_tensor(l)))
+    return l.detach().numpy().astype(dtype)
+
+
+def _describe_tensor(t):
+    import torch
+    return ("%s %s on %s" % (t.dtype, tuple(t.shape), t.device)) if torch.is_tensor(t) else type(t).__name__
 
 
 def waic_loglik(model, draws, dtype=np.float64):
     """The pointwise log-likelihood l [S][n] of the definition for draws [S][k], in `dtype`: the likelihood
-    alone, without the prior_div term and without the guard."""
+    alone, without the prior_div term and without the guard.  A PointwiseFun is evaluated by its fn on CPU tensors."""
+    from .models import PointwiseFun
     model = _waic_model(model)
     th = np.asarray(draws, dtype=dtype)
     if th.ndim != 2 or th.shape[1] != model.k:
-        raise ValueError("draws must be [S][%d] for this family; got shape %s" % (model.k, th.shape))
+        raise ValueError("draws must be [S][%d] for this %s; got shape %s"
+                         % (model.k, "model" if isinstance(model, PointwiseFun) else "family", th.shape))
+    if isinstance(model, PointwiseFun):
+        return _pointwise_loglik(model, th, dtype)
     ic, p, n = int(model.intercept), model.p, int(model.y.shape[0])
     y = model.y.astype(dtype)
     eta = np.zeros((th.shape[0], n), dtype=dtype)
@@ -1877,6 +1899,15 @@ def waic_loglik(model, draws, dtype=np.float64):
         return -(np.log(sigma) + half_log_2pi)[:, None] - dtype(0.5) * r * r / (sigma * sigma)[:, None]
 
 
+def _bad_draws(model, th):
+    """the draws with a parameter that is not finite, or (Gaussian families) a sigma that is not > 0"""
+    from .models import PointwiseFun
+    bad = ~np.isfinite(th).all(axis=1)
+    if not isinstance(model, PointwiseFun) and model.family != abi.FAM_LOGISTIC:
+        bad |= ~(th[:, -1] > 0)
+    return int(bad.sum())
+
+
 def _se(v):
     """sqrt(n var(v)) with divisor n - 1 (NaN for n = 1), in the dtype of v"""
     n = v.shape[-1]
@@ -1885,14 +1916,12 @@ def _se(v):
         return np.sqrt(n * ((d * d).sum(axis=-1) / v.dtype.type(n - 1)))
 
 
-def waic_host(model, draws, dtype=np.float64):
-    """The plain numpy restatement of waic() on draws [S][k]: the CPU reference and the documentation of the definition.  With
-    dtype = np.longdouble it is the truth the tests hold the device to.  Returns a namespace with pointwise [n][4] = {elpd_i,
-    p_waic_i, lppd_i, mean_i} and the totals elpd_waic, p_waic, lppd, waic, se_elpd, se_p, se_lppd, n_high, bad_draws,
-    bad_points, all in `dtype`."""
-    model = _waic_model(model)
-    th = np.asarray(draws, dtype=dtype)
-    l = np.ascontiguousarray(waic_loglik(model, th, dtype).T)        # [n][S]: the sums run along a row (numpy: pairwise)
+def waic_host_matrix(l, dtype=np.float64, bad_draws=0):
+    """waic_host on the matrix l [S][n] of pointwise log-likelihoods itself, in `dtype`: what waic_host computes once it has
+    evaluated the model.  bad_draws is passed through (a matrix knows nothing of the draws)."""
+    l = np.ascontiguousarray(np.asarray(l, dtype=dtype).T)           # [n][S]: the sums run along a row (numpy: pairwise)
+    if l.ndim != 2:
+        raise ValueError("l must be a matrix [S][n]; got shape %s" % (l.T.shape,))
     S = l.shape[1]
     if S < 2:
         raise ValueError("WAIC needs at least 2 draws; got %d" % S)
@@ -1902,14 +1931,22 @@ def waic_host(model, draws, dtype=np.float64):
         mean = l[:, 0] + (l - l[:, :1]).sum(axis=1) / dtype(S)       # (shifted by the first draw: equal draws give it back)
         p_waic = ((l - mean[:, None]) ** 2).sum(axis=1) / dtype(S - 1)
     point = np.stack([lppd - p_waic, p_waic, lppd, mean], axis=1)
-    bad = ~np.isfinite(th).all(axis=1)
-    if model.family != abi.FAM_LOGISTIC:
-        bad |= ~(th[:, -1] > 0)
     tot = point[:, :3].sum(axis=0)
     se = [_se(point[:, q]) for q in range(3)]
     return SimpleNamespace(pointwise=point, elpd_waic=tot[0], p_waic=tot[1], lppd=tot[2], waic=dtype(-2) * tot[0], se_elpd=se[0],
-                           se_p=se[1], se_lppd=se[2], n_high=int((point[:, 1] > WAIC_HIGH).sum()), bad_draws=int(bad.sum()),
+                           se_p=se[1], se_lppd=se[2], n_high=int((point[:, 1] > WAIC_HIGH).sum()), bad_draws=int(bad_draws),
                            bad_points=int((~np.isfinite(point).all(axis=1)).sum()))
+
+
+def waic_host(model, draws, dtype=np.float64):
+    """The plain numpy restatement of waic() on draws [S][k]: the CPU reference and the documentation of the definition.  With
+    dtype = np.longdouble it is the truth the tests hold the device to.  Returns a namespace with pointwise [n][4] = {elpd_i,
+    p_waic_i, lppd_i, mean_i} and the totals elpd_waic, p_waic, lppd, waic, se_elpd, se_p, se_lppd, n_high, bad_draws,
+    bad_points, all in `dtype`.  model: a family, or a PointwiseFun whose fn runs on CPU tensors; it is waic_loglik followed by
+    waic_host_matrix."""
+    model = _waic_model(model)
+    th = np.asarray(draws, dtype=dtype)
+    return waic_host_matrix(waic_loglik(model, th, dtype), dtype, _bad_draws(model, th))
 
 
 class WaicResult:
@@ -2005,24 +2042,117 @@ def _raise_bad_draws(total_row):
                          % int(total_row[8]))
 
 
-def waic(x, model, autoburnin=False):
+def _pointwise_trampoline(model, dev, stream, view, caught):
+    """model.fn as a fmcmc_pointwise_fn: the device buffers as tensors, fn under the call's stream as torch's current stream, its
+    result copied into `ll`.  An exception raised in fn (or by the check of what it returned) is kept in `caught` and the
+    trampoline returns non-zero: the library abandons the call (FMCMC_ERR_FUN) and the caller raises the exception itself."""
+    import torch
+    fn = model.fn
+
+    def trampoline(theta_p, B, k, n, ll_p, stream_p, user):
+        try:
+            with torch.cuda.stream(stream):
+                l = fn(view(theta_p, (B, k)))
+                if not torch.is_tensor(l) or l.dtype != torch.float64 or l.device != dev or tuple(l.shape) != (B, n):
+                    raise ValueError("pointwise_fun: fn(theta) must return a float64 tensor of shape [%d, %d] on %s; got %s"
+                                     % (B, n, dev, _describe_tensor(l)))
+                view(ll_p, (B, n)).copy_(l)
+            return 0
+        except BaseException as e:   # (nothing may unwind through the C frames)
+            caught.append(e)
+            return 1
+
+    return abi.POINTWISE_FN(trampoline)
+
+
+def enqueue_pointwise(dc, model, row0, N, block_rows=None, what="waic", want_tail=False):
+    """The one call site of fmcmc_waic_fun_dev (what = "waic") and fmcmc_loo_fun_dev ("loo") on the current torch stream: the
+    window [row0, row0 + N) of the rows of `dc` under the PointwiseFun `model`, in blocks of at most block_rows rows (rounded up
+    to whole tiles of 16 rows; None: the library's choice).  Returns the device tensors (point [1][n][4], total [1][10], work)
+    or (point [1][n][6], total [1][12], work, tail [1][n][M] or None), shaped as the grouped calls shape theirs.  The WAIC call
+    only enqueues; the LOO call synchronises the stream once (include/fmcmc_amd.h)."""
+    import torch
+    from .engine import _Views
+    o = _open(dc, None, "score")
+    loo_ = what == "loo"
+    n, Cn, N, row0 = model.n, o.Cn, int(N), int(row0)
+    if o.k != model.k:
+        raise ValueError("the result has k = %d parameters, the pointwise_fun has %d" % (o.k, model.k))
+    if row0 < 0 or N < 1 or row0 + N > dc.nrows:
+        raise ValueError("the window [%d, %d) is outside the %d kept rows" % (row0, row0 + N, dc.nrows))
+    if Cn * N < 2:
+        raise ValueError("%s needs at least 2 draws; got %d" % ("LOO" if loo_ else "WAIC", Cn * N))
+    br = 0 if block_rows is None else int(block_rows)
+    if br < 0:
+        raise ValueError("block_rows = %d: give a number of rows, or None for the library's choice" % br)
+    M = loo_tail_len(Cn * N)
+    if loo_ and M > LOO_MAX_TAIL:
+        raise NotImplementedError("%d draws ask for a tail of %d; supported are tails up to %d" % (Cn * N, M, LOO_MAX_TAIL))
+    nwork = (o.L.fmcmc_loo_fun_work_len if loo_ else o.L.fmcmc_waic_fun_work_len)(n, Cn, N, br)
+    if nwork < 1:
+        raise ValueError(abi.last_error())
+    width = 6 if loo_ else 4
+    point = torch.full((1, n, width), float("nan"), dtype=torch.float64, device=o.dev)
+    total = torch.full((1, 12 if loo_ else 10), float("nan"), dtype=torch.float64, device=o.dev)
+    tail = torch.full((1, n, M), float("nan"), dtype=torch.float64, device=o.dev) if loo_ and want_tail else None
+    work = _doubles(o, nwork)
+    stream = torch.cuda.current_stream(o.dev)
+    caught = []
+    cb = _pointwise_trampoline(model, o.dev, stream, _Views(o.dev), caught)
+    head = (cb, None, n, o.smp.data_ptr(), Cn, o.k, o.cap, row0, N, br, work.data_ptr(), point.data_ptr())
+    with torch.cuda.device(o.dev):
+        if loo_:
+            rc = o.L.fmcmc_loo_fun_dev(*head, tail.data_ptr() if tail is not None else None, total.data_ptr(),
+                                       C.c_void_p(stream.cuda_stream))
+        else:
+            rc = o.L.fmcmc_waic_fun_dev(*head, total.data_ptr(), C.c_void_p(stream.cuda_stream))
+    if caught:
+        raise caught[0]
+    _waic_rc(rc)
+    return (point, total, work, tail) if loo_ else (point, total, work)
+
+
+def _raise_bad_fun_draws(count):
+    if count != 0:
+        raise ValueError("%d draw(s) with a parameter that is not finite among the rows to score" % int(count))
+
+
+def _no_batch_pointwise(x, model, what):
+    from .mcmc import McmcBatch
+    from .models import PointwiseFun
+    if isinstance(x, McmcBatch) and isinstance(model, PointwiseFun):
+        raise TypeError("%s() of an McmcBatch needs the model_batch the datasets came from: a pointwise_fun scores one dataset "
+                        "(the grouped form is not implemented); call %s(ans[d], ...) per dataset." % (what, what))
+
+
+def waic(x, model, autoburnin=False, block_rows=None):
     """The widely applicable information criterion (Watanabe 2010; Gelman, Hwang and Vehtari 2014; loo::waic) of a result under
     the model it was sampled from, or another one of the same parameters: x a DeviceChains (read in place), an Mcmc or a McmcList
-    (uploaded first), model a gaussian_linreg / logistic / iid_normal object; an McmcBatch with a model_batch gives a WaicBatch,
-    one WaicResult per dataset from one grouped call (waic_batch).  With `autoburnin` the rows are coda's window (the second
-    half).  The S x n matrix of pointwise log-likelihoods is never formed: the device turns tiles of it into four running
-    numbers per observation (csrc/diag_waic.hpp)."""
+    (uploaded first), model a gaussian_linreg / logistic / iid_normal object or a pointwise_fun (a user-defined model: its fn is
+    called on blocks of at most block_rows draws; None: the library's choice); an McmcBatch with a model_batch gives a
+    WaicBatch, one WaicResult per dataset from one grouped call (waic_batch).  With `autoburnin` the rows are coda's window (the
+    second half).  The S x n matrix of pointwise log-likelihoods is never formed: the device turns tiles of it into four running
+    numbers per observation (csrc/diag_waic.hpp, csrc/diag_pointwise.hpp)."""
     from .convergence import _window
     from .mcmc import McmcBatch
+    from .models import PointwiseFun
+    _no_batch_pointwise(x, model, "waic")
     if isinstance(x, McmcBatch):
         return waic_batch(x, model, autoburnin)
     model = _waic_model(model)
+    if block_rows is not None and not isinstance(model, PointwiseFun):
+        raise ValueError("block_rows applies to a pointwise_fun only: a family is evaluated inside the kernel")
     dc = _as_device_chains(x)
     row0, N = _window(dc.iters) if autoburnin else (0, int(dc.nrows))
     Cn = int(dc._samples.shape[0])
-    point, total, _work = enqueue_waic_groups(dc, model.device_model(dc._samples.device), 1, Cn, row0, N)
-    th = total[0].cpu().numpy()
-    _raise_bad_draws(th)
+    if isinstance(model, PointwiseFun):
+        point, total, _work = enqueue_pointwise(dc, model, row0, N, block_rows, "waic")
+        th = total[0].cpu().numpy()
+        _raise_bad_fun_draws(th[8])
+    else:
+        point, total, _work = enqueue_waic_groups(dc, model.device_model(dc._samples.device), 1, Cn, row0, N)
+        th = total[0].cpu().numpy()
+        _raise_bad_draws(th)
     return WaicResult(point[0].cpu().numpy(), th, Cn * N, point[0])
 
 
@@ -2144,15 +2274,12 @@ def _loo_smooth(tl, cut):
         return k, np.log(ecut + sigma * np.expm1(-k * np.log1p(-p)) / k)
 
 
-def loo_host(model, draws, dtype=np.float64):
-    """The plain numpy restatement of loo() on draws [S][k]: the CPU reference and the executable form of the definition
-    (INTEGRATION.md 2.2).  With dtype = np.longdouble it is the truth the tests hold the device to.  Returns a namespace with
-    pointwise [n][6] = {elpd_loo_i, p_loo_i, lppd_i, pareto_k_i, n_eff_i, cutoff_i}, pareto_k, n_eff, tail [n][M] (the M largest
-    -l, ascending, before the smoothing), smoothed [n][M] (the tail's log weights after the shift and the smoothing, before the
-    cap at 0), the totals of LOO_TOTAL and tail_len, k_threshold."""
-    model = _waic_model(model)
-    th = np.asarray(draws, dtype=dtype)
-    l = np.ascontiguousarray(waic_loglik(model, th, dtype).T)        # [n][S]
+def loo_host_matrix(l, dtype=np.float64, bad_draws=0):
+    """loo_host on the matrix l [S][n] of pointwise log-likelihoods itself, in `dtype`: what loo_host computes once it has
+    evaluated the model.  bad_draws is passed through (a matrix knows nothing of the draws)."""
+    l = np.ascontiguousarray(np.asarray(l, dtype=dtype).T)           # [n][S]
+    if l.ndim != 2:
+        raise ValueError("l must be a matrix [S][n]; got shape %s" % (l.T.shape,))
     n, S = l.shape
     if S < 2:
         raise ValueError("LOO needs at least 2 draws; got %d" % S)
@@ -2176,9 +2303,6 @@ def loo_host(model, draws, dtype=np.float64):
             lppd = top + np.log(np.exp(l[i] - top).sum() / dtype(S))
             elpd = num - np.log(den)
             point[i] = (elpd, lppd - elpd, lppd, k, den * den / np.exp(dtype(2) * lw).sum(), cutoff)
-    bad = ~np.isfinite(th).all(axis=1)
-    if model.family != abi.FAM_LOGISTIC:
-        bad |= ~(th[:, -1] > 0)
     tot = point[:, :3].sum(axis=0)
     se = [_se(point[:, q]) for q in range(3)]
     tau = loo_k_threshold(S)
@@ -2187,7 +2311,19 @@ def loo_host(model, draws, dtype=np.float64):
     return SimpleNamespace(pointwise=point, pareto_k=kk, n_eff=point[:, 4], tail=tail, smoothed=smoothed, elpd_loo=tot[0],
                            p_loo=tot[1], lppd=tot[2], looic=dtype(-2) * tot[0], se_elpd=se[0], se_p=se[1], se_lppd=se[2],
                            n_k_bad=int((kk > tau).sum()), n_k_very_bad=int((kk > 1).sum()), max_k=kk.max(),
-                           bad_draws=int(bad.sum()), bad_points=int((~okp).sum()), tail_len=M, k_threshold=tau)
+                           bad_draws=int(bad_draws), bad_points=int((~okp).sum()), tail_len=M, k_threshold=tau)
+
+
+def loo_host(model, draws, dtype=np.float64):
+    """The plain numpy restatement of loo() on draws [S][k]: the CPU reference and the executable form of the definition
+    (INTEGRATION.md 2.2).  With dtype = np.longdouble it is the truth the tests hold the device to.  Returns a namespace with
+    pointwise [n][6] = {elpd_loo_i, p_loo_i, lppd_i, pareto_k_i, n_eff_i, cutoff_i}, pareto_k, n_eff, tail [n][M] (the M largest
+    -l, ascending, before the smoothing), smoothed [n][M] (the tail's log weights after the shift and the smoothing, before the
+    cap at 0), the totals of LOO_TOTAL and tail_len, k_threshold.  model: a family, or a PointwiseFun whose fn runs on CPU
+    tensors; it is waic_loglik followed by loo_host_matrix."""
+    model = _waic_model(model)
+    th = np.asarray(draws, dtype=dtype)
+    return loo_host_matrix(waic_loglik(model, th, dtype), dtype, _bad_draws(model, th))
 
 
 class LooResult:
@@ -2299,23 +2435,33 @@ def _raise_bad_loo_draws(total_row):
                          % int(total_row[10]))
 
 
-def loo(x, model, autoburnin=False):
+def loo(x, model, autoburnin=False, block_rows=None):
     """Pareto-smoothed importance-sampling leave-one-out cross-validation (Vehtari, Gelman and Gabry 2017; loo::loo with r_eff =
     1) of a result under the model it was sampled from, or another one of the same parameters, with the Pareto k of every
     observation: the arguments of waic(); a LooResult, or a LooBatch for an McmcBatch with a model_batch.  The S x n matrix of
     pointwise log-likelihoods is never formed: the device selects the M largest importance ratios of every observation exactly
-    (csrc/diag_loo.hpp)."""
+    (csrc/diag_loo.hpp; a pointwise_fun: csrc/diag_pointwise.hpp, its fn sweeps a subsample and then all draws once, and nine
+    more times where an observation needs the exact fallback)."""
     from .convergence import _window
     from .mcmc import McmcBatch
+    from .models import PointwiseFun
+    _no_batch_pointwise(x, model, "loo")
     if isinstance(x, McmcBatch):
         return loo_batch(x, model, autoburnin)
     model = _waic_model(model)
+    if block_rows is not None and not isinstance(model, PointwiseFun):
+        raise ValueError("block_rows applies to a pointwise_fun only: a family is evaluated inside the kernel")
     dc = _as_device_chains(x)
     row0, N = _window(dc.iters) if autoburnin else (0, int(dc.nrows))
     Cn = int(dc._samples.shape[0])
-    point, total, _work, _tail = enqueue_loo_groups(dc, model.device_model(dc._samples.device), 1, Cn, row0, N)
-    th = total[0].cpu().numpy()
-    _raise_bad_loo_draws(th)
+    if isinstance(model, PointwiseFun):
+        point, total, _work, _tail = enqueue_pointwise(dc, model, row0, N, block_rows, "loo")
+        th = total[0].cpu().numpy()
+        _raise_bad_fun_draws(th[10])
+    else:
+        point, total, _work, _tail = enqueue_loo_groups(dc, model.device_model(dc._samples.device), 1, Cn, row0, N)
+        th = total[0].cpu().numpy()
+        _raise_bad_loo_draws(th)
     return LooResult(point[0].cpu().numpy(), th, Cn * N, point[0])
 
 

@@ -692,6 +692,52 @@ int fmcmc_loo_groups_dev(const fmcmc_model* m0, int64_t x_stride, int64_t y_stri
                          double* work, double* point /* [G][n][6] */, double* tail /* [G][n][M] or NULL */,
                          double* total /* [G][12] */, void* hip_stream);
 
+/* ---- WAIC and PSIS-LOO of a user-defined model: the pointwise log-likelihood as a batched callback -----------------------------
+ * Batched pointwise log-likelihood: ll[b][i] = log p(y_i | theta[b][0..k-1]) for b < B, i < n, the likelihood alone (no prior),
+ * row-major.  The rules of fmcmc_logpost_fn: theta and ll are DEVICE pointers (theta is read-only), the function is called on
+ * the calling host thread, its work is enqueued on hip_stream or it synchronises before returning; 0 = ok, anything else
+ * abandons the call with FMCMC_ERR_FUN, and fmcmc_last_error() names the pass ("fold"; "sample", "collect", "histogram 0" ..
+ * "histogram 7", "second collect"), the block (0-based within the pass) and the code. */
+typedef int (*fmcmc_pointwise_fn)(const double* theta /* [B][k] */, int64_t B, int32_t k, int64_t n,
+                                  double* ll /* [B][n], row-major */, void* hip_stream, void* user);
+
+/* fmcmc_waic_dev / fmcmc_loo_dev with the family replaced by `fun` and its n >= 1 observations: the draws, the window, the plan of
+ * parts (fmcmc_waic_parts, fmcmc_loo_plan) and the layouts and meanings of point, tail and total are theirs, with bad_draws = the
+ * draws with a parameter that is not finite (no sigma is known here); an l that is NaN makes its observation a bad_point, an l
+ * of -Inf is a draw of likelihood zero.  1 <= k <= FMCMC_MAX_K.
+ * The S' x n matrix is never stored.  The draws are taken block after block: a block is a run of consecutive units (WAIC's tile
+ * of 16 rows of one chain, u = c T + t, the last tile of a chain shorter), gathered into a row-major [B][k] buffer, handed to
+ * `fun`, and the [B][n] block it fills is read once before the next one overwrites it.  block_rows bounds B: it is rounded up to
+ * whole units; 0 is the library's choice, fmcmc_pointwise_block_rows(n, nchains, N, 0): b = 2^25 / (16 n) units (a block of
+ * about 256 MiB), all U units where b >= U, else b rounded down to whole parts of the plan where a part fits, else max(1, b).
+ * Every floating sum has an order that (nchains, N, n) alone decide: point, tail and total hold the same bits
+ * for every block_rows, on every call, wherever the window sits in `samples`.
+ * fmcmc_waic_fun_dev: one sweep of `fun` over the S' draws (pass "fold"); kernels and callbacks are enqueued on hip_stream and
+ *   nothing is synchronised.
+ * fmcmc_loo_fun_dev: `fun` on the rows of the plan's subsample only (pass "sample": out[3] rows of fmcmc_loo_plan), the threshold,
+ *   one sweep over all draws ("collect"), the flags.  Then the call SYNCHRONISES hip_stream once, to read how many observations
+ *   are flagged: with none (the common case) the finish follows; otherwise eight more sweeps ("histogram d") and a last one
+ *   ("second collect"), which use the flagged observations' columns only.  That is the only synchronisation.
+ * work: device scratch of fmcmc_*_fun_work_len(n, nchains, N, block_rows) doubles (0 for arguments the call refuses; the same
+ *   block_rows as the call's): a count per unit, the partials [parts][n][4], the accumulators carried from block to block
+ *   [2][4][6][n], the two buffers [B][FMCMC_MAX_K] and [B][n]; for LOO then the subsample, the buffers, the state words at
+ *   fmcmc_loo_fun_state_offset(...) + 8 i (as for fmcmc_loo_state_offset; -1 for arguments the call refuses) and the histograms
+ *   of fmcmc_loo_dev.  A call does not depend on what work held.
+ * Argument errors are found before any device call and leave their text in fmcmc_last_error(); `samples` is only read; nothing
+ * is written past the documented lengths.  After FMCMC_ERR_FUN point, tail and total hold nothing of meaning; the next call is
+ * not affected. */
+int64_t fmcmc_pointwise_block_rows(int64_t n, int64_t nchains, int64_t N, int64_t block_rows);
+int64_t fmcmc_waic_fun_work_len(int64_t n, int64_t nchains, int64_t N, int64_t block_rows);
+int fmcmc_waic_fun_dev(fmcmc_pointwise_fn fun, void* user, int64_t n, const double* samples, int64_t nchains, int32_t k,
+                       int64_t S, int64_t row0, int64_t N, int64_t block_rows, double* work,
+                       double* point /* [n][4] */, double* total /* [10] */, void* hip_stream);
+int64_t fmcmc_loo_fun_work_len(int64_t n, int64_t nchains, int64_t N, int64_t block_rows);
+int64_t fmcmc_loo_fun_state_offset(int64_t n, int64_t nchains, int64_t N, int64_t block_rows);
+int fmcmc_loo_fun_dev(fmcmc_pointwise_fn fun, void* user, int64_t n, const double* samples, int64_t nchains, int32_t k,
+                      int64_t S, int64_t row0, int64_t N, int64_t block_rows, double* work,
+                      double* point /* [n][6] */, double* tail /* [n][M] or NULL */, double* total /* [12] */,
+                      void* hip_stream);
+
 /* Materialises the canonical Philox stream of a call in device memory, in the FED layout of fmcmc_run:
  * logu[C][nsteps] (entry i-1 = log accept-uniform of loop step i), z[C][nsteps][kz] (N(0,1) when student_df == 0;
  * Student-t with student_df degrees of freedom when student_df > 0 -- kernel_ram: kf for the default qfun rt(k, k),
