@@ -308,6 +308,12 @@ class DeviceChains:
         from .summary import loo
         return loo(self, model, autoburnin, block_rows)
 
+    def predict(self, model, newdata=None, probs=(0.025, 0.5, 0.975), kind="epred", autoburnin=False):
+        """Fitted values (newdata None) or predictions at new covariates under `model` (a gaussian_linreg / logistic object), with
+        their sd and credible band per point: a PredictResult."""
+        from .summary import predict
+        return predict(self, model, newdata, probs, kind, autoburnin)
+
     def rank_scores(self, fold=False, cols=None):
         """The rank-normalised scores behind rhat(), a device tensor [p][2 C][N // 2] (for rank plots)."""
         from .summary import rank_scores

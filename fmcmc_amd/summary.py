@@ -2501,3 +2501,209 @@ def loo_compare(a, b):
     """The difference of two models on the same observations, as loo::loo_compare forms it: the arithmetic of waic_compare on
     column 0 (elpd_loo_i) of the pointwise arrays.  Two LooResult (or loo_host results) give two numbers, two LooBatch arrays [D]."""
     return waic_compare(a, b)
+
+
+# ------------------------------------------------------------------------------------------------ predict()
+PREDICT_KINDS = {"linpred": abi.PREDICT_LINPRED, "epred": abi.PREDICT_EPRED}
+PREDICT_POINT = ("mean", "sd", "sd_pred", "mean_eta")           # the head of a row of `point`, before the quantiles
+
+
+def _predict_model(model):
+    """a gaussian_linreg or logistic object, as it is; anything else cannot be predicted from"""
+    from .models import BatchedFun, LogPosterior, PointwiseFun
+    if isinstance(model, (BatchedFun, PointwiseFun)):
+        raise TypeError("predict() needs one of the regression families (gaussian_linreg, logistic): a %s says nothing of a new "
+                        "point, and a prediction callback is not implemented." % type(model).__name__)
+    if not isinstance(model, LogPosterior):
+        raise TypeError("predict() needs a gaussian_linreg or logistic object; got a %s" % type(model).__name__)
+    if model.family == abi.FAM_IID_NORMAL:
+        raise ValueError("iid_normal has no covariates to predict at: its mean and sd are columns of summary().")
+    return model
+
+
+def _predict_probs(probs):
+    probs = tuple(float(q) for q in np.atleast_1d(np.asarray(() if probs is None else probs, dtype=np.float64)))
+    if len(probs) > abi.SUMMARY_MAX_PROBS:
+        raise ValueError("at most %d probs per call; got %d" % (abi.SUMMARY_MAX_PROBS, len(probs)))
+    for q in probs:
+        if not (np.isfinite(q) and 0.0 <= q <= 1.0):
+            raise ValueError("probs must lie in [0, 1]; got %r" % q)
+    return probs
+
+
+def _predict_kind(kind):
+    if kind not in PREDICT_KINDS:
+        raise ValueError("kind must be \"linpred\" or \"epred\"; got %r" % (kind,))
+    return kind
+
+
+def _predict_newdata(model, newdata):
+    """newdata as a float64 matrix [m][p], the model's own X for None"""
+    if newdata is None:
+        return model.X if model.p else np.zeros((int(model.y.shape[0]), 0))
+    Xn = np.asarray(newdata, dtype=np.float64)
+    if Xn.ndim == 1:
+        Xn = Xn[:, None] if model.p == 1 else Xn[None, :]
+    if Xn.ndim != 2 or Xn.shape[1] != model.p:
+        raise ValueError("newdata has %s column(s) but the model has p = %d covariates"
+                         % (Xn.shape[1] if Xn.ndim == 2 else "shape %s, not" % (Xn.shape,), model.p))
+    if Xn.shape[0] < 1:
+        raise ValueError("newdata has no rows")
+    return Xn
+
+
+def _expit(eta):
+    """1 / (1 + exp(-eta)) in the branch form of the device: exp of a non-positive argument only"""
+    with np.errstate(all="ignore"):
+        e = np.exp(-np.abs(eta))
+        return np.where(eta >= 0, 1 / (1 + e), e / (1 + e))
+
+
+def predict_host(model, draws, newdata=None, probs=(0.025, 0.5, 0.975), kind="epred", dtype=np.float64):
+    """The plain numpy restatement of predict() on draws [S][k]: the CPU reference and the documentation of the definition
+    (INTEGRATION.md §2.2).  With dtype = np.longdouble it is the truth the tests hold the device to.  Returns a namespace with
+    mean, sd, sd_pred (None for the logistic family), mean_eta, quantiles [m][nprobs], point [m][4 + nprobs] (the device's
+    layout), eta [S][m], ndraws and bad_draws, all in `dtype`."""
+    model, kind, probs = _predict_model(model), _predict_kind(kind), _predict_probs(probs)
+    Xn = _predict_newdata(model, newdata).astype(dtype)
+    th = np.asarray(draws, dtype=dtype)
+    if th.ndim != 2 or th.shape[1] != model.k:
+        raise ValueError("draws must be [S][%d] for this family; got shape %s" % (model.k, th.shape))
+    S, m = th.shape[0], Xn.shape[0]
+    if S < 2:
+        raise ValueError("a prediction needs at least 2 draws; got %d" % S)
+    ic, p = int(model.intercept), model.p
+    gauss = model.family == abi.FAM_GAUSSIAN_LINREG
+    eta = np.zeros((S, m), dtype=dtype)
+    if ic:
+        eta = eta + th[:, :1]
+    if p:
+        eta = eta + th[:, ic:ic + p] @ Xn.T
+    sig = not gauss and kind == "epred"
+    q = _expit(eta) if sig else eta
+
+    def moments(v):
+        with np.errstate(all="ignore"):
+            mean = v[0] + (v - v[:1]).sum(axis=0) / dtype(S)       # (shifted by the first draw: equal draws give it back)
+            return mean, ((v - mean[None, :]) ** 2).sum(axis=0) / dtype(S - 1)
+
+    mean, var = moments(q)
+    mean_eta, var_eta = moments(eta) if sig else (mean, var)
+    with np.errstate(all="ignore"):
+        sd = np.sqrt(var)
+        sd_pred = np.sqrt(var_eta + (th[:, -1] ** 2).sum() / dtype(S)) if gauss else None
+    quant = np.zeros((m, len(probs)), dtype=dtype)
+    if probs:
+        srt = np.sort(eta, axis=0)
+        index, lo, hi = type7_ranks(S, probs)
+        os_ = np.stack([srt[lo - 1].T, srt[hi - 1].T], axis=-1)     # [m][nprobs][2]
+        if sig:
+            os_ = _expit(os_)
+        if dtype is np.float64:
+            quant = type7_quantiles(os_, S, probs)
+        else:                                                        # type7_quantiles' rule in `dtype`
+            h = (index - lo).astype(dtype)
+            with np.errstate(invalid="ignore", over="ignore"):
+                mixed = (1 - h) * os_[..., 0] + h * os_[..., 1]
+            quant = np.where((index > lo) & (os_[..., 1] != os_[..., 0]), mixed, os_[..., 0])
+    third = sd_pred if gauss else np.full(m, np.nan, dtype=dtype)
+    point = np.concatenate([np.stack([mean, sd, third, mean_eta], axis=1), quant], axis=1)
+    return SimpleNamespace(mean=mean, sd=sd, sd_pred=sd_pred, mean_eta=mean_eta, quantiles=quant, point=point, eta=eta, probs=probs,
+                           kind=kind, ndraws=S, bad_draws=_bad_draws(model, th))
+
+
+class PredictResult:
+    """predict() of a result: per point mean and sd of the fitted value (kind "epred": E[y | x], "linpred": the linear predictor),
+    sd_pred = the sd of the posterior predictive of a new y at the point (Gaussian family; None for the logistic one), quantiles
+    [m][nprobs] at probs (the credible band), mean_eta; ndraws = the S draws, npoints = m.  point_dev is the device tensor
+    [m][4 + nprobs] = {mean, sd, sd_pred, mean of eta, quantiles} they were copied from."""
+
+    def __init__(self, point, probs, kind, ndraws, gauss, point_dev=None):
+        self.probs = tuple(float(q) for q in probs)
+        point = np.asarray(point, dtype=np.float64).reshape(-1, 4 + len(self.probs))
+        self.mean, self.sd, self.mean_eta = point[:, 0].copy(), point[:, 1].copy(), point[:, 3].copy()
+        self.sd_pred = point[:, 2].copy() if gauss else None
+        self.quantiles = point[:, 4:].copy()
+        self.kind, self.ndraws, self.npoints, self.point_dev = kind, int(ndraws), int(point.shape[0]), point_dev
+
+    quantile_names = property(lambda self: ["%g%%" % (100.0 * q) for q in self.probs])
+
+    def __str__(self):
+        m = self.npoints
+        rows = np.arange(m) if m <= 20 else np.concatenate([np.arange(10), np.arange(m - 10, m)])
+        cols, names = [self.mean, self.sd], ["Mean", "SD"]
+        if self.sd_pred is not None:
+            cols.append(self.sd_pred)
+            names.append("SD pred")
+        matrix = np.concatenate([np.stack(cols, axis=1), self.quantiles], axis=1)[rows]
+        table = _fmt_table(["[%d]" % (i + 1) for i in rows], names + self.quantile_names, matrix).split("\n")
+        if m > 20:
+            table.insert(11, "...")
+        out = ["", "Prediction (%s) at %d point%s from %d draws" % (self.kind, m, "" if m == 1 else "s", self.ndraws), ""]
+        return "\n".join(out + table) + "\n"
+
+    def __repr__(self):
+        return "<PredictResult kind=%s npoints=%d nprobs=%d>" % (self.kind, self.npoints, len(self.probs))
+
+
+def enqueue_predict(dc, dm, row0, N, kind, probs):
+    """The one call site of fmcmc_predict_dev (current torch stream): the window [row0, row0 + N) of the rows of `dc` at the
+    points of the device model dm (its X; y is not read).  Returns the device tensors (point [m][4 + nprobs], total [4], work);
+    nothing is synchronised."""
+    import torch
+    o = _open(dc, None, "predict from")
+    if dm.device != o.dev and (dm.device.index is not None or dm.device.type != o.dev.type):
+        raise ValueError("the model's data are on %s, the draws on %s" % (dm.device, o.dev))
+    if o.k != dm.k:
+        raise ValueError("the result has k = %d parameters, the model's family has %d" % (o.k, dm.k))
+    if row0 < 0 or N < 1 or row0 + N > dc.nrows:
+        raise ValueError("the window [%d, %d) is outside the %d kept rows" % (row0, row0 + N, dc.nrows))
+    if o.Cn * int(N) < 2:
+        raise ValueError("a prediction needs at least 2 draws; got %d" % (o.Cn * int(N)))
+    cm = dm.c()
+    probs_h = np.ascontiguousarray(probs, dtype=np.float64)
+    nwork = o.L.fmcmc_predict_work_len(C.byref(cm), o.Cn, int(N), len(probs))
+    if nwork < 1:
+        _waic_rc(abi.ERR_ARG)
+    point = torch.full((dm.n, 4 + len(probs)), float("nan"), dtype=torch.float64, device=o.dev)
+    total = torch.full((4,), float("nan"), dtype=torch.float64, device=o.dev)
+    work = _doubles(o, nwork)
+    with torch.cuda.device(o.dev):
+        rc = o.L.fmcmc_predict_dev(C.byref(cm), o.smp.data_ptr(), o.Cn, o.k, o.cap, int(row0), int(N), PREDICT_KINDS[kind],
+                                   probs_h.ctypes.data_as(C.POINTER(C.c_double)), len(probs), work.data_ptr(), point.data_ptr(),
+                                   total.data_ptr(), _stream(o.dev))
+    _waic_rc(rc)
+    return point, total, work
+
+
+def predict(x, model, newdata=None, probs=(0.025, 0.5, 0.975), kind="epred", autoburnin=False):
+    """What the fitted model says at a point: x a DeviceChains (read in place), an Mcmc or a McmcList (uploaded first), model the
+    gaussian_linreg or logistic object it was sampled from (or another one of the same parameters), newdata [m][p] the new
+    covariates (None: the model's own X, the fitted values).  Per point the mean and sd of the linear predictor (kind "linpred")
+    or of E[y | x] ("epred": the same for the Gaussian family, the probability for the logistic one), the type-7 quantiles at
+    probs (at most 16) and, Gaussian, the sd of the posterior predictive of a new y: a PredictResult.  With `autoburnin` the rows
+    are coda's window (the second half).  The S x m matrix is never formed: the device folds tiles of it and selects the exact
+    order statistics (csrc/diag_predict.hpp).  An McmcBatch is taken per dataset: predict(ans[d], models[d], ...)."""
+    from .convergence import _window
+    from .engine import DeviceModel
+    from .mcmc import McmcBatch
+    if isinstance(x, McmcBatch):
+        raise TypeError("predict() takes one dataset at a time (the grouped form is not implemented): call "
+                        "predict(ans[d], models[d], ...) per dataset.")
+    model, kind, probs = _predict_model(model), _predict_kind(kind), _predict_probs(probs)
+    Xn = None if newdata is None else _predict_newdata(model, newdata)
+    dc = _as_device_chains(x)
+    dev = dc._samples.device
+    if Xn is None:
+        dm = model.device_model(dev)
+    else:                                              # (the model's constructor path; the user's model object is not touched)
+        dm = DeviceModel(model.family, Xn if model.p else None, np.zeros(Xn.shape[0]), model.intercept, model.guard,
+                         model.prior_div, device=dev)
+    row0, N = _window(dc.iters) if autoburnin else (0, int(dc.nrows))
+    Cn = int(dc._samples.shape[0])
+    point, total, _work = enqueue_predict(dc, dm, row0, N, kind, probs)
+    th = total.cpu().numpy()
+    if th[1] != 0:
+        raise ValueError("%d draw(s) with a parameter that is not finite or a sigma that is not > 0 among the rows to predict from"
+                         % int(th[1]))
+    return PredictResult(point.cpu().numpy(), probs, kind, Cn * N, model.family == abi.FAM_GAUSSIAN_LINREG, point)

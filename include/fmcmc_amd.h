@@ -738,6 +738,36 @@ int fmcmc_loo_fun_dev(fmcmc_pointwise_fn fun, void* user, int64_t n, const doubl
                       double* point /* [n][6] */, double* tail /* [n][M] or NULL */, double* total /* [12] */,
                       void* hip_stream);
 
+/* ---- Fitted values, predictions at new covariates and their credible bands, the device part -------------------------------------
+ * The definition is INTEGRATION.md 2.2 (fmcmc_amd/summary.py: predict_host is its executable form).  Draws and window as for
+ * fmcmc_waic_dev; S' = nchains N >= 2 (at most 2^31 - 1).  m: FMCMC_FAM_GAUSSIAN_LINREG or FMCMC_FAM_LOGISTIC; m->X is the DEVICE
+ * pointer to the new points Xn in the model's own layout [p][n] (n = m->n points), m->intercept applies, m->y is not read.
+ * FMCMC_FAM_IID_NORMAL has no covariates: FMCMC_ERR_UNSUPPORTED.
+ *   eta[s][i] = (b0_s) + sum_j Xn[i][j] beta_sj, the fma chain of v_mfma_f64_16x16x4 over (b0, beta) . (1, x_i);
+ *   kind 0 (linpred): q = eta; kind 1 (epred): q = eta (Gaussian), q = 1 / (1 + exp(-eta)) (logistic; with e = fmh_exp(-|eta|):
+ *   1 / (1 + e) for eta >= 0, e / (1 + e) below).
+ * point (device, [n][4 + nprobs]) = {mean_i and sd_i of q over the draws (divisor S' - 1), sd_pred_i = sqrt(var_i(eta) + mean_s
+ *   sigma_s^2) (the sd of the posterior predictive of a new y at x_i; NaN for the logistic family), the mean of eta, and the
+ *   type-7 quantiles of q at probs[0 .. nprobs)}: the two neighbouring order statistics are EXACTLY what a full sort of the
+ *   device's own eta gives, ties included; they are mapped to q first and then interpolated, (1 - h) lo + h hi in two rounded
+ *   products and one rounded sum, lo itself where h = 0 or hi == lo.  probs is a HOST array, read during the call; nprobs <= 16.
+ * total (device, [4]) = {S', bad_draws (a coefficient that is not finite, Gaussian: a sigma that is not > 0), the mean of
+ *   sigma^2 (NaN for the logistic family), 0}.  A call with bad_draws > 0 is not repaired: its numbers mean nothing.
+ * The draws are split into parts as for fmcmc_waic_dev with n := m->n (fmcmc_waic_parts); partial {count, mean, M2} are merged
+ * by Chan's update in a fixed order and the order statistics are selected on integer keys (integer atomics only): the same bits
+ * on every call and every gfx950, wherever the window sits in `samples`; the row of a point does not depend on the other points
+ * of a call while both calls have n <= 1024 or both n > 1024.
+ * work: device scratch of fmcmc_predict_work_len(m, nchains, N, nprobs) doubles (0 for arguments the call refuses; needs no
+ *   device): two sums per 256 draws, the partials [min(256, ceil(U / 32))][n][4], two 8-byte state words per point and rank
+ *   ([n][2 nprobs][2]) and the 256-bin histograms of min(2 nprobs, 8) ranks per point (the ranks are selected in batches of 8,
+ *   each batch in eight passes over all draws).  Never smaller for a larger N, n or nprobs.  A call does not depend on what work held.
+ * Every kernel is enqueued on hip_stream; nothing is synchronised, `samples` and the model are only read, nothing is written
+ * past the documented lengths.  Argument errors are found before any device call and leave their text in fmcmc_last_error(). */
+int64_t fmcmc_predict_work_len(const fmcmc_model* m, int64_t nchains, int64_t N, int32_t nprobs);
+int fmcmc_predict_dev(const fmcmc_model* m /* X = Xn [p][m->n]; y not read */, const double* samples, int64_t nchains, int32_t k,
+                      int64_t S, int64_t row0, int64_t N, int32_t kind, const double* probs /* host */, int32_t nprobs,
+                      double* work, double* point /* [n][4 + nprobs] */, double* total /* [4] */, void* hip_stream);
+
 /* Materialises the canonical Philox stream of a call in device memory, in the FED layout of fmcmc_run:
  * logu[C][nsteps] (entry i-1 = log accept-uniform of loop step i), z[C][nsteps][kz] (N(0,1) when student_df == 0;
  * Student-t with student_df degrees of freedom when student_df > 0 -- kernel_ram: kf for the default qfun rt(k, k),
