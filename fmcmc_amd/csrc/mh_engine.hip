@@ -1045,6 +1045,18 @@ int fmcmc_detmath_dev(int which, const double* x, double* out, int64_t n, uint64
   return hipGetLastError() == hipSuccess ? FMCMC_OK : FMCMC_ERR_DEVICE;
 }
 
+// The host build of the same text, for the codes whose host twin is not in the CPU oracle (11, 12: fmh_pnorm_both).
+int fmcmc_detmath_host(int which, const double* x, double* out, int64_t n) {
+  if (which != 11 && which != 12) { set_err("fmcmc_detmath_host: which = %d; 11 (Phi) or 12 (1 - Phi)", which); return FMCMC_ERR_ARG; }
+  if (n > 0 && (!x || !out)) { set_err("fmcmc_detmath_host: null argument"); return FMCMC_ERR_ARG; }
+  for (int64_t i = 0; i < n; i++) {
+    double lo, up;
+    fmh_pnorm_both(x[i], &lo, &up);
+    out[i] = which == 11 ? lo : up;
+  }
+  return FMCMC_OK;
+}
+
 // The kernel arrays the host side needs (fixed, lb, ub; scale of the uniform kernels; scheme_seq) and a copy of the kernel
 // pointing at them.  `fixed`, `lb`, `ub` (and scale / scheme_seq where they are checked) live on the device.  A caller that
 // passes their host copies (fmcmc_kernel.h_*) gets a call that only enqueues work; otherwise the few bytes are read back,

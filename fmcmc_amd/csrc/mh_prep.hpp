@@ -25,7 +25,9 @@ __global__ void detmath_kernel(int which, const double* x, double* out, long lon
     case 8: r = 1.0 / v; break;
     case 9: r = fmh_logit_g(v); break;   // g(|v|), the per-observation term of the logistic family
     case 10: r = fmh_unif(seed, (unsigned)(i & 0xffff), (unsigned)(i >> 16), (unsigned)(i % 7)); break;
-    case 12: r = fmh_tan_0_halfpi(v); break;
+    case 11: { double up; fmh_pnorm_both(v, &r, &up); break; }   // Phi(v)
+    case 12: { double lo; fmh_pnorm_both(v, &lo, &r); break; }   // 1 - Phi(v)
+    case 13: r = fmh_tan_0_halfpi(v); break;
     default: r = fmh_nan();
   }
   out[i] = r;

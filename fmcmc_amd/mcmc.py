@@ -314,6 +314,12 @@ class DeviceChains:
         from .summary import predict
         return predict(self, model, newdata, probs, kind, autoburnin)
 
+    def predictive(self, model, newdata=None, y=None, probs=(0.025, 0.5, 0.975), autoburnin=False, max_passes=100):
+        """The posterior predictive distribution of a new observation y at every point under `model` (a gaussian_linreg object):
+        its quantiles at probs (prediction intervals) and the PIT of the given y: a PredictiveResult."""
+        from .summary import predictive
+        return predictive(self, model, newdata, y, probs, autoburnin, max_passes)
+
     def rank_scores(self, fold=False, cols=None):
         """The rank-normalised scores behind rhat(), a device tensor [p][2 C][N // 2] (for rank plots)."""
         from .summary import rank_scores

@@ -2707,3 +2707,312 @@ def predict(x, model, newdata=None, probs=(0.025, 0.5, 0.975), kind="epred", aut
         raise ValueError("%d draw(s) with a parameter that is not finite or a sigma that is not > 0 among the rows to predict from"
                          % int(th[1]))
     return PredictResult(point.cpu().numpy(), probs, kind, Cn * N, model.family == abi.FAM_GAUSSIAN_LINREG, point)
+
+
+# ------------------------------------------------------------------------------------------------ predictive()
+PREDICTIVE_BATCH = 8                    # csrc/diag_predictive.hpp: PDV_BATCH
+PNORM_REL = 5.73e-16                         # include/fmh_detmath.h: FMH_PNORM_REL
+NDTR_REL = 8 * 2.0 ** -52               # budget of scipy.special.ndtr in predictive_host (Cephes: a few ulp in either tail)
+# The rounds of predictive(): passes enqueued before `total` is read (the one synchronisation of a round).  predictive_host on the
+# families of tests/predictive_cases.py: a near-normal posterior finishes every (point, prob) in 2 to 4 passes, so the first round
+# is 4; what is left then is a hard case (chains that disagree: up to about 30 passes), and later rounds take 8 at a time.
+PREDICTIVE_ROUNDS = (4, 8)
+_EPS = 2.0 ** -52
+
+
+def predictive_tol(nchains, N, n, probs):
+    """tol(p) = c eps min(p, 1 - p) of fmcmc_predictive_dev and c itself: csrc/diag_predictive.hpp: pdv_c, the same line"""
+    upp, nparts = waic_parts(nchains, N, n)
+    U = int(nchains) * ((int(N) + 15) // 16)
+    c = 0.5 * (4 * min(upp, U) + 3 + (nparts - 1) + 2) + 2.0 * PNORM_REL / _EPS
+    pr = np.asarray(probs, dtype=np.float64)
+    return c * _EPS * np.where(pr > 0.5, 1.0 - pr, pr), c
+
+
+def predictive_host_tol(S, probs):
+    """the same for predictive_host's own sums: numpy adds the S rows of a column one after the other (S - 1 additions), then the
+    division and the subtraction; a term carries NDTR_REL"""
+    c = 0.5 * (int(S) - 1 + 2) + NDTR_REL / _EPS
+    pr = np.asarray(probs, dtype=np.float64)
+    return c * _EPS * np.where(pr > 0.5, 1.0 - pr, pr), c
+
+
+def _predictive_model(model):
+    from .models import BatchedFun, LogPosterior, PointwiseFun
+    if isinstance(model, (BatchedFun, PointwiseFun)):
+        raise TypeError("predictive() needs a gaussian_linreg object: a %s says nothing of a new observation, and a predictive "
+                        "callback is not implemented; simulate y from to_host() draws instead." % type(model).__name__)
+    if not isinstance(model, LogPosterior):
+        raise TypeError("predictive() needs a gaussian_linreg object; got a %s" % type(model).__name__)
+    if model.family == abi.FAM_LOGISTIC:
+        raise ValueError("the predictive distribution of a logistic y is Bernoulli(q) with q the mean of E[y | x]: call "
+                         "predict(x, model, newdata, kind=\"epred\") and read its mean.")
+    if model.family == abi.FAM_IID_NORMAL:
+        raise ValueError("iid_normal has no covariates to predict at: its mean and sd are columns of summary().")
+    return model
+
+
+def _predictive_probs(probs):
+    probs = tuple(float(q) for q in np.atleast_1d(np.asarray(() if probs is None else probs, dtype=np.float64)))
+    if len(probs) > abi.SUMMARY_MAX_PROBS:
+        raise ValueError("at most %d probs per call; got %d" % (abi.SUMMARY_MAX_PROBS, len(probs)))
+    for q in probs:
+        if not (0.0 < q < 1.0):
+            raise ValueError("probs must lie strictly inside (0, 1): the predictive distribution has no least or largest value; "
+                             "got %r" % q)
+    return probs
+
+
+def _predictive_y(model, newdata, y, m):
+    """the values to take the PIT at: the model's own y for the model's own points, else what was given (or None)"""
+    if y is None:
+        return np.asarray(model.y, dtype=np.float64) if newdata is None else None
+    y = np.asarray(y, dtype=np.float64).ravel()
+    if y.shape[0] != m:
+        raise ValueError("y has %d entries but there are %d points" % (y.shape[0], m))
+    return y
+
+
+def predictive_cdf_host(eta, sigma, t, dtype=np.float64):
+    """(F, 1 - F) [m][...] of the mixture at t [m][...]: Phi by scipy.special.ndtr per element in float64 (of u formed in
+    `dtype`), the two means over the S draws in `dtype`, each a direct sum.  eta [S][m], sigma [S]."""
+    from scipy.special import ndtr
+    t = np.asarray(t, dtype=dtype)
+    S, m = eta.shape
+    lower, upper = np.zeros(t.shape, dtype=dtype), np.zeros(t.shape, dtype=dtype)
+    tt = t.reshape(m, -1)
+    lo2, up2 = lower.reshape(m, -1), upper.reshape(m, -1)
+    rs = (1 / np.asarray(sigma, dtype=dtype))[:, None]
+    with np.errstate(all="ignore"):
+        for j in range(tt.shape[1]):
+            u = ((tt[None, :, j] - np.asarray(eta, dtype=dtype)) * rs).astype(np.float64)
+            lo2[:, j] = ndtr(u).astype(dtype).sum(axis=0) / dtype(S)
+            up2[:, j] = ndtr(-u).astype(dtype).sum(axis=0) / dtype(S)
+    return lower, upper
+
+
+def predictive_host(model, draws, newdata=None, y=None, probs=(0.025, 0.5, 0.975), dtype=np.float64, max_passes=100):
+    """The plain numpy restatement of predictive() on draws [S][k]: the executable definition, the same
+    brackets, the same step rule and the same two stopping criteria as csrc/diag_predictive.hpp, with Phi from scipy.special.ndtr
+    and the sums of numpy in `dtype`.  Returns a namespace: mean, sd_pred, quantiles [m][nprobs], pit, pit_upper (None without y),
+    converged, passes, residual (g at the returned t), width (of the final bracket), lo0, hi0 (the bracket at pass 0), tol
+    [nprobs], eta [S][m], sigma [S], ndraws, bad_draws."""
+    from scipy.special import ndtr, ndtri
+    model, probs = _predictive_model(model), _predictive_probs(probs)
+    Xn = _predict_newdata(model, newdata).astype(dtype)
+    th = np.asarray(draws, dtype=dtype)
+    if th.ndim != 2 or th.shape[1] != model.k:
+        raise ValueError("draws must be [S][%d] for this family; got shape %s" % (model.k, th.shape))
+    S, m = th.shape[0], Xn.shape[0]
+    if S < 2:
+        raise ValueError("a prediction needs at least 2 draws; got %d" % S)
+    yv = _predictive_y(model, newdata, y, m)
+    ic, p, nprobs = int(model.intercept), model.p, len(probs)
+    eta = np.zeros((S, m), dtype=dtype)
+    if ic:
+        eta = eta + th[:, :1]
+    if p:
+        eta = eta + th[:, ic:ic + p] @ Xn.T
+    sigma = th[:, -1]
+    with np.errstate(all="ignore"):
+        rs = (1 / sigma)[:, None]
+        mean = eta[0] + (eta - eta[:1]).sum(axis=0) / dtype(S)
+        var = ((eta - mean[None, :]) ** 2).sum(axis=0) / dtype(S - 1)
+        sd_pred = np.sqrt(var + (sigma ** 2).sum() / dtype(S))
+    pr = np.asarray(probs, dtype=np.float64)
+    upper_side = pr > 0.5
+    side = np.where(upper_side, 1.0 - pr, pr).astype(dtype)
+    tol = predictive_host_tol(S, pr)[0].astype(dtype)
+    z = ndtri(pr).astype(dtype)
+    mn, mx, smin, smax = eta.min(axis=0), eta.max(axis=0), sigma.min(), sigma.max()
+    with np.errstate(all="ignore"):
+        lo = mn[:, None] + z[None, :] * np.where(z < 0, smax, smin)[None, :]
+        hi = mx[:, None] + z[None, :] * np.where(z < 0, smin, smax)[None, :]
+        pad = dtype(2.0 ** -46) * (np.abs(z) * smax)[None, :] + dtype(2.0 ** -50) * np.maximum(np.abs(lo), np.abs(hi))
+        lo, hi = lo - pad, hi + pad
+        t = np.clip(mean[:, None] + sd_pred[:, None] * z[None, :], lo, hi)
+    lo0, hi0 = lo.copy(), hi.copy()
+    g = np.full((m, nprobs), np.nan, dtype=dtype)
+    done = np.zeros((m, nprobs), dtype=np.int64)
+    w1 = np.full((m, nprobs), np.inf, dtype=dtype)
+    w2 = w1.copy()
+    inv_sqrt_2pi = dtype(0.3989422804014327)
+    with np.errstate(all="ignore"):
+        for npass in range(1, int(max_passes) + 1):
+            if nprobs == 0 or done.all():
+                break
+            for j in range(nprobs):
+                a = np.flatnonzero(done[:, j] == 0)
+                if a.size == 0:
+                    continue
+                u = (t[None, a, j] - eta[:, a]) * rs
+                u64 = u.astype(np.float64)
+                tail = ndtr(-u64 if upper_side[j] else u64).astype(dtype).sum(axis=0) / dtype(S)
+                f = (np.exp(-0.5 * u * u) * inv_sqrt_2pi * rs).sum(axis=0) / dtype(S)
+                gj = side[j] - tail if upper_side[j] else tail - side[j]
+                gprev = g[a, j]
+                g[a, j] = gj
+                fin = np.abs(gj) <= tol[j]
+                tj, loj, hij = t[a, j], lo[a, j], hi[a, j]
+                loj = np.where(~fin & (gj < 0), tj, loj)
+                hij = np.where(~fin & ~(gj < 0), tj, hij)
+                w = hij - loj
+                narrow = ~fin & (w <= 2 * np.spacing(np.maximum(np.abs(loj), np.abs(hij)).astype(np.float64)))
+                tn = tj - gj / f
+                stalled = (w > 0.5 * w2[a, j]) & (np.abs(gj) > 0.5 * np.abs(gprev))
+                newton = (f > 0) & (tn > loj) & (tn < hij) & ~stalled
+                tn = np.where(newton, tn, loj + 0.5 * w)
+                go = ~fin & ~narrow
+                lo[a, j], hi[a, j] = loj, hij
+                tf = tj - gj / f                                     # (finished by |g| <= tol: the last correction is applied)
+                t[a, j] = np.where(go, tn, np.where(fin & (f > 0) & (tf > loj) & (tf < hij), tf, tj))
+                w2[a, j] = np.where(go, w1[a, j], w2[a, j])
+                w1[a, j] = np.where(go, w, w1[a, j])
+                done[a, j] = np.where(go, 0, npass)
+    pit = pit_upper = None
+    if yv is not None:
+        pit, pit_upper = predictive_cdf_host(eta, sigma, yv.astype(dtype), dtype)
+    return SimpleNamespace(mean=mean, sd_pred=sd_pred, quantiles=t, pit=pit, pit_upper=pit_upper, converged=done > 0, passes=done,
+                           residual=g, width=hi - lo, lo0=lo0, hi0=hi0, tol=tol, eta=eta, sigma=sigma, probs=probs, ndraws=S,
+                           bad_draws=_bad_draws(model, th), y=yv)
+
+
+class PredictiveResult:
+    """predictive() of a result: per point the mean and sd (sd_pred) of the posterior predictive distribution of a new observation
+    y, its quantiles [m][nprobs] at probs (the prediction band), pit = F(y) and pit_upper = 1 - F(y) of the given y (None without
+    y), and for every quantile converged, passes (the evaluation pass at which it finished, 0: not yet) and residual (g = F - p
+    at the returned value); ndraws = the S draws, npoints = m, total_passes = the passes that were run.  point_dev is the device
+    tensor [m][4 + 4 nprobs] they were copied from."""
+
+    def __init__(self, point, probs, ndraws, y=None, total_passes=0, point_dev=None):
+        self.probs = tuple(float(q) for q in probs)
+        npr = len(self.probs)
+        point = np.asarray(point, dtype=np.float64).reshape(-1, 4 + 4 * npr)
+        self.mean, self.sd_pred = point[:, 0].copy(), point[:, 1].copy()
+        self.y = None if y is None else np.asarray(y, dtype=np.float64).copy()
+        self.pit = None if y is None else point[:, 2].copy()
+        self.pit_upper = None if y is None else point[:, 3].copy()
+        per = point[:, 4:].reshape(point.shape[0], npr, 4)
+        self.quantiles, self.residual, self.width = per[:, :, 0].copy(), per[:, :, 1].copy(), per[:, :, 2].copy()
+        self.passes = per[:, :, 3].astype(np.int64)
+        self.converged = self.passes > 0
+        self.ndraws, self.npoints, self.total_passes, self.point_dev = int(ndraws), int(point.shape[0]), int(total_passes), point_dev
+
+    quantile_names = property(lambda self: ["%g%%" % (100.0 * q) for q in self.probs])
+
+    def coverage(self, lower_prob, upper_prob):
+        """the share of the given y inside [quantile at lower_prob, quantile at upper_prob] (both among probs)"""
+        if self.y is None:
+            raise ValueError("coverage() needs the y that predictive() was given")
+        try:
+            a, b = self.probs.index(float(lower_prob)), self.probs.index(float(upper_prob))
+        except ValueError:
+            raise ValueError("coverage(%r, %r): both must be among probs = %r" % (lower_prob, upper_prob, self.probs)) from None
+        return float(((self.quantiles[:, a] <= self.y) & (self.y <= self.quantiles[:, b])).mean())
+
+    def __str__(self):
+        m = self.npoints
+        rows = np.arange(m) if m <= 20 else np.concatenate([np.arange(10), np.arange(m - 10, m)])
+        cols, names = [self.mean, self.sd_pred], ["Mean", "SD pred"]
+        if self.pit is not None:
+            cols.append(self.pit)
+            names.append("PIT")
+        matrix = np.concatenate([np.stack(cols, axis=1), self.quantiles], axis=1)[rows]
+        table = _fmt_table(["[%d]" % (i + 1) for i in rows], names + self.quantile_names, matrix).split("\n")
+        if m > 20:
+            table.insert(11, "...")
+        out = ["", "Posterior predictive of y at %d point%s from %d draws (%d pass%s)"
+               % (m, "" if m == 1 else "s", self.ndraws, self.total_passes, "" if self.total_passes == 1 else "es"), ""]
+        left = int((~self.converged).sum())
+        tail = ["", "%d quantile(s) not converged" % left] if left else []
+        return "\n".join(out + table + tail) + "\n"
+
+    def __repr__(self):
+        return "<PredictiveResult npoints=%d nprobs=%d passes=%d>" % (self.npoints, len(self.probs), self.total_passes)
+
+
+def enqueue_predictive(dc, dm, row0, N, probs, npasses, with_y=True, state=None):
+    """The one call site of fmcmc_predictive_dev (current torch stream): `npasses` evaluation passes on the window [row0, row0 + N)
+    of the rows of `dc` at the points of the device model dm (its X; its y for the PIT when with_y).  state: the (point, total,
+    work) that a previous call with the same arguments returned: the call resumes from it.  Returns the device tensors (point
+    [m][4 + 4 nprobs], total [6], work); nothing is synchronised."""
+    import torch
+    o = _open(dc, None, "predict from")
+    if dm.device != o.dev and (dm.device.index is not None or dm.device.type != o.dev.type):
+        raise ValueError("the model's data are on %s, the draws on %s" % (dm.device, o.dev))
+    if o.k != dm.k:
+        raise ValueError("the result has k = %d parameters, the model's family has %d" % (o.k, dm.k))
+    if row0 < 0 or N < 1 or row0 + N > dc.nrows:
+        raise ValueError("the window [%d, %d) is outside the %d kept rows" % (row0, row0 + N, dc.nrows))
+    if o.Cn * int(N) < 2:
+        raise ValueError("a prediction needs at least 2 draws; got %d" % (o.Cn * int(N)))
+    cm = dm.c()
+    if not with_y:
+        cm.y = None
+    probs_h = np.ascontiguousarray(probs, dtype=np.float64)
+    if state is None:
+        nwork = o.L.fmcmc_predictive_work_len(C.byref(cm), o.Cn, int(N), len(probs))
+        if nwork < 1:
+            _waic_rc(abi.ERR_ARG)
+        point = torch.full((dm.n, 4 + 4 * len(probs)), float("nan"), dtype=torch.float64, device=o.dev)
+        total = torch.full((6,), float("nan"), dtype=torch.float64, device=o.dev)
+        work = _doubles(o, nwork)
+    else:
+        point, total, work = state
+    with torch.cuda.device(o.dev):
+        rc = o.L.fmcmc_predictive_dev(C.byref(cm), o.smp.data_ptr(), o.Cn, o.k, o.cap, int(row0), int(N),
+                                      probs_h.ctypes.data_as(C.POINTER(C.c_double)), len(probs), int(npasses),
+                                      0 if state is None else 1, work.data_ptr(), point.data_ptr(), total.data_ptr(),
+                                      _stream(o.dev))
+    _waic_rc(rc)
+    return point, total, work
+
+
+def predictive(x, model, newdata=None, y=None, probs=(0.025, 0.5, 0.975), autoburnin=False, max_passes=100):
+    """What the fitted model says of a new OBSERVATION: x a DeviceChains (read in place), an Mcmc or a McmcList (uploaded first),
+    model the gaussian_linreg object it was sampled from, newdata [m][p] the new covariates (None: the model's own X), y the
+    values to take the probability integral transform at (None: the model's own y for the model's own points, no PIT for
+    newdata).  Per point the mean and sd of the posterior predictive distribution, its quantiles at probs (at most 16, strictly
+    inside (0, 1)): R's predict(lm, interval = "prediction") for the posterior, the PIT of y and, through
+    PredictiveResult.coverage(), the share of y inside an interval.  The predictive distribution is the mixture of the S normals
+    N(eta_si, sigma_s^2); its quantiles are found by a bracketed Newton iteration on the device (csrc/diag_predictive.hpp), the
+    S x m matrix is never formed and nothing is simulated.  The passes are enqueued in rounds (PREDICTIVE_ROUNDS); after each the
+    count of unfinished quantiles is read; what is unfinished after max_passes is returned with converged = False and a
+    warning.  An McmcBatch is taken per dataset: predictive(ans[d], models[d], ...)."""
+    import warnings
+    from .convergence import _window
+    from .engine import DeviceModel
+    from .mcmc import McmcBatch
+    if isinstance(x, McmcBatch):
+        raise TypeError("predictive() takes one dataset at a time (the grouped form is not implemented): call "
+                        "predictive(ans[d], models[d], ...) per dataset.")
+    model, probs = _predictive_model(model), _predictive_probs(probs)
+    if int(max_passes) < 1:
+        raise ValueError("max_passes must be at least 1; got %r" % (max_passes,))
+    Xn = None if newdata is None else _predict_newdata(model, newdata)
+    m = int(model.y.shape[0]) if Xn is None else int(Xn.shape[0])
+    yv = _predictive_y(model, newdata, y, m)
+    dc = _as_device_chains(x)
+    dev = dc._samples.device
+    if Xn is None and y is None:
+        dm = model.device_model(dev)
+    else:                                              # (the model's constructor path; the user's model object is not touched)
+        Xp = (model.X if Xn is None else Xn) if model.p else None
+        dm = DeviceModel(model.family, Xp, np.zeros(m) if yv is None else yv, model.intercept, model.guard, model.prior_div,
+                         device=dev)
+    row0, N = _window(dc.iters) if autoburnin else (0, int(dc.nrows))
+    Cn = int(dc._samples.shape[0])
+    state, used, left = None, 0, None
+    while used < int(max_passes) and left != 0:
+        n = min(PREDICTIVE_ROUNDS[0] if state is None else PREDICTIVE_ROUNDS[1], int(max_passes) - used)
+        state = enqueue_predictive(dc, dm, row0, N, probs, n, yv is not None, state)
+        used += n
+        th = state[1].cpu().numpy()
+        if th[1] != 0:
+            raise ValueError("%d draw(s) with a parameter that is not finite or a sigma that is not > 0 among the rows to predict "
+                             "from" % int(th[1]))
+        left = int(th[5])
+    if left:
+        warnings.warn("predictive(): %d of %d quantiles had not converged after max_passes = %d evaluation passes; they are "
+                      "returned with converged = False" % (left, m * len(probs), int(max_passes)), RuntimeWarning, stacklevel=2)
+    return PredictiveResult(state[0].cpu().numpy(), probs, Cn * N, yv, used, state[0])

@@ -768,6 +768,41 @@ int fmcmc_predict_dev(const fmcmc_model* m /* X = Xn [p][m->n]; y not read */, c
                       int64_t S, int64_t row0, int64_t N, int32_t kind, const double* probs /* host */, int32_t nprobs,
                       double* work, double* point /* [n][4 + nprobs] */, double* total /* [4] */, void* hip_stream);
 
+/* ---- The posterior predictive distribution of a new observation y at a point: quantiles and PIT, the device part ----------------
+ * The definition is INTEGRATION.md 2.2 (fmcmc_amd/summary.py: predictive_host is its executable form).  Draws, window and eta as
+ * for fmcmc_predict_dev; S' = nchains N >= 2 (at most 2^31 - 1).  m: FMCMC_FAM_GAUSSIAN_LINREG only; m->X is the DEVICE pointer
+ * to the points Xn [p][n], m->y the DEVICE pointer to the n values to take the PIT at, or NULL.  FMCMC_FAM_LOGISTIC (the
+ * predictive distribution of its y is Bernoulli(mean of epred), which fmcmc_predict_dev returns) and FMCMC_FAM_IID_NORMAL:
+ * FMCMC_ERR_UNSUPPORTED.
+ *   F_i(t) = (1 / S') sum_s Phi((t - eta_si) / sigma_s), Phi = fmh_pnorm_both (include/fmh_detmath.h); u = (t - eta) (1 / sigma).
+ *   The quantile at p is the root of g(t) = F_i(t) - p; for p > 1/2 the upper tails are summed and g = (1 - p) - (1 - F_i)(t).
+ * point (device, [n][4 + 4 nprobs]) = {mean_i of eta, sd_pred_i = sqrt(var_i(eta) + mean_s sigma_s^2) (both as fmcmc_predict_dev
+ *   defines them), pit_i = F_i(y_i), pit_upper_i = 1 - F_i(y_i) (two direct sums; NaN without m->y), then per prob: t (the
+ *   quantile, or the last iterate), g at t, the width hi - lo of the bracket, the pass at which it finished (0: not yet)}.
+ *   A (point, prob) is finished when |g| <= c 2^-52 min(p, 1 - p), c the rounding budget of the sum (csrc/diag_predictive.hpp:
+ *   pdv_c; a function of the plan), or when the bracket is no wider than 2 ulp of its larger end.
+ * total (device, [6]) = {S', bad_draws (as fmcmc_predict_dev), the mean of sigma^2, min sigma, max sigma, the count of (point,
+ *   prob) not yet finished}.  A call with bad_draws > 0 is not repaired: its numbers mean nothing.
+ * probs: a HOST array, read during the call; nprobs <= 16 (0: the PIT and the head alone), each strictly inside (0, 1).
+ * npasses >= 1 evaluation passes are enqueued, each one sweep over all draws per batch of 8 probs (a workgroup whose points are all
+ *   finished returns at once).  resume = 0 starts: the draw pass, the fold, the brackets, the PIT.  resume = 1 continues from
+ *   the state that a previous call left in `work`: the caller passes the same arguments and the same `work`; two calls of 4 passes
+ *   give the bits of one call of 8.
+ * The draws are split into parts as for fmcmc_waic_dev with n := m->n; every sum has a fixed order, there are no floating-point
+ * atomics: the same bits on every call and every gfx950, wherever the window sits in `samples`; the row of a point does not
+ * depend on the other points of a call while both calls have n <= 1024 or both n > 1024.
+ * work: device scratch of fmcmc_predictive_work_len(m, nchains, N, nprobs) doubles (0 for arguments the call refuses; needs no
+ *   device): four values per 256 draws, 1 / sigma per draw, the fold's partials [parts][n][4], a head [n][4], the state
+ *   [n][nprobs + 1][8], the evaluation's partials [parts][n][8][2] and the PIT's [parts][n][2].  A call with resume = 0 does not
+ *   depend on what work held.
+ * Every kernel is enqueued on hip_stream; nothing is synchronised, `samples` and the model are only read, nothing is written
+ * past the documented lengths.  Argument errors are found before any device call and leave their text in fmcmc_last_error(). */
+int64_t fmcmc_predictive_work_len(const fmcmc_model* m, int64_t nchains, int64_t N, int32_t nprobs);
+int fmcmc_predictive_dev(const fmcmc_model* m /* X = Xn [p][m->n]; y [m->n] or NULL */, const double* samples, int64_t nchains,
+                         int32_t k, int64_t S, int64_t row0, int64_t N, const double* probs /* host */, int32_t nprobs,
+                         int32_t npasses, int32_t resume, double* work, double* point /* [n][4 + 4 nprobs] */,
+                         double* total /* [6] */, void* hip_stream);
+
 /* Materialises the canonical Philox stream of a call in device memory, in the FED layout of fmcmc_run:
  * logu[C][nsteps] (entry i-1 = log accept-uniform of loop step i), z[C][nsteps][kz] (N(0,1) when student_df == 0;
  * Student-t with student_df degrees of freedom when student_df > 0 -- kernel_ram: kf for the default qfun rt(k, k),
@@ -780,9 +815,13 @@ int fmcmc_rng_stream_dev(uint64_t seed, int64_t step_base, int64_t chain_base, i
 
 /* Diagnostic: evaluate the canonical math / RNG primitives on the device, element-wise
  * (which: 0 log, 1 exp, 2 log1p, 3 qnorm, 4 log accept-u, 5 normal, 6 student-t(df=x), 7 sqrt,
- * 8 reciprocal, 9 fused log1p(exp(x)) for x <= 0, 10 uniform variate). Used by tests to prove host/device bit-equality of include/fmh_*.h. */
+ * 8 reciprocal, 9 fused log1p(exp(x)) for x <= 0, 10 uniform variate, 11 Phi(x) and 12 1 - Phi(x) of fmh_pnorm_both,
+ * 13 tan on [0, pi/2]). Used by tests to prove host/device bit-equality of include/fmh_*.h.
+ * fmcmc_detmath_host: the host build of the same text for which = 11 and 12 (x and out are host arrays; needs no device); the
+ * other codes have their host twin in the CPU oracle. */
 int fmcmc_detmath_dev(int which, const double* x, double* out, int64_t n, uint64_t seed,
                       void* hip_stream);
+int fmcmc_detmath_host(int which, const double* x, double* out, int64_t n);
 
 #ifdef __cplusplus
 }

@@ -301,4 +301,92 @@ FMH_HD double fmh_qnorm(double p) {
   return (q < 0.0) ? -val : val;
 }
 
+/* Standard normal distribution function, both tails at once: *lower = Phi(x), *upper = 1 - Phi(x) = Phi(-x), each with a RELATIVE
+ * accuracy, down to the smallest subnormal (Phi(-38.4) ~ 1e-323).  Cody (1969), "Rational Chebyshev approximations for the error
+ * function", Math. Comp. 23, in the three ranges of |x| of his Algorithm 715 (the routine behind R's pnorm), restated with
+ * fma-Horner sums:
+ *   y <= 0.67448975   Phi(x) = 1/2 + x R1(x^2), R1 of degree (4, 4): both tails by one addition each;
+ *   y <= sqrt(32)     Phi(-y) = exp(-y^2 / 2) R2(y), R2 of degree (8, 8);
+ *   y <  39           Phi(-y) = exp(-y^2 / 2) (1 / sqrt(2 pi) - R3(1 / y^2) / y^2) / y, R3 of degree (5, 5); beyond: 0 and 1.
+ * exp(-y^2 / 2) would carry the rounding of y^2 (half an ulp of up to 760) into the result; with ysq = trunc(16 y) / 16 the square
+ * ysq^2 is exact (at most 20 bits), del = (y - ysq) (y + ysq) is small, and exp(-y^2 / 2) = exp(-ysq^2 / 2) exp(-del / 2).
+ * The far tail is 1 - near tail: an error of 2^-53 absolute there.  lower(x) and upper(-x) are the same operations on the same
+ * values: equal bit for bit.  NaN gives NaN twice.  *ex, where it is not NULL, receives exp(-x^2 / 2) by the same split (the
+ * density's numerator: a Newton step on Phi wants it and two of the three ranges have it anyway).
+ * Measured against 50-digit arithmetic (tests/test_pnorm_host.py): see FMH_PNORM_REL. */
+#define FMH_INV_SQRT_2PI 0.398942280401432677939946059934
+/* the largest relative error of the smaller-than-1/2 tail found by tests/test_pnorm_host.py on its grid (normal results; a
+ * subnormal result is held to one spacing of the subnormals); the test asserts twice this, and so does everything that budgets
+ * an evaluation of fmh_pnorm_both (csrc/diag_predictive.hpp: the constant c of the convergence test) */
+#define FMH_PNORM_REL 5.73e-16
+FMH_HD double fmh_exp_mhalf_sq_(double y) { /* exp(-y^2 / 2), 0 <= y < 39 */
+  const double ysq = __builtin_trunc(y * 16.0) * 0.0625;
+  const double del = (y - ysq) * (y + ysq);
+  return fmh_exp(-ysq * ysq * 0.5) * fmh_exp(-del * 0.5);
+}
+FMH_HD void fmh_pnorm_ex(double x, double* lower, double* upper, double* ex) {
+  const double y = fmh_abs(x);
+  double near, far, e;   /* near: the tail on x's side of 0 seen from -|x|, i.e. Phi(-y); far = Phi(y) */
+  if (fmh_isnan(x)) { *lower = x; *upper = x; if (ex) *ex = x; return; }
+  if (y <= 0.67448975) {
+    const double xsq = y > 1.11e-16 ? x * x : 0.0;
+    double num = fmh_fma(FMH_K(0.065682337918207449113), xsq, FMH_K(2.2352520354606839287));
+    num = fmh_fma(num, xsq, FMH_K(161.02823106855587881));
+    num = fmh_fma(num, xsq, FMH_K(1067.6894854603709582));
+    num = fmh_fma(num, xsq, FMH_K(18154.981253343561249));
+    double den = xsq + FMH_K(47.20258190468824187);
+    den = fmh_fma(den, xsq, FMH_K(976.09855173777669322));
+    den = fmh_fma(den, xsq, FMH_K(10260.932208618978205));
+    den = fmh_fma(den, xsq, FMH_K(45507.789335026729956));
+    const double t = x * num / den;
+    *lower = 0.5 + t;
+    *upper = 0.5 - t;
+    if (ex) *ex = fmh_exp_mhalf_sq_(y);
+    return;
+  }
+  if (y >= 39.0) {
+    near = 0.0; far = 1.0; e = 0.0;
+  } else {
+    double t;
+    if (y <= 5.656854249492380195206754896838) {
+      double num = fmh_fma(FMH_K(1.0765576773720192317e-8), y, FMH_K(0.39894151208813466764));
+      num = fmh_fma(num, y, FMH_K(8.8831497943883759412));
+      num = fmh_fma(num, y, FMH_K(93.506656132177855979));
+      num = fmh_fma(num, y, FMH_K(597.27027639480026226));
+      num = fmh_fma(num, y, FMH_K(2494.5375852903726711));
+      num = fmh_fma(num, y, FMH_K(6848.1904505362823326));
+      num = fmh_fma(num, y, FMH_K(11602.651437647350124));
+      num = fmh_fma(num, y, FMH_K(9842.7148383839780218));
+      double den = y + FMH_K(22.266688044328115691);
+      den = fmh_fma(den, y, FMH_K(235.38790178262499861));
+      den = fmh_fma(den, y, FMH_K(1519.377599407554805));
+      den = fmh_fma(den, y, FMH_K(6485.558298266760755));
+      den = fmh_fma(den, y, FMH_K(18615.571640885098091));
+      den = fmh_fma(den, y, FMH_K(34900.952721145977266));
+      den = fmh_fma(den, y, FMH_K(38912.003286093271411));
+      den = fmh_fma(den, y, FMH_K(19685.429676859990727));
+      t = num / den;
+    } else {
+      const double r = 1.0 / (y * y);
+      double num = fmh_fma(FMH_K(0.02307344176494017303), r, FMH_K(0.21589853405795699));
+      num = fmh_fma(num, r, FMH_K(0.1274011611602473639));
+      num = fmh_fma(num, r, FMH_K(0.022235277870649807));
+      num = fmh_fma(num, r, FMH_K(0.001421619193227893466));
+      num = fmh_fma(num, r, FMH_K(2.9112874951168792e-5));
+      double den = r + FMH_K(1.28426009614491121);
+      den = fmh_fma(den, r, FMH_K(0.468238212480865118));
+      den = fmh_fma(den, r, FMH_K(0.0659881378689285515));
+      den = fmh_fma(den, r, FMH_K(0.00378239633202758244));
+      den = fmh_fma(den, r, FMH_K(7.29751555083966205e-5));
+      t = (FMH_K(FMH_INV_SQRT_2PI) - r * num / den) / y;
+    }
+    e = fmh_exp_mhalf_sq_(y);
+    near = e * t;
+    far = 1.0 - near;
+  }
+  if (ex) *ex = e;
+  if (x < 0.0) { *lower = near; *upper = far; } else { *lower = far; *upper = near; }
+}
+FMH_HD void fmh_pnorm_both(double x, double* lower, double* upper) { fmh_pnorm_ex(x, lower, upper, (double*)0); }
+
 #endif /* FMH_DETMATH_H */
