@@ -41,7 +41,7 @@ EXPORTS = ["fmcmc_abi_version", "fmcmc_last_error", "fmcmc_last_kernel", "fmcmc_
            "fmcmc_rank_ess_groups_work_len", "fmcmc_rank_ess_groups_out_len", "fmcmc_rank_ess_groups_dev",
            "fmcmc_waic_part_rows", "fmcmc_waic_parts", "fmcmc_waic_work_len", "fmcmc_waic_dev", "fmcmc_waic_groups_dev",
            "fmcmc_loo_tail_len", "fmcmc_loo_plan", "fmcmc_loo_work_len", "fmcmc_loo_state_offset", "fmcmc_loo_dev",
-           "fmcmc_loo_groups_dev",
+           "fmcmc_loo_groups_dev", "fmcmc_loo_predictive_work_len", "fmcmc_loo_predictive_dev",
            "fmcmc_pointwise_block_rows", "fmcmc_waic_fun_work_len", "fmcmc_waic_fun_dev", "fmcmc_loo_fun_work_len",
            "fmcmc_loo_fun_state_offset", "fmcmc_loo_fun_dev", "fmcmc_predict_work_len", "fmcmc_predict_dev",
            "fmcmc_predictive_work_len", "fmcmc_predictive_dev", "fmcmc_detmath_host"]
@@ -282,6 +282,11 @@ def lib():
         L.fmcmc_loo_groups_dev.argtypes = [C.POINTER(Model), C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
                                            C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p]
+        L.fmcmc_loo_predictive_work_len.restype = C.c_int64
+        L.fmcmc_loo_predictive_work_len.argtypes = [C.POINTER(Model), C.c_int64, C.c_int64]
+        L.fmcmc_loo_predictive_dev.restype = C.c_int
+        L.fmcmc_loo_predictive_dev.argtypes = [C.POINTER(Model), C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         for name in ("fmcmc_pointwise_block_rows", "fmcmc_waic_fun_work_len", "fmcmc_loo_fun_work_len",
                      "fmcmc_loo_fun_state_offset"):
             getattr(L, name).restype = C.c_int64

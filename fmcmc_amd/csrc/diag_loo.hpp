@@ -26,7 +26,8 @@
 //   loo_finish_kernel            a workgroup an observation: bitonic sort of the buffer (descending, keys, in place), so that
 //                                nothing depends on the order in which the atomics appended; the tail, the cutoff, the
 //                                leftovers folded in sorted order, the generalised-Pareto fit (G x M log1p terms, the tail in
-//                                LDS), the smoothing and the six numbers of `point`.
+//                                LDS), the smoothing and the six numbers of `point`; where the internal launcher is given `lw`
+//                                (diag_loo_predictive.hpp), the capped log weights of the tail ranks as well.
 //   loo_total_kernel             a workgroup a group: sums, standard errors, the Pareto-k counts.
 // The plan (loo_plan) is a function of (chains per group, N, n) alone; counts are integers; every floating sum has a fixed
 // order: the same bits on every call, wherever the window sits and whichever groups share the call.
@@ -102,6 +103,7 @@ struct LooArgs {
   WaicArgs W;
   LooPlan L;
   double* point; double* tail; double* total;
+  double* lw = nullptr;                 // [n][M] or null: the capped log weights of the tail ranks, ascending (diag_loo_predictive.hpp)
   double tau;
   int pass, only;
 };
@@ -454,6 +456,7 @@ __global__ __launch_bounds__(LOO_T) void loo_finish_kernel(LooArgs Q) {
       lw = fmh_log(ecut + sigma * expm1(-kpar * fmh_log1p(-p)) / kpar);
     }
     lw = lw < 0.0 ? lw : 0.0;
+    if (Q.lw) Q.lw[go * M + j] = lw;
     const double e = fmh_exp(lw);
     t0 += fmh_exp(lw - tl);
     t1 += e;
@@ -545,7 +548,7 @@ int loo_launch_tiles(const char* who, const LooArgs& Q, unsigned G, unsigned gy,
 
 int loo_run(const char* who, const fmcmc_model* m0, int64_t x_stride, int64_t y_stride, const double* samples, int64_t ngroups,
             int64_t chains_per_group, int32_t k, int64_t S, int64_t row0, int64_t N, const int32_t* active, double* work,
-            double* point, double* tail, double* total, void* hip_stream) {
+            double* point, double* tail, double* lw, double* total, void* hip_stream) {
   if (!work || !point || !total) return fail(FMCMC_ERR_ARG, "%s: null argument", who);
   int rc = loo_check(who, m0, x_stride, y_stride, samples, ngroups, chains_per_group, k, S, row0, N);
   if (rc != FMCMC_OK) return rc;
@@ -557,7 +560,7 @@ int loo_run(const char* who, const fmcmc_model* m0, int64_t x_stride, int64_t y_
   A.k = k;
   A.P = waic_plan(m0, ngroups, chains_per_group, N);
   Q.L = loo_plan(A.P, ngroups, chains_per_group, N, m0->n);
-  Q.point = point; Q.tail = tail; Q.total = total;
+  Q.point = point; Q.tail = tail; Q.lw = lw; Q.total = total;
   const double dS = (double)(chains_per_group * N), tau = 1.0 - 1.0 / log10(dS);
   Q.tau = tau < 0.7 ? tau : 0.7;
   Q.pass = 0; Q.only = 0;
@@ -635,12 +638,13 @@ int fmcmc_loo_groups_dev(const fmcmc_model* m0, int64_t x_stride, int64_t y_stri
                          int64_t chains_per_group, int32_t k, int64_t S, int64_t row0, int64_t N, const int32_t* active,
                          double* work, double* point, double* tail, double* total, void* hip_stream) {
   return loo_run("fmcmc_loo_groups_dev", m0, x_stride, y_stride, samples, ngroups, chains_per_group, k, S, row0, N, active, work,
-                 point, tail, total, hip_stream);
+                 point, tail, nullptr, total, hip_stream);
 }
 
 int fmcmc_loo_dev(const fmcmc_model* m, const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N,
                   double* work, double* point, double* tail, double* total, void* hip_stream) {
-  return loo_run("fmcmc_loo_dev", m, 0, 0, samples, 1, nchains, k, S, row0, N, nullptr, work, point, tail, total, hip_stream);
+  return loo_run("fmcmc_loo_dev", m, 0, 0, samples, 1, nchains, k, S, row0, N, nullptr, work, point, tail, nullptr, total,
+                 hip_stream);
 }
 
 }  // extern "C"

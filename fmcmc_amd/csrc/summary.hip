@@ -825,6 +825,7 @@ int fmcmc_autocov_dev(const double* samples, int64_t nchains, int32_t k, int64_t
 
 #include "diag_waic.hpp"   // fmcmc_waic_dev, fmcmc_waic_groups_dev (block_sum and diag_common.hpp come from above)
 #include "diag_loo.hpp"    // fmcmc_loo_dev, fmcmc_loo_groups_dev (the plan, the draw kernel and the checks of diag_waic.hpp)
+#include "diag_loo_predictive.hpp"   // fmcmc_loo_predictive_dev (the whole call of diag_loo.hpp, then one more sweep of its tiles)
 #include "diag_pointwise.hpp"   // fmcmc_waic_fun_dev, fmcmc_loo_fun_dev (the plans, merges and finishing kernels of the two above)
 #include "diag_predict.hpp"     // fmcmc_predict_dev (the split into parts of diag_waic.hpp, the keys of diag_common.hpp)
 #include "diag_predictive.hpp"  // fmcmc_predictive_dev (the parts of diag_waic.hpp, the Chan merges and the checks of diag_predict.hpp)

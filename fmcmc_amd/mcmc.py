@@ -320,6 +320,12 @@ class DeviceChains:
         from .summary import predictive
         return predictive(self, model, newdata, y, probs, autoburnin, max_passes)
 
+    def loo_predictive(self, model, autoburnin=False):
+        """The leave-one-out predictive mean, sd and PIT of every observation under `model` (a gaussian_linreg / logistic object)
+        from the PSIS weights of loo(): a LooPredictiveResult."""
+        from .summary import loo_predictive
+        return loo_predictive(self, model, autoburnin)
+
     def rank_scores(self, fold=False, cols=None):
         """The rank-normalised scores behind rhat(), a device tensor [p][2 C][N // 2] (for rank plots)."""
         from .summary import rank_scores

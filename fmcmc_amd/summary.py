@@ -3016,3 +3016,240 @@ def predictive(x, model, newdata=None, y=None, probs=(0.025, 0.5, 0.975), autobu
         warnings.warn("predictive(): %d of %d quantiles had not converged after max_passes = %d evaluation passes; they are "
                       "returned with converged = False" % (left, m * len(probs), int(max_passes)), RuntimeWarning, stacklevel=2)
     return PredictiveResult(state[0].cpu().numpy(), probs, Cn * N, yv, used, state[0])
+
+
+# ------------------------------------------------------------------------------------------------ loo_predictive()
+LOO_PREDICTIVE_POINT = ("mean", "sd", "pit", "pareto_k", "n_eff", "elpd_loo")   # the columns of fmcmc_loo_predictive_dev's `point`
+
+
+def _loo_predictive_model(model):
+    """a gaussian_linreg or logistic object, as it is; anything else has no leave-one-out predictive here"""
+    from .models import BatchedFun, LogPosterior, PointwiseFun
+    if isinstance(model, (BatchedFun, PointwiseFun)):
+        raise TypeError("loo_predictive() needs one of the regression families (gaussian_linreg, logistic): a %s says nothing of "
+                        "the mean or the distribution of an observation, and a predictive callback is not implemented."
+                        % type(model).__name__)
+    if not isinstance(model, LogPosterior):
+        raise TypeError("loo_predictive() needs a gaussian_linreg or logistic object; got a %s" % type(model).__name__)
+    if model.family == abi.FAM_IID_NORMAL:
+        raise ValueError("iid_normal has no covariates to predict at: its mean and sd are columns of summary().")
+    return model
+
+
+def _loo_run_means(rs, w, first):
+    """w [S] (the weights of the ascending rs by rank) made a function of the value: over every run of equal rs that reaches
+    rank `first` or beyond, the mean of w (summed in rank order); the ranks below such runs keep their w"""
+    a = int(np.searchsorted(rs, rs[first], side="left"))
+    seg = rs[a:]
+    starts = np.flatnonzero(np.concatenate([[True], seg[1:] != seg[:-1]]))
+    cnt = np.diff(np.append(starts, seg.size))
+    out = w.copy()
+    out[a:] = np.repeat(np.add.reduceat(w[a:], starts) / cnt.astype(w.dtype), cnt)
+    return out
+
+
+def loo_predictive_host_matrix(l, d, sigma=None, dtype=np.float64, y=None):
+    """loo_predictive_host on the matrices themselves, in `dtype`: l [S][n] the pointwise log-likelihoods, d [S][n] = eta - y_i
+    with sigma [S] (Gaussian family; y [n] is added to the mean, 0 without it), or d = eta with sigma None (logistic).
+    Everything up to the smoothing is loo_host_matrix's; the weights are then a function of the VALUE of r = -l (INTEGRATION.md
+    2.2): below the cutoff exp(r - R), above it the mean of exp(min(smoothed_j, 0)) over the tail ranks of that value, at it
+    the mean over the whole run that straddles the boundary.  Returns a namespace: mean, sd, pit (NaN for the logistic family),
+    pareto_k, n_eff, elpd_i (loo's), point [n][6] (the device's layout), sum_w [n] (the sum of the weights), weights [n][S] (in
+    the order of the draws) and loo (loo_host_matrix's result)."""
+    from scipy.special import ndtr
+    l = np.asarray(l, dtype=dtype)
+    d = np.asarray(d, dtype=dtype)
+    if l.ndim != 2 or d.shape != l.shape:
+        raise ValueError("l and d must be matrices [S][n] of one shape; got %s and %s" % (l.shape, d.shape))
+    S, n = l.shape
+    gauss = sigma is not None
+    if gauss:
+        sigma = np.asarray(sigma, dtype=dtype)
+        if sigma.shape != (S,):
+            raise ValueError("sigma must be [%d]; got shape %s" % (S, sigma.shape))
+    lo = loo_host_matrix(l, dtype)
+    M = lo.tail_len
+    nan = dtype(np.nan)
+    mean, sd, pit = (np.full(n, nan, dtype=dtype) for _ in range(3))
+    sum_w, weights = np.zeros(n, dtype=dtype), np.zeros((n, S), dtype=dtype)
+    with np.errstate(all="ignore"):
+        for i in range(n):
+            r = -l[:, i]
+            order = np.argsort(r, kind="stable")
+            rs = r[order]
+            R = lo.tail[i, -1]
+            lam = np.minimum(lo.smoothed[i], dtype(0))
+            w = _loo_run_means(rs, np.exp(np.concatenate([rs[:S - M] - R, lam])), S - M)
+            om = np.empty(S, dtype=dtype)
+            om[order] = w
+            weights[i] = om
+            den = om.sum()
+            sum_w[i] = den
+            di = d[:, i]
+            if gauss:
+                e_d = (om * di).sum() / den
+                e_q = (om * (di * di + sigma * sigma)).sum() / den
+                mean[i] = e_d
+                sd[i] = np.sqrt(e_q - e_d * e_d)
+                phi = ndtr(((-di) * (1 / sigma)).astype(np.float64)).astype(dtype)
+                pit[i] = (om * phi).sum() / den
+            else:
+                q = (om * _expit(di)).sum() / den
+                mean[i] = q
+                sd[i] = np.sqrt(q * (1 - q))
+        if gauss and y is not None:
+            mean = np.asarray(y, dtype=dtype) + mean
+    bad = np.isnan(lo.pointwise[:, [0, 3, 4, 5]]).any(axis=1)
+    mean[bad], sd[bad], pit[bad] = nan, nan, nan
+    point = np.stack([mean, sd, pit, lo.pareto_k, lo.n_eff, lo.pointwise[:, 0]], axis=1)
+    return SimpleNamespace(mean=mean, sd=sd, pit=pit, pareto_k=lo.pareto_k, n_eff=lo.n_eff, elpd_i=lo.pointwise[:, 0], point=point,
+                           sum_w=sum_w, weights=weights, loo=lo, bad_points=int((~np.isfinite(point[:, :2]).all(axis=1)).sum()))
+
+
+def loo_predictive_host(model, draws, dtype=np.float64):
+    """The plain numpy restatement of loo_predictive() on draws [S][k]: the CPU reference and the executable form of the
+    definition.  With dtype = np.longdouble it is the truth the tests hold the device to.  It is
+    waic_loglik and the linear predictor followed by loo_predictive_host_matrix, whose namespace it returns, with y and
+    bad_draws."""
+    model = _loo_predictive_model(model)
+    th = np.asarray(draws, dtype=dtype)
+    l = waic_loglik(model, th, dtype)
+    ic, p = int(model.intercept), model.p
+    y = model.y.astype(dtype)
+    eta = np.zeros(l.shape, dtype=dtype)
+    if ic:
+        eta = eta + th[:, :1]
+    if p:
+        eta = eta + th[:, ic:ic + p] @ model.X.astype(dtype).T
+    if model.family == abi.FAM_GAUSSIAN_LINREG:
+        out = loo_predictive_host_matrix(l, eta - y[None, :], th[:, -1], dtype, y)
+    else:
+        out = loo_predictive_host_matrix(l, eta, None, dtype)
+    out.y, out.bad_draws = y, _bad_draws(model, th)
+    out.loo.bad_draws = out.bad_draws
+    return out
+
+
+class LooPredictiveResult:
+    """loo_predictive() of a result: per observation the leave-one-out predictive mean and sd, pit (the LOO probability integral
+    transform of y_i; NaN for the logistic family, whose mean is the LOO probability of y_i = 1), pareto_k and n_eff, the y they
+    are held against, residuals = y - mean, loo (the LooResult of the same call) and bad_points (the rows that are not
+    finite).  family is "gaussian_linreg" or "logistic"; point_dev the device tensor [n][6] the arrays were copied from."""
+
+    def __init__(self, point, loo_point, total, ndraws, y, family, point_dev=None):
+        point = np.asarray(point, dtype=np.float64).reshape(-1, 6)
+        total = np.asarray(total, dtype=np.float64).reshape(13)
+        self.point, self.point_dev, self.family = point, point_dev, family
+        self.mean, self.sd, self.pit = point[:, 0].copy(), point[:, 1].copy(), point[:, 2].copy()
+        self.pareto_k, self.n_eff = point[:, 3].copy(), point[:, 4].copy()
+        self.loo = LooResult(loo_point, total[:12], ndraws)
+        self.y = np.asarray(y, dtype=np.float64).copy()
+        self.residuals = self.y - self.mean
+        self.bad_points = int(total[12]) if np.isfinite(total[12]) else -1
+        self.ndraws, self.nobs = int(ndraws), int(point.shape[0])
+
+    def _need_pit(self, what):
+        if self.family != "gaussian_linreg":
+            raise ValueError("%s needs the PIT, which the logistic family has none of: its mean is the LOO probability of y = 1"
+                             % what)
+
+    def coverage(self, prob=0.9):
+        """the share of the observations inside the central LOO predictive interval of probability `prob`: those whose pit lies
+        in [(1 - prob) / 2, (1 + prob) / 2]"""
+        self._need_pit("coverage()")
+        prob = float(prob)
+        if not (0.0 < prob < 1.0):
+            raise ValueError("prob must lie strictly inside (0, 1); got %r" % prob)
+        return float(((self.pit >= 0.5 * (1.0 - prob)) & (self.pit <= 0.5 * (1.0 + prob))).mean())
+
+    def pit_hist(self, bins=10):
+        """(counts, edges) of the LOO-PIT values over [0, 1] in `bins` equal bins: flat under a calibrated model"""
+        self._need_pit("pit_hist()")
+        return np.histogram(self.pit[np.isfinite(self.pit)], bins=int(bins), range=(0.0, 1.0))
+
+    def metrics(self):
+        """Gaussian family: rmse, mae and r2 = 1 - sum (y - mean)^2 / sum (y - ybar)^2 of the LOO means; logistic: brier = the
+        mean of (mean - y)^2 and accuracy = the share of y on the side of 1/2 that the LOO probability is on"""
+        e = self.residuals
+        if self.family == "gaussian_linreg":
+            return dict(rmse=float(np.sqrt((e * e).mean())), mae=float(np.abs(e).mean()),
+                        r2=float(1.0 - (e * e).sum() / ((self.y - self.y.mean()) ** 2).sum()))
+        return dict(brier=float((e * e).mean()), accuracy=float(((self.mean > 0.5) == (self.y != 0)).mean()))
+
+    def __str__(self):
+        out = ["", "Leave-one-out predictive checks of %d observations from %d draws (%s)" % (self.nobs, self.ndraws, self.family),
+               ""]
+        m = self.metrics()
+        if self.family == "gaussian_linreg":
+            out += ["%-12s %9.4g" % (k, m[k]) for k in ("rmse", "mae", "r2")]
+            out += ["%-12s %9.3f" % ("coverage %d%%" % round(100 * p), self.coverage(p)) for p in (0.5, 0.9)]
+        else:
+            out += ["%-12s %9.4g" % (k, m[k]) for k in ("brier", "accuracy")]
+        out += ["------", ""]
+        lo = self.loo
+        if lo.n_k_bad == 0:
+            out += ["All Pareto k estimates are good (k < %.2g)." % lo.k_threshold]
+        else:
+            out += ["%d (%.1f%%) Pareto k estimates above %.2g: the LOO expectations of these observations are not to be trusted."
+                    % (lo.n_k_bad, 100.0 * lo.n_k_bad / self.nobs, lo.k_threshold)]
+        if self.bad_points > 0:
+            out += ["%d observation(s) without a finite result" % self.bad_points]
+        return "\n".join(out) + "\n"
+
+    def __repr__(self):
+        return "<LooPredictiveResult %s n=%d max_k=%.3g>" % (self.family, self.nobs, self.loo.max_k)
+
+
+def enqueue_loo_predictive(dc, dm, row0, N):
+    """The one call site of fmcmc_loo_predictive_dev (current torch stream): the window [row0, row0 + N) of the rows of `dc` under
+    the device model dm.  Returns the device tensors (point [n][6], loo_point [n][6], total [13], work); nothing is
+    synchronised."""
+    import torch
+    o = _open(dc, None, "score")
+    if dm.device != o.dev and (dm.device.index is not None or dm.device.type != o.dev.type):
+        raise ValueError("the model's data are on %s, the draws on %s" % (dm.device, o.dev))
+    if o.k != dm.k:
+        raise ValueError("the result has k = %d parameters, the model's family has %d" % (o.k, dm.k))
+    if row0 < 0 or N < 1 or row0 + N > dc.nrows:
+        raise ValueError("the window [%d, %d) is outside the %d kept rows" % (row0, row0 + N, dc.nrows))
+    if o.Cn * int(N) < 2:
+        raise ValueError("LOO needs at least 2 draws; got %d" % (o.Cn * int(N)))
+    M = loo_tail_len(o.Cn * int(N))
+    if M > LOO_MAX_TAIL:
+        raise NotImplementedError("%d draws ask for a tail of %d; supported are tails up to %d" % (o.Cn * int(N), M, LOO_MAX_TAIL))
+    cm = dm.c()
+    nwork = o.L.fmcmc_loo_predictive_work_len(C.byref(cm), o.Cn, int(N))
+    if nwork < 1:
+        _waic_rc(abi.ERR_ARG)
+    point = torch.full((dm.n, 6), float("nan"), dtype=torch.float64, device=o.dev)
+    loo_point = torch.full((dm.n, 6), float("nan"), dtype=torch.float64, device=o.dev)
+    total = torch.full((13,), float("nan"), dtype=torch.float64, device=o.dev)
+    work = _doubles(o, nwork)
+    with torch.cuda.device(o.dev):
+        rc = o.L.fmcmc_loo_predictive_dev(C.byref(cm), o.smp.data_ptr(), o.Cn, o.k, o.cap, int(row0), int(N), work.data_ptr(),
+                                          point.data_ptr(), loo_point.data_ptr(), total.data_ptr(), _stream(o.dev))
+    _waic_rc(rc)
+    return point, loo_point, total, work
+
+
+def loo_predictive(x, model, autoburnin=False):
+    """Leave-one-out predictive checks (loo::E_loo, bayesplot::ppc_loo_pit) of a result under the gaussian_linreg or logistic
+    model it was sampled from: x a DeviceChains (read in place), an Mcmc or a McmcList (uploaded first).  Per observation the
+    LOO predictive mean and sd and, for the Gaussian family, the LOO-PIT of y_i, all expectations under the Pareto-smoothed
+    importance weights of loo(), which is computed in the same call (LooPredictiveResult.loo); coverage(), pit_hist() and
+    metrics() (LOO-R2, RMSE, the Brier score) are derived on the host.  The S x n matrix is never formed
+    (csrc/diag_loo_predictive.hpp).  An McmcBatch is taken per dataset: loo_predictive(ans[d], models[d])."""
+    from .convergence import _window
+    from .mcmc import McmcBatch
+    if isinstance(x, McmcBatch):
+        raise TypeError("loo_predictive() takes one dataset at a time (the grouped form is not implemented): call "
+                        "loo_predictive(ans[d], models[d]) per dataset.")
+    model = _loo_predictive_model(model)
+    dc = _as_device_chains(x)
+    row0, N = _window(dc.iters) if autoburnin else (0, int(dc.nrows))
+    Cn = int(dc._samples.shape[0])
+    point, loo_point, total, _work = enqueue_loo_predictive(dc, model.device_model(dc._samples.device), row0, N)
+    th = total.cpu().numpy()
+    _raise_bad_loo_draws(th)
+    family = "gaussian_linreg" if model.family == abi.FAM_GAUSSIAN_LINREG else "logistic"
+    return LooPredictiveResult(point.cpu().numpy(), loo_point.cpu().numpy(), th, Cn * N, model.y, family, point)

@@ -692,6 +692,32 @@ int fmcmc_loo_groups_dev(const fmcmc_model* m0, int64_t x_stride, int64_t y_stri
                          double* work, double* point /* [G][n][6] */, double* tail /* [G][n][M] or NULL */,
                          double* total /* [G][12] */, void* hip_stream);
 
+/* ---- Leave-one-out predictive checks from the PSIS weights (loo::E_loo, bayesplot::ppc_loo_pit), the device part ------------------
+ * The whole of fmcmc_loo_dev on the same arguments, then one more sweep of the draws; the definition is INTEGRATION.md 2.2
+ * (fmcmc_amd/summary.py: loo_predictive_host is its executable form).  m: FMCMC_FAM_GAUSSIAN_LINREG or FMCMC_FAM_LOGISTIC;
+ * FMCMC_FAM_IID_NORMAL: FMCMC_ERR_UNSUPPORTED.  With lambda_j = min(the smoothed log weight of tail rank j, 0), R the largest r and
+ * c the cutoff, a draw whose r = v is below c weighs exp(v - R); above c, the mean of exp(lambda_j) over the tail ranks whose r
+ * equals v; at c, [sum of exp(lambda_j) over the c_T tail ranks equal to c + (count(c) - c_T) exp(c - R)] / count(c).  "Equal"
+ * is the equality of the device's own r.  E_loo[h] = sum_s omega_s h_s / sum_s omega_s.
+ * point (device, [n][6]) = {mean_i, sd_i, pit_i, pareto_k_i, n_eff_i, elpd_loo_i}: gaussian_linreg, d = eta - y_i: mean_i = y_i +
+ *   E_loo[d], sd_i = sqrt(E_loo[d^2 + sigma^2] - E_loo[d]^2), pit_i = E_loo[Phi(-d (1 / sigma))], Phi the lower tail of
+ *   fmh_pnorm_both; logistic: mean_i = E_loo[expit(eta)], sd_i = sqrt(mean_i (1 - mean_i)), pit_i = NaN.  The last three are
+ *   fmcmc_loo_dev's.  A row whose fmcmc_loo_dev row is NaN, or whose counts of draws above and at the cutoff are not those of the
+ *   tail (the sweep found other r than the selection did), is NaN.
+ * loo_point (device, [n][6], or NULL) and total[0 .. 12): bit for bit what fmcmc_loo_dev writes to point and total on the same
+ *   arguments; total[12] = the rows of `point` whose mean or sd is not finite.  total has 13 entries.
+ * work: device scratch of fmcmc_loo_predictive_work_len(m, nchains, N) doubles (0 for arguments the call refuses; needs no
+ *   device): fmcmc_loo_work_len(m, 1, nchains, N), then the tail, its capped log weights and the run means [3][n][M], 8 n
+ *   doubles, 1 / sigma and sigma^2 per draw (gaussian_linreg) and the partials [parts][n][10].  A call does not depend on what
+ *   work held.
+ * Every kernel is enqueued on hip_stream; nothing is synchronised, there are no floating-point atomics and every sum has a fixed
+ * order: the same bits on every call, wherever the window sits in `samples`.  The checks, their texts and the status codes are
+ * fmcmc_loo_dev's. */
+int64_t fmcmc_loo_predictive_work_len(const fmcmc_model* m, int64_t nchains, int64_t N);
+int fmcmc_loo_predictive_dev(const fmcmc_model* m, const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0,
+                             int64_t N, double* work, double* point /* [n][6] */, double* loo_point /* [n][6] or NULL */,
+                             double* total /* [13] */, void* hip_stream);
+
 /* ---- WAIC and PSIS-LOO of a user-defined model: the pointwise log-likelihood as a batched callback -----------------------------
  * Batched pointwise log-likelihood: ll[b][i] = log p(y_i | theta[b][0..k-1]) for b < B, i < n, the likelihood alone (no prior),
  * row-major.  The rules of fmcmc_logpost_fn: theta and ll are DEVICE pointers (theta is read-only), the function is called on
