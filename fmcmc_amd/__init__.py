@@ -17,9 +17,10 @@ from .summary import (summary, effective_size, McmcSummary, heidel, HeidelDiag, 
                       RhatDiagBatch, ess_batch, EssDiagBatch, waic, waic_batch, waic_compare, waic_host, WaicResult, WaicBatch,
                       loo, loo_batch, loo_compare, loo_host, loo_plan, LooResult, LooBatch, waic_host_matrix,
                       loo_host_matrix, waic_loglik, predict, predict_host, PredictResult, predictive, predictive_host,
-                      PredictiveResult, loo_predictive, loo_predictive_host, loo_predictive_host_matrix, LooPredictiveResult)
+                      PredictiveResult, loo_predictive, loo_predictive_host, loo_predictive_host_matrix, LooPredictiveResult,
+                      ppc, ppc_host, PpcResult, posterior_predict, posterior_predict_selection)
 
-__all__ = ["loo_predictive", "loo_predictive_host", "loo_predictive_host_matrix", "LooPredictiveResult", "predictive", "predictive_host", "PredictiveResult", "predict", "predict_host", "PredictResult", "pointwise_fun", "PointwiseFun", "waic_host_matrix", "loo_host_matrix", "waic_loglik", "loo", "loo_batch", "loo_compare", "loo_host", "loo_plan", "LooResult", "LooBatch", "waic", "waic_batch", "waic_compare", "waic_host", "WaicResult", "WaicBatch", "ess_batch", "EssDiagBatch", "rhat_batch", "RhatDiagBatch", "ess", "EssDiag", "ess_host", "geyer_tau", "rhat", "RhatDiag", "rank_scores", "convergence_rhat", "rhat_host", "MCMC_batch", "McmcBatch", "GelmanDiagBatch", "McmcSummaryBatch", "summary_batch", "bulk_plan", "model_batch", "ModelBatch", "hpd_interval", "HpdInterval", "autocorr_diag", "AutocorrDiag", "crosscorr", "raftery", "raftery_diag", "RafteryDiag", "chain_quantiles", "summary", "effective_size", "McmcSummary", "heidel", "HeidelDiag", "gelman_diag", "GelmanDiag", "MCMC", "MCMC_without_conv_checker", "MCMC_with_conv_checker", "kernel_normal",
+__all__ = ["ppc", "ppc_host", "PpcResult", "posterior_predict", "posterior_predict_selection", "loo_predictive", "loo_predictive_host", "loo_predictive_host_matrix", "LooPredictiveResult", "predictive", "predictive_host", "PredictiveResult", "predict", "predict_host", "PredictResult", "pointwise_fun", "PointwiseFun", "waic_host_matrix", "loo_host_matrix", "waic_loglik", "loo", "loo_batch", "loo_compare", "loo_host", "loo_plan", "LooResult", "LooBatch", "waic", "waic_batch", "waic_compare", "waic_host", "WaicResult", "WaicBatch", "ess_batch", "EssDiagBatch", "rhat_batch", "RhatDiagBatch", "ess", "EssDiag", "ess_host", "geyer_tau", "rhat", "RhatDiag", "rank_scores", "convergence_rhat", "rhat_host", "MCMC_batch", "McmcBatch", "GelmanDiagBatch", "McmcSummaryBatch", "summary_batch", "bulk_plan", "model_batch", "ModelBatch", "hpd_interval", "HpdInterval", "autocorr_diag", "AutocorrDiag", "crosscorr", "raftery", "raftery_diag", "RafteryDiag", "chain_quantiles", "summary", "effective_size", "McmcSummary", "heidel", "HeidelDiag", "gelman_diag", "GelmanDiag", "MCMC", "MCMC_without_conv_checker", "MCMC_with_conv_checker", "kernel_normal",
            "kernel_normal_reflective", "kernel_adapt", "kernel_am", "kernel_ram", "kernel_unif",
            "kernel_unif_reflective", "kernel_nmirror", "kernel_umirror", "gaussian_linreg",
            "logistic", "iid_normal", "batched_fun", "BatchedFun", "convergence_gelman", "convergence_geweke", "convergence_heildel", "convergence_auto",

@@ -44,7 +44,10 @@ EXPORTS = ["fmcmc_abi_version", "fmcmc_last_error", "fmcmc_last_kernel", "fmcmc_
            "fmcmc_loo_groups_dev", "fmcmc_loo_predictive_work_len", "fmcmc_loo_predictive_dev",
            "fmcmc_pointwise_block_rows", "fmcmc_waic_fun_work_len", "fmcmc_waic_fun_dev", "fmcmc_loo_fun_work_len",
            "fmcmc_loo_fun_state_offset", "fmcmc_loo_fun_dev", "fmcmc_predict_work_len", "fmcmc_predict_dev",
-           "fmcmc_predictive_work_len", "fmcmc_predictive_dev", "fmcmc_detmath_host"]
+           "fmcmc_predictive_work_len", "fmcmc_predictive_dev", "fmcmc_detmath_host",
+           "fmcmc_ppc_work_len", "fmcmc_ppc_dev", "fmcmc_ppc_yrep_dev", "fmcmc_ppc_elem_host"]
+PPC_MAX_SEL = 65535            # selected draws of one fmcmc_ppc_yrep_dev call
+PPC_STATS = ("mean", "sd", "min", "max", "chisq")   # the statistics of fmcmc_ppc_dev's counts, in the order of `total`
 PREDICT_LINPRED, PREDICT_EPRED = 0, 1   # fmcmc_predict_dev: kind
 LOO_PLAN_LEN = 16              # FMCMC_LOO_PLAN_LEN
 BATCH_STREAM_DATA = 1          # fmcmc_mcmc_run_batch_*: flags bit, read the datasets from global memory every step
@@ -310,6 +313,19 @@ def lib():
                                            _dp, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.fmcmc_detmath_host.restype = C.c_int
         L.fmcmc_detmath_host.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
+        L.fmcmc_ppc_work_len.restype = C.c_int64
+        L.fmcmc_ppc_work_len.argtypes = [C.POINTER(Model), C.c_int64, C.c_int64]
+        L.fmcmc_ppc_dev.restype = C.c_int
+        L.fmcmc_ppc_dev.argtypes = [C.POINTER(Model), C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                    C.c_uint64, C.c_int64, C.c_int64, C.c_int64, _dp, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]
+        L.fmcmc_ppc_yrep_dev.restype = C.c_int
+        L.fmcmc_ppc_yrep_dev.argtypes = [C.POINTER(Model), C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_uint64, C.c_int64,
+                                         C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64, C.c_void_p,
+                                         C.c_void_p]
+        L.fmcmc_ppc_elem_host.restype = C.c_int
+        L.fmcmc_ppc_elem_host.argtypes = [C.c_int32, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_double,
+                                          C.c_void_p, C.c_void_p]
         L.fmcmc_rng_stream_dev.restype = C.c_int
         L.fmcmc_rng_stream_dev.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                            C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -829,3 +829,4 @@ int fmcmc_autocov_dev(const double* samples, int64_t nchains, int32_t k, int64_t
 #include "diag_pointwise.hpp"   // fmcmc_waic_fun_dev, fmcmc_loo_fun_dev (the plans, merges and finishing kernels of the two above)
 #include "diag_predict.hpp"     // fmcmc_predict_dev (the split into parts of diag_waic.hpp, the keys of diag_common.hpp)
 #include "diag_predictive.hpp"  // fmcmc_predictive_dev (the parts of diag_waic.hpp, the Chan merges and the checks of diag_predict.hpp)
+#include "diag_ppc.hpp"         // fmcmc_ppc_dev, fmcmc_ppc_yrep_dev, fmcmc_ppc_elem_host (the checks and the draw kernel of diag_predict.hpp)

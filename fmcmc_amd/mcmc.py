@@ -326,6 +326,17 @@ class DeviceChains:
         from .summary import loo_predictive
         return loo_predictive(self, model, autoburnin)
 
+    def ppc(self, model, seed=1, autoburnin=False):
+        """The posterior predictive check of the rows under `model` (a gaussian_linreg / logistic object): per draw the mean, sd,
+        min, max and chi-square discrepancy of one replicated data set, and their p-values against y: a PpcResult."""
+        from .summary import ppc
+        return ppc(self, model, seed, autoburnin)
+
+    def posterior_predict(self, model, ndraws=50, seed=1, autoburnin=False):
+        """The replicated data sets of ndraws evenly spaced draws under `model`, a device tensor [ndraws][n]."""
+        from .summary import posterior_predict
+        return posterior_predict(self, model, ndraws, seed, autoburnin)
+
     def rank_scores(self, fold=False, cols=None):
         """The rank-normalised scores behind rhat(), a device tensor [p][2 C][N // 2] (for rank plots)."""
         from .summary import rank_scores

@@ -13,6 +13,7 @@ the rank-normalised bulk and tail effective sample size that is read beside it (
 There is no CPU fallback.
 """
 import ctypes as C
+import math
 from types import SimpleNamespace
 
 import numpy as np
@@ -3253,3 +3254,330 @@ def loo_predictive(x, model, autoburnin=False):
     _raise_bad_loo_draws(th)
     family = "gaussian_linreg" if model.family == abi.FAM_GAUSSIAN_LINREG else "logistic"
     return LooPredictiveResult(point.cpu().numpy(), loo_point.cpu().numpy(), th, Cn * N, model.y, family, point)
+
+
+# ------------------------------------------------------------------------------------------------ ppc()
+PPC_NAMES = ("mean_rep", "sd_rep", "min_rep", "max_rep", "chisq_rep", "chisq_obs")   # the columns of fmcmc_ppc_dev's `stats`
+PPC_STATS = abi.PPC_STATS
+PPC_CAP = 1e-12                         # the project's cap for fixed-order means, in the metric |got - truth| / max(1, |truth|)
+
+
+def _ppc_model(model, who="ppc"):
+    """a gaussian_linreg or logistic object, as it is; anything else has no replicated data here"""
+    from .models import BatchedFun, LogPosterior, PointwiseFun
+    if isinstance(model, (BatchedFun, PointwiseFun)):
+        raise TypeError("%s() needs one of the regression families (gaussian_linreg, logistic): a %s says nothing of a new "
+                        "observation, and a predictive callback is not implemented." % (who, type(model).__name__))
+    if not isinstance(model, LogPosterior):
+        raise TypeError("%s() needs a gaussian_linreg or logistic object; got a %s" % (who, type(model).__name__))
+    if model.family == abi.FAM_IID_NORMAL:
+        raise ValueError("iid_normal has no covariates to predict at: its mean and sd are columns of summary().")
+    return model
+
+
+def _ppc_refuse_batch(x, who, call):
+    from .mcmc import McmcBatch
+    if isinstance(x, McmcBatch):
+        raise TypeError("%s() takes one dataset at a time (the grouped form is not implemented): call %s per dataset." % (who, call))
+
+
+def ppc_observed(model):
+    """T(y) for mean, sd (divisor n - 1; NaN for n = 1), min and max: longdouble, rounded to float64 [4]"""
+    y = np.asarray(model.y, dtype=np.longdouble).ravel()
+    n = y.size
+    mean = y.sum() / n
+    with np.errstate(all="ignore"):
+        sd = np.sqrt(((y - mean) ** 2).sum() / np.longdouble(n - 1)) if n > 1 else np.longdouble("nan")
+    return np.array([mean, sd, y.min(), y.max()], dtype=np.float64)
+
+
+def ppc_variates(model, chain_ids, ids, seed=1):
+    """[S][n]: the variate of every element from fmcmc_ppc_elem_host (the device's own text, built for the host): z = fmh_qnorm(u)
+    for the Gaussian family, u for the logistic one.  They do not depend on eta."""
+    n = int(np.asarray(model.y).shape[0])
+    chain_ids, ids = np.asarray(chain_ids, dtype=np.int64).ravel(), np.asarray(ids, dtype=np.int64).ravel()
+    out = np.empty((ids.size, n), dtype=np.float64)
+    eta, yrep = np.zeros(n), np.empty(n)
+    L = abi.lib()
+    for s in range(ids.size):
+        rc = L.fmcmc_ppc_elem_host(int(model.family), int(seed), int(chain_ids[s]), int(ids[s]), n, eta.ctypes.data, 1.0,
+                                   yrep.ctypes.data, out[s].ctypes.data)
+        _waic_rc(rc)
+    return out
+
+
+def _fma64(a, b, c):
+    """round(a b + c) with one rounding, element by element in float64 (exact rational arithmetic where all three are finite)"""
+    from fractions import Fraction
+    a, b, c = np.broadcast_arrays(*(np.asarray(v, dtype=np.float64) for v in (a, b, c)))
+    with np.errstate(all="ignore"):
+        out = a * b + c
+    fin = np.isfinite(a) & np.isfinite(b) & np.isfinite(c)
+    one = getattr(math, "fma", None) or (lambda x, y, z: float(Fraction(x) * Fraction(y) + Fraction(z)))
+    flat, fa, fb, fc = out.ravel(), a.ravel(), b.ravel(), c.ravel()
+    for i in np.flatnonzero(fin.ravel()):
+        try:
+            flat[i] = one(float(fa[i]), float(fb[i]), float(fc[i]))
+        except OverflowError:
+            pass                                       # (the two roundings already gave the infinity)
+    return flat.reshape(out.shape)
+
+
+def ppc_fold(v, crep, cobs, dtype=np.float64):
+    """The device's fold of a draw over its n observations, in `dtype` (csrc/diag_ppc.hpp): v, crep, cobs [S][n] -> [S][6] = mean,
+    sd, min, max, chisq_rep, chisq_obs.  Lane c = 0 .. 15 takes i = c, c + 16, ... in that order, its sums shifted by the first
+    value; the lanes are merged in lane order by Chan's update.  In float64 these are the device's operations one by one."""
+    v, crep, cobs = (np.asarray(a, dtype=dtype) for a in (v, crep, cobs))
+    S, n = v.shape
+    acc = None
+    with np.errstate(all="ignore"):
+        for c in range(min(16, n)):
+            idx = range(c, n, 16)
+            cnt = dtype(len(idx))
+            K = v[:, c]
+            sd, sdd, cr, co = (np.zeros(S, dtype=dtype) for _ in range(4))
+            mn, mx = K.copy(), K.copy()
+            for i in idx:
+                x = v[:, i]
+                d = x - K
+                sd = sd + d
+                sdd = sdd + d * d
+                mn = np.where((x < mn) | np.isnan(x), x, mn)
+                mx = np.where((x > mx) | np.isnan(x), x, mx)
+                cr = cr + crep[:, i]
+                co = co + cobs[:, i]
+            mean = K + sd / cnt
+            M2 = sdd - sd * sd / cnt
+            M2 = np.where(M2 < 0, dtype(0), M2)
+            b = (cnt, mean, M2, mn, mx, cr, co)
+            if acc is None:
+                acc = b
+                continue
+            a = acc
+            oc = a[0] + b[0]
+            delta = b[1] - a[1]
+            acc = (oc, a[1] + delta * (b[0] / oc), (a[2] + b[2]) + delta * delta * (a[0] * b[0] / oc),
+                   np.where((b[3] < a[3]) | np.isnan(b[3]), b[3], a[3]), np.where((b[4] > a[4]) | np.isnan(b[4]), b[4], a[4]),
+                   a[5] + b[5], a[6] + b[6])
+        sd_all = np.sqrt(acc[2] / (dtype(n) - dtype(1)))
+    return np.stack([acc[1], sd_all, acc[3], acc[4], acc[5], acc[6]], axis=1)
+
+
+def ppc_counts(stats, tobs):
+    """[5][3] integers: per statistic (mean, sd, min, max, chisq) the draws with T_rep > T_obs, T_rep == T_obs and a value that is
+    not finite on either side; for chisq T_obs is the draw's own chisq_obs"""
+    out = np.zeros((5, 3), dtype=np.int64)
+    for j in range(5):
+        rep = stats[:, j]
+        obs = stats[:, 5] if j == 4 else np.full(rep.shape, tobs[j], dtype=stats.dtype)
+        nf = ~(np.isfinite(rep) & np.isfinite(obs))
+        out[j] = ((~nf & (rep > obs)).sum(), (~nf & (rep == obs)).sum(), nf.sum())
+    return out
+
+
+def ppc_host(model, draws, chain_ids, ids, seed=1, dtype=np.float64):
+    """The host restatement of ppc() on draws [S][k] with their keys chain_ids [S] and ids [S]: the executable definition
+    (INTEGRATION.md §2.2).  The variates come from fmcmc_ppc_elem_host, everything else is numpy in `dtype`; with dtype =
+    np.longdouble it is the truth the tests hold the device to.  Returns a namespace with stats [S][6] (PPC_NAMES), yrep [S][n],
+    variate, eta, observed [4] (float64), counts [5][3], pvalue and p_gt [5], ndraws, bad_draws and the a-priori bounds, from the
+    inputs alone: e [S][n] = (k' + 2) 2^-53 (|b0| + sum |x beta|), the bound of the device's eta; d = e + 2^-53 |y_rep| and dmax
+    [S] its largest value over i; flips: the (s, i) of the logistic family with |u - p| <= e / 4 + 4 x 2^-53, where the device's
+    y_rep may be the other value; near [5]: per statistic the draws whose |T_rep - T_obs| is within that statistic's bound (min,
+    max: dmax, and 0 for the logistic family, whose y_rep are exact where no flip is possible, so that a tie there is decided;
+    mean, sd: PPC_CAP max(1, |T|); chisq: that for both sides, but for the draws whose two sums have the same terms, which are
+    equal in any arithmetic), by which a device count may differ."""
+    model = _ppc_model(model, "ppc_host")
+    th = np.asarray(draws, dtype=dtype)
+    if th.ndim != 2 or th.shape[1] != model.k:
+        raise ValueError("draws must be [S][%d] for this family; got shape %s" % (model.k, th.shape))
+    S = th.shape[0]
+    if S < 2:
+        raise ValueError("a prediction needs at least 2 draws; got %d" % S)
+    ic, p = int(model.intercept), model.p
+    gauss = model.family == abi.FAM_GAUSSIAN_LINREG
+    X = _predict_newdata(model, None).astype(dtype)
+    y = np.asarray(model.y, dtype=dtype).ravel()
+    n = y.size
+    eta = np.zeros((S, n), dtype=dtype)
+    if ic:
+        eta = eta + th[:, :1]
+    if p:
+        eta = eta + th[:, ic:ic + p] @ X.T
+    var = ppc_variates(model, chain_ids, ids, seed)
+    U = np.longdouble(2.0) ** -53
+    tl = np.abs(np.asarray(draws, dtype=np.longdouble))
+    e = (ic + p + 2) * U * ((tl[:, :1] if ic else 0) + tl[:, ic:ic + p] @ np.abs(np.asarray(X, dtype=np.longdouble)).T
+                            + np.zeros((S, n), dtype=np.longdouble))
+    with np.errstate(all="ignore"):
+        if gauss:
+            sigma = th[:, -1:]
+            z = var.astype(dtype)
+            yrep = _fma64(sigma + 0 * z, z, eta) if dtype is np.float64 else sigma * z + eta   # (the device's single rounding)
+            crep = z * z
+            r = (y[None, :] - eta) * (dtype(1) / sigma)
+            cobs = r * r
+            flips = np.zeros((0, 2), dtype=np.int64)
+        else:
+            pr = _expit(eta)
+            yrep = (var.astype(dtype) < pr).astype(dtype)
+            em, ep = np.exp(-eta), np.exp(eta)
+            crep = np.where(yrep != 0, em, ep)
+            cobs = np.where(y[None, :] != 0, em, ep) + np.zeros_like(eta)
+            flips = np.argwhere(np.abs(var.astype(np.longdouble) - pr.astype(np.longdouble)) <= e / 4 + 4 * U)
+        stats = ppc_fold(yrep, crep, cobs, dtype)
+        tobs = ppc_observed(model)
+        counts = ppc_counts(stats, tobs.astype(dtype))
+        d = e + U * np.abs(yrep.astype(np.longdouble))
+        dmax = d.max(axis=1)
+        sl = stats.astype(np.longdouble)
+        cap = lambda v: PPC_CAP * np.maximum(1, np.abs(v))
+        bounds = [cap(sl[:, 0]), cap(sl[:, 1]), dmax if gauss else 0 * dmax, dmax if gauss else 0 * dmax, cap(sl[:, 4]) + cap(sl[:, 5])]
+        near = np.zeros(5, dtype=np.int64)
+        for j in range(5):
+            obs = sl[:, 5] if j == 4 else np.longdouble(tobs[j])
+            decided = (crep == cobs).all(axis=1) if j == 4 else False      # (the same terms in the same order: equal sums)
+            near[j] = int(((np.abs(sl[:, j] - obs) <= bounds[j]) & (bounds[j] > 0) & ~decided).sum())
+        usable = counts[:, 2] < S
+        pvalue = np.where(usable, (counts[:, 0] + counts[:, 1]) / float(S), np.nan)
+        p_gt = np.where(usable, counts[:, 0] / float(S), np.nan)
+    return SimpleNamespace(stats=stats, yrep=yrep, variate=var, eta=eta, observed=tobs, counts=counts, pvalue=pvalue, p_gt=p_gt,
+                           ndraws=S, bad_draws=_bad_draws(model, np.asarray(draws, dtype=np.float64)), e=e, d=d, dmax=dmax,
+                           flips=flips, near=near)
+
+
+class PpcResult:
+    """ppc() of a result: stats, a DeviceChains [C][6][N] of the replicated statistics per draw (PPC_NAMES; summary(),
+    hpd_interval(), ess() and rhat() apply to it), observed = T(y) per statistic (chisq: None, it is compared per draw), pvalue =
+    (gt + eq) / S' and p_gt = gt / S' per statistic, counts [5][3] = {gt, eq, not finite}, ndraws = S', bad_draws."""
+
+    def __init__(self, stats, observed, total, family):
+        total = np.asarray(total, dtype=np.float64)
+        self.stats, self.family = stats, family
+        self.ndraws, self.bad_draws = int(total[0]), int(total[1])
+        self.counts = total[2:2 + 15].astype(np.int64).reshape(5, 3)
+        self.observed = dict(zip(PPC_STATS, [float(v) for v in observed] + [None]))
+        S = float(self.ndraws)
+        usable = self.counts[:, 2] < self.ndraws
+        self.pvalue = {s: (float((c[0] + c[1]) / S) if u else float("nan")) for s, c, u in zip(PPC_STATS, self.counts, usable)}
+        self.p_gt = {s: (float(c[0] / S) if u else float("nan")) for s, c, u in zip(PPC_STATS, self.counts, usable)}
+
+    def table(self):
+        """[5][4]: T(y), the mean and sd of T(y_rep) over the draws (summary() of stats), p; chisq: the mean of chisq_obs for T(y)"""
+        try:
+            st = summary(self.stats, quantiles=()).statistics
+        except (ValueError, NotImplementedError):            # (fewer than 3 rows a chain: no summary)
+            st = np.full((6, 4), np.nan)
+        obs = [self.observed[s] for s in PPC_STATS[:4]] + [st[5, 0]]
+        return np.array([[obs[j], st[j, 0], st[j, 1], self.pvalue[s]] for j, s in enumerate(PPC_STATS)], dtype=np.float64)
+
+    def __str__(self):
+        out = ["", "Posterior predictive check from %d draws (%s)" % (self.ndraws, self.family), ""]
+        return "\n".join(out + [_fmt_table(list(PPC_STATS), ["T(y)", "Mean T(y_rep)", "SD T(y_rep)", "p"], self.table())]) + "\n"
+
+    def __repr__(self):
+        return "<PpcResult ndraws=%d %s>" % (self.ndraws, " ".join("p(%s)=%.3g" % kv for kv in self.pvalue.items()))
+
+
+def _ppc_open(dc, dm, who):
+    o = _open(dc, None, who)
+    if dm.device != o.dev and (dm.device.index is not None or dm.device.type != o.dev.type):
+        raise ValueError("the model's data are on %s, the draws on %s" % (dm.device, o.dev))
+    if o.k != dm.k:
+        raise ValueError("the result has k = %d parameters, the model's family has %d" % (o.k, dm.k))
+    return o
+
+
+def enqueue_ppc(dc, dm, row0, N, seed, tobs):
+    """The one call site of fmcmc_ppc_dev (current torch stream): the window [row0, row0 + N) of the rows of `dc` under the device
+    model dm, keyed by dc.chain_base, id0 = dc.iters[row0] and id_step = dc.thin.  Returns the device tensors (stats [C][6][N],
+    total [17], work); nothing is synchronised."""
+    import torch
+    o = _ppc_open(dc, dm, "check")
+    if row0 < 0 or N < 1 or row0 + N > dc.nrows:
+        raise ValueError("the window [%d, %d) is outside the %d kept rows" % (row0, row0 + N, dc.nrows))
+    if o.Cn * int(N) < 2:
+        raise ValueError("a prediction needs at least 2 draws; got %d" % (o.Cn * int(N)))
+    cm = dm.c()
+    nwork = o.L.fmcmc_ppc_work_len(C.byref(cm), o.Cn, int(N))
+    if nwork < 1:
+        _waic_rc(abi.ERR_ARG)
+    stats = torch.full((o.Cn, len(PPC_NAMES), int(N)), float("nan"), dtype=torch.float64, device=o.dev)
+    total = torch.full((2 + 15,), float("nan"), dtype=torch.float64, device=o.dev)
+    work = _doubles(o, nwork)
+    tobs_h = np.ascontiguousarray(tobs, dtype=np.float64)
+    with torch.cuda.device(o.dev):
+        rc = o.L.fmcmc_ppc_dev(C.byref(cm), o.smp.data_ptr(), o.Cn, o.k, o.cap, int(row0), int(N), int(seed), int(dc.chain_base),
+                               int(dc.iters[row0]), int(dc.thin), tobs_h.ctypes.data_as(C.POINTER(C.c_double)), work.data_ptr(),
+                               stats.data_ptr(), total.data_ptr(), _stream(o.dev))
+    _waic_rc(rc)
+    return stats, total, work
+
+
+def ppc(x, model, seed=1, autoburnin=False):
+    """The posterior predictive check of Gelman, Meng and Stern (bayesplot::ppc_stat): x a DeviceChains (read in place), an Mcmc
+    or a McmcList (uploaded first), model the gaussian_linreg or logistic object it was sampled from.  Every draw replicates the
+    data once, y_rep ~ p(y | theta_s), from a Philox stream keyed by (seed, chain id, the row's iteration label, i), so the same
+    draw gives the same y_rep wherever it sits; per draw the mean, sd, min and max of y_rep and the chi-square discrepancy of
+    y_rep and of y at the draw's own theta; p = the share of draws with T(y_rep) >= T(y).  The S x n matrix is never stored
+    (csrc/diag_ppc.hpp).  Returns a PpcResult; its `stats` are a DeviceChains, a derived chain.  With `autoburnin` the rows are
+    coda's window (the second half).  An McmcBatch is taken per dataset: ppc(ans[d], models[d])."""
+    from .convergence import _window
+    from .mcmc import DeviceChains
+    _ppc_refuse_batch(x, "ppc", "ppc(ans[d], models[d])")
+    model = _ppc_model(model)
+    dc = _as_device_chains(x)
+    row0, N = _window(dc.iters) if autoburnin else (0, int(dc.nrows))
+    observed = ppc_observed(model)
+    stats, total, _work = enqueue_ppc(dc, model.device_model(dc._samples.device), row0, N, seed, observed)
+    th = total.cpu().numpy()
+    if th[1] != 0:
+        raise ValueError("%d draw(s) with a parameter that is not finite or a sigma that is not > 0 among the rows to predict from"
+                         % int(th[1]))
+    derived = DeviceChains(stats, None, None, np.asarray(dc.iters)[row0:row0 + N], dc.thin, list(PPC_NAMES), dc.chain_base,
+                           dc.nchains_total)
+    return PpcResult(derived, observed, th, "gaussian_linreg" if model.family == abi.FAM_GAUSSIAN_LINREG else "logistic")
+
+
+def posterior_predict_selection(nchains, N, ndraws):
+    """The draws posterior_predict() takes of the nchains N draws of a window, chain after chain: draw j = 0 .. ndraws - 1 is the
+    flat index floor(j nchains N / ndraws), i.e. (chain, row) = divmod(index, N); ndraws is cut to nchains N."""
+    total = int(nchains) * int(N)
+    nd = min(int(ndraws), total)
+    if nd < 1:
+        raise ValueError("ndraws = %d: at least one draw is needed" % int(ndraws))
+    flat = (np.arange(nd, dtype=np.int64) * total) // nd
+    return flat // int(N), flat % int(N)
+
+
+def enqueue_ppc_yrep(dc, dm, seed, sel_chain, sel_row):
+    """The one call site of fmcmc_ppc_yrep_dev (current torch stream): the replicated data sets of the draws (sel_chain[i], row
+    sel_row[i] of dc's rows), a device tensor [nsel][n]; nothing is synchronised."""
+    import torch
+    o = _ppc_open(dc, dm, "replicate")
+    sc, sr = np.ascontiguousarray(sel_chain, dtype=np.int64), np.ascontiguousarray(sel_row, dtype=np.int64)
+    if sc.shape != sr.shape or sc.ndim != 1 or sc.size < 1:
+        raise ValueError("sel_chain and sel_row must be two vectors of one length >= 1")
+    if sr.min() < 0 or sr.max() >= dc.nrows:
+        raise ValueError("a selected row is outside the %d kept rows" % dc.nrows)
+    yrep = torch.full((int(sc.size), dm.n), float("nan"), dtype=torch.float64, device=o.dev)
+    cm = dm.c()
+    i64 = C.POINTER(C.c_int64)
+    with torch.cuda.device(o.dev):
+        rc = o.L.fmcmc_ppc_yrep_dev(C.byref(cm), o.smp.data_ptr(), o.Cn, o.k, o.cap, int(seed), int(dc.chain_base),
+                                    int(dc.iters[0]), int(dc.thin), sc.ctypes.data_as(i64), sr.ctypes.data_as(i64), int(sc.size),
+                                    yrep.data_ptr(), _stream(o.dev))
+    _waic_rc(rc)
+    return yrep
+
+
+def posterior_predict(x, model, ndraws=50, seed=1, autoburnin=False):
+    """Replicated data sets themselves, a device tensor [ndraws][n] (what bayesplot::ppc_dens_overlay plots): the y_rep of ndraws
+    draws evenly spaced over the window, chain after chain (posterior_predict_selection), bit for bit what ppc() with the same
+    seed folded for those draws.  At most 65535 draws a call."""
+    from .convergence import _window
+    _ppc_refuse_batch(x, "posterior_predict", "posterior_predict(ans[d], models[d])")
+    model = _ppc_model(model, "posterior_predict")
+    dc = _as_device_chains(x)
+    row0, N = _window(dc.iters) if autoburnin else (0, int(dc.nrows))
+    chain, row = posterior_predict_selection(int(dc._samples.shape[0]), N, ndraws)
+    return enqueue_ppc_yrep(dc, model.device_model(dc._samples.device), seed, chain, row0 + row)

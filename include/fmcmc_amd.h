@@ -829,6 +829,44 @@ int fmcmc_predictive_dev(const fmcmc_model* m /* X = Xn [p][m->n]; y [m->n] or N
                          int32_t npasses, int32_t resume, double* work, double* point /* [n][4 + 4 nprobs] */,
                          double* total /* [6] */, void* hip_stream);
 
+/* ---- Posterior predictive checks from replicated data (Gelman, Meng and Stern 1996; bayesplot::ppc_stat), the device part ---------
+ * The definition is INTEGRATION.md 2.2 (fmcmc_amd/summary.py: ppc_host is its executable form).  Draws, window and eta as for
+ * fmcmc_predict_dev at the model's own X; S' = nchains N >= 2.  m: FMCMC_FAM_GAUSSIAN_LINREG or FMCMC_FAM_LOGISTIC with the DEVICE
+ * pointers X [p][n] and y [n]; FMCMC_FAM_IID_NORMAL: FMCMC_ERR_UNSUPPORTED.
+ *   Draw s = row r of chain c of the window has the keys (seed, chain id = chain_base + c, id = id0 + id_step r); both ids must fit
+ *   32 bits (else FMCMC_ERR_UNSUPPORTED).  The uniform of observation i is lane i & 1 of fmh_uniform2(seed, id, chain id, i >> 1,
+ *   FMH_STREAM_PPC) (include/fmh_philox.h).  Gaussian: z = fmh_qnorm(u), y_rep = fmh_fma(sigma_s, z, eta_si).  Logistic: y_rep =
+ *   1 if u < expit(eta_si), else 0, expit in the branch form of fmcmc_predict_dev.
+ * stats (device, [nchains][6][N], the layout of `samples`) = per draw {mean, sd (divisor n - 1; NaN for n = 1), min, max of y_rep
+ *   over the n observations, chisq_rep, chisq_obs}: Gaussian chisq_rep = sum z^2, chisq_obs = sum ((y_i - eta_si) (1 / sigma_s))^2;
+ *   logistic each is sum fmh_exp(v ? -eta : eta), v = y_rep resp. y.  The fold over i = 0 .. n - 1 is a function of n alone: lane
+ *   c = 0 .. 15 takes i = c, c + 16, ... in that order with its sums shifted by the first value; the 16 lanes are merged in lane
+ *   order by Chan's update (sums: added; min, max: compared).  No floating-point atomics: a draw's six numbers depend on its theta,
+ *   its two ids, the model and the seed alone, not on nchains, N, row0 or the other draws.
+ * tobs (HOST, [4]) = T(y) for mean, sd, min, max.  total (device, [17]) = {S', bad_draws (as fmcmc_predict_dev), then for each of
+ *   mean, sd, min, max, chisq the counts of draws with T_rep > T_obs, T_rep == T_obs, and a value that is not finite on either
+ *   side (counted in neither of the first two)}; for chisq the comparison is chisq_rep against the draw's own chisq_obs.
+ * work: device scratch of fmcmc_ppc_work_len(m, nchains, N) doubles (0 for arguments the call refuses; needs no device): two sums
+ *   per 256 draws and 16 integer words.  A call does not depend on what work held.
+ * fmcmc_ppc_yrep_dev writes the replicated data sets themselves, yrep (device, [nsel][n]), of nsel <= 65535 selected draws
+ *   (sel_chain[i] in [0, nchains), sel_row[i] in [0, S): HOST arrays, read during the call; the id of row r is id0 + id_step r,
+ *   so id0 belongs to row 0 of the buffer): the same text per element, bit for bit what the fold of fmcmc_ppc_dev consumed.  It
+ *   needs nchains S >= 2 and does not read m->y.
+ * Every kernel is enqueued on hip_stream; nothing is synchronised, `samples` and the model are only read, nothing is written
+ * past the documented lengths.  Argument errors are found before any device call and leave their text in fmcmc_last_error().
+ * fmcmc_ppc_elem_host: the host build of the same per-element text on host arrays (needs no device): given eta [n] of the draw
+ *   with the keys (seed, chain_id, id) and its sigma (Gaussian), yrep [n] and variate [n] = z (Gaussian) or u (logistic), bit
+ *   for bit the device's. */
+int64_t fmcmc_ppc_work_len(const fmcmc_model* m, int64_t nchains, int64_t N);
+int fmcmc_ppc_dev(const fmcmc_model* m, const double* samples, int64_t nchains, int32_t k, int64_t S, int64_t row0, int64_t N,
+                  uint64_t seed, int64_t chain_base, int64_t id0, int64_t id_step, const double* tobs /* host, [4] */,
+                  double* work, double* stats /* [nchains][6][N] */, double* total /* [17] */, void* hip_stream);
+int fmcmc_ppc_yrep_dev(const fmcmc_model* m, const double* samples, int64_t nchains, int32_t k, int64_t S, uint64_t seed,
+                       int64_t chain_base, int64_t id0, int64_t id_step, const int64_t* sel_chain /* host */,
+                       const int64_t* sel_row /* host */, int64_t nsel, double* yrep /* [nsel][n] */, void* hip_stream);
+int fmcmc_ppc_elem_host(int32_t family, uint64_t seed, int64_t chain_id, int64_t id, int64_t n, const double* eta, double sigma,
+                        double* yrep, double* variate);
+
 /* Materialises the canonical Philox stream of a call in device memory, in the FED layout of fmcmc_run:
  * logu[C][nsteps] (entry i-1 = log accept-uniform of loop step i), z[C][nsteps][kz] (N(0,1) when student_df == 0;
  * Student-t with student_df degrees of freedom when student_df > 0 -- kernel_ram: kf for the default qfun rt(k, k),

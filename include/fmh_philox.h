@@ -34,6 +34,7 @@
 #define FMH_STREAM_GAMMA 2u    /* block = j*FMH_GAMMA_TRIES + attempt: (normal, uniform) pair */
 #define FMH_STREAM_UNIF 3u     /* block j/2, lane j%2: U(0,1) for free parameter j (uniform kernels) */
 #define FMH_STREAM_SCHEME 4u   /* block 0, word 0: update column of plan row `step` (scheme = "random") */
+#define FMH_STREAM_PPC 5u      /* step = a kept row's iteration label, block i/2, lane i%2: the variate of observation i (ppc()) */
 #define FMH_GAMMA_TRIES 64u
 
 typedef struct { uint32_t v[4]; } fmh_u32x4;
